@@ -10,7 +10,12 @@ collective (FM index replicated per GPU). Every rank keeps its part of the outpu
 parts (RCCL all-gather) and the step's fixed-size alignment records go to rank 0 with a gatherv (RCCL over xGMI) - inside the timed
 region, while the following steps compute (the gather streams per batch). Prints ONE JSON line on rank 0.
 
-  python bench.py --gpus 1 --steps K --warmup W
+A plain run does only what its headline figure needs: set up, warm up, time the K steps, write the last step's outputs when
+--dump-outputs is given, print the line. --full adds every secondary measurement and check to the line: the CPU baseline and the
+parity sample against the oracle, per-kernel device times of the timed region, the one-lane instrumented pass and the rooflines
+it feeds, the same K steps with the reads in host memory, and (metric configuration) the repeat-rich leg.
+
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python bench.py --gpus N ...                 (spawns its N ranks itself, one per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -56,9 +61,14 @@ def parse():
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("FLX_BENCH_INFLIGHT", 3)),
                     help="steps submitted to the context at a time (host threads calling align_reads); every step still runs in "
                          "full inside the timed region")
-    ap.add_argument("--no-isolated-pass", action="store_true", help="skip the one-lane instrumented pass (timeline profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks: CPU baseline and oracle parity sample, per-kernel times, the one-lane "
+                         "pass and its rooflines, the host-inputs leg, the repeat-rich leg (the --no-* flags below switch single ones off)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's part) as float64 .npy files into DIR")
+    ap.add_argument("--no-isolated-pass", action="store_true", help="--full: skip the one-lane instrumented pass (timeline profiling)")
     ap.add_argument("--isolated-only", action="store_true",
-                    help="only the one-lane instrumented pass (used under rocprofv3 so that its per-kernel averages are those of roofline)")
+                    help="--full: only the one-lane instrumented pass (used under rocprofv3 so that its per-kernel averages are those of roofline)")
     ap.add_argument("--genome", type=int, default=0, help="synthetic reference length in total; 0 = the config's")
     ap.add_argument("--chromosomes", type=int, default=0, help="sequences the reference is cut into; 0 = the config's")
     ap.add_argument("--read-length", type=int, default=0)
@@ -66,12 +76,14 @@ def parse():
     ap.add_argument("--interval-optimization", action="store_true")
     ap.add_argument("--gather-cigars", action="store_true", help="N > 1: the per-step gather to rank 0 also moves the CIGAR words (default: the fixed-size records)")
     ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("FLX_BENCH_CPU_SAMPLE", 768)))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle run (CPU baseline and parity sample)")
     ap.add_argument("--dump-gathered", default="", help="rank 0 saves the record table of timed step 0 as it arrives from all ranks (numpy .npy; tests)")
-    ap.add_argument("--no-host-inputs-leg", action="store_true", help="skip the second timed region (reads in pageable host memory: H2D and Peq build inside the clock)")
-    ap.add_argument("--no-repeat-rich-leg", action="store_true", help="metric configuration only: skip the secondary line on the repeat-rich (hg38-like) reference")
+    ap.add_argument("--no-host-inputs-leg", action="store_true", help="--full: skip the second timed region (reads in pageable host memory: H2D and Peq build inside the clock)")
+    ap.add_argument("--no-repeat-rich-leg", action="store_true", help="--full, metric configuration only: skip the secondary line on the repeat-rich (hg38-like) reference")
     ap.add_argument("--repeat-rich-steps", type=int, default=8)
     args = ap.parse_args()
+    if args.isolated_only and not args.full:
+        ap.error("--isolated-only is a --full measurement")
     cfg = CONFIGS[args.config]
     args.genome = args.genome or cfg["genome"]
     args.chromosomes = args.chromosomes or cfg["chromosomes"]
@@ -93,6 +105,41 @@ def usable_cores():
     return n
 
 
+def cigar_words(rows, cig):
+    """the CIGAR words of `rows` (records as RunResult.rows), record after record"""
+    import numpy as np
+    if not len(rows):
+        return np.zeros(0, np.uint32)
+    lens = rows[:, 6]
+    idx = np.repeat(rows[:, 5] - np.concatenate(([0], np.cumsum(lens)[:-1])), lens) + np.arange(int(lens.sum()))
+    return np.asarray(cig, dtype=np.uint32)[idx]
+
+
+DUMP_READS = 32                     # reads of the last step whose records --dump-outputs writes in full (about 2 M CIGAR words at 10 kb @ 8 %)
+DUMP_MAX_CIGAR_WORDS = 4 << 20      # 32 MB of float64: the files stay under 64 MB whatever the workload
+
+
+def dump_outputs(out_dir, res, n_reads):
+    """what one step of the timed path returned, as float64 .npy files (every value is an integer below 2^53, so exactly):
+      records_per_read.npy  [n_reads]   records of every read of the batch
+      skipped.npy           [n_reads]   1 where the read was skipped (over floxer's length limit)
+      records.npy           [n, 6]      read, flag, reference, position, edit distance and CIGAR length of every record of DUMP_READS
+                                        reads drawn with a fixed seed, in output order (the CIGAR offset is left out: where a chunk's
+                                        CIGARs land in the output depends on the lanes' timing)
+      cigars.npy            [m]         those records' CIGAR words, record after record (the first DUMP_MAX_CIGAR_WORDS of them)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = res.rows
+    sample = np.sort(np.random.default_rng(0).choice(n_reads, size=min(DUMP_READS, n_reads), replace=False))
+    sel = rows[np.isin(rows[:, 0], sample)]
+    out = {"records_per_read": np.bincount(rows[:, 0], minlength=n_reads)[:n_reads],
+           "skipped": np.asarray(res.skipped[:n_reads]),
+           "records": sel[:, [0, 1, 2, 3, 4, 6]].reshape(-1, 6),
+           "cigars": cigar_words(sel, res.cigars)[:DUMP_MAX_CIGAR_WORDS]}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(np.float64))
+
+
 def compare_with_oracle(got, exp, n_sample):
     """records of the reads [0, n_sample) of a product result against an oracle run over exactly those reads: same number of records,
     and record by record (in output order) the same read, flag, reference, position, edit distance and CIGAR words"""
@@ -108,14 +155,8 @@ def compare_with_oracle(got, exp, n_sample):
     if not np.array_equal(g[:, 6], e[:, 6]):
         return out
     # CIGAR words: gather both sides' slabs in record order and compare once
-    def words(rows, cig):
-        if not len(rows):
-            return np.zeros(0, np.uint32)
-        lens = rows[:, 6]
-        idx = np.repeat(rows[:, 5] - np.concatenate(([0], np.cumsum(lens)[:-1])), lens) + np.arange(int(lens.sum()))
-        return np.asarray(cig, dtype=np.uint32)[idx]
     out["cigar_words"] = int(e[:, 6].sum())
-    out["equal"] = bool(np.array_equal(words(g, got.cigars), words(e, exp.cigars)))
+    out["equal"] = bool(np.array_equal(cigar_words(g, got.cigars), cigar_words(e, exp.cigars)))
     return out
 
 
@@ -237,17 +278,19 @@ def main():
                     res = f.result()
                     D.exchange_counts(res.n_records, len(res.cigars), rank, world, device=dev)
         log("warm")
-        ctx.enable_kernel_timing(True)
-        ctx.reset_kernel_stats()
+        if args.full:
+            ctx.enable_kernel_timing(True)
+            ctx.reset_kernel_stats()
         ctx.path_counters(reset=True)
 
         def timed_region(inputs):
-            """K steps over `inputs` (one per timed batch): (seconds (max over ranks), records, seconds rank 0 spent gathering, result of step 0)"""
+            """K steps over `inputs` (one per timed batch): (seconds (max over ranks), records, seconds rank 0 spent gathering, result of
+            step 0, result of the last step)"""
             tpool = ThreadPoolExecutor(max_workers=max(1, args.inflight))
             g_s = 0.0 if world > 1 else None
             gathered_rows = 0
             n_rec = 0
-            first = None
+            first = last = None
             barrier()
             t_start = time.perf_counter()
             # a step = the whole hot path over one batch. Batches are independent (floxer itself streams reads through a thread
@@ -258,6 +301,8 @@ def main():
                 res = f.result()
                 if si == 0:
                     first = res
+                if si == args.steps - 1:
+                    last = res
                 # the only exchanges between ranks: the sizes of the ranks' parts of this step (= where each part goes in the job's
                 # output, which is the parts in rank order), then the step's records to rank 0 - while the next steps compute
                 counts = D.exchange_counts(res.n_records, len(res.cigars), rank, world, device=dev)
@@ -291,18 +336,23 @@ def main():
                 secs = float(t.item())
                 if rank == 0:
                     assert gathered_rows == n_rec, (gathered_rows, n_rec)
-            return secs, n_rec, g_s, first
+            return secs, n_rec, g_s, first, last
 
-        elapsed, n_records, gather_s, first_result = timed_region(resident[first_timed:first_timed + n_timed_batches])
+        elapsed, n_records, gather_s, first_result, last_result = timed_region(resident[first_timed:first_timed + n_timed_batches])
         log(f"timed region {elapsed:.2f} s")
+        if args.dump_outputs and rank == 0:
+            last_batch = batches[first_timed + (args.steps - 1) % n_timed_batches]
+            dump_outputs(args.dump_outputs, last_result, len(last_batch[1]) - 1)
+            log(f"outputs of the last step written to {args.dump_outputs}")
 
-        stats = ctx.kernel_stats()
         path = ctx.path_counters()
-        ctx.enable_kernel_timing(False)
+        if args.full:
+            stats = ctx.kernel_stats()
+            ctx.enable_kernel_timing(False)
         # ---- what floxer's own stopwatch spans (floxer.cpp:154-179: query reading to last record): the same K steps with the reads in
         #      pageable host memory, flx_align_reads: the H2D copy, the reverse complements, the 2-bit form and the Peq planes inside the clock
-        if not args.no_host_inputs_leg:
-            host_elapsed, host_records, _, _ = timed_region(batches[first_timed:first_timed + n_timed_batches])
+        if args.full and not args.no_host_inputs_leg:
+            host_elapsed, host_records, _, _, _ = timed_region(batches[first_timed:first_timed + n_timed_batches])
             assert host_records == n_records, (host_records, n_records)
             log(f"timed region, host inputs {host_elapsed:.2f} s")
     # the timed region's context and its resident batches leave the GPU before the one-lane pass makes its own (a repeat-rich reference
@@ -316,7 +366,7 @@ def main():
     #      HIP-event time (on the launch stream) is its own duration. Outside the timed region; feeds "roofline".
     iso_stats = {}
     parity_failed = False
-    if rank == 0 and not args.no_isolated_pass:
+    if rank == 0 and args.full and not args.no_isolated_pass:
         os.environ["FLX_LANES"] = "1"
         ctx1 = F.context(index, device=local_rank, image=image)
         al1 = F.aligner(ctx1, p)
@@ -343,7 +393,7 @@ def main():
         parity = None
         ext_per_read = None
         ext_source = None
-        if not args.no_cpu_baseline and world == 1:            # (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and world == 1:            # (rank 0 at N = 1 only)
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O                      # the checker, timed as the reported CPU baseline only
             ncores = usable_cores()
@@ -369,7 +419,7 @@ def main():
                              f"(CPU restatement of floxer's path) on {ncores} threads; index build excluded on both sides (the oracle's "
                              "index is laid out around the suffix array and BWTs imported from the product's index)",
                    "cursor_extensions_per_read": round(ext_per_read, 1)}
-        if ext_per_read is None:
+        if args.full and ext_per_read is None:
             # no oracle run in this invocation: the count of a committed run on this workload (a function of reference, reads and flags)
             try:
                 t = json.load(open(os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_oracle_extensions.json")))
@@ -458,7 +508,7 @@ def main():
         repeat_rich_line = None
         index_device_bytes = int(index.device_bytes)
         index_derived_bytes = int(index.derived_device_bytes)
-        if (world == 1 and not args.no_repeat_rich_leg and not args.repeat_rich and not args.isolated_only and args.config == "grch38"
+        if (args.full and world == 1 and not args.no_repeat_rich_leg and not args.repeat_rich and not args.isolated_only and args.config == "grch38"
                 and (args.genome, args.read_length, args.error_rate) == (CONFIGS["grch38"]["genome"], 10000, 0.08)):
             del image, index, genome, pool, batches
             if not args.no_cpu_baseline:
@@ -466,7 +516,7 @@ def main():
             import gc
             gc.collect()
             torch.cuda.empty_cache()
-            cmd = [sys.executable, os.path.abspath(__file__), "--repeat-rich", "--steps", str(args.repeat_rich_steps), "--warmup", "3", "--no-cpu-baseline",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--repeat-rich", "--steps", str(args.repeat_rich_steps), "--warmup", "3", "--no-cpu-baseline",
                    "--no-isolated-pass", "--no-host-inputs-leg", "--lanes", str(args.lanes), "--inflight", str(args.inflight)]
             if args.interval_optimization:
                 cmd.append("--interval-optimization")
@@ -506,17 +556,20 @@ def main():
             "gbases_per_s": round(value * mean_len / 1e9, 5), "records": n_records, "index_build_s": round(index_s, 2),
             "index_device_bytes": index_device_bytes, "index_derived_device_bytes": index_derived_bytes,
             "gather_s": None if gather_s is None else round(gather_s, 3),      # time rank 0 spent in the per-step gathers (inside the timed region)
-            "roofline": roofline, "roofline_fm_search": roofline_fm, "roofline_timed_region": roofline_timed, "cpu_baseline": cpu,
-            "parity_sample": parity,
-            # `value` = inputs resident in HBM when the clock starts (the contract's definition); value_host_inputs = the same K steps with
-            # the reads in pageable host memory (flx_align_reads: H2D, reverse complements, 2-bit form and Peq planes inside the clock) -
-            # what floxer's own stopwatch spans (floxer.cpp:154-179) minus file parsing
-            "value_host_inputs": None if host_elapsed is None else round(total_reads / host_elapsed, 2),
-            "ms_per_step_host_inputs": None if host_elapsed is None else round(host_elapsed / args.steps * 1e3, 3),
-            "repeat_rich": repeat_rich_line,
             "path": {k: int(v) for k, v in path.items()} if path else None,
-            "kernels": table(stats), "kernels_isolated": table(iso_stats),
         }
+        if args.full:
+            line.update({
+                "roofline": roofline, "roofline_fm_search": roofline_fm, "roofline_timed_region": roofline_timed, "cpu_baseline": cpu,
+                "parity_sample": parity,
+                # `value` = inputs resident in HBM when the clock starts (the contract's definition); value_host_inputs = the same K steps
+                # with the reads in pageable host memory (flx_align_reads: H2D, reverse complements, 2-bit form and Peq planes inside the
+                # clock) - what floxer's own stopwatch spans (floxer.cpp:154-179) minus file parsing
+                "value_host_inputs": None if host_elapsed is None else round(total_reads / host_elapsed, 2),
+                "ms_per_step_host_inputs": None if host_elapsed is None else round(host_elapsed / args.steps * 1e3, 3),
+                "repeat_rich": repeat_rich_line,
+                "kernels": table(stats), "kernels_isolated": table(iso_stats),
+            })
         print(json.dumps(line), flush=True)
         if parity is not None and not parity["equal"]:
             print(f"bench.py: the product's records differ from the oracle's on the parity sample: {parity}", file=sys.stderr, flush=True)
