@@ -8,6 +8,7 @@ libfloxer_amd.so:
     searcher(ctx, config).search_seeds()   search::searcher         (search.hpp:104-112)
     align(reference, query, config)        alignment::align         (alignment.hpp:73-77), batched as align_batch
     aligner(ctx, params).align_reads()     spawn_search_task + query_verifier::verify + write_alignments_for_query
+    output_options(...), select_records()  not floxer's: duplicate alignments dropped / alignments per read capped (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -204,7 +205,9 @@ class context:
         check(lib().flx_ctx_get_path_counters(self.h, C.byref(pc)))
         if reset:
             check(lib().flx_ctx_reset_path_counters(self.h))
-        return {n: int(getattr(pc, n)) for n, _ in capi.PathCounters._fields_ if n != "reserved"}
+        out = {n: int(getattr(pc, n)) for n, _ in capi.PathCounters._fields_ if n != "reserved"}
+        out["records_dropped"] = int(pc.reserved[0])          # records that output options left out (records: those written)
+        return out
 
     def kernel_stats(self):
         arr = (capi.KernelStat * 32)()
@@ -375,6 +378,32 @@ class RunResult:
         return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), cigar_string(self.cigars[r[5]: r[5] + r[6]])) for r in self.rows]
 
 
+def output_options(drop_duplicates=False, max_alignments=0):
+    """flx_output_options (include/floxer_amd.h); not floxer's options, both off by default (then the records are floxer's):
+    drop_duplicates: of a read's records with equal reference, strand, start, NM and CIGAR only the first is written;
+    max_alignments: N > 0 writes the N records of a read with the smallest (NM, index), in output order (1: the primary only)."""
+    if max_alignments < 0:
+        raise FloxerError("max_alignments must be >= 0 (0: no cap)")
+    return capi.OutputOptions(int(bool(drop_duplicates)), 0, int(max_alignments))
+
+
+_REC_DTYPE = np.dtype([("read", "<u8"), ("flag", "<u4"), ("ref", "<i4"), ("pos", "<i4"), ("nm", "<u4"), ("coff", "<u8"),
+                       ("clen", "<u4"), ("res", "<u4")])
+
+
+def select_records(run_result, options):
+    """keep mask (bool array, one entry per record) of flx_select_records: the output options' rule applied to the records of a
+    RunResult, e.g. one made without options"""
+    raw = np.ascontiguousarray(run_result.raw, dtype=_REC_DTYPE)
+    cig = np.ascontiguousarray(run_result.cigars, dtype=np.uint32)
+    if len(cig) == 0:
+        cig = np.zeros(1, np.uint32)
+    keep = np.zeros(max(1, len(raw)), dtype=np.uint8)
+    check(lib().flx_select_records(raw.ctypes.data_as(C.POINTER(capi.Record)), len(raw), ptr(cig, u32p), C.byref(options),
+                                   ptr(keep, u8p)))
+    return keep[: len(raw)].astype(bool)
+
+
 def _pool_and_offsets(reads):
     if isinstance(reads, tuple):
         pool, offs = as_u8(reads[0]), np.ascontiguousarray(reads[1], dtype=np.uint64)
@@ -412,9 +441,7 @@ def _collect_run(run, n):
     try:
         nr = lib().flx_run_num_records(run)
         nc = lib().flx_run_num_cigar_words(run)
-        rec_dtype = np.dtype([("read", "<u8"), ("flag", "<u4"), ("ref", "<i4"), ("pos", "<i4"), ("nm", "<u4"), ("coff", "<u8"),
-                              ("clen", "<u4"), ("res", "<u4")])
-        raw = np.empty(max(1, nr), dtype=rec_dtype)
+        raw = np.empty(max(1, nr), dtype=_REC_DTYPE)
         cig = np.empty(max(1, nc), dtype=np.uint32)
         skipped = np.zeros(max(1, n), dtype=np.uint8)
         check(lib().flx_run_copy(run, raw.ctypes.data_as(C.POINTER(capi.Record)), ptr(cig, u32p), ptr(skipped, u8p)))
@@ -425,15 +452,24 @@ def _collect_run(run, n):
 
 
 class aligner:
-    def __init__(self, ctx, p):
-        self.ctx, self.params = ctx, p
+    def __init__(self, ctx, p, output=None):
+        """output: output_options(...), None: every alignment is written (floxer's output)"""
+        self.ctx, self.params, self.output = ctx, p, output
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
         run = C.c_void_p()
+        opt = C.byref(self.output) if self.output is not None else None
         if isinstance(reads, resident_reads):
-            check(lib().flx_align_reads_resident(self.ctx.h, C.byref(self.params), reads.h, C.byref(run)))
+            if opt is None:
+                check(lib().flx_align_reads_resident(self.ctx.h, C.byref(self.params), reads.h, C.byref(run)))
+            else:
+                check(lib().flx_align_reads_resident_with_options(self.ctx.h, C.byref(self.params), reads.h, opt, C.byref(run)))
             return _collect_run(run, reads.n)
         pool, offs, n = _pool_and_offsets(reads)
-        check(lib().flx_align_reads(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(run)))
+        if opt is None:
+            check(lib().flx_align_reads(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(run)))
+        else:
+            check(lib().flx_align_reads_with_options(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, opt,
+                                                     C.byref(run)))
         return _collect_run(run, n)

@@ -71,6 +71,11 @@ class Record(C.Structure):
                 ("num_errors", C.c_uint32), ("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class OutputOptions(C.Structure):
+    _fields_ = [("drop_duplicates", C.c_uint32), ("reserved", C.c_uint32), ("max_alignments_per_read", C.c_uint64),
+                ("reserved2", C.c_uint64 * 2)]
+
+
 class PathCounters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("seeds", "seeds_with_anchors", "seeds_excluded_by_hard_cap", "seeds_selected_on_host", "anchors",
                                           "cursor_extensions", "inner_tests_requested", "root_alignments_requested",
@@ -95,6 +100,7 @@ EXPORTED = [
     "flx_ctx_reset_path_counters", "flx_stats_create", "flx_stats_free", "flx_stats_merge", "flx_stats_num_queries", "flx_stats_format",
     "flx_ctx_set_stats", "flx_device_count", "flx_index_matches_reference", "flx_sam_set_threads", "flx_index_image_layout",
     "flx_index_image_upload", "flx_index_meta_export", "flx_index_meta_import", "flx_ctx_create_on_image",
+    "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records",
 ]
 
 _lib = None
@@ -180,6 +186,11 @@ def lib():
     L.flx_reads_upload.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64, C.POINTER(C.c_void_p)]
     L.flx_reads_free.argtypes = [C.c_void_p]
     L.flx_align_reads_resident.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_void_p)]
+    L.flx_align_reads_with_options.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(OutputOptions),
+                                               C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_with_options.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(OutputOptions),
+                                                        C.POINTER(C.c_void_p)]
+    L.flx_select_records.argtypes = [C.POINTER(Record), C.c_uint64, u32p, C.POINTER(OutputOptions), u8p]
     L.flx_run_num_records.restype = C.c_uint64
     L.flx_run_num_records.argtypes = [C.c_void_p]
     L.flx_run_num_cigar_words.restype = C.c_uint64

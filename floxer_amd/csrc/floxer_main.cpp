@@ -62,6 +62,8 @@ struct Options {
     bool has_timeout = false;
     std::string stats, stats_input_hint;
     std::string devices;
+    bool drop_duplicate_alignments = false;
+    uint64_t max_alignments = 0;                  // 0: no cap
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; };
@@ -75,6 +77,8 @@ const OptDef OPTS[] = {
     {'x', "timeout", false}, {'S', "stats", false}, {'H', "stats-input-hint", false},
     // not in the reference: the HIP devices to run on ("0", "0-7", "0,2,4", "all"; default: FLX_DEVICES, else device 0)
     {'G', "devices", false},
+    // not in the reference either: output options (flx_output_options); without them every alignment verification found is written
+    {'D', "drop-duplicate-alignments", true}, {'N', "max-alignments", false},
 };
 
 struct CliError { std::string msg; };
@@ -164,6 +168,8 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "timeout") { o.timeout = parse_u64(n, value); o.has_timeout = true; }
         else if (n == "stats") o.stats = value;
         else if (n == "devices") o.devices = value;
+        else if (n == "drop-duplicate-alignments") o.drop_duplicate_alignments = true;
+        else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
             o.stats_input_hint = value;
@@ -566,6 +572,10 @@ int main(int argc, char** argv) {
     p.direct_full_verification = o.direct_full_verification;
     p.without_cigar = o.without_cigar;
     p.num_anchors_per_verification_task = o.num_anchors_per_task;
+    flx_output_options out_opt;
+    memset(&out_opt, 0, sizeof(out_opt));
+    out_opt.drop_duplicates = o.drop_duplicate_alignments;
+    out_opt.max_alignments_per_read = o.max_alignments;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -596,7 +606,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run);
+        f.rc = flx_align_reads_with_options(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &out_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));

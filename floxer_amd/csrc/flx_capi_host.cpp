@@ -6,6 +6,7 @@
 #include <memory>
 
 #include "flx_fm_core.hpp"
+#include "flx_select.hpp"
 
 namespace flx {
 const char* last_error_cstr();
@@ -152,5 +153,27 @@ int flx_index_meta_import(const uint8_t* buf, uint64_t len, flx_index** out) {
     return FLX_OK;
 }
 
+int flx_select_records(const flx_record* records, uint64_t n, const uint32_t* cigar_words, const flx_output_options* options, uint8_t* keep) {
+    if ((n && (!records || !keep))) { set_error("flx_select_records: null argument"); return FLX_ERR_INVALID; }
+    if (!output_options_valid(options)) return FLX_ERR_INVALID;
+    bool const drop = options && options->drop_duplicates;
+    u64 const cap = options ? options->max_alignments_per_read : 0;
+    std::vector<SelectKey> keys;
+    SelectScratch scratch;
+    for (u64 lo = 0; lo < n;) {
+        u64 hi = lo + 1;
+        while (hi < n && records[hi].read_index == records[lo].read_index) ++hi;
+        keys.resize(hi - lo);
+        for (u64 i = lo; i < hi; ++i) {
+            flx_record const& r = records[i];
+            if (r.cigar_length && !cigar_words) { set_error("flx_select_records: records with a CIGAR and no CIGAR words"); return FLX_ERR_INVALID; }
+            keys[i - lo] = SelectKey{(u64)(uint32_t)r.position, r.reference_id, r.flag, r.num_errors, r.cigar_length,
+                                     r.cigar_length ? cigar_words + r.cigar_offset : nullptr};
+        }
+        select_read_records(keys.data(), keys.size(), drop, cap, keep + lo, scratch);
+        lo = hi;
+    }
+    return FLX_OK;
+}
 
 }  // extern "C"

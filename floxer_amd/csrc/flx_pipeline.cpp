@@ -18,6 +18,7 @@
 
 #include "flx_context.hpp"
 #include "flx_fm_core.hpp"
+#include "flx_select.hpp"
 #include "flx_stats.hpp"
 
 namespace flx {
@@ -1839,10 +1840,15 @@ extern "C" void flx_reads_free(flx_reads* reads) {
 
 extern "C" int flx_align_reads(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets,
                                uint64_t n_reads, flx_run** out) {
+    return flx_align_reads_with_options(ctx, P, read_pool, read_offsets, n_reads, nullptr, out);
+}
+extern "C" int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets,
+                                            uint64_t n_reads, const flx_output_options* O, flx_run** out) {
+    if (!output_options_valid(O)) return FLX_ERR_INVALID;
     flx_reads* rd = nullptr;
     int rc = flx_reads_upload(ctx, read_pool, read_offsets, n_reads, &rd);
     if (rc) return rc;
-    rc = flx_align_reads_resident(ctx, P, rd, out);
+    rc = flx_align_reads_resident_with_options(ctx, P, rd, O, out);
     flx_reads_free(rd);
     return rc;
 }
@@ -1850,7 +1856,7 @@ extern "C" int flx_align_reads(flx_ctx* ctx, const flx_params* P, const uint8_t*
 namespace {
 
 // one contiguous slice of the batch on one lane; produces the slice's records (read_index relative to the whole batch)
-int align_slice(Lane* lane, const flx_params* P, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run) {
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run) {
     flx_ctx* ctx = lane->ctx;
     FLX_HIP(hipSetDevice(ctx->device));
     HostIndex const& H = *ctx->hidx;
@@ -2429,7 +2435,14 @@ int align_slice(Lane* lane, const flx_params* P, const flx_reads* RD, u64 first_
     // ---- records (alignment.cpp:37-79, output.cpp:49-108): per reference in id order, alignments in verification order
     hvec<hvec<u32>> roots_of_read(reads.size());
     for (u32 i = 0; i < root_anchor.size(); ++i) roots_of_read[A[root_anchor[i]].read].push_back(i);   // already in verification order
+    // output options (flx_select.hpp): a read's records are selected once they are formed and its statistics are taken
+    bool const select = output_options_active(O);
+    u64 n_dropped = 0;
+    std::vector<SelectKey> sel_keys;
+    std::vector<u8> sel_keep;
+    SelectScratch sel_scratch;
     for (size_t r = 0; r < reads.size(); ++r) {
+        size_t const rec0 = run->records.size();
         bool have_best = false;
         u32 best = 0;
         for (u32 i : roots_of_read[r]) if (root_res[i].exists && (!have_best || root_res[i].nm < best)) { best = root_res[i].nm; have_best = true; }
@@ -2446,6 +2459,25 @@ int align_slice(Lane* lane, const flx_params* P, const flx_reads* RD, u64 first_
                                                   root_res[i].cigar_off, root_res[i].cigar_len, 0});
             }
         if (!primary_written) run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
+        if (select && run->records.size() - rec0 > 1) {
+            // (records in the loop's order: the read's mapped roots by reference, the start key unsaturated)
+            size_t const n = run->records.size() - rec0;
+            sel_keys.clear();
+            for (u32 ref = 0; ref < H.seq_len.size(); ++ref)
+                for (u32 i : roots_of_read[r]) {
+                    if (A[root_anchor[i]].ref_id != ref || !root_res[i].exists) continue;
+                    flx_record const& rec = run->records[rec0 + sel_keys.size()];
+                    sel_keys.push_back(SelectKey{root_res[i].start, rec.reference_id, rec.flag, rec.num_errors, rec.cigar_length,
+                                                 rec.cigar_length ? cig.data() + rec.cigar_offset : nullptr});
+                }
+            sel_keep.resize(n);
+            select_read_records(sel_keys.data(), n, O->drop_duplicates != 0, O->max_alignments_per_read, sel_keep.data(), sel_scratch);
+            size_t w = rec0;
+            for (size_t j = 0; j < n; ++j)
+                if (sel_keep[j]) run->records[w++] = run->records[rec0 + j];
+            n_dropped += run->records.size() - w;
+            run->records.resize(w);
+        }
         if (st_local) {                                                                                  // parallelization.cpp:262-268
             u64 n_al = 0;
             for (u32 i : roots_of_read[r]) if (root_res[i].exists) { ++n_al; st_local->at(Stats::EDIT_DISTANCE).add(root_res[i].nm); }
@@ -2457,6 +2489,30 @@ int align_slice(Lane* lane, const flx_params* P, const flx_reads* RD, u64 first_
         for (size_t r = 0; r < reads.size(); ++r) st_local->at(Stats::MS_VERIFICATION).add((u64)((total_ms - search_ms) / (double)std::max<size_t>(1, reads.size())));
         stats_merge_locked(ctx->read_stats, *st_local);
     }
+    if (select) {
+        // the CIGAR words of the kept records only: records that shared (or overlapped in) words before share them afterwards
+        hvec<u32> order;
+        for (u32 j = 0; j < run->records.size(); ++j) {
+            if (run->records[j].cigar_length) order.push_back(j);
+            else run->records[j].cigar_offset = 0;
+        }
+        std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return run->records[a].cigar_offset < run->records[b].cigar_offset; });
+        hvec<u32> kept_words;
+        u64 seg_start = 0, seg_end = 0, seg_base = 0;
+        for (u32 j : order) {
+            flx_record& rec = run->records[j];
+            u64 const off = rec.cigar_offset, end = off + rec.cigar_length;
+            if (kept_words.empty() || off >= seg_end) {
+                seg_start = off; seg_end = end; seg_base = kept_words.size();
+                kept_words.insert(kept_words.end(), cig.begin() + (long)off, cig.begin() + (long)end);
+            } else if (end > seg_end) {
+                kept_words.insert(kept_words.end(), cig.begin() + (long)seg_end, cig.begin() + (long)end);
+                seg_end = end;
+            }
+            rec.cigar_offset = seg_base + (off - seg_start);
+        }
+        cig.swap(kept_words);
+    }
     run->cigars = std::move(cig);
     {
         u64 found = 0;
@@ -2464,7 +2520,7 @@ int align_slice(Lane* lane, const flx_params* P, const flx_reads* RD, u64 first_
         std::lock_guard<std::mutex> g(ctx->mu);
         flx_path_counters& pc = ctx->path;
         pc.inner_tests_requested += n_inner_requested; pc.root_alignments_requested += root_reqs.size(); pc.root_alignments_found += found;
-        pc.records += run->records.size(); pc.reads += end_read - first_read;
+        pc.records += run->records.size(); pc.reads += end_read - first_read; pc.reserved[0] += n_dropped;
     }
     prof.mark("records");
     return FLX_OK;
@@ -2473,6 +2529,11 @@ int align_slice(Lane* lane, const flx_params* P, const flx_reads* RD, u64 first_
 }  // namespace
 
 extern "C" int flx_align_reads_resident(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, flx_run** out) {
+    return flx_align_reads_resident_with_options(ctx, P, RD, nullptr, out);
+}
+extern "C" int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_output_options* O,
+                                                     flx_run** out) {
+    if (!output_options_valid(O)) return FLX_ERR_INVALID;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
@@ -2542,7 +2603,7 @@ extern "C" int flx_align_reads_resident(flx_ctx* ctx, const flx_params* P, const
             u64 const a = chunk_first[c], b = chunk_first[c + 1];
             parts[c].skipped.assign(n_reads, 0);
             LaneLease lease(ctx, ctx->external_stream ? 0 : -1);      // waits while other calls on this context hold all lanes
-            rcs[c] = align_slice(lease.lane, P, RD, a, b, &parts[c]);
+            rcs[c] = align_slice(lease.lane, P, O, RD, a, b, &parts[c]);
             if (rcs[c]) { errs[c] = flx_last_error(); failed.store(true); }
             else { lease.lane->has_run = true; if (!ctx->external_stream) ctx->warm_one_cold_lane(lease.lane); }
         }

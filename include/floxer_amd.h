@@ -216,6 +216,34 @@ typedef struct flx_reads flx_reads;
 int flx_reads_upload(flx_ctx* ctx, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads, flx_reads** out);
 void flx_reads_free(flx_reads* reads);
 int flx_align_reads_resident(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, flx_run** out);
+
+/* Output options: not floxer's, which writes every alignment verification found (alignment.cpp:39-46, output.cpp:48). Both are off
+ * when the struct is zeroed, and with both off the records are floxer's, byte for byte. Applied per read to its records in output
+ * order (per reference id ascending, verification order within a reference):
+ *   drop_duplicates != 0: of the mapped records with equal reference id, strand (flag bit 16), start, NM and CIGAR words (compared
+ *     word by word) only the first is kept: floxer's alignment operator== (alignment.cpp:20-34) plus the reference id;
+ *   max_alignments_per_read = N > 0: of the mapped records left, the N with the smallest (NM, index in output order) are kept and
+ *     written in their original order; N = 1 keeps exactly the primary.
+ * Kept records are unchanged (no flag is rewritten); the unmapped record of a read without alignments is always kept. --stats and
+ * flx_path_counters.root_alignments_found still describe what verification found; flx_path_counters.records counts records written
+ * and reserved[0] the records dropped. The reserved fields must be 0. */
+typedef struct flx_output_options {
+    uint32_t drop_duplicates;
+    uint32_t reserved;
+    uint64_t max_alignments_per_read;    /* 0: no cap */
+    uint64_t reserved2[2];
+} flx_output_options;
+/* flx_align_reads / flx_align_reads_resident with output options (NULL: none, the same as the calls without them) */
+int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets,
+                                 uint64_t n_reads, const flx_output_options* options, flx_run** out);
+int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_params* params, const flx_reads* reads,
+                                          const flx_output_options* options, flx_run** out);
+/* The same rule on any record array (host only): the records of a read are contiguous and in output order, as in every flx_run.
+ * keep[i] = 1 when record i is kept, else 0. Starts compare by `position` (the pipeline compares the unsaturated start; the two
+ * differ only for sequences of 2^31 symbols or more). cigar_words may be NULL when no record has a CIGAR. */
+int flx_select_records(const flx_record* records, uint64_t n, const uint32_t* cigar_words, const flx_output_options* options,
+                       uint8_t* keep);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -240,7 +268,7 @@ typedef struct flx_path_counters {
     uint64_t seeds, seeds_with_anchors, seeds_excluded_by_hard_cap, seeds_selected_on_host, anchors, cursor_extensions;
     uint64_t inner_tests_requested, root_alignments_requested, root_alignments_found, records, reads;
     uint64_t search_reruns;      /* search launches repeated because a chunk's hits or queued subtrees outgrew their buffers */
-    uint64_t reserved[4];
+    uint64_t reserved[4];        /* reserved[0]: records_dropped, the records flx_output_options left out (records counts those written) */
 } flx_path_counters;
 int flx_ctx_get_path_counters(flx_ctx* ctx, flx_path_counters* out);
 int flx_ctx_reset_path_counters(flx_ctx* ctx);
