@@ -1739,17 +1739,13 @@ static AlignShape choose_align_shape_uncached(u32 n, u32 m, u32 k, bool band, bo
             // (A cost by instructions issued, r * (35 + 25 w), which prefers four words per lane over one at the same w * r, made
             // the existence tests a third slower: more distinct shapes per round = more launches, and fewer resident waves per CU
             // with the larger LDS tables; measured in round 2, gpurun_out r02u.)
-            // (FLX_SHAPE_MODEL=a,b: throughput form by instructions issued instead, r * (a + b * w): per column a lane pays `a` whatever its
-            // words and `b` per word)
             // Round 4, rings that wait: cost = the block-steps the job's lanes sit through, lanes x steps x words - what the launch issues for
             // the job whether a lane has a block to compute or not - among the shapes whose schedule is at most `stretch` percent of the one round 3 chose
-            static int const model_a = [] { const char* e = getenv("FLX_SHAPE_MODEL"); int a = 0, b = 0; return e && sscanf(e, "%d,%d", &a, &b) == 2 ? a : 0; }();
-            static int const model_b = [] { const char* e = getenv("FLX_SHAPE_MODEL"); int a = 0, b = 0; return e && sscanf(e, "%d,%d", &a, &b) == 2 ? b : 0; }();
             u64 cost;
             if (may_wait) {
                 if (steps * 100 > shortest * (u64)stretch) continue;
                 cost = steps * r * (8 * w + 1);
-            } else cost = parallel ? (u64)w * 1000 + r : model_b ? (u64)r * (u64)(model_a + model_b * (int)w) * 16 + w : (u64)w * r * 1000 + w;
+            } else cost = parallel ? (u64)w * 1000 + r : (u64)w * r * 1000 + w;
             if (cost < best_cost) { best_cost = cost; best = AlignShape{w, r, band ? 1u : 0u, ring_queue_for(delay)}; }
         }
     return best;

@@ -95,14 +95,14 @@ hipEvent_t Lane::get_event() {
 hvec<DeviceBuffer*> lane_workspaces(Lane& l) {
     return {&l.seq, &l.seq_rev, &l.peq, &l.peq_rev, &l.scheme, &l.seeds, &l.stack, &l.hits, &l.counters, &l.rows, &l.rows_out, &l.jobs,
             &l.job_out, &l.trace, &l.tjobs, &l.tjob_out, &l.cigar, &l.user_text, &l.user_text_rev, &l.lastrow, &l.row_windows, &l.row_out,
-            &l.seed_cnt, &l.hit_off, &l.grouped, &l.sel_stat, &l.sel_n, &l.sel_off, &l.sel_out, &l.sel_tmp, &l.sel_rows, &l.sel_row_off, &l.sel_sparse, &l.sel_lists, &l.vr, &l.lane_rows,
+            &l.seed_cnt, &l.hit_off, &l.grouped, &l.sel_stat, &l.sel_n, &l.sel_off, &l.sel_out, &l.sel_tmp, &l.sel_rows, &l.sel_row_off, &l.sel_sparse, &l.sel_lists, &l.vr,
             &l.qpack, &l.items, &l.seed_gen, &l.mailboxes};
 }
 // FLX_ALLOC_DEBUG: the address ranges of a lane's workspaces (a GPU memory fault reports an address)
 static void dump_lane_buffers(Lane& l, const char* when) {
     static const char* const names[] = {"seq", "seq_rev", "peq", "peq_rev", "scheme", "seeds", "stack", "hits", "counters", "rows", "rows_out", "jobs", "job_out",
         "trace", "tjobs", "tjob_out", "cigar", "user_text", "user_text_rev", "lastrow", "row_windows", "row_out", "seed_cnt", "hit_off", "grouped", "sel_stat",
-        "sel_n", "sel_off", "sel_out", "sel_tmp", "sel_rows", "sel_row_off", "sel_sparse", "sel_lists", "vr", "lane_rows", "qpack", "items", "seed_gen", "mailboxes"};
+        "sel_n", "sel_off", "sel_out", "sel_tmp", "sel_rows", "sel_row_off", "sel_sparse", "sel_lists", "vr", "qpack", "items", "seed_gen", "mailboxes"};
     auto const ws = lane_workspaces(l);
     for (size_t i = 0; i < ws.size(); ++i)
         if (ws[i]->ptr) fprintf(stderr, "[flx alloc] lane %d %s %s %p .. %p\n", l.id, when, names[i], ws[i]->ptr, (void*)((char*)ws[i]->ptr + ws[i]->cap));
@@ -893,24 +893,43 @@ int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
     return FLX_OK;
 }
 
-// FLX_EXISTS_LANES=1: the existence tests through the lane-per-job kernel with Ukkonen's cutoff (flx_lanes.hip) instead of the ring form of
-// flx_device.hip. It computes a ninth of the blocks, and the pipeline runs as fast with either (it is not short of issue slots,
-// profiles/r03_experiments.txt 5-6); alone the ring form is the faster one (40 against 60 ms per 16384 reads: a job's word groups run
-// side by side on its ring, one after the other on its lane), so the ring form is the default.
-static bool exists_lane_form() { return getenv("FLX_EXISTS_LANES") != nullptr; }
-// its waves and the blocks its per-lane rows hold for windows of at most `width` diagonals (n - m + 2k); false: the rows would not fit the LDS
-// lanes a job gets in the lane form (ed_exists_team_kernel): one for small nodes (many jobs, short chains), more for the large ones of
-// which there are few with thousands of blocks each; rows = the smallest node of the launch. FLX_EXISTS_TEAM fixes it.
-static u32 exists_team_size(u64 rows) {
-    if (const char* e = getenv("FLX_EXISTS_TEAM")) { int const fixed = atoi(e); if (fixed > 0) return (u32)fixed; }      // (read per call: tests switch it)
-    u64 const groups = (rows + 63) / 64;
-    return groups >= 48 ? 16u : groups >= 20 ? 8u : groups >= 8 ? 4u : groups >= 4 ? 2u : 1u;
-}
-static bool exists_lane_setup(u64 max_jobs, i64 width, u32& waves, u32& cap_blocks, u32 team = 1) {
-    cap_blocks = (u32)((64 + std::max<i64>(width, 0)) / 16 + 3) | 1u;                   // (odd: the lanes' rows start in different banks)
-    static u32 const max_waves = [] { const char* e = getenv("FLX_EXISTS_LANE_WAVES"); return (u32)(e ? std::max(1, atoi(e)) : 4096); }();
-    waves = (u32)std::max<u64>(std::min<u64>(max_waves, (max_jobs * team + 63) / 64), 1);
-    return DeviceApi::exists_lane_lds_bytes(cap_blocks) <= 150 * 1024;
+// K3 / K4 over the requests [begin, end) of one call: one launch per shape class, the classes in ShapeKey order, the jobs of a class in
+// request order (TRACE launches: widest window first, equal widths in request order). A job writes to out_index = its request - begin.
+// per_job(request, job) sets what the caller's form adds to the job (trace arena and last-row offsets: it is called in job order) and
+// returns the bytes the job moves beyond its n + m sequence symbols (the launch's accounting).
+struct ShapeLaunch { ShapeKey key; u32 first, count; u64 word_steps, bytes; };
+template <class PerJob>
+int launch_by_shape(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<AlignShape> const& shapes, size_t begin, size_t end,
+                    const char* kernel_name, const char* what, bool trace, u16* d_lastrow, PerJob&& per_job) {
+    std::map<ShapeKey, hvec<u32>> by_shape;
+    for (size_t i = begin; i < end; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded}].push_back((u32)i);
+    hvec<DevAlignJob> jobs;
+    jobs.reserve(end - begin);
+    hvec<ShapeLaunch> launches;
+    for (auto& kv : by_shape) {
+        auto& ids = kv.second;
+        if (trace) std::stable_sort(ids.begin(), ids.end(), [&](u32 a, u32 b) { return reqs[a].n > reqs[b].n; });
+        ShapeLaunch l{kv.first, (u32)jobs.size(), (u32)ids.size(), 0, 0};
+        for (u32 id : ids) {
+            AlignRequest const& r = reqs[id];
+            jobs.push_back(DevAlignJob{r.ref_off, r.q_off, 0, r.n, r.m, r.k, (u32)(id - begin), 0});
+            l.word_steps += job_word_steps(r.n, r.m, r.k, shapes[id]);
+            l.bytes += (u64)r.n + r.m + per_job(id, jobs.back());
+        }
+        launches.push_back(l);
+    }
+    int rc;
+    if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
+    if ((rc = ctx->job_out.ensure((end - begin) * sizeof(DevAlignOut)))) return rc;
+    for (auto const& l : launches) {
+        if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[%s]%s W %u R %u banded %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", kernel_name, what, l.key.w, l.key.g, l.key.banded, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
+        rc = timed_launch(ctx, kernel_name, l.bytes, l.word_steps, [&] {
+            return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count, AlignShape{l.key.w, l.key.g, l.key.banded}, trace,
+                                    trace ? ctx->trace.as<u64>() : nullptr, ctx->job_out.as<DevAlignOut>(), d_lastrow);
+        });
+        if (rc) return rc;
+    }
+    return FLX_OK;
 }
 
 // score + end column for every (distinct) request (no trace)
@@ -919,84 +938,11 @@ int run_score_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
     outs.assign(reqs.size(), DevAlignOut{0xFFFFFFFFu, 0});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer jprof("score-jobs");
-    i64 lane_width = 0;
-    for (auto const& r : reqs) lane_width = std::max<i64>(lane_width, (i64)r.n - (i64)r.m + 2 * (i64)r.k);
-    u32 waves = 0, cap_blocks = 0;
-    u64 rows_min = ~0ull;
-    for (auto const& r : reqs) rows_min = std::min<u64>(rows_min, r.m);
-    u32 const team = exists_team_size(rows_min);
-    if (exists_lane_form() && choose_align_shape(reqs[0].n, reqs[0].m, reqs[0].k).banded && exists_lane_setup(reqs.size(), lane_width, waves, cap_blocks, team)) {
-        // one launch for every shape: a lane per job
-        hvec<DevAlignJob> jobs(reqs.size());
-        u64 steps = 0, bytes = 0;
-        for (u32 i = 0; i < reqs.size(); ++i) {
-            AlignRequest const& r = reqs[i];
-            if (r.m > align_supported_max_query()) { set_error("query longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
-            jobs[i] = DevAlignJob{r.ref_off, r.q_off, 0, r.n, r.m, r.k, i, 0};
-            steps += job_word_steps(r.n, r.m, r.k, AlignShape{1, 1, 1});
-            bytes += (u64)r.n + r.m;
-        }
-        int rc;
-        if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
-        if ((rc = ctx->job_out.ensure(reqs.size() * sizeof(DevAlignOut)))) return rc;
-        if ((rc = ctx->counters.ensure(128))) return rc;
-        FLX_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 128, ctx->stream));
-        rc = timed_launch(ctx, kernel_name, bytes, steps, [&] {
-            return DeviceApi::align_exists_lanes(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>(), (u32)jobs.size(), nullptr, ctx->counters.as<u32>(),
-                                                 waves, cap_blocks, ctx->job_out.as<DevAlignOut>(),
-                                                 getenv("FLX_ALIGN_DEBUG") ? (unsigned long long*)((char*)ctx->counters.ptr + 64) : nullptr, team);
-        });
-        if (rc) return rc;
-        u32 cnt[32];
-        if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, reqs.size() * sizeof(DevAlignOut)))) return rc;
-        if ((rc = d2h(ctx, cnt, ctx->counters.ptr, 128))) return rc;
-        jprof.mark("launch");
-        rc = ctx->sync();
-        jprof.mark("wait");
-        if (rc) return rc;
-        if (cnt[1]) { set_error("existence tests: a window did not fit the row buffers"); return FLX_ERR_INTERNAL; }
-        if (getenv("FLX_ALIGN_DEBUG")) {
-            unsigned long long st[8];
-            memcpy(st, (char*)cnt + 64, sizeof(st));
-            fprintf(stderr, "[%s lanes] jobs %zu waves %u cap %u: blocks %llu, wave iterations %llu, lane iterations %llu, groups %llu\n", kernel_name, jobs.size(), waves, cap_blocks, st[0], st[1], st[2], st[3]);
-        }
-        return FLX_OK;
-    }
-    std::map<ShapeKey, hvec<u32>> by_shape;
-    {
-        hvec<AlignShape> shapes;
-        if (int const rc = choose_shapes(reqs, shapes)) return rc;
-        jprof.mark("shapes");
-        for (u32 i = 0; i < reqs.size(); ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded}].push_back(i);
-    }
-    jprof.mark("by-shape");
-    hvec<DevAlignJob> jobs;
-    jobs.reserve(reqs.size());
-    struct Launch { ShapeKey key; u32 first, count; u64 word_steps, bytes; };
-    hvec<Launch> launches;
-    for (auto& kv : by_shape) {
-        auto& ids = kv.second;
-        Launch l{kv.first, (u32)jobs.size(), (u32)ids.size(), 0, 0};
-        for (u32 id : ids) {
-            AlignRequest const& r = reqs[id];
-            jobs.push_back(DevAlignJob{r.ref_off, r.q_off, 0, r.n, r.m, r.k, id, 0});
-            l.word_steps += job_word_steps(r.n, r.m, r.k, AlignShape{kv.first.w, kv.first.g, kv.first.banded});
-            l.bytes += (u64)r.n + r.m;
-        }
-        launches.push_back(l);
-    }
-    jprof.mark("job-list");
+    hvec<AlignShape> shapes;
     int rc;
-    if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
-    if ((rc = ctx->job_out.ensure(reqs.size() * sizeof(DevAlignOut)))) return rc;
-    for (auto const& l : launches) {
-        if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[%s] W %u R %u banded %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", kernel_name, l.key.w, l.key.g, l.key.banded, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
-        rc = timed_launch(ctx, kernel_name, l.bytes, l.word_steps, [&] {
-            return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count,
-                                    AlignShape{l.key.w, l.key.g, l.key.banded}, false, nullptr, ctx->job_out.as<DevAlignOut>());
-        });
-        if (rc) return rc;
-    }
+    if ((rc = choose_shapes(reqs, shapes))) return rc;
+    jprof.mark("shapes");
+    if ((rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, 0, reqs.size(), kernel_name, "", false, nullptr, [](u32, DevAlignJob&) { return (u64)0; }))) return rc;
     if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, reqs.size() * sizeof(DevAlignOut)))) return rc;
     jprof.mark("launch");
     rc = ctx->sync();
@@ -1238,43 +1184,22 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u8* d_query, const u
         if ((rc = ctx->trace.ensure(std::max<size_t>(used * 16 + 64, ctx->trace.ptr ? 0 : std::min<size_t>(ctx->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2)))) return rc;
 
         // ---- K4 over the unions of this arena chunk, with their last rows
-        std::map<ShapeKey, hvec<u32>> by_shape;
-        for (size_t i = begin; i < next; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded}].push_back((u32)i);
-        hvec<DevAlignJob> jobs;
         hvec<u64> trace_off(count), row_off(count);
-        struct Launch { ShapeKey key; u32 first, count; u64 word_steps, bytes; };
-        hvec<Launch> launches;
         u64 off = 0, rows = 0;
-        for (auto& kv : by_shape) {
-            auto& ids = kv.second;
-            std::stable_sort(ids.begin(), ids.end(), [&](u32 a, u32 b) { return ureqs[a].n > ureqs[b].n; });
-            Launch l{kv.first, (u32)jobs.size(), (u32)ids.size(), 0, 0};
-            for (u32 id : ids) {
-                AlignRequest const& r = ureqs[id];
-                trace_off[id - begin] = off;
-                row_off[id - begin] = rows;
-                jobs.push_back(DevAlignJob{r.ref_off, r.q_off, off, r.n, r.m, r.k, (u32)(id - begin), rows});
-                off += slots[id];
-                rows += ((u64)r.n + 15) / 16 * 16;   // K4 stores a block's 16 last-row values as two 16-byte words
-                l.word_steps += job_word_steps(r.n, r.m, r.k, shapes[id]);
-                TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
-                l.bytes += (u64)r.n + r.m + (tl.carry_slots + tl.ckpt_slots) * 16 + 2ull * r.n;
-            }
-            launches.push_back(l);
-        }
-        if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
-        if ((rc = ctx->job_out.ensure(count * sizeof(DevAlignOut)))) return rc;
+        for (size_t i = begin; i < next; ++i) rows += ((u64)ureqs[i].n + 15) / 16 * 16;      // K4 stores a block's 16 last-row values as two 16-byte words
         if ((rc = ctx->lastrow.ensure(rows * 2 + 64))) return rc;
         FLX_HIP(hipMemsetAsync(ctx->lastrow.ptr, 0xFF, rows * 2, ctx->stream));
-        for (auto const& l : launches) {
-            if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[ed_align_trace] unions W %u R %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", l.key.w, l.key.g, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
-            rc = timed_launch(ctx, "ed_align_trace", l.bytes, l.word_steps, [&] {
-                return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count,
-                                        AlignShape{l.key.w, l.key.g, l.key.banded}, true, ctx->trace.as<u64>(), ctx->job_out.as<DevAlignOut>(),
-                                        ctx->lastrow.as<u16>());
-            });
-            if (rc) return rc;
-        }
+        rows = 0;
+        rc = launch_by_shape(ctx, d_text, d_peq, ureqs, shapes, begin, next, "ed_align_trace", " unions", true, ctx->lastrow.as<u16>(), [&](u32 id, DevAlignJob& job) {
+            AlignRequest const& r = ureqs[id];
+            job.trace_off = trace_off[id - begin] = off;
+            job.lastrow_off = row_off[id - begin] = rows;
+            off += slots[id];
+            rows += ((u64)r.n + 15) / 16 * 16;
+            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
+            return (tl.carry_slots + tl.ckpt_slots) * 16 + 2ull * r.n;
+        });
+        if (rc) return rc;
         // ---- every member's rightmost minimum over its own columns
         hvec<DevRowWindow> wins;
         hvec<u32> win_member;                // uniq index per window
@@ -1393,44 +1318,18 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u8* d_query, const 
         // the arena is taken whole on first use (its size is the configured budget): no reallocation between batches
         if ((rc = ctx->trace.ensure(std::max<size_t>(used * 16 + 64, ctx->trace.ptr ? 0 : std::min<size_t>(ctx->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2)))) return rc;
 
-        std::map<ShapeKey, hvec<u32>> by_shape;
-        for (size_t i = begin; i < next; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded}].push_back((u32)i);
-        hvec<DevAlignJob> jobs;
         hvec<u64> trace_off(count);
-        struct Launch { ShapeKey key; u32 first, count; u64 word_steps, bytes; };
-        hvec<Launch> launches;
         u64 off = 0;
-        for (auto& kv : by_shape) {
-            auto& ids = kv.second;
-            std::stable_sort(ids.begin(), ids.end(), [&](u32 a, u32 b) { return reqs[a].n > reqs[b].n; });
-            Launch l{kv.first, (u32)jobs.size(), (u32)ids.size(), 0, 0};
-            for (u32 id : ids) {
-                AlignRequest const& r = reqs[id];
-                trace_off[id - begin] = off;
-                jobs.push_back(DevAlignJob{r.ref_off, r.q_off, off, r.n, r.m, r.k, (u32)(id - begin), 0});
-                off += slots[id];
-                u64 const ws = job_word_steps(r.n, r.m, r.k, shapes[id]);
-                l.word_steps += ws;
-                // reference + query symbols read; trace written: full form 16 B per word-step, checkpointed form its carry and
-                // checkpoint regions
-                if (shapes[id].banded) {
-                    TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
-                    l.bytes += (u64)r.n + r.m + (tl.carry_slots + tl.ckpt_slots) * 16;
-                } else l.bytes += (u64)r.n + r.m + ws * 16;
-            }
-            launches.push_back(l);
-        }
-        tprof.mark("prep");
-        if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
-        if ((rc = ctx->job_out.ensure(count * sizeof(DevAlignOut)))) return rc;
-        for (auto const& l : launches) {
-            if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[ed_align_trace] W %u R %u banded %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", l.key.w, l.key.g, l.key.banded, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
-            rc = timed_launch(ctx, "ed_align_trace", l.bytes, l.word_steps, [&] {
-                return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count,
-                                        AlignShape{l.key.w, l.key.g, l.key.banded}, true, ctx->trace.as<u64>(), ctx->job_out.as<DevAlignOut>());
-            });
-            if (rc) return rc;
-        }
+        // (bytes: reference + query symbols read; trace written: full form 16 B per word-step, checkpointed form its carry and checkpoint regions)
+        rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, begin, next, "ed_align_trace", "", true, nullptr, [&](u32 id, DevAlignJob& job) {
+            AlignRequest const& r = reqs[id];
+            job.trace_off = trace_off[id - begin] = off;
+            off += slots[id];
+            if (!shapes[id].banded) return job_word_steps(r.n, r.m, r.k, shapes[id]) * 16;
+            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
+            return (tl.carry_slots + tl.ckpt_slots) * 16;
+        });
+        if (rc) return rc;
         hvec<DevAlignOut> outs(count);
         if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, count * sizeof(DevAlignOut)))) return rc;
         if ((rc = ctx->sync())) return rc;
@@ -2145,83 +2044,7 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
         vprof.mark("upload");
         u64 const few_waves = align_few_waves();
         u64 prev_jobs = n_climbing / 2, acc_steps = 0, acc_bytes = 0, acc_req = 0;
-        unsigned long long* lane_stats = nullptr;               // FLX_ALIGN_DEBUG: the lane-per-job kernel's counters, per round
-        if (getenv("FLX_ALIGN_DEBUG")) {
-            if ((rc = lane->counters.ensure(128))) return rc;
-            lane_stats = (unsigned long long*)((char*)lane->counters.ptr + 64);
-        }
-        // ---- The rounds whose size classes are known in advance (lane-per-job existence kernel: no launch shape to choose from the last
-        //      round's job count) are queued back to back, two per class (the members of a union window without an alignment are tested
-        //      alone in the round after it): a round reads what the round before it left on the device, one that finds nothing to ask for
-        //      returns at once, and the host waits once, behind the last. What is still climbing then goes through the loop below.
-        u32 round = 0;
-        if (exists_lane_form() && !lane_stats && getenv("FLX_ROUNDS_QUEUED") && n_climbing > 0) {      // (measured: 130-136 k reads/s queued, 135-142 k with a wait per round)
-            struct RoundClass { u64 limit; u32 nw_max; i64 width_max; };
-            hvec<RoundClass> plan;
-            {
-                hvec<std::pair<u32, u32>> sizes;                       // (rows, errors) of every inner node below a root
-                for (auto const& nd : nodes) if (nd.parent != 0xFFFFFFFFu) sizes.emplace_back(nd.rows, nd.errors);
-                std::sort(sizes.begin(), sizes.end());
-                size_t i = 0;
-                while (i < sizes.size() && sizes[i].first < smallest) ++i;
-                while (i < sizes.size()) {
-                    RoundClass c{(u64)sizes[i].first * round_span_percent() / 100, 0, 0};
-                    for (; i < sizes.size() && sizes[i].first <= c.limit; ++i) {
-                        c.nw_max = std::max(c.nw_max, (sizes[i].first + 63u) / 64u);
-                        c.width_max = std::max<i64>(c.width_max, 4 * (i64)sizes[i].second + 1);
-                    }
-                    plan.push_back(c);
-                    plan.push_back(c);
-                }
-            }
-            bool queued = !plan.empty();
-            u32 const max_jobs = (u32)std::min<u64>(2ull * n_climbing, 2ull * n);
-            for (size_t r = 0; queued && r < plan.size(); ++r) {
-                RoundClass const& c = plan[r];
-                AlignShape const shape = DeviceApi::shape_holding(c.nw_max, c.width_max, false);
-                u32 lane_waves = 0, lane_cap = 0;
-                u64 const cap = shape.words_per_lane == 0 ? 0 : DeviceApi::shape_width_cap(c.nw_max, shape);
-                u64 const width_cap = std::min<u64>(cap, std::max<u64>(8 * (u64)c.width_max, 1024));
-                if (shape.words_per_lane == 0 || !shape.banded || !exists_lane_setup(max_jobs, (i64)std::max<u64>(width_cap, (u64)c.width_max), lane_waves, lane_cap)) {
-                    queued = false;                                    // (a class the lane form does not take: the loop below from here on)
-                    break;
-                }
-                if (r == 0) FLX_HIP(hipMemsetAsync(B.scalars + VR2_PENDING, 1, 4, lane->stream));      // (non-zero: the first queued round always runs)
-                int const e1 = DeviceApi::vr2_request(lane->stream, B, n_queries, (u32)std::min<u64>(c.limit, 0xFFFFFFFFu), shape.words_per_lane,
-                                                      (u32)std::min<u64>(width_cap, 0xFFFFFFFFull), round, true);
-                if (e1) { set_error(std::string("verification round: ") + hipGetErrorString((hipError_t)e1)); return FLX_ERR_NO_DEVICE; }
-                rc = timed_launch(lane, "ed_align_exists", 0, 0, [&] {
-                    return DeviceApi::align_exists_lanes(lane->stream, d_text, d_peq, B.jobs, max_jobs, B.scalars + VR2_N_JOBS + (round & 1u), B.scalars + VR2_QUEUE,
-                                                         lane_waves, lane_cap, B.outs, nullptr);
-                });
-                if (rc) return rc;
-                u64 const next_limit = r + 1 < plan.size() ? plan[r + 1].limit : 0xFFFFFFFFull;
-                int const e2 = DeviceApi::vr2_apply(lane->stream, B, n, lane->vr_host_scalars, (u32)std::min<u64>(next_limit, 0xFFFFFFFFu), round);
-                if (e2) { set_error(std::string("verification round: ") + hipGetErrorString((hipError_t)e2)); return FLX_ERR_NO_DEVICE; }
-                ++round;
-            }
-            if (round > 0) {
-                if ((rc = lane->sync())) return rc;
-                u32 sc[VR2_SCALARS];
-                memcpy(sc, lane->vr_host_scalars, sizeof(sc));
-                if (sc[VR2_QUEUE_ERR]) { set_error("existence tests: a window did not fit the row buffers"); return FLX_ERR_INTERNAL; }
-                u64 ws, by;
-                memcpy(&ws, &sc[VR2_WORD_STEPS], 8);
-                memcpy(&by, &sc[VR2_BYTES], 8);
-                if (ctx->timing) {
-                    std::lock_guard<std::mutex> g(ctx->mu);
-                    auto it = ctx->stats.find("ed_align_exists");
-                    if (it != ctx->stats.end()) { it->second.algorithmic_bytes += by; it->second.work_units += ws; }
-                }
-                n_inner_requested += sc[VR2_N_REQ];
-                acc_steps = ws; acc_bytes = by; acc_req = sc[VR2_N_REQ];
-                prev_jobs = sc[VR2_N_JOBS + ((round - 1u) & 1u)];
-                n_climbing = sc[VR2_N_CLIMBING];
-                smallest = sc[VR2_SMALLEST];
-                vprof.mark("round");
-            }
-        }
-        for (; n_climbing > 0; ++round) {
+        for (u32 round = 0; n_climbing > 0; ++round) {
             u64 const limit = (u64)smallest * round_span_percent() / 100;
             // One launch shape for the round: the cheapest that holds the window of every node in the round's size class, or the one
             // with the fewest words per lane when the round has few jobs (they would leave most SIMDs without a wave; the last round's
@@ -2239,21 +2062,12 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
             // what the shape holds beyond that goes to the clusters' union windows (a shape holds a job when every word group has a lane of
             // its own, when the ring's lanes are free again before their next group starts: 64 W (R - 1) + R + 1 > diagonals, or when the
             // steps a revolution of the ring has to wait fit the launch's hand-over slots: flx_internal.hpp, ring_delay)
-            u64 const cap = DeviceApi::shape_width_cap(nw_max, shape);
-            // (the lane-per-job kernel holds any window its row buffers hold: unions up to the ring shape's cap, or eight windows' width)
-            u32 lane_waves = 0, lane_cap = 0;
+            u64 const width_cap = DeviceApi::shape_width_cap(nw_max, shape);
             u32 const max_jobs = (u32)std::min<u64>(2ull * n_climbing, 2ull * n);
-            u64 const lane_width_cap = std::min<u64>(cap, std::max<u64>(8 * (u64)width_max, 1024));
-            u32 const team = exists_team_size(smallest);
-            bool const lane_form = exists_lane_form() && shape.banded && exists_lane_setup(max_jobs, (i64)std::max<u64>(lane_width_cap, (u64)width_max), lane_waves, lane_cap, team);
-            u64 const width_cap = lane_form ? lane_width_cap : cap;
             int const e1 = DeviceApi::vr2_request(lane->stream, B, n_queries, (u32)std::min<u64>(limit, 0xFFFFFFFFu), shape.words_per_lane,
                                                   (u32)std::min<u64>(width_cap, 0xFFFFFFFFull), round);
             if (e1) { set_error(std::string("verification round: ") + hipGetErrorString((hipError_t)e1)); return FLX_ERR_NO_DEVICE; }
             rc = timed_launch(lane, "ed_align_exists", 0, 0, [&] {
-                if (lane_form)
-                    return DeviceApi::align_exists_lanes(lane->stream, d_text, d_peq, B.jobs, max_jobs, B.scalars + VR2_N_JOBS + (round & 1u), B.scalars + VR2_QUEUE,
-                                                         lane_waves, lane_cap, B.outs, lane_stats, team);
                 // (a fixed grid of at most this many waves takes the round's job groups in turn; FLX_EXISTS_MAX_WAVES: how much of the chip one
                 // round's launch may hold while the other lanes' kernels want room)
                 static u32 const exists_waves = [] { const char* e = getenv("FLX_EXISTS_MAX_WAVES"); return (u32)(e ? std::max(64, atoi(e)) : 8192); }();
@@ -2275,18 +2089,10 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
                 if (it != ctx->stats.end()) { it->second.algorithmic_bytes += by - acc_bytes; it->second.work_units += ws - acc_steps; }
             }
             u64 const round_req = sc[VR2_N_REQ] - acc_req;
-            u64 const round_ws = ws - acc_steps;
             acc_steps = ws; acc_bytes = by; acc_req = sc[VR2_N_REQ];
             n_inner_requested += round_req;
             if (round_req == 0 && sc[VR2_N_CLIMBING] >= n_climbing) { set_error("verification rounds do not advance"); return FLX_ERR_INTERNAL; }
             prev_jobs = sc[VR2_N_JOBS + (round & 1u)];
-            if (lane_stats) {
-                unsigned long long st[8];
-                FLX_HIP(hipMemcpy(st, lane_stats, sizeof(st), hipMemcpyDeviceToHost));
-                FLX_HIP(hipMemset(lane_stats, 0, sizeof(st)));
-                fprintf(stderr, "[exists round %u] rows %u..%llu jobs %llu waves %u cap %u: blocks %llu, wave iterations %llu (x64 = %llu), lane iterations %llu, groups %llu; word-steps %llu\n", round, smallest,
-                        (unsigned long long)limit, (unsigned long long)prev_jobs, lane_waves, lane_cap, st[0], st[1], st[1] * 64, st[2], st[3], (unsigned long long)round_ws);
-            }
             n_climbing = sc[VR2_N_CLIMBING];
             smallest = sc[VR2_SMALLEST];
             vprof.mark("round");

@@ -615,10 +615,9 @@ def test_root_unions_and_their_fallback():
 
 def test_existence_kernel_forms_give_the_same_records():
     """the existence tests run as a ring of lanes per job over the static band, 16 columns per step (ed_exists_block_kernel), by default;
-    one column per step with FLX_EXISTS_STEPWISE=1 (ed_band_kernel); one lane per job with Ukkonen's cutoff with FLX_EXISTS_LANES=1
-    (ed_exists_lane_kernel), also with the rounds queued without the host in between (FLX_ROUNDS_QUEUED=1). The switches of the ring forms
-    are read once per process, so the other forms run in children: same records, all equal to the oracle's, on reads whose trees reach
-    every launch shape of the lower levels and the ring-scheduled upper ones"""
+    one column per step with FLX_EXISTS_STEPWISE=1 (ed_band_kernel). The switch is read once per process, so the stepwise form runs in a
+    child: same records, both equal to the oracle's, on reads whose trees reach every launch shape of the lower levels and the
+    ring-scheduled upper ones"""
     import subprocess, sys, json
     genome = S.make_genome(500000, 2, seed=161)
     reads, _, _ = S.make_reads(genome, 24, 6000, 0.08, seed=162)
@@ -630,23 +629,17 @@ def test_existence_kernel_forms_give_the_same_records():
             "g = S.make_genome(500000, 2, seed=161); r, _, _ = S.make_reads(g, 24, 6000, 0.08, seed=162);"
             "c = F.context(F.fmindex(g)); print(json.dumps(F.aligner(c, F.params(error_probability=0.08)).align_reads(r).records()))"
             % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    for env in ({"FLX_EXISTS_STEPWISE": "1"}, {"FLX_EXISTS_LANES": "1"}, {"FLX_EXISTS_LANES": "1", "FLX_ROUNDS_QUEUED": "1"},
-                {"FLX_EXISTS_LANES": "1", "FLX_EXISTS_TEAM": "1"}, {"FLX_EXISTS_LANES": "1", "FLX_EXISTS_TEAM": "8"}):
-        out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, check=True)
-        assert [tuple(r) for r in json.loads(out.stdout.strip().split("\n")[-1])] == exp.records(), env
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, FLX_EXISTS_STEPWISE="1"), capture_output=True, text=True, check=True)
+    assert [tuple(r) for r in json.loads(out.stdout.strip().split("\n")[-1])] == exp.records()
 
 
-@pytest.mark.parametrize("team", [None, "2", "4", "8", "16"])
-def test_existence_with_cutoff_matches_oracle(small_genome, monkeypatch, team):
-    """ed_exists_lane_kernel / ed_exists_team_kernel<P> (FLX_EXISTS_LANES=1; team: P lanes per job, each on every P-th word group one block
-    behind the lane of the group above - also with more lanes than a job has groups) against the oracle's Myers on what the cutoff has to get right: several occurrences in one window (tandem
-    repeats with periods around the group height, a second occurrence far to the right of the first), budgets from 0 to more than the
-    query is long, low-complexity sequence (every diagonal alive), occurrences at either edge of the window, windows shorter than the
-    query, N runs; ragged sizes across word-group boundaries in one launch"""
+def test_existence_ring_form_on_the_hardest_corpus_matches_oracle(small_genome):
+    """the default existence form (ed_exists_block_kernel: a ring of lanes per job over the static band) against the oracle's Myers on
+    the hardest existence jobs of the suite: several occurrences in one window (tandem repeats with periods around the group height, a
+    second occurrence far to the right of the first), budgets from 0 to more than the query is long, low-complexity sequence (every
+    diagonal alive), occurrences at either edge of the window, windows shorter than the query, N runs; ragged sizes across word-group
+    boundaries in one launch"""
     _, _, ctx, _ = small_genome
-    monkeypatch.setenv("FLX_EXISTS_LANES", "1")
-    if team:
-        monkeypatch.setenv("FLX_EXISTS_TEAM", team)
     rng = np.random.default_rng(77)
     refs, queries, jobs = [], [], []
     ro = qo = 0
@@ -704,7 +697,7 @@ def test_existence_with_cutoff_matches_oracle(small_genome, monkeypatch, team):
             n_yes += 1
         assert g == exp, (ql, rl, k)
     assert 0.2 * len(jobs) < n_yes < 0.95 * len(jobs)
-    # the same jobs ask for the end positions too (the cutoff keeps the rightmost minimum of the last row)
+    # the same jobs ask for the end positions too (the rightmost minimum of the last row)
     jobs1 = [j[:5] + (1,) for j in jobs]
     got1 = F.align_batch(ctx, qpool, jobs1, reference_pool=rpool)
     for (ro_, rl, qo_, ql, k, mode), g in zip(jobs1, got1):
