@@ -9,6 +9,7 @@ libfloxer_amd.so:
     align(reference, query, config)        alignment::align         (alignment.hpp:73-77), batched as align_batch
     aligner(ctx, params).align_reads()     spawn_search_task + query_verifier::verify + write_alignments_for_query
     output_options(...), select_records()  not floxer's: duplicate alignments dropped / alignments per read capped (opt-in)
+    output_options(mapq=True), assign_mapq()  not floxer's: mapping quality from a read's distinct loci (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -374,17 +375,24 @@ class RunResult:
                                     raw["clen"].astype(np.int64)], axis=1) if len(raw) else np.zeros((0, 7), dtype=np.int64))
         return self._rows
 
+    @property
+    def mapq(self):
+        """flx_record.reserved of every record: its mapping quality when the run was made with output_options(mapq=True), else 0"""
+        return self.raw["res"].astype(np.int64)
+
     def records(self):
         return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), cigar_string(self.cigars[r[5]: r[5] + r[6]])) for r in self.rows]
 
 
-def output_options(drop_duplicates=False, max_alignments=0):
-    """flx_output_options (include/floxer_amd.h); not floxer's options, both off by default (then the records are floxer's):
+def output_options(drop_duplicates=False, max_alignments=0, mapq=False):
+    """flx_output_options (include/floxer_amd.h); not floxer's options, all off by default (then the records are floxer's):
     drop_duplicates: of a read's records with equal reference, strand, start, NM and CIGAR only the first is written;
-    max_alignments: N > 0 writes the N records of a read with the smallest (NM, index), in output order (1: the primary only)."""
+    max_alignments: N > 0 writes the N records of a read with the smallest (NM, index), in output order (1: the primary only);
+    mapq: every record carries a mapping quality made of the read's distinct loci (RunResult.mapq), computed from all of the read's
+    records before the two options above drop any."""
     if max_alignments < 0:
         raise FloxerError("max_alignments must be >= 0 (0: no cap)")
-    return capi.OutputOptions(int(bool(drop_duplicates)), 0, int(max_alignments))
+    return capi.OutputOptions(int(bool(drop_duplicates)), int(bool(mapq)), int(max_alignments))
 
 
 _REC_DTYPE = np.dtype([("read", "<u8"), ("flag", "<u4"), ("ref", "<i4"), ("pos", "<i4"), ("nm", "<u4"), ("coff", "<u8"),
@@ -402,6 +410,27 @@ def select_records(run_result, options):
     check(lib().flx_select_records(raw.ctypes.data_as(C.POINTER(capi.Record)), len(raw), ptr(cig, u32p), C.byref(options),
                                    ptr(keep, u8p)))
     return keep[: len(raw)].astype(bool)
+
+
+def assign_mapq(run_result, read_lengths=None):
+    """mapping qualities (uint8 array, one entry per record) of flx_assign_mapq: the rule of output_options(mapq=True) applied to the
+    records of a RunResult that holds all records of its reads. read_lengths (one entry per read of the batch): the span of a
+    record without CIGAR; None: spans come from the CIGARs only"""
+    raw = np.ascontiguousarray(run_result.raw, dtype=_REC_DTYPE)
+    cig = np.ascontiguousarray(run_result.cigars, dtype=np.uint32)
+    if len(cig) == 0:
+        cig = np.zeros(1, np.uint32)
+    lens = None
+    if read_lengths is not None:
+        lens = np.ascontiguousarray(read_lengths, dtype=np.uint64)
+        if len(raw) and int(raw["read"].max()) >= len(lens):
+            raise FloxerError("assign_mapq: read_lengths is shorter than the largest read index")
+        if len(lens) == 0:
+            lens = np.zeros(1, np.uint64)
+    out = np.zeros(max(1, len(raw)), dtype=np.uint8)
+    check(lib().flx_assign_mapq(raw.ctypes.data_as(C.POINTER(capi.Record)), len(raw), ptr(cig, u32p),
+                                ptr(lens, u64p) if lens is not None else None, ptr(out, u8p)))
+    return out[: len(raw)]
 
 
 def _pool_and_offsets(reads):

@@ -72,7 +72,7 @@ class Record(C.Structure):
 
 
 class OutputOptions(C.Structure):
-    _fields_ = [("drop_duplicates", C.c_uint32), ("reserved", C.c_uint32), ("max_alignments_per_read", C.c_uint64),
+    _fields_ = [("drop_duplicates", C.c_uint32), ("mapq", C.c_uint32), ("max_alignments_per_read", C.c_uint64),
                 ("reserved2", C.c_uint64 * 2)]
 
 
@@ -100,7 +100,7 @@ EXPORTED = [
     "flx_ctx_reset_path_counters", "flx_stats_create", "flx_stats_free", "flx_stats_merge", "flx_stats_num_queries", "flx_stats_format",
     "flx_ctx_set_stats", "flx_device_count", "flx_index_matches_reference", "flx_sam_set_threads", "flx_index_image_layout",
     "flx_index_image_upload", "flx_index_meta_export", "flx_index_meta_import", "flx_ctx_create_on_image",
-    "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records",
+    "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records", "flx_assign_mapq", "flx_sam_set_mapq",
 ]
 
 _lib = None
@@ -191,6 +191,7 @@ def lib():
     L.flx_align_reads_resident_with_options.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(OutputOptions),
                                                         C.POINTER(C.c_void_p)]
     L.flx_select_records.argtypes = [C.POINTER(Record), C.c_uint64, u32p, C.POINTER(OutputOptions), u8p]
+    L.flx_assign_mapq.argtypes = [C.POINTER(Record), C.c_uint64, u32p, u64p, u8p]
     L.flx_run_num_records.restype = C.c_uint64
     L.flx_run_num_records.argtypes = [C.c_void_p]
     L.flx_run_num_cigar_words.restype = C.c_uint64
@@ -213,6 +214,7 @@ def lib():
     L.flx_device_count.restype = C.c_int
     L.flx_index_matches_reference.argtypes = [C.c_void_p, u8p, u64p, C.c_uint32]
     L.flx_sam_set_threads.argtypes = [C.c_void_p, C.c_uint32]
+    L.flx_sam_set_mapq.argtypes = [C.c_void_p, C.c_int]
     L.flx_ctx_get_path_counters.argtypes = [C.c_void_p, C.POINTER(PathCounters)]
     L.flx_ctx_reset_path_counters.argtypes = [C.c_void_p]
     L.flx_sim_genome.argtypes = [C.c_uint64, C.c_uint64, u8p]

@@ -64,9 +64,10 @@ struct Options {
     std::string devices;
     bool drop_duplicate_alignments = false;
     uint64_t max_alignments = 0;                  // 0: no cap
+    bool mapping_quality = false;
 };
 
-struct OptDef { char short_id; const char* long_id; bool flag; };
+struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // note: printed by --help
 const OptDef OPTS[] = {
     {'r', "reference", false}, {'q', "queries", false}, {'o', "output", false}, {'i', "index", false}, {'l', "logfile", false},
     {'c', "console-debug-logs", true}, {'e', "query-errors", false}, {'p', "error-probability", false}, {'s', "seed-errors", false},
@@ -79,6 +80,8 @@ const OptDef OPTS[] = {
     {'G', "devices", false},
     // not in the reference either: output options (flx_output_options); without them every alignment verification found is written
     {'D', "drop-duplicate-alignments", true}, {'N', "max-alignments", false},
+    // nor this one: MAPQ from the read's distinct loci (flx_output_options.mapq, flx_mapq.hpp) instead of floxer's 255
+    {'Q', "mapping-quality", true, "not floxer's: MAPQ from the read's distinct loci within its error budget instead of 255 (0..60; computed before -D / -N drop records)"},
 };
 
 struct CliError { std::string msg; };
@@ -128,7 +131,7 @@ Options parse_cli(int argc, char** argv) {
         }
         if (arg == "-h" || arg == "--help") {
             fprintf(stderr, "floxer (MI355X-native path) - usage: ./floxer --reference hg38.fasta --queries reads.fastq --error-probability 0.07 --output mapped_reads.bam\n");
-            for (auto const& d : OPTS) fprintf(stderr, "  -%c, --%s%s\n", d.short_id, d.long_id, d.flag ? "" : " <value>");
+            for (auto const& d : OPTS) fprintf(stderr, "  -%c, --%s%s%s%s\n", d.short_id, d.long_id, d.flag ? "" : " <value>", d.note ? "    " : "", d.note ? d.note : "");
             exit(0);
         }
         if (arg == "--version") { fprintf(stderr, "%s\n", flx_version()); exit(0); }
@@ -169,6 +172,7 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "stats") o.stats = value;
         else if (n == "devices") o.devices = value;
         else if (n == "drop-duplicate-alignments") o.drop_duplicate_alignments = true;
+        else if (n == "mapping-quality") o.mapping_quality = true;
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -576,6 +580,8 @@ int main(int argc, char** argv) {
     memset(&out_opt, 0, sizeof(out_opt));
     out_opt.drop_duplicates = o.drop_duplicate_alignments;
     out_opt.max_alignments_per_read = o.max_alignments;
+    out_opt.mapq = o.mapping_quality;            // (the options go with every batch, whichever device context aligns it)
+    flx_sam_set_mapq(out, o.mapping_quality);
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);

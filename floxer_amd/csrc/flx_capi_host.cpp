@@ -6,6 +6,7 @@
 #include <memory>
 
 #include "flx_fm_core.hpp"
+#include "flx_mapq.hpp"
 #include "flx_select.hpp"
 
 namespace flx {
@@ -171,6 +172,30 @@ int flx_select_records(const flx_record* records, uint64_t n, const uint32_t* ci
                                      r.cigar_length ? cigar_words + r.cigar_offset : nullptr};
         }
         select_read_records(keys.data(), keys.size(), drop, cap, keep + lo, scratch);
+        lo = hi;
+    }
+    return FLX_OK;
+}
+
+int flx_assign_mapq(const flx_record* records, uint64_t n, const uint32_t* cigar_words, const uint64_t* read_lengths, uint8_t* mapq) {
+    if ((n && (!records || !mapq))) { set_error("flx_assign_mapq: null argument"); return FLX_ERR_INVALID; }
+    std::vector<MapqKey> keys;
+    MapqScratch scratch;
+    for (u64 lo = 0; lo < n;) {
+        u64 hi = lo + 1;
+        while (hi < n && records[hi].read_index == records[lo].read_index) ++hi;
+        keys.resize(hi - lo);
+        scratch.spans.clear();
+        for (u64 i = lo; i < hi; ++i) {
+            flx_record const& r = records[i];
+            if (r.cigar_length && !cigar_words) { set_error("flx_assign_mapq: records with a CIGAR and no CIGAR words"); return FLX_ERR_INVALID; }
+            u64 span = 0;
+            if (r.flag & 4u) span = 0;
+            else if (r.cigar_length) span = cigar_reference_span_cached(cigar_words + r.cigar_offset, r.cigar_length, scratch);
+            else if (read_lengths) span = read_lengths[r.read_index];
+            keys[i - lo] = MapqKey{(u64)(uint32_t)r.position, span, r.reference_id, r.flag, r.num_errors};
+        }
+        read_mapq(keys.data(), keys.size(), mapq + lo, scratch);
         lo = hi;
     }
     return FLX_OK;

@@ -1,5 +1,5 @@
 // SAM / BAM record writer with the reference's record conventions (output.cpp:49-108, 197-212; seqan3::sam_file_output):
-//   header @HD VN:1.6 + one @SQ per reference; MAPQ 255; RNEXT * / PNEXT 0 / TLEN 0; NM tag on mapped records;
+//   header @HD VN:1.6 + one @SQ per reference; MAPQ 255 (flx_sam_set_mapq: the records' own, not floxer's); RNEXT * / PNEXT 0 / TLEN 0; NM tag on mapped records;
 //   the primary record carries the forward read + qualities, secondary records have empty SEQ/QUAL;
 //   unmapped records: flag 4, RNAME *, no tags. Format chosen by extension (output.hpp:33-38). BGZF via zlib.
 #include <zlib.h>
@@ -29,6 +29,7 @@ struct flx_sam_writer {
     std::vector<uint64_t> ref_lens;
     std::vector<uint8_t> pending;    // BAM: uncompressed bytes that do not fill a BGZF block yet
     unsigned threads = 1;            // record formatting and BGZF compression run on this many threads (flx_sam_set_threads)
+    bool mapq_from_records = false;  // MAPQ column: flx_record.reserved instead of 255 (flx_sam_set_mapq)
     bool failed = false;
 };
 
@@ -568,13 +569,19 @@ extern "C" int flx_sam_open(const char* path, const char* const* ref_ids, const 
 }
 
 namespace {
+// the reference span of the CIGAR array summed last (BAM bin): one per part of one flx_sam_write call, so that it never outlives the
+// caller's CIGAR buffer (another call's buffer may have the same address and length and other words)
+struct SpanCache { const uint32_t* of = nullptr; uint32_t len = 0; int64_t span = 0; };
+
 // one record as SAM text or as a BAM record, appended to `out`; false: the record cannot be represented (error set)
 // cigar_at (BAM): where in `out` the record's CIGAR array starts (SIZE_MAX: it has none of its own)
 bool format_record(flx_sam_writer const* w, flx_record const& r, const char* const* read_ids, const uint8_t* read_pool,
                    const uint64_t* read_offsets, const char* const* quals, const uint32_t* cigar_words, std::vector<uint8_t>& out, std::string& err,
-                   size_t* cigar_at = nullptr) {
+                   SpanCache& span_cache, size_t* cigar_at = nullptr) {
     static const char ops[] = "MIDNSHP=X";
     const char* id = read_ids[r.read_index];
+    if (w->mapq_from_records && r.reserved > 254u) { err = std::string("mapping quality above 254 in the record of read ") + id; return false; }
+    uint32_t const mapq = w->mapq_from_records ? r.reserved : 255u;
     bool const unmapped = (r.flag & 4u) != 0;
     bool const with_seq = unmapped || !(r.flag & 256u);        // primary or unmapped carry SEQ/QUAL (output.cpp:69-72, 97-105)
     const uint8_t* seq = read_pool + read_offsets[r.read_index];
@@ -595,7 +602,8 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         if (unmapped) out.push_back('*'); else app(w->ref_ids[(size_t)r.reference_id].data(), w->ref_ids[(size_t)r.reference_id].size());
         out.push_back('\t');
         app_num((long long)r.position + 1);                      // seqan3 writes ref_offset + 1 (also for the 0 floxer passes when unmapped)
-        app("\t255\t", 5);
+        if (mapq == 255u) app("\t255\t", 5);
+        else { out.push_back('\t'); app_num(mapq); out.push_back('\t'); }
         if (r.cigar_length == 0) out.push_back('*');
         else for (uint32_t c = 0; c < r.cigar_length; ++c) { app_num(cig[c] >> 4); out.push_back((uint8_t)ops[cig[c] & 15]); }
         app("\t*\t0\t0\t", 7);
@@ -611,18 +619,15 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
     size_t const l_name = strlen(id) + 1;
     if (l_name > 255) { err = std::string("read name longer than 254 characters cannot be written to BAM: ") + id; return false; }
     // (the forty records of a read at one locus share one CIGAR array: its span is summed once)
-    thread_local const uint32_t* span_of = nullptr;
-    thread_local uint32_t span_len = 0;
-    thread_local int64_t span = 0;
-    if (span_of != cig || span_len != r.cigar_length || !cig) {
-        span = 0;
+    if (span_cache.of != cig || span_cache.len != r.cigar_length || !cig) {
+        int64_t span = 0;
         for (uint32_t c = 0; c < r.cigar_length; ++c) {
             uint32_t const op = cig[c] & 15, len = cig[c] >> 4;
             if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += len;
         }
-        span_of = cig; span_len = r.cigar_length;
+        span_cache = SpanCache{cig, r.cigar_length, span};
     }
-    int64_t const ref_span = span;
+    int64_t const ref_span = span_cache.span;
     // more than 65535 operations do not fit n_cigar_op: the record carries kSmN and the real CIGAR in the CG:B,I tag (SAM spec 4.2.2)
     bool const long_cigar = r.cigar_length > 65535u;
     size_t const start = out.size();
@@ -633,7 +638,7 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
     put32(unmapped ? -1 : r.reference_id);
     put32(pos);
     out.push_back((uint8_t)l_name);
-    out.push_back(255);
+    out.push_back((uint8_t)mapq);
     put16((uint16_t)reg2bin(pos, pos + (ref_span ? ref_span : 1)));
     put16((uint16_t)(long_cigar ? 2u : r.cigar_length));
     put16((uint16_t)r.flag);
@@ -682,6 +687,12 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
 extern "C" int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads) {
     if (!w) { set_error("null writer"); return FLX_ERR_INVALID; }
     w->threads = std::max(1u, std::min(n_threads, 64u));
+    return FLX_OK;
+}
+
+extern "C" int flx_sam_set_mapq(flx_sam_writer* w, int from_records) {
+    if (!w) { set_error("null writer"); return FLX_ERR_INVALID; }
+    w->mapq_from_records = from_records != 0;
     return FLX_OK;
 }
 
@@ -739,10 +750,11 @@ extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, con
                 else if (done >= (4u << 20)) { base += done; raw.erase(raw.begin(), raw.begin() + (long)done); done = 0; }
             };
             size_t prev_cigar_at = SIZE_MAX;                   // stream position of the previous record's CIGAR array
+            SpanCache span_cache;
             for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i) {
                 size_t cigar_at = SIZE_MAX;
                 uint64_t const t_format = prof_ns();
-                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], &cigar_at)) break;
+                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at)) break;
                 if (writer_profile()) g_ns_format += prof_ns() - t_format;
                 if (cigar_at != SIZE_MAX) {
                     cigar_at += base;
@@ -778,8 +790,9 @@ extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, con
             }
             parts[p].reserve(2 * guess);
         }
+        SpanCache span_cache;
         for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i)
-            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p])) break;
+            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache)) break;
     });
     for (auto const& e : errs) if (!e.empty()) { set_error(e); return FLX_ERR_INVALID; }
     for (auto const& part : parts) {

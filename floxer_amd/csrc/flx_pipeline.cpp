@@ -18,6 +18,7 @@
 
 #include "flx_context.hpp"
 #include "flx_fm_core.hpp"
+#include "flx_mapq.hpp"
 #include "flx_select.hpp"
 #include "flx_stats.hpp"
 
@@ -2247,6 +2248,11 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
     std::vector<SelectKey> sel_keys;
     std::vector<u8> sel_keep;
     SelectScratch sel_scratch;
+    // mapping quality (flx_mapq.hpp): from all of a read's records, before any of them is dropped
+    bool const mapq = O && O->mapq;
+    std::vector<MapqKey> mq_keys;
+    std::vector<u8> mq_q;
+    MapqScratch mq_scratch;
     for (size_t r = 0; r < reads.size(); ++r) {
         size_t const rec0 = run->records.size();
         bool have_best = false;
@@ -2263,8 +2269,20 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
                 else flag |= 256u;
                 run->records.push_back(flx_record{reads[r].read_index, flag, (int32_t)ref, saturate_i32(root_res[i].start), root_res[i].nm,
                                                   root_res[i].cigar_off, root_res[i].cigar_len, 0});
+                if (mapq) {
+                    if (mq_keys.empty()) mq_scratch.spans.clear();
+                    u64 const span = root_res[i].cigar_len ? cigar_reference_span_cached(cig.data() + root_res[i].cigar_off, root_res[i].cigar_len, mq_scratch)
+                                                           : reads[r].len;
+                    mq_keys.push_back(MapqKey{root_res[i].start, span, (int32_t)ref, flag, root_res[i].nm});
+                }
             }
         if (!primary_written) run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
+        if (mapq && !mq_keys.empty()) {
+            mq_q.resize(mq_keys.size());
+            read_mapq(mq_keys.data(), mq_keys.size(), mq_q.data(), mq_scratch);
+            for (size_t j = 0; j < mq_keys.size(); ++j) run->records[rec0 + j].reserved = mq_q[j];
+            mq_keys.clear();
+        }
         if (select && run->records.size() - rec0 > 1) {
             // (records in the loop's order: the read's mapped roots by reference, the start key unsaturated)
             size_t const n = run->records.size() - rec0;

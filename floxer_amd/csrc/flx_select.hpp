@@ -22,9 +22,10 @@ struct SelectKey {            // one record of a read, in output order
 
 struct SelectScratch { std::vector<uint64_t> hash; std::vector<uint32_t> order, kept; };
 
-// NULL is no options; the reserved fields must be 0 (set_error otherwise)
+// NULL is no options; the reserved fields must be 0 and mapq 0 or 1 (set_error otherwise)
 inline bool output_options_valid(const flx_output_options* o) {
-    if (o && (o->reserved || o->reserved2[0] || o->reserved2[1])) { set_error("flx_output_options: the reserved fields must be 0"); return false; }
+    if (o && (o->reserved2[0] || o->reserved2[1])) { set_error("flx_output_options: the reserved fields must be 0"); return false; }
+    if (o && o->mapq > 1) { set_error("flx_output_options: mapq must be 0 or 1"); return false; }
     return true;
 }
 inline bool output_options_active(const flx_output_options* o) { return o && (o->drop_duplicates || o->max_alignments_per_read); }

@@ -203,7 +203,7 @@ typedef struct flx_record {          /* one SAM/BAM record, output.cpp:49-108 */
     uint32_t num_errors;             /* NM */
     uint64_t cigar_offset;
     uint32_t cigar_length;
-    uint32_t reserved;
+    uint32_t reserved;               /* MAPQ when the run was made with flx_output_options.mapq, else 0 */
 } flx_record;
 
 typedef struct flx_run flx_run;      /* result of one batch */
@@ -217,19 +217,26 @@ int flx_reads_upload(flx_ctx* ctx, const uint8_t* read_pool, const uint64_t* rea
 void flx_reads_free(flx_reads* reads);
 int flx_align_reads_resident(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, flx_run** out);
 
-/* Output options: not floxer's, which writes every alignment verification found (alignment.cpp:39-46, output.cpp:48). Both are off
- * when the struct is zeroed, and with both off the records are floxer's, byte for byte. Applied per read to its records in output
+/* Output options: not floxer's, which writes every alignment verification found (alignment.cpp:39-46, output.cpp:48). All are off
+ * when the struct is zeroed, and with all off the records are floxer's, byte for byte. Applied per read to its records in output
  * order (per reference id ascending, verification order within a reference):
  *   drop_duplicates != 0: of the mapped records with equal reference id, strand (flag bit 16), start, NM and CIGAR words (compared
  *     word by word) only the first is kept: floxer's alignment operator== (alignment.cpp:20-34) plus the reference id;
  *   max_alignments_per_read = N > 0: of the mapped records left, the N with the smallest (NM, index in output order) are kept and
  *     written in their original order; N = 1 keeps exactly the primary.
+ *   mapq = 1 (0: off, anything else is refused): flx_record.reserved of every record receives a mapping quality made of the read's
+ *     distinct loci, computed from all of the read's records before the two options above select among them, so that the primary
+ *     kept by max_alignments_per_read = 1 tells of the loci that were dropped. Records that overlap on one (reference, strand) are one
+ *     locus with the smallest NM of its records; with b the NM of the primary's locus, n the loci of that NM and s the next larger NM
+ *     of a locus: n >= 2 gives 3, 2, 1 for n = 2, 3, 4 and 0 beyond, a single locus 60, else min(60, 10 * (s - b)) (the factor 10 is
+ *     this project's convention, not fitted to anything). The records of the primary's locus get the value, all others 0. The full
+ *     rule and its limits: floxer_amd/csrc/flx_mapq.hpp. No other field of any record changes.
  * Kept records are unchanged (no flag is rewritten); the unmapped record of a read without alignments is always kept. --stats and
  * flx_path_counters.root_alignments_found still describe what verification found; flx_path_counters.records counts records written
  * and reserved[0] the records dropped. The reserved fields must be 0. */
 typedef struct flx_output_options {
     uint32_t drop_duplicates;
-    uint32_t reserved;
+    uint32_t mapq;
     uint64_t max_alignments_per_read;    /* 0: no cap */
     uint64_t reserved2[2];
 } flx_output_options;
@@ -243,6 +250,10 @@ int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_params* params
  * differ only for sequences of 2^31 symbols or more). cigar_words may be NULL when no record has a CIGAR. */
 int flx_select_records(const flx_record* records, uint64_t n, const uint32_t* cigar_words, const flx_output_options* options,
                        uint8_t* keep);
+/* The mapq rule on any record array (host only; records as for flx_select_records, the records' `reserved` is not read): mapq[i]
+ * receives record i's mapping quality. Call it on all of a read's records, before any selection. A record without CIGAR spans
+ * read_lengths[read_index] reference symbols; read_lengths may be NULL: then the span comes from the CIGAR only (1 without one). */
+int flx_assign_mapq(const flx_record* records, uint64_t n, const uint32_t* cigar_words, const uint64_t* read_lengths, uint8_t* mapq);
 
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
@@ -298,6 +309,9 @@ int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, const uint8_t*
 int flx_sam_close(flx_sam_writer* w);
 /* record formatting and BGZF block compression of flx_sam_write on n_threads host threads (default 1; output bytes do not depend on it) */
 int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads);
+/* MAPQ column: from_records = 0 (default) writes 255, "not available", as floxer does; != 0 writes records[i].reserved (what a run made
+ * with flx_output_options.mapq stores there; a value above 254 makes flx_sam_write fail with FLX_ERR_INVALID) */
+int flx_sam_set_mapq(flx_sam_writer* w, int from_records);
 
 /* ------------------------------------------------------------------------------------------------ synthetic inputs
  * The reference's simulator (src/main/simulated_dataset.cpp:30-49, 81-223), multi-threaded and with a portable generator:
