@@ -1,0 +1,750 @@
+// Alignment job batches (K0/K3/K4/K5, alignment.cpp:83-181): de-duplication, launch shapes, one launch per shape class, and the score,
+// trace, root-union and existence forms built on them; the C ABI of seam 2.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <numeric>
+#include <string>
+
+#include "flx_pipeline.hpp"
+
+namespace flx {
+
+u64 round_span_percent() {
+    static u64 const v = getenv("FLX_ROUND_SPAN") ? std::max<u64>(100, strtoull(getenv("FLX_ROUND_SPAN"), nullptr, 10)) : 150;
+    return v;
+}
+u64 align_few_waves() {
+    const char* env = getenv("FLX_ALIGN_FEW_WAVES");
+    return env ? strtoull(env, nullptr, 10) : 512;
+}
+
+namespace {
+
+// word-steps the launch really performs for one job: the whole matrix, or only the band -k <= col-row <= n-m+k
+u64 job_word_steps(u32 n, u32 m, u32 k, AlignShape sh) {
+    u64 const nw = (m + 63) / 64;
+    if (!sh.banded) return (u64)n * nw;
+    i64 const W = sh.words_per_lane, band_hi = (i64)n - (i64)m + (i64)k;
+    u64 total = 0;
+    for (i64 g = 0; g * W < (i64)nw; ++g) {
+        i64 const r0 = 64 * W * g, r1 = std::min<i64>(m, r0 + 64 * W);
+        i64 const lo = std::max<i64>(0, r0 - (i64)k), hi = std::min<i64>((i64)n - 1, r1 - 1 + band_hi);
+        if (hi >= lo) total += (u64)(hi - lo + 1) * (u64)std::min<i64>(W, (i64)nw - g * W);
+    }
+    return total;
+}
+
+struct ShapeKey {
+    u32 w, g, banded;
+    bool operator<(ShapeKey const& o) const { return w != o.w ? w < o.w : g != o.g ? g < o.g : banded < o.banded; }
+};
+
+// Anchors of one locus produce many identical (window, node) jobs (sibling leaves share their parent's window, anchors with the
+// same indel drift share the root window). Identical inputs give identical outputs, so each distinct job runs once.
+struct ReqKey {
+    u64 ref_off, q_off; u32 n, m, k;
+    bool operator==(ReqKey const& o) const { return ref_off == o.ref_off && q_off == o.q_off && n == o.n && m == o.m && k == o.k; }
+};
+struct ReqKeyHash {
+    size_t operator()(ReqKey const& r) const {
+        u64 h = r.ref_off * 0x9E3779B97F4A7C15ull ^ (r.q_off + 0x7F4A7C15ull) * 0xC2B2AE3D27D4EB4Full;
+        h ^= ((u64)r.n << 40) ^ ((u64)r.m << 20) ^ r.k;
+        h ^= h >> 29;
+        return (size_t)(h * 0xBF58476D1CE4E5B9ull);
+    }
+};
+void dedup_requests(hvec<AlignRequest> const& reqs, hvec<AlignRequest>& uniq, hvec<u32>& uniq_of) {
+    // open-addressing table of indices into `uniq` (power-of-two size, linear probing)
+    size_t cap = 16;
+    while (cap < reqs.size() * 2 + 1) cap <<= 1;
+    hvec<u32> table(cap, 0xFFFFFFFFu);
+    ReqKeyHash const hasher;
+    uniq.clear();
+    uniq.reserve(reqs.size());
+    uniq_of.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        AlignRequest const& r = reqs[i];
+        ReqKey const key{r.ref_off, r.q_off, r.n, r.m, r.k};
+        size_t h = hasher(key) & (cap - 1);
+        while (true) {
+            u32 const e = table[h];
+            if (e == 0xFFFFFFFFu) { table[h] = (u32)uniq.size(); uniq_of[i] = (u32)uniq.size(); uniq.push_back(r); break; }
+            AlignRequest const& u = uniq[e];
+            if (u.ref_off == r.ref_off && u.q_off == r.q_off && u.n == r.n && u.m == r.m && u.k == r.k) { uniq_of[i] = e; break; }
+            h = (h + 1) & (cap - 1);
+        }
+    }
+}
+
+// Shapes for the jobs of one call. Many jobs: each gets the shape that costs the fewest wave slots. Few jobs (they would leave
+// most SIMDs without a wave): all get one common shape with the fewest words per lane, i.e. more, shorter-running waves and a
+// single launch.
+int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
+    shapes.resize(reqs.size());
+    u64 lanes = 0;
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        shapes[i] = choose_align_shape(reqs[i].n, reqs[i].m, reqs[i].k);
+        if (shapes[i].words_per_lane == 0) { set_error("query longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
+        lanes += shapes[i].lanes_per_job;
+    }
+    auto fits = [](AlignRequest const& r, AlignShape const& sh) {
+        u32 const nw = (r.m + 63) / 64, W = sh.words_per_lane, R = sh.lanes_per_job;
+        i64 const width = (i64)r.n - (i64)r.m + 2 * (i64)r.k;
+        if ((nw + W - 1) / W <= R || (sh.banded && (i64)64 * W * (R - 1) + R + 1 > width)) return true;
+        return sh.banded && sh.queue != 0 && ring_delay(r.n, r.m, r.k, W, R) + 1u <= RING_QUEUE_MAX;      // (a ring that waits: DeviceApi::align gives it the largest queue)
+    };
+    if (!reqs.empty() && lanes / 64 >= align_few_waves()) {
+        // A launch lasts at least as long as its longest job, and the jobs of a batch differ by a few columns (unions of a locus' windows): the
+        // shape is chosen per class of query words, for the class's widest band - a ring's delay is the job's own (ring_delay), so the narrower
+        // jobs of the class lose nothing on it. (Per job, 10-kb root alignments over a repeat-rich reference fell into a dozen launches of two
+        // shapes and took 171 ms per 16384 reads instead of 46.)
+        std::map<u32, size_t> widest;                        // query words -> request with the widest band
+        auto width_of = [](AlignRequest const& r) { return (i64)r.n - (i64)r.m + 2 * (i64)r.k; };
+        for (size_t i = 0; i < reqs.size(); ++i) {
+            u32 const nw = (reqs[i].m + 63) / 64;
+            auto it = widest.find(nw);
+            if (it == widest.end() || width_of(reqs[i]) > width_of(reqs[it->second])) widest[nw] = i;
+        }
+        for (size_t i = 0; i < reqs.size(); ++i) {
+            AlignShape const cand = shapes[widest[(reqs[i].m + 63) / 64]];
+            if (fits(reqs[i], cand)) shapes[i] = cand;
+        }
+        // a handful of jobs with a shape of their own join the most common shape that can hold them instead of getting a launch
+        std::map<ShapeKey, std::pair<u32, u32>> count;       // jobs, queue
+        for (auto const& sh : shapes) { auto& c = count[ShapeKey{sh.words_per_lane, sh.lanes_per_job, sh.banded}]; c.first++; c.second = std::max(c.second, sh.queue); }
+        if (count.size() > 1) {
+            for (size_t i = 0; i < reqs.size(); ++i) {
+                ShapeKey const mine{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded};
+                if (count[mine].first >= 64) continue;
+                u32 best_n = 0;
+                AlignShape best = shapes[i];
+                for (auto const& kv : count) {
+                    AlignShape const cand{kv.first.w, kv.first.g, kv.first.banded, kv.second.second};
+                    if (kv.second.first >= 64 && kv.second.first > best_n && fits(reqs[i], cand)) { best_n = kv.second.first; best = cand; }
+                }
+                shapes[i] = best;
+            }
+        }
+        return FLX_OK;
+    }
+    if (reqs.empty()) return FLX_OK;
+    AlignShape common{0, 0, shapes[0].banded};
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        AlignShape const p = choose_align_shape(reqs[i].n, reqs[i].m, reqs[i].k, true);
+        if (p.words_per_lane > common.words_per_lane) common.words_per_lane = p.words_per_lane;
+    }
+    // lanes each job needs at the common words per lane
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        u32 const nw = (reqs[i].m + 63) / 64, W = common.words_per_lane;
+        i64 const width = (i64)reqs[i].n - (i64)reqs[i].m + 2 * (i64)reqs[i].k;
+        u32 r = 1;
+        while (r < 64 && !((nw + W - 1) / W <= r || (common.banded && (i64)64 * W * (r - 1) + r + 1 > width))) r *= 2;
+        if (r > common.lanes_per_job) common.lanes_per_job = r;
+    }
+    for (auto& sh : shapes) sh = common;
+    return FLX_OK;
+}
+
+// K3 / K4 over the requests [begin, end) of one call: one launch per shape class, the classes in ShapeKey order, the jobs of a class in
+// request order (TRACE launches: widest window first, equal widths in request order). A job writes to out_index = its request - begin.
+// per_job(request, job) sets what the caller's form adds to the job (trace arena and last-row offsets: it is called in job order) and
+// returns the bytes the job moves beyond its n + m sequence symbols (the launch's accounting).
+struct ShapeLaunch { ShapeKey key; u32 first, count; u64 word_steps, bytes; };
+template <class PerJob>
+int launch_by_shape(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<AlignShape> const& shapes, size_t begin, size_t end,
+                    const char* kernel_name, const char* what, bool trace, u16* d_lastrow, PerJob&& per_job) {
+    std::map<ShapeKey, hvec<u32>> by_shape;
+    for (size_t i = begin; i < end; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded}].push_back((u32)i);
+    hvec<DevAlignJob> jobs;
+    jobs.reserve(end - begin);
+    hvec<ShapeLaunch> launches;
+    for (auto& kv : by_shape) {
+        auto& ids = kv.second;
+        if (trace) std::stable_sort(ids.begin(), ids.end(), [&](u32 a, u32 b) { return reqs[a].n > reqs[b].n; });
+        ShapeLaunch l{kv.first, (u32)jobs.size(), (u32)ids.size(), 0, 0};
+        for (u32 id : ids) {
+            AlignRequest const& r = reqs[id];
+            jobs.push_back(DevAlignJob{r.ref_off, r.q_off, 0, r.n, r.m, r.k, (u32)(id - begin), 0});
+            l.word_steps += job_word_steps(r.n, r.m, r.k, shapes[id]);
+            l.bytes += (u64)r.n + r.m + per_job(id, jobs.back());
+        }
+        launches.push_back(l);
+    }
+    int rc;
+    if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
+    if ((rc = ctx->job_out.ensure((end - begin) * sizeof(DevAlignOut)))) return rc;
+    for (auto const& l : launches) {
+        if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[%s]%s W %u R %u banded %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", kernel_name, what, l.key.w, l.key.g, l.key.banded, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
+        rc = timed_launch(ctx, kernel_name, l.bytes, l.word_steps, [&] {
+            return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count, AlignShape{l.key.w, l.key.g, l.key.banded}, trace,
+                                    trace ? ctx->trace.as<u64>() : nullptr, ctx->job_out.as<DevAlignOut>(), d_lastrow);
+        });
+        if (rc) return rc;
+    }
+    return FLX_OK;
+}
+
+// score + end column for every (distinct) request (no trace)
+int run_score_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
+                          hvec<DevAlignOut>& outs, const char* kernel_name) {
+    outs.assign(reqs.size(), DevAlignOut{0xFFFFFFFFu, 0});
+    if (reqs.empty()) return FLX_OK;
+    PhaseTimer jprof("score-jobs");
+    hvec<AlignShape> shapes;
+    int rc;
+    if ((rc = choose_shapes(reqs, shapes))) return rc;
+    jprof.mark("shapes");
+    if ((rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, 0, reqs.size(), kernel_name, "", false, nullptr, [](u32, DevAlignJob&) { return (u64)0; }))) return rc;
+    if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, reqs.size() * sizeof(DevAlignOut)))) return rc;
+    jprof.mark("launch");
+    rc = ctx->sync();
+    jprof.mark("wait");
+    return rc;
+}
+
+// score, begin position and CIGAR for every (distinct) request
+int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+                          hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
+    results.assign(reqs.size(), TraceResult{});
+    if (reqs.empty()) return FLX_OK;
+    PhaseTimer tprof("trace-jobs");
+    hvec<AlignShape> shapes;
+    if (int const src = choose_shapes(reqs, shapes)) return src;
+    hvec<u64> slots(reqs.size());
+    u64 const budget_slots = std::max<u64>(ctx->trace_budget_bytes / 16, 1);
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        slots[i] = align_trace_slots(reqs[i].n, reqs[i].m, reqs[i].k, shapes[i]);
+        if (slots[i] > budget_slots) { set_error("one alignment needs more trace memory than the configured budget (FLX_TRACE_ARENA_MB)"); return FLX_ERR_CAPACITY; }
+    }
+    int rc;
+    size_t next = 0;
+    while (next < reqs.size()) {
+        // ---- chunk of jobs whose trace planes fit the arena
+        size_t begin = next;
+        u64 used = 0;
+        while (next < reqs.size() && used + slots[next] <= budget_slots) { used += slots[next]; ++next; }
+        size_t const count = next - begin;
+        // the arena is taken whole on first use (its size is the configured budget): no reallocation between batches
+        if ((rc = ctx->trace.ensure(std::max<size_t>(used * 16 + 64, ctx->trace.ptr ? 0 : std::min<size_t>(ctx->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2)))) return rc;
+
+        hvec<u64> trace_off(count);
+        u64 off = 0;
+        // (bytes: reference + query symbols read; trace written: full form 16 B per word-step, checkpointed form its carry and checkpoint regions)
+        rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, begin, next, "ed_align_trace", "", true, nullptr, [&](u32 id, DevAlignJob& job) {
+            AlignRequest const& r = reqs[id];
+            job.trace_off = trace_off[id - begin] = off;
+            off += slots[id];
+            if (!shapes[id].banded) return job_word_steps(r.n, r.m, r.k, shapes[id]) * 16;
+            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
+            return (tl.carry_slots + tl.ckpt_slots) * 16;
+        });
+        if (rc) return rc;
+        hvec<DevAlignOut> outs(count);
+        if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, count * sizeof(DevAlignOut)))) return rc;
+        if ((rc = ctx->sync())) return rc;
+        tprof.mark("K4");
+
+        // ---- traceback for the jobs that have an alignment within k
+        hvec<DevTraceJob> tjobs;
+        hvec<u32> tjob_req;
+        u64 cigar_words = 0, path_steps = 0;
+        for (size_t c = 0; c < count; ++c) {
+            if (outs[c].score == 0xFFFFFFFFu) continue;
+            size_t const id = begin + c;
+            AlignRequest const& r = reqs[id];
+            AlignShape const sh = shapes[id];
+            u32 const nw = (r.m + 63) / 64;
+            u32 const L = sh.banded ? sh.lanes_per_job : (nw + sh.words_per_lane - 1) / sh.words_per_lane;
+            u32 const cap = 2 * outs[c].score + 2;      // runs <= 2*NM + 1
+            tjobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off[c], cigar_words, r.n, r.m, L, sh.words_per_lane, outs[c].end_col,
+                                        cap, (u32)tjob_req.size(), r.k});
+            tjob_req.push_back((u32)id);
+            cigar_words += cap;
+            path_steps += (u64)r.m + outs[c].score;
+        }
+        if (!tjobs.empty()) {
+            if ((rc = h2d(ctx, ctx->tjobs, tjobs.data(), tjobs.size() * sizeof(DevTraceJob)))) return rc;
+            if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
+            if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
+            rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
+                return DeviceApi::traceback(ctx->stream, d_text, d_query, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(),
+                                            (u32)tjobs.size(), shapes[begin].banded != 0, ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
+            });
+            if (rc) return rc;
+            tprof.mark("tb-prep");
+            hvec<DevTraceOut> touts(tjobs.size());
+            size_t const pool_base = cigar_pool.size();
+            cigar_pool.resize(pool_base + cigar_words);          // slabs are kept as they are (gaps included): no host repacking
+            tprof.mark("pool-resize");
+            if ((rc = d2h(ctx, touts.data(), ctx->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
+            if ((rc = d2h(ctx, cigar_pool.data() + pool_base, ctx->cigar.ptr, cigar_words * 4))) return rc;
+            if ((rc = ctx->sync())) return rc;
+            tprof.mark("K5+d2h");
+            for (size_t j = 0; j < tjobs.size(); ++j) {
+                if (touts[j].cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+                TraceResult& res = results[tjob_req[j]];
+                res.exists = true;
+                res.nm = outs[tjob_req[j] - begin].score;
+                res.begin = touts[j].begin;
+                res.cigar_off = pool_base + tjobs[j].cigar_off + touts[j].cigar_start;
+                res.cigar_len = touts[j].cigar_len;
+            }
+        }
+    }
+    return FLX_OK;
+}
+
+}  // namespace
+
+int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
+                   hvec<DevAlignOut>& outs, const char* kernel_name) {
+    hvec<AlignRequest> uniq;
+    hvec<u32> uniq_of;
+    dedup_requests(reqs, uniq, uniq_of);
+    hvec<DevAlignOut> uouts;
+    int rc = run_score_jobs_unique(ctx, d_text, d_peq, uniq, uouts, kernel_name);
+    if (rc) return rc;
+    outs.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) outs[i] = uouts[uniq_of[i]];
+    return FLX_OK;
+}
+
+// score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
+int run_trace_jobs(Lane* ctx, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
+    hvec<AlignRequest> uniq;
+    hvec<u32> uniq_of;
+    dedup_requests(reqs, uniq, uniq_of);
+    hvec<TraceResult> ures;
+    int rc = run_trace_jobs_unique(ctx, d_text, d_query, d_peq, uniq, ures, cigar_pool);
+    if (rc) return rc;
+    results.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
+    return FLX_OK;
+}
+
+// Existence tests of one locus. Anchors of the same read at the same locus test the same node in windows shifted by their indel
+// drift. Existence is monotone in the window: an alignment inside the intersection I of such windows lies inside every one of them,
+// and if their union U holds none then neither does any of them. So a cluster first tests I (one job instead of one per member);
+// only if that fails it tests U, and only if U holds an alignment that I does not are the members tested one by one.
+// outs[i].score is 0xFFFFFFFF for "no alignment within k" and some score <= k of a contained alignment otherwise (callers of
+// this function only look at that distinction); outs[i].end_col is not meaningful.
+int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, ExistsTimes& times) {
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](int slot) { auto const t1 = std::chrono::steady_clock::now(); times.ms[slot] += std::chrono::duration<double, std::milli>(t1 - t0).count(); t0 = t1; };
+    // The requests come in anchor order, and the anchors of a read and orientation are in leaf order: all requests for one node
+    // (the leaves below it are a contiguous range) form one run of equal (query rows, errors). Sorting a run by reference
+    // position puts equal windows and the windows of one locus next to each other: no hash table, no sort of the whole round.
+    // (Requests for one node that are not adjacent would only be tested more than once.)
+    static int const disabled = (getenv("FLX_NO_UNION") || getenv("FLX_NO_EXISTS_CLUSTERS")) ? 1 : 0;
+    hvec<AlignRequest> uniq;
+    hvec<u32> uniq_of(reqs.size());
+    hvec<u32> order;                                          // position in `uniq` (identity: kept for the code below)
+    struct Cluster { u32 first, count; u64 lo_start, hi_start, lo_end, hi_end; };     // members = uniq[first .. first+count)
+    hvec<Cluster> clusters;
+    uniq.reserve(reqs.size());
+    hvec<u32> run;
+    for (size_t i0 = 0; i0 < reqs.size();) {
+        size_t i1 = i0 + 1;
+        while (i1 < reqs.size() && reqs[i1].q_off == reqs[i0].q_off && reqs[i1].m == reqs[i0].m && reqs[i1].k == reqs[i0].k) ++i1;
+        run.resize(i1 - i0);
+        for (size_t j = 0; j < run.size(); ++j) run[j] = (u32)(i0 + j);
+        if (run.size() > 1)
+            std::sort(run.begin(), run.end(), [&](u32 x, u32 y) { return reqs[x].ref_off != reqs[y].ref_off ? reqs[x].ref_off < reqs[y].ref_off : reqs[x].n < reqs[y].n; });
+        bool first_of_run = true;
+        for (u32 idx : run) {
+            AlignRequest const& r = reqs[idx];
+            if (!first_of_run && uniq.back().ref_off == r.ref_off && uniq.back().n == r.n) { uniq_of[idx] = (u32)uniq.size() - 1; continue; }
+            uniq_of[idx] = (u32)uniq.size();
+            if (!first_of_run && !disabled) {
+                Cluster& c = clusters.back();
+                if (r.ref_off <= uniq[c.first].ref_off + std::max<u64>(8, r.m / 8)) {
+                    c.count++;
+                    c.hi_start = std::max(c.hi_start, r.ref_off);
+                    c.lo_end = std::min(c.lo_end, r.ref_off + r.n);
+                    c.hi_end = std::max(c.hi_end, r.ref_off + r.n);
+                    uniq.push_back(r);
+                    continue;
+                }
+            }
+            clusters.push_back(Cluster{(u32)uniq.size(), 1, r.ref_off, r.ref_off, r.ref_off + r.n, r.ref_off + r.n});
+            uniq.push_back(r);
+            first_of_run = false;
+        }
+        i0 = i1;
+    }
+    order.resize(uniq.size());
+    std::iota(order.begin(), order.end(), 0u);
+    lap(0);
+    hvec<DevAlignOut> uouts(uniq.size(), DevAlignOut{0xFFFFFFFFu, 0});
+    // ---- one launch: single windows on their own, clusters on their intersection and (speculatively: a separate round trip
+    //      to the GPU costs a chunk more than the extra jobs) on their union
+    hvec<AlignRequest> jobs;
+    hvec<u32> job_cluster;                                   // cluster index, bit 31 set for the union job
+    for (u32 ci = 0; ci < clusters.size(); ++ci) {
+        Cluster const& c = clusters[ci];
+        AlignRequest r = uniq[order[c.first]];
+        if (c.count == 1) { jobs.push_back(r); job_cluster.push_back(ci); continue; }
+        if (c.lo_end > c.hi_start) {                         // the common columns (none: straight to the union and the members)
+            AlignRequest i = r;
+            i.ref_off = c.hi_start;
+            i.n = (u32)(c.lo_end - c.hi_start);
+            jobs.push_back(i);
+            job_cluster.push_back(ci);
+        }
+        r.ref_off = c.lo_start;
+        r.n = (u32)(c.hi_end - c.lo_start);
+        jobs.push_back(r);
+        job_cluster.push_back(ci | 0x80000000u);
+    }
+    hvec<DevAlignOut> jouts;
+    lap(1);
+    int rc = run_score_jobs_unique(ctx, d_text, d_peq, jobs, jouts, "ed_align_exists");
+    if (rc) return rc;
+    lap(2);
+    hvec<u8> state(clusters.size(), 0);                      // 0 undecided, 1 all pass, 2 all fail
+    hvec<u32> pass_score(clusters.size(), 0);
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        u32 const ci = job_cluster[j] & 0x7FFFFFFFu;
+        bool const is_union = job_cluster[j] >> 31;
+        bool const found = jouts[j].score != 0xFFFFFFFFu;
+        if (!is_union) {
+            if (found) { state[ci] = 1; pass_score[ci] = jouts[j].score; }
+            else if (clusters[ci].count == 1) state[ci] = 2;
+        } else if (!found) state[ci] = 2;                   // (an intersection cannot hold an alignment the union does not)
+    }
+    // ---- phase C: members of the clusters that are still undecided, one by one
+    jobs.clear();
+    hvec<u32> job_member;
+    for (u32 ci = 0; ci < clusters.size(); ++ci) {
+        Cluster const& c = clusters[ci];
+        if (state[ci] != 0) continue;
+        for (u32 j = 0; j < c.count; ++j) { jobs.push_back(uniq[order[c.first + j]]); job_member.push_back(order[c.first + j]); }
+    }
+    if (!jobs.empty()) {
+        if ((rc = run_score_jobs_unique(ctx, d_text, d_peq, jobs, jouts, "ed_align_exists"))) return rc;
+        for (size_t j = 0; j < jobs.size(); ++j) uouts[job_member[j]] = jouts[j];
+    }
+    for (u32 ci = 0; ci < clusters.size(); ++ci) {
+        if (state[ci] == 0) continue;
+        Cluster const& c = clusters[ci];
+        for (u32 j = 0; j < c.count; ++j) uouts[order[c.first + j]] = DevAlignOut{state[ci] == 1 ? pass_score[ci] : 0xFFFFFFFFu, 0};
+    }
+    if (getenv("FLX_ALIGN_DEBUG")) {
+        size_t multi = 0, decided_a = 0;
+        for (u32 ci = 0; ci < clusters.size(); ++ci) if (clusters[ci].count > 1) { ++multi; if (state[ci] == 1) ++decided_a; }
+        fprintf(stderr, "[exists clusters] requests %zu distinct %zu clusters %zu (of several windows %zu, passed on the intersection %zu) one by one %zu\n",
+                reqs.size(), uniq.size(), clusters.size(), multi, decided_a, jobs.size());
+    }
+    outs.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) outs[i] = uouts[uniq_of[i]];
+    lap(3);
+    return FLX_OK;
+}
+
+// Root alignments of one locus. Anchors of the same read at the same locus ask for windows that differ by a few columns (their
+// indel drift), ten per read with floxer's defaults, and nearly always get the same alignment. One DP over the union U of such
+// windows serves them all, exactly:
+//   * a window w is a column range of U, and D_U <= D_w cell by cell (U only adds start columns), with equality on every cell of
+//     a D_U-optimal path that starts inside w;
+//   * let j be the rightmost column of w with the minimal D_U[m][.] = v over w. If the path traced back from (m, j) in D_U starts at
+//     a column of w, then D_w = D_U along it, so min D_w = v, j is also the rightmost minimum of D_w (right of j D_w >= D_U > v), and
+//     the trace decisions along the path agree (a move D_U rejects is rejected by D_w as well, a move D_U takes leads to a cell of
+//     the path): score, end, begin and CIGAR of w are those read off U;
+//   * v > k: no alignment in w either; the path starts left of w (rare): w is aligned on its own as before.
+// The band of U contains the band of every member, and a banded value is exact whenever it is <= k.
+constexpr u64 UNION_MAX_SHIFT = 256;      // members start within this many columns of the first member of their union
+
+int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
+    hvec<AlignRequest> uniq;
+    hvec<u32> uniq_of;
+    dedup_requests(reqs, uniq, uniq_of);
+    hvec<TraceResult> ures(uniq.size());
+    bool usable = !uniq.empty() && choose_align_shape(uniq[0].n, uniq[0].m, uniq[0].k).banded != 0 && !getenv("FLX_NO_UNION");
+    for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
+    // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
+    struct Union { AlignRequest req; u32 first_member, n_members; };
+    hvec<u32> order(uniq.size());
+    hvec<Union> unions;
+    hvec<u32> members;                       // indices into uniq, grouped by union
+    if (usable) {
+        std::iota(order.begin(), order.end(), 0u);
+        std::sort(order.begin(), order.end(), [&](u32 a, u32 b) {
+            AlignRequest const &x = uniq[a], &y = uniq[b];
+            if (x.q_off != y.q_off) return x.q_off < y.q_off;
+            if (x.m != y.m) return x.m < y.m;
+            if (x.k != y.k) return x.k < y.k;
+            return x.ref_off < y.ref_off;
+        });
+        for (u32 id : order) {
+            AlignRequest const& r = uniq[id];
+            if (!unions.empty()) {
+                Union& u = unions.back();
+                if (u.req.q_off == r.q_off && u.req.m == r.m && u.req.k == r.k && r.ref_off <= u.req.ref_off + UNION_MAX_SHIFT) {
+                    u64 const end = std::max<u64>(u.req.ref_off + u.req.n, r.ref_off + r.n);
+                    u.req.n = (u32)(end - u.req.ref_off);
+                    u.n_members++;
+                    members.push_back(id);
+                    continue;
+                }
+            }
+            unions.push_back(Union{r, (u32)members.size(), 1});
+            members.push_back(id);
+        }
+    }
+    if (!usable || unions.size() == uniq.size()) {          // nothing to share: the plain path
+        int const rc = run_trace_jobs_unique(ctx, d_text, d_query, d_peq, uniq, ures, cigar_pool);
+        if (rc) return rc;
+        results.resize(reqs.size());
+        for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
+        return FLX_OK;
+    }
+
+    hvec<AlignRequest> ureqs(unions.size());
+    for (size_t i = 0; i < unions.size(); ++i) ureqs[i] = unions[i].req;
+    hvec<AlignShape> shapes;
+    if (int const src = choose_shapes(ureqs, shapes)) return src;
+    hvec<u64> slots(ureqs.size());
+    u64 const budget_slots = std::max<u64>(ctx->trace_budget_bytes / 16, 1);
+    for (size_t i = 0; i < ureqs.size(); ++i) {
+        slots[i] = align_trace_slots(ureqs[i].n, ureqs[i].m, ureqs[i].k, shapes[i]);
+        if (slots[i] > budget_slots) { set_error("one alignment needs more trace memory than the configured budget (FLX_TRACE_ARENA_MB)"); return FLX_ERR_CAPACITY; }
+    }
+    hvec<AlignRequest> fallback;
+    hvec<u32> fallback_of;                   // uniq index of each fallback request
+    int rc;
+    size_t next = 0;
+    while (next < ureqs.size()) {
+        size_t const begin = next;
+        u64 used = 0;
+        while (next < ureqs.size() && used + slots[next] <= budget_slots) { used += slots[next]; ++next; }
+        size_t const count = next - begin;
+        if ((rc = ctx->trace.ensure(std::max<size_t>(used * 16 + 64, ctx->trace.ptr ? 0 : std::min<size_t>(ctx->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2)))) return rc;
+
+        // ---- K4 over the unions of this arena chunk, with their last rows
+        hvec<u64> trace_off(count), row_off(count);
+        u64 off = 0, rows = 0;
+        for (size_t i = begin; i < next; ++i) rows += ((u64)ureqs[i].n + 15) / 16 * 16;      // K4 stores a block's 16 last-row values as two 16-byte words
+        if ((rc = ctx->lastrow.ensure(rows * 2 + 64))) return rc;
+        FLX_HIP(hipMemsetAsync(ctx->lastrow.ptr, 0xFF, rows * 2, ctx->stream));
+        rows = 0;
+        rc = launch_by_shape(ctx, d_text, d_peq, ureqs, shapes, begin, next, "ed_align_trace", " unions", true, ctx->lastrow.as<u16>(), [&](u32 id, DevAlignJob& job) {
+            AlignRequest const& r = ureqs[id];
+            job.trace_off = trace_off[id - begin] = off;
+            job.lastrow_off = row_off[id - begin] = rows;
+            off += slots[id];
+            rows += ((u64)r.n + 15) / 16 * 16;
+            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
+            return (tl.carry_slots + tl.ckpt_slots) * 16 + 2ull * r.n;
+        });
+        if (rc) return rc;
+        // ---- every member's rightmost minimum over its own columns
+        hvec<DevRowWindow> wins;
+        hvec<u32> win_member;                // uniq index per window
+        hvec<u32> win_union;                 // union index (absolute) per window
+        for (size_t ui = begin; ui < next; ++ui)
+            for (u32 j = 0; j < unions[ui].n_members; ++j) {
+                u32 const id = members[unions[ui].first_member + j];
+                AlignRequest const& r = uniq[id];
+                wins.push_back(DevRowWindow{row_off[ui - begin] + (r.ref_off - ureqs[ui].ref_off), r.n, r.k, (u32)wins.size(), 0});
+                win_member.push_back(id);
+                win_union.push_back((u32)ui);
+            }
+        if ((rc = h2d(ctx, ctx->row_windows, wins.data(), wins.size() * sizeof(DevRowWindow)))) return rc;
+        if ((rc = ctx->row_out.ensure(wins.size() * sizeof(DevAlignOut)))) return rc;
+        rc = timed_launch(ctx, "ed_lastrow_min", rows * 2, wins.size(), [&] {
+            return DeviceApi::lastrow_min(ctx->stream, ctx->lastrow.as<u16>(), ctx->row_windows.as<DevRowWindow>(), (u32)wins.size(), ctx->row_out.as<DevAlignOut>());
+        });
+        if (rc) return rc;
+        hvec<DevAlignOut> wouts(wins.size());
+        if ((rc = d2h(ctx, wouts.data(), ctx->row_out.ptr, wins.size() * sizeof(DevAlignOut)))) return rc;
+        if ((rc = ctx->sync())) return rc;
+
+        // ---- one traceback per distinct (union, end column)
+        hvec<DevTraceJob> tjobs;
+        hvec<u32> win_tjob(wins.size(), 0xFFFFFFFFu);
+        u64 cigar_words = 0, path_steps = 0;
+        {
+            size_t w0 = 0;
+            while (w0 < wins.size()) {                     // windows of one union are consecutive
+                size_t w1 = w0;
+                while (w1 < wins.size() && win_union[w1] == win_union[w0]) ++w1;
+                u32 const ui = win_union[w0];
+                AlignRequest const& ur = ureqs[ui];
+                AlignShape const sh = shapes[ui];
+                for (size_t w = w0; w < w1; ++w) {
+                    if (wouts[w].score == 0xFFFFFFFFu) continue;
+                    u32 const end_in_union = (u32)(uniq[win_member[w]].ref_off - ur.ref_off) + wouts[w].end_col;
+                    for (size_t v = w0; v < w; ++v)
+                        if (win_tjob[v] != 0xFFFFFFFFu && tjobs[win_tjob[v]].end_col == end_in_union) { win_tjob[w] = win_tjob[v]; break; }
+                    if (win_tjob[w] != 0xFFFFFFFFu) continue;
+                    u32 const cap = 2 * wouts[w].score + 2;
+                    win_tjob[w] = (u32)tjobs.size();
+                    tjobs.push_back(DevTraceJob{ur.ref_off, ur.q_off, trace_off[ui - begin], cigar_words, ur.n, ur.m, sh.lanes_per_job, sh.words_per_lane,
+                                                end_in_union, cap, (u32)tjobs.size(), ur.k});
+                    cigar_words += cap;
+                    path_steps += (u64)ur.m + wouts[w].score;
+                }
+                w0 = w1;
+            }
+        }
+        hvec<DevTraceOut> touts(tjobs.size());
+        size_t const pool_base = cigar_pool.size();
+        if (!tjobs.empty()) {
+            if ((rc = h2d(ctx, ctx->tjobs, tjobs.data(), tjobs.size() * sizeof(DevTraceJob)))) return rc;
+            if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
+            if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
+            rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
+                return DeviceApi::traceback(ctx->stream, d_text, d_query, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(),
+                                            (u32)tjobs.size(), true, ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
+            });
+            if (rc) return rc;
+            cigar_pool.resize(pool_base + cigar_words);
+            if ((rc = d2h(ctx, touts.data(), ctx->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
+            if ((rc = d2h(ctx, cigar_pool.data() + pool_base, ctx->cigar.ptr, cigar_words * 4))) return rc;
+            if ((rc = ctx->sync())) return rc;
+        }
+        // ---- members take the union's alignment when its path starts inside their window
+        for (size_t w = 0; w < wins.size(); ++w) {
+            u32 const id = win_member[w];
+            if (wouts[w].score == 0xFFFFFFFFu) continue;                       // no alignment within k in this window
+            DevTraceOut const& t = touts[win_tjob[w]];
+            if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+            u64 const shift = uniq[id].ref_off - ureqs[win_union[w]].ref_off;
+            static int const force_own = getenv("FLX_UNION_ALIGN_OWN") ? 1 : 0;        // test hook: as if every path left its window
+            if (t.begin < shift || force_own) { fallback_of.push_back(id); fallback.push_back(uniq[id]); continue; }
+            TraceResult& res = ures[id];
+            res.exists = true;
+            res.nm = wouts[w].score;
+            res.begin = (u32)(t.begin - shift);
+            res.cigar_off = pool_base + tjobs[win_tjob[w]].cigar_off + t.cigar_start;
+            res.cigar_len = t.cigar_len;
+        }
+    }
+    if (!fallback.empty()) {
+        hvec<TraceResult> fres;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_query, d_peq, fallback, fres, cigar_pool))) return rc;
+        for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
+    }
+    if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", reqs.size(), uniq.size(), unions.size(), fallback.size());
+    results.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
+    return FLX_OK;
+}
+
+int build_peq(Lane* ctx, const u8* d_seq, u64 len, DeviceBuffer& peq) {
+    u64 const n_words = len / 64 + 2;
+    int rc = peq.ensure(n_words * 6 * 8 + 64);
+    if (rc) return rc;
+    return timed_launch(ctx, "peq_build", len + n_words * 48, n_words, [&] { return DeviceApi::build_peq(ctx->stream, d_seq, len, peq.as<u64>()); });
+}
+
+int ensure_reversed_text(Lane* lane) {
+    flx_ctx* ctx = lane->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (ctx->text_rev_ready) return FLX_OK;
+    HostIndex const& H = *ctx->hidx;
+    hvec<u8> rev(H.n);
+    if (H.text.size() == H.n) std::reverse_copy(H.text.begin(), H.text.end(), rev.begin());
+    else {                                       // a context on a received image: the text is in HBM only
+        FLX_HIP(hipMemcpy(rev.data(), ctx->didx.text, H.n, hipMemcpyDeviceToHost));
+        std::reverse(rev.begin(), rev.end());
+    }
+    const u8* first = nullptr;
+    int rc = upload_padded(lane, ctx->text_rev, rev.data(), rev.size(), &first);
+    if (rc) return rc;
+    FLX_HIP(hipStreamSynchronize(lane->stream));
+    ctx->text_rev_ready = true;
+    return FLX_OK;
+}
+
+}  // namespace flx
+
+using namespace flx;
+
+// ================================================================================================ C ABI: seam 2
+extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
+                               uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
+                               uint32_t* cigar_pool, uint64_t* cigar_pool_words) {
+    if (!ctx || (n_jobs && (!jobs || !out || !query_pool))) { set_error("flx_align_batch: null argument"); return FLX_ERR_INVALID; }
+    FLX_HIP(hipSetDevice(ctx->device));
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    u64 const text_len = ref_pool ? ref_pool_len : ctx->hidx->n;
+    bool any_rev = false, any_trace = false;
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_align_job const& j = jobs[i];
+        if (j.query_length == 0 || j.query_offset + j.query_length > query_pool_len || j.ref_offset + j.ref_length > text_len || j.mode > 2) {
+            set_error("flx_align_batch: job outside its pools"); return FLX_ERR_INVALID;
+        }
+        if (j.query_length > align_supported_max_query()) { set_error("query longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
+        any_rev |= j.mode == FLX_MODE_WITHOUT_CIGAR;
+        any_trace |= j.mode == FLX_MODE_WITH_CIGAR;
+    }
+    int rc;
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    Lane* L = lease.lane;
+    const u8* d_text = ctx->didx.text;
+    const u8* d_text_rev = nullptr;
+    hvec<u8> tmp;
+    if (ref_pool) {
+        if ((rc = upload_padded(L, L->user_text, ref_pool, ref_pool_len, &d_text))) return rc;
+        if (any_rev) {
+            tmp.assign(ref_pool, ref_pool + ref_pool_len);
+            std::reverse(tmp.begin(), tmp.end());
+            if ((rc = upload_padded(L, L->user_text_rev, tmp.data(), tmp.size(), &d_text_rev))) return rc;
+            if ((rc = L->sync())) return rc;
+        }
+    } else if (any_rev) {
+        if ((rc = ensure_reversed_text(L))) return rc;
+        d_text_rev = ctx->text_rev.as<u8>() + TEXT_PAD;
+    }
+    if ((rc = h2d(L, L->seq, query_pool, query_pool_len, 192))) return rc;
+    if ((rc = build_peq(L, L->seq.as<u8>(), query_pool_len, L->peq))) return rc;
+    hvec<u8> qrev;
+    if (any_rev) {
+        qrev.assign(query_pool, query_pool + query_pool_len);
+        std::reverse(qrev.begin(), qrev.end());
+        if ((rc = h2d(L, L->seq_rev, qrev.data(), qrev.size(), 64))) return rc;
+        if ((rc = build_peq(L, L->seq_rev.as<u8>(), query_pool_len, L->peq_rev))) return rc;
+    }
+    hvec<AlignRequest> score_reqs, rev_reqs, trace_reqs;
+    hvec<u32> score_ids, rev_ids, trace_ids;
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_align_job const& j = jobs[i];
+        if (j.mode == FLX_MODE_EXISTS) { score_reqs.push_back({j.ref_offset, j.query_offset, j.ref_length, j.query_length, j.num_allowed_errors}); score_ids.push_back((u32)i); }
+        else if (j.mode == FLX_MODE_WITHOUT_CIGAR) {
+            rev_reqs.push_back({text_len - j.ref_offset - j.ref_length, query_pool_len - j.query_offset - j.query_length, j.ref_length, j.query_length, j.num_allowed_errors});
+            rev_ids.push_back((u32)i);
+        } else { trace_reqs.push_back({j.ref_offset, j.query_offset, j.ref_length, j.query_length, j.num_allowed_errors}); trace_ids.push_back((u32)i); }
+    }
+    for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_align_result{0, 0, 0, 0, 0, 0};
+    hvec<DevAlignOut> outs;
+    if ((rc = run_score_jobs(L, d_text, L->peq.as<u64>(), score_reqs, outs, "ed_align_exists"))) return rc;
+    for (size_t i = 0; i < outs.size(); ++i)
+        if (outs[i].score != 0xFFFFFFFFu) { out[score_ids[i]].exists = 1; out[score_ids[i]].num_errors = outs[i].score; }
+    if ((rc = run_score_jobs(L, d_text_rev, L->peq_rev.as<u64>(), rev_reqs, outs, "ed_align_exists"))) return rc;
+    for (size_t i = 0; i < outs.size(); ++i)
+        if (outs[i].score != 0xFFFFFFFFu) {
+            flx_align_result& r = out[rev_ids[i]];
+            r.exists = 1; r.num_errors = outs[i].score; r.begin = rev_reqs[i].n - outs[i].end_col;      // alignment.cpp:135
+        }
+    hvec<TraceResult> tres;
+    hvec<u32> cig;
+    if ((rc = run_trace_jobs(L, d_text, L->seq.as<u8>(), L->peq.as<u64>(), trace_reqs, tres, cig))) return rc;
+    uint64_t const cap = cigar_pool_words ? *cigar_pool_words : 0;
+    if (cigar_pool_words) *cigar_pool_words = cig.size();
+    if (any_trace && (!cigar_pool || cig.size() > cap)) { set_error("cigar pool too small"); return FLX_ERR_CAPACITY; }
+    if (!cig.empty()) memcpy(cigar_pool, cig.data(), cig.size() * 4);
+    for (size_t i = 0; i < tres.size(); ++i)
+        if (tres[i].exists) {
+            flx_align_result& r = out[trace_ids[i]];
+            r.exists = 1; r.num_errors = tres[i].nm; r.begin = tres[i].begin; r.cigar_offset = tres[i].cigar_off; r.cigar_length = tres[i].cigar_len;
+        }
+    return FLX_OK;
+}

@@ -64,7 +64,7 @@ struct Lane {
     int wait_idle();                 // the stream has drained (the thread sleeps on a blocking event unless FLX_SPIN_SYNC is set)
     int sync();                      // wait_idle + fold pending timings into the context's statistics
     std::vector<DeviceBuffer*> workspaces();
-    int size_like(Lane& other);      // grow this lane's workspaces to the other lane's capacities                      // stream synchronize + fold pending timings into the context's statistics
+    int size_like(Lane& other);      // grow this lane's workspaces to the other lane's capacities
     hipEvent_t get_event();
     void release_all();
 };
@@ -140,20 +140,5 @@ int timed_launch(Lane* lane, const char* name, u64 bytes, u64 units, F&& launch)
     lane->pending.push_back(PendingTiming{name, a, b, bytes, units});
     return FLX_OK;
 }
-
-// ---- pipeline pieces (flx_pipeline.cpp)
-struct HostAnchor { u32 seed_index, leaf, ref_id, errors; u64 pos; };
-struct SeedStats { u32 useful, raw, excluded_soft, fully_excluded; };
-
-// d_seq_pool_or_null: the pool is resident (then d_qpack_or_null may be its 2-bit form); seed_flags (per seed, SEED_* of
-// flx_fm_core.hpp) may be null when the host pool is given (they are read off it)
-int search_seeds_device(Lane* lane, const u8* d_seq_pool_or_null, const u8* h_seq_pool, u64 pool_len, const flx_seed* seeds,
-                        u64 n_seeds, const flx_search_config& cfg, hvec<HostAnchor>& anchors, hvec<SeedStats>& stats,
-                        hvec<DevHit>* raw_hits, u64 raw_max_hits, const u32* d_qpack_or_null = nullptr, const u8* seed_flags = nullptr,
-                        const SeedGen* gen = nullptr);
-// gen: `seeds` is null and the chunk's seeds are written on the device from this description (their ids = the order the caller would have
-// listed them in: read by read, forward then reverse complement, leaf by leaf); the anchors' leaf is left to the caller; returns
-// SEARCH_NEEDS_HOST_SEEDS (nothing done that counts) for the forms that read the list (ordered walk, host-side grouping): call again with it.
-constexpr int SEARCH_NEEDS_HOST_SEEDS = 1;
 
 }  // namespace flx

@@ -34,7 +34,7 @@ constexpr u32 VR2_TILE = 256;
 constexpr u32 VR2_THREADS = 64;
 constexpr u64 VR2_NO_KEY = ~0ull;
 
-__device__ __forceinline__ u64 vr2_word_steps(u32 n, u32 m, u32 k, u32 W) {          // job_word_steps of flx_pipeline.cpp, banded
+__device__ __forceinline__ u64 vr2_word_steps(u32 n, u32 m, u32 k, u32 W) {          // job_word_steps of flx_align_jobs.cpp, banded
     u64 const nw = (m + 63u) / 64u;
     i64 const band_hi = (i64)n - (i64)m + (i64)k;
     u64 total = 0;

@@ -1,7 +1,7 @@
 // Search and alignment statistics in the reference's form (include/statistics.hpp:24-172, src/lib/statistics.cpp): one count and
 // eighteen fixed-bin histograms with the same names, thresholds ("real_nanopore" / "simulated" scales, statistics.cpp:7-62) and
 // the same terminal and TOML renderings (statistics.cpp:64-145, 421-447), so that tooling written for `floxer --stats` reads this
-// build's output. The values come from what the batch pipeline holds anyway (flx_pipeline.cpp: seeds, per-seed selection
+// build's output. The values come from what the batch pipeline holds anyway (flx_verify.cpp: seeds, per-seed selection
 // counters, the window of every requested DP, the records).
 // Deviation: the reference measures wall-clock milliseconds per query inside its worker threads; here a query's search /
 // verification time is its chunk's phase time divided by the chunk's reads (the GPU works on whole chunks at a time).

@@ -1,0 +1,731 @@
+// One chunk of reads on one lane: the level-synchronous PEX verification driver (verification.cpp:8-245) as a list of stages.
+// align_slice at the end of the file calls them in order; what a stage leaves for the later ones is in the Slice (flx_pipeline.hpp).
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <queue>
+#include <string>
+#include <vector>
+
+#include "flx_mapq.hpp"
+#include "flx_pipeline.hpp"
+#include "flx_select.hpp"
+
+namespace flx {
+
+namespace {
+
+struct half_open { u64 start, end; };
+half_open trim_both(half_open a, u64 amount) {                                                  // intervals.cpp:48-58
+    u64 const new_end = std::max(a.start + 1, amount > a.end ? 0 : a.end - amount);
+    u64 const new_start = std::min(new_end - 1, a.start + amount);
+    return {new_start, new_end};
+}
+struct VerifiedIntervals {                                                                     // intervals.cpp:84-127
+    hvec<half_open> ivs;
+    bool contains(half_open t) const {
+        for (auto const& e : ivs) if (e.start <= t.start && e.end >= t.end) return true;      // equal or contains
+        return false;
+    }
+    void insert(half_open t) { if (!contains(t)) ivs.push_back(t); }
+};
+
+Span compute_span(u64 anchor_pos, flx_pex_node const& node, u64 leaf_from, u64 reflen, double ratio) {   // verification.cpp:157-184
+    u64 const base = (u64)(node.to - node.from + 1) + 2ull * node.num_errors + 1;
+    u64 const extra = ratio == 0.0 ? 0 : fp_aware_ceil(base * ratio);        // (inner nodes: no extension, fp_aware_ceil(0) = 0)
+    i64 const start_signed = (i64)anchor_pos - (i64)(leaf_from - node.from) - (i64)node.num_errors - (i64)extra;
+    u64 const start = start_signed >= 0 ? (u64)start_signed : 0;
+    u64 const length = std::min(base + 2 * extra, reflen - start);
+    return {start, length, extra};
+}
+
+struct pr_task { int priority; int id; bool operator<(pr_task const& o) const { return priority < o.priority; } };
+// order in which one worker runs the verification packages of a read (BS::thread_pool's priority queue), parallelization.cpp:131-148
+hvec<int> package_order(int n) {
+    std::priority_queue<pr_task> q;
+    for (int i = 0; i < n; ++i) q.push(pr_task{16383, i});
+    q.push(pr_task{-16384, -1});
+    hvec<int> order;
+    while (!q.empty()) { pr_task t = q.top(); q.pop(); if (t.id < 0) break; order.push_back(t.id); }
+    return order;
+}
+
+// the window in which an anchor tests (or aligns) a node of its read's tree
+AlignRequest window_request(Slice const& S, HostIndex const& H, AnchorState const& a, flx_pex_node const& node, double ratio, Span* span_out) {
+    ReadState const& rs = S.reads[a.read];
+    flx_pex_node const& leaf = rs.tree_ref().leaves[a.leaf];
+    Span const sp = compute_span(a.pos, node, leaf.from, H.seq_len[a.ref_id], ratio);
+    if (span_out) *span_out = sp;
+    return AlignRequest{H.seq_start[a.ref_id] + sp.offset, rs.pool_off[a.orientation] + node.from, (u32)sp.length,
+                        node.to - node.from + 1, node.num_errors};
+}
+
+// ---- 1. reads -> PEX trees (parallelization.cpp:77-98); the reads that the input rules skip are marked in run->skipped
+int plan_reads(Slice& S, const flx_params* P, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run) {
+    hvec<ReadState>& reads = S.reads;
+    auto& tree_cache = S.tree_cache;
+    reads.reserve(end_read - first_read);
+    for (u64 i = first_read; i < end_read; ++i) {
+        u64 const len = RD->lens[i];
+        if (len == 0 || len > 100000) { run->skipped[i] = 1; continue; }                       // input.cpp:95-110
+        u64 const k = P->query_error_probability >= 0 ? fp_aware_ceil(len * P->query_error_probability) : P->query_num_errors;
+        if (len <= k || k < P->pex_seed_num_errors) { run->skipped[i] = 1; continue; }         // input.cpp:115-129
+        if (len > align_supported_max_query()) { set_error("read longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
+        ReadState rs;
+        rs.read_index = i;
+        rs.len = (u32)len;
+        rs.k = (u32)k;
+        {
+            auto it = tree_cache.find(std::make_pair(len, k));
+            if (it == tree_cache.end())
+                it = tree_cache.emplace(std::make_pair(len, k), std::make_unique<PexTree>(build_pex_tree(len, k, P->pex_seed_num_errors, P->bottom_up_pex_tree_building != 0))).first;
+            rs.tree_ptr = it->second.get();
+        }
+        rs.pool_off[0] = RD->pool_off[i];
+        rs.pool_off[1] = RD->pool_off[i] + len;
+        reads.push_back(std::move(rs));
+    }
+    return FLX_OK;
+}
+
+// the seeds as a list (the host's selection, statistics, FLX_HOST_SEEDS=1)
+void build_host_seeds(Slice& S, const flx_reads* RD) {
+    hvec<ReadState> const& reads = S.reads;
+    hvec<flx_seed>& seeds = S.seeds;
+    hvec<u8>& seed_flags = S.seed_flags;
+    u64 const step = S.step, n_seeds_total = S.seed_first[reads.size()];
+    seeds.clear(); seed_flags.clear();
+    seeds.reserve(n_seeds_total); seed_flags.reserve(n_seeds_total);
+    for (size_t r = 0; r < reads.size(); ++r)
+        for (int o = 0; o < 2; ++o)
+            for (u64 l = 0; l < reads[r].tree_ref().leaves.size(); l += step) {
+                flx_pex_node const& leaf = reads[r].tree_ref().leaves[l];
+                seeds.push_back(flx_seed{reads[r].pool_off[o] + leaf.from, leaf.to - leaf.from + 1, leaf.num_errors, (u32)l, 0});
+                seed_flags.push_back(RD->flags[reads[r].read_index]);
+            }
+}
+
+// ---- 2. the seeds: every step-th leaf of a read's tree, forward then reverse complement (pex.cpp:258-277). Seed s of the chunk =
+//      (read, orientation, leaf) by the reads' seed ranges: seed_first[r] .. seed_first[r + 1], n_sampled(r) per orientation.
+int plan_seeds(Slice& S, const flx_params* P, const flx_reads* RD) {
+    hvec<ReadState> const& reads = S.reads;
+    u64 const step = S.step = std::max<u64>(1, P->seed_sampling_step_size);
+    auto n_sampled = [&](ReadState const& r) { return S.n_sampled(r); };
+    hvec<u32>& seed_first = S.seed_first;
+    seed_first.assign(reads.size() + 1, 0);
+    for (size_t r = 0; r < reads.size(); ++r) seed_first[r + 1] = seed_first[r] + 2u * n_sampled(reads[r]);
+    u64 const n_seeds_total = seed_first[reads.size()];
+    // the same as a description the device writes the seeds from: per tree its sampled leaves with their class (errors, length) and rank
+    // within the class, per read where its seeds of each class start in launch order (heaviest class first: more errors, then shorter)
+    SeedGen& gen = S.gen;
+    bool const use_gen = S.use_gen = !getenv("FLX_HOST_SEEDS") && n_seeds_total > 0 && n_seeds_total < (1ull << 31);
+    if (use_gen) {
+        struct TreePlan { u32 leaf_first; hvec<u32> class_key, class_count; };
+        std::map<const PexTree*, TreePlan> plans;
+        struct GlobalClass { u64 pos = 0; u32 scheme_off = 0, nsearch = 0; };
+        std::map<u32, GlobalClass> global;                             // class key -> seeds of the class in the chunk, then its next launch position; its scheme
+        for (auto const& rs : reads) {
+            auto it = plans.find(rs.tree_ptr);
+            if (it == plans.end()) {
+                TreePlan tp;
+                tp.leaf_first = (u32)gen.leaves.size();
+                for (u64 l = 0; l < rs.tree_ref().leaves.size(); l += step) {
+                    flx_pex_node const& leaf = rs.tree_ref().leaves[l];
+                    u32 const length = leaf.to - leaf.from + 1, key = ((3u - std::min<u32>(leaf.num_errors, 3u)) << 24) | length;
+                    size_t c = 0;
+                    while (c < tp.class_key.size() && tp.class_key[c] != key) ++c;
+                    if (c == tp.class_key.size()) { tp.class_key.push_back(key); tp.class_count.push_back(0); }
+                    gen.leaves.push_back(DevSeedLeaf{leaf.from, length, (u32)c, tp.class_count[c]++});
+                    gen.max_errors = std::max(gen.max_errors, leaf.num_errors);
+                    gen.max_length = std::max(gen.max_length, length);
+                }
+                it = plans.emplace(rs.tree_ptr, std::move(tp)).first;
+            }
+            for (size_t c = 0; c < it->second.class_key.size(); ++c) global[it->second.class_key[c]].pos += 2ull * it->second.class_count[c];
+        }
+        if (gen.max_errors > 3) { set_error("seed errors must be in [0,3] (floxer_cli.cpp:299)"); return FLX_ERR_INVALID; }
+        u64 pos = 0;
+        for (auto& kv : global) {                                      // ascending key = heaviest class first
+            u32 const errors = 3u - (kv.first >> 24), length = kv.first & 0xFFFFFFu;
+            auto const e = expanded_scheme(errors, length);
+            kv.second.scheme_off = (u32)gen.scheme_table.size();
+            kv.second.nsearch = e.empty() ? 0 : (u32)(e.size() / length);
+            gen.scheme_table.insert(gen.scheme_table.end(), e.begin(), e.end());
+            u64 const n = kv.second.pos;
+            kv.second.pos = pos;
+            pos += n;
+        }
+        gen.reads.reserve(reads.size());
+        for (size_t r = 0; r < reads.size(); ++r) {
+            ReadState const& rs = reads[r];
+            TreePlan const& tp = plans.find(rs.tree_ptr)->second;
+            gen.reads.push_back(DevSeedRead{rs.pool_off[0], rs.pool_off[1], tp.leaf_first, n_sampled(rs), seed_first[r], (u32)gen.classes.size(), RD->flags[rs.read_index], 0});
+            for (size_t c = 0; c < tp.class_key.size(); ++c) {
+                auto& g = global[tp.class_key[c]];
+                u32 const errors = 3u - (tp.class_key[c] >> 24), length = tp.class_key[c] & 0xFFFFFFu;
+                gen.classes.push_back(DevSeedClass{(u32)g.pos, tp.class_count[c], g.scheme_off, (length + errors + 3) | (g.nsearch << 24)});
+                g.pos += 2ull * tp.class_count[c];
+            }
+        }
+        gen.n_seeds = n_seeds_total;
+    } else build_host_seeds(S, RD);
+    return FLX_OK;
+}
+
+// ---- 3. seeding: the anchors of the chunk's seeds, in seed order
+int search_seeds(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) {
+    hvec<u8> const& pool = RD->pool;
+    const u8* d_pool = RD->d_pool.as<u8>();
+    hvec<HostAnchor>& anchors = S.anchors;
+    hvec<SeedStats>& sstats = S.sstats;
+    // statistics in the reference's form (flx_stats.cpp), when the context has a statistics object attached
+    if (lane->ctx->read_stats) S.st_local = std::make_unique<Stats>(stats_simulated(lane->ctx->read_stats));
+    S.t_slice = std::chrono::steady_clock::now();
+    // (K1 starts behind K0 and the pool's 2-bit form: the event is recorded when the first call on these reads has queued both)
+    FLX_HIP(hipStreamWaitEvent(lane->stream, RD->peq_event, 0));
+    int rc = S.use_gen ? search_seeds_device(lane, d_pool, pool.data(), pool.size(), nullptr, 0, P->search, anchors, sstats, nullptr, 0,
+                                       RD->d_pack.ptr ? RD->d_pack.as<u32>() : nullptr, nullptr, &S.gen)
+                 : SEARCH_NEEDS_HOST_SEEDS;
+    if (rc == SEARCH_NEEDS_HOST_SEEDS) {
+        if (S.use_gen) build_host_seeds(S, RD);
+        rc = search_seeds_device(lane, d_pool, pool.data(), pool.size(), S.seeds.data(), S.seeds.size(), P->search, anchors, sstats, nullptr, 0,
+                                 RD->d_pack.ptr ? RD->d_pack.as<u32>() : nullptr, S.seed_flags.data());
+    }
+    return rc;
+}
+
+// per-query seed statistics, and every anchor's seed -> (read, orientation, leaf)
+void anchors_to_reads(Slice& S) {
+    hvec<ReadState>& reads = S.reads;
+    hvec<u32> const& seed_first = S.seed_first;
+    hvec<HostAnchor> const& anchors = S.anchors;
+    hvec<SeedStats> const& sstats = S.sstats;
+    u64 const step = S.step;
+    auto n_sampled = [&](ReadState const& r) { return S.n_sampled(r); };
+    Stats* const st_local = S.st_local.get();
+    double const search_ms = S.search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t_slice).count();
+    if (st_local) {
+        // per query: its length, its seeds (forward then reverse complement: one contiguous run of the seed list) and their
+        // selection counters (statistics.cpp:283-295, 367-419)
+        hvec<SeedStatRow> rows;
+        for (size_t r = 0; r < reads.size(); ++r) {
+            st_local->at(Stats::QUERY_LENGTHS).add(reads[r].len);
+            rows.clear();
+            u32 const nl = n_sampled(reads[r]);
+            for (u32 si = seed_first[r]; si < seed_first[r + 1]; ++si) {
+                flx_pex_node const& leaf = reads[r].tree_ref().leaves[(u64)((si - seed_first[r]) % nl) * step];
+                st_local->at(Stats::ERRORS_PER_SEED).add(leaf.num_errors);
+                st_local->at(Stats::SEED_LENGTHS).add(leaf.to - leaf.from + 1);
+                rows.push_back(SeedStatRow{sstats[si].useful, sstats[si].raw, sstats[si].excluded_soft});
+            }
+            st_local->at(Stats::SEEDS_PER_QUERY).add(rows.size());
+            st_local->add_search_result(rows.data(), rows.size());
+            st_local->at(Stats::MS_SEARCH).add((u64)(search_ms / (double)std::max<size_t>(1, reads.size())));
+        }
+    }
+    hvec<AnchorState>& A = S.A;
+    A.assign(anchors.size(), AnchorState{});
+    u32 rd_i = 0;
+    for (size_t a = 0; a < anchors.size(); ++a) {
+        // the anchor's seed -> (read, orientation, leaf); the anchors come seed by seed, so the read mostly stays or moves on by one
+        u32 const si = anchors[a].seed_index;
+        if (si < seed_first[rd_i] || si >= seed_first[rd_i + 1]) {
+            if (si >= seed_first[rd_i + 1] && rd_i + 2 < seed_first.size() && si < seed_first[rd_i + 2]) ++rd_i;
+            else rd_i = (u32)(std::upper_bound(seed_first.begin(), seed_first.end(), si) - seed_first.begin() - 1);
+        }
+        u32 const nl = n_sampled(reads[rd_i]), local = si - seed_first[rd_i];
+        u8 const orientation = local >= nl ? 1 : 0;
+        A[a].read = rd_i;
+        A[a].orientation = orientation;
+        A[a].leaf = (u32)((u64)(local - (orientation ? nl : 0u)) * step);
+        A[a].ref_id = anchors[a].ref_id;
+        A[a].pos = anchors[a].pos;
+        reads[rd_i].anchor_ids[orientation].push_back((u32)a);
+    }
+}
+
+// ---- 4. verification order of each read: packages (forward then reverse complement, <= N anchors each) in the order one
+//      worker would run them (parallelization.cpp:14-43, 230)
+void verification_order(Slice& S, const flx_params* P) {
+    hvec<ReadState> const& reads = S.reads;
+    hvec<hvec<u32>>& exec_order = S.exec_order;
+    exec_order.assign(reads.size(), hvec<u32>{});
+    for (size_t r = 0; r < reads.size(); ++r) {
+        hvec<std::pair<u32, u32>> pkgs;          // (first, count) into a concatenated list
+        hvec<u32> concat;
+        for (int o = 0; o < 2; ++o) {
+            auto const& ids = reads[r].anchor_ids[o];
+            for (size_t i = 0; i < ids.size(); i += P->num_anchors_per_verification_task) {
+                u32 const cnt = (u32)std::min<size_t>(P->num_anchors_per_verification_task, ids.size() - i);
+                pkgs.emplace_back((u32)concat.size(), cnt);
+                concat.insert(concat.end(), ids.begin() + i, ids.begin() + i + cnt);
+            }
+        }
+        for (int pid : package_order((int)pkgs.size()))
+            for (u32 j = 0; j < pkgs[pid].second; ++j) exec_order[r].push_back(concat[pkgs[pid].first + j]);
+    }
+}
+
+// ---- 5. hierarchical verification, level-synchronous (verification.cpp:44-117): inner nodes only test existence and do
+//      not depend on the interval cache, so all anchors climb together; an anchor stops at its first failing node.
+// every anchor's first inner node; returns how many anchors have one to test
+u32 start_climb(Slice& S, const flx_params* P) {
+    u32 n_climbing = 0;
+    for (auto& a : S.A) {
+        ReadState const& rs = S.reads[a.read];
+        flx_pex_node const& leaf = rs.tree_ref().leaves[a.leaf];
+        if (P->direct_full_verification || leaf.parent_id == FLX_NULL_ID) { a.at_root = true; continue; }   // verification.cpp:23-42, 52-72
+        a.node = leaf.parent_id;
+        if (rs.tree_ref().inner[a.node].parent_id == FLX_NULL_ID) a.at_root = true;
+        n_climbing += !a.at_root;
+    }
+    return n_climbing;
+}
+
+// Anchors do not wait for each other and their tests do not depend on any order, so a round tests the anchors whose
+// current node is in the smallest size class still pending (PEX trees are unbalanced: the same node is reached after a
+// different number of steps from different leaves). All tests of a node size then share one launch, and identical
+// (window, node) tests requested by anchors that started at different depths are found by the de-duplication.
+// The rounds run with the anchors' state resident on the device (requests, de-duplication, clusters and the moves up the trees
+// are kernels; the host launches K3 on each round's job list and decides per cluster). FLX_HOST_ROUNDS=1, or a statistics
+// object on the context (it wants every request's window), selects climb_on_host instead; both give the same records.
+int climb_on_device(Slice& S, Lane* lane, const flx_reads* RD) {
+    flx_ctx* ctx = lane->ctx;
+    HostIndex const& H = *ctx->hidx;
+    hvec<ReadState> const& reads = S.reads;
+    hvec<AnchorState>& A = S.A;
+    const u8* d_text = ctx->didx.text;
+    const u64* const d_peq = RD->d_peq.as<u64>();              // built once per resident read set (flx_align_reads_resident)
+    int rc;
+    u32 const n = (u32)A.size();
+    PhaseTimer vprof("rounds");
+    // ---- node table of the chunk's trees, anchors, the anchors of every query (read x orientation: contiguous, the anchors are in
+    //      seed order)
+    std::map<const PexTree*, u32> tree_base;
+    hvec<DevVrNode> nodes;
+    for (auto const& kv : S.tree_cache) {
+        PexTree const& t = *kv.second;
+        tree_base[&t] = (u32)nodes.size();
+        for (auto const& nd : t.inner) nodes.push_back(DevVrNode{nd.parent_id, nd.from, nd.to - nd.from + 1, nd.num_errors});
+    }
+    if (nodes.empty()) nodes.push_back(DevVrNode{0xFFFFFFFFu, 0, 1, 0});
+    u32 const n_queries = (u32)(2 * reads.size());
+    hvec<u32> q_first(n_queries + 1, 0);
+    hvec<DevVrAnchor> da(n);
+    hvec<u32> h_node(n);
+    hvec<u8> h_status(n);
+    u32 n_climbing = 0, smallest = 0xFFFFFFFFu;
+    for (u32 i = 0; i < n; ++i) {
+        AnchorState const& a = A[i];
+        ReadState const& rs = reads[a.read];
+        flx_pex_node const& leaf = rs.tree_ref().leaves[a.leaf];
+        u32 const tb = tree_base[rs.tree_ptr];
+        u32 const query = 2u * a.read + a.orientation;
+        q_first[query + 1]++;
+        da[i] = DevVrAnchor{(i64)a.pos - (i64)leaf.from, H.seq_start[a.ref_id], H.seq_len[a.ref_id], rs.pool_off[a.orientation], tb, query};
+        bool const climbs = a.alive && !a.at_root;
+        h_node[i] = climbs ? a.node : 0u;
+        h_status[i] = climbs ? VR_CLIMBING : a.at_root ? VR_AT_ROOT : VR_DEAD;
+        if (climbs) { ++n_climbing; smallest = std::min(smallest, nodes[tb + a.node].rows); }
+        if (i > 0 && 2u * A[i - 1].read + A[i - 1].orientation > query) { set_error("verification rounds: anchors out of query order"); return FLX_ERR_INTERNAL; }
+    }
+    for (u32 qi = 0; qi < n_queries; ++qi) q_first[qi + 1] += q_first[qi];
+    // ---- one device buffer cut into the arrays of Vr2Buffers
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t const at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    size_t const o_anchors = take((size_t)n * sizeof(DevVrAnchor)), o_nodes = take(nodes.size() * sizeof(DevVrNode)), o_qfirst = take(((size_t)n_queries + 1) * 4),
+                 o_node = take((size_t)n * 4), o_status = take(n), o_slot = take((size_t)n * 4), o_jobs = take((size_t)n * 2 * sizeof(DevAlignJob)),
+                 o_outs = take((size_t)n * 2 * sizeof(DevAlignOut)), o_scalars = take(VR2_SCALARS * 4);
+    vprof.mark("anchor-table");
+    if ((rc = lane->vr.ensure(off))) return rc;
+    char* const base = (char*)lane->vr.ptr;
+    Vr2Buffers B{};
+    B.anchors = (const DevVrAnchor*)(base + o_anchors); B.nodes = (const DevVrNode*)(base + o_nodes); B.q_first = (const u32*)(base + o_qfirst);
+    B.node = (u32*)(base + o_node); B.status = (u8*)(base + o_status); B.a_slot = (u32*)(base + o_slot);
+    B.jobs = (DevAlignJob*)(base + o_jobs); B.outs = (DevAlignOut*)(base + o_outs); B.scalars = (u32*)(base + o_scalars);
+    FLX_HIP(hipMemcpyAsync(base + o_anchors, da.data(), (size_t)n * sizeof(DevVrAnchor), hipMemcpyHostToDevice, lane->stream));
+    FLX_HIP(hipMemcpyAsync(base + o_nodes, nodes.data(), nodes.size() * sizeof(DevVrNode), hipMemcpyHostToDevice, lane->stream));
+    FLX_HIP(hipMemcpyAsync(base + o_qfirst, q_first.data(), ((size_t)n_queries + 1) * 4, hipMemcpyHostToDevice, lane->stream));
+    FLX_HIP(hipMemcpyAsync(base + o_node, h_node.data(), (size_t)n * 4, hipMemcpyHostToDevice, lane->stream));
+    FLX_HIP(hipMemcpyAsync(base + o_status, h_status.data(), n, hipMemcpyHostToDevice, lane->stream));
+    FLX_HIP(hipMemsetAsync(base + o_slot, 0xFF, (size_t)n * 4, lane->stream));
+    FLX_HIP(hipMemsetAsync(B.scalars, 0, VR2_SCALARS * 4, lane->stream));
+    if (!lane->vr_host_scalars) FLX_HIP(hipHostMalloc((void**)&lane->vr_host_scalars, VR2_SCALARS * 4, hipHostMallocMapped));
+    vprof.mark("upload");
+    u64 const few_waves = align_few_waves();
+    u64 prev_jobs = n_climbing / 2, acc_steps = 0, acc_bytes = 0, acc_req = 0;
+    for (u32 round = 0; n_climbing > 0; ++round) {
+        u64 const limit = (u64)smallest * round_span_percent() / 100;
+        // One launch shape for the round: the cheapest that holds the window of every node in the round's size class, or the one
+        // with the fewest words per lane when the round has few jobs (they would leave most SIMDs without a wave; the last round's
+        // job count is the estimate: either shape holds every job)
+        u32 nw_max = 0;
+        i64 width_max = 0;
+        for (auto const& nd : nodes)
+            if (nd.rows >= smallest && nd.rows <= limit) {
+                nw_max = std::max(nw_max, (nd.rows + 63u) / 64u);
+                width_max = std::max<i64>(width_max, 4 * (i64)nd.errors + 1);            // a window of its own: n - m + 2k = (2e + 1) + 2e
+            }
+        AlignShape const shape_t = DeviceApi::shape_holding(nw_max, width_max, false), shape_p = DeviceApi::shape_holding(nw_max, width_max, true);
+        if (shape_t.words_per_lane == 0 || shape_p.words_per_lane == 0) { set_error("query longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
+        AlignShape const shape = prev_jobs * shape_t.lanes_per_job / 64 >= few_waves ? shape_t : shape_p;
+        // what the shape holds beyond that goes to the clusters' union windows (a shape holds a job when every word group has a lane of
+        // its own, when the ring's lanes are free again before their next group starts: 64 W (R - 1) + R + 1 > diagonals, or when the
+        // steps a revolution of the ring has to wait fit the launch's hand-over slots: flx_internal.hpp, ring_delay)
+        u64 const width_cap = DeviceApi::shape_width_cap(nw_max, shape);
+        u32 const max_jobs = (u32)std::min<u64>(2ull * n_climbing, 2ull * n);
+        int const e1 = DeviceApi::vr2_request(lane->stream, B, n_queries, (u32)std::min<u64>(limit, 0xFFFFFFFFu), shape.words_per_lane,
+                                              (u32)std::min<u64>(width_cap, 0xFFFFFFFFull), round);
+        if (e1) { set_error(std::string("verification round: ") + hipGetErrorString((hipError_t)e1)); return FLX_ERR_NO_DEVICE; }
+        rc = timed_launch(lane, "ed_align_exists", 0, 0, [&] {
+            // (a fixed grid of at most this many waves takes the round's job groups in turn; FLX_EXISTS_MAX_WAVES: how much of the chip one
+            // round's launch may hold while the other lanes' kernels want room)
+            static u32 const exists_waves = [] { const char* e = getenv("FLX_EXISTS_MAX_WAVES"); return (u32)(e ? std::max(64, atoi(e)) : 8192); }();
+            return DeviceApi::align_exists_counted(lane->stream, d_text, d_peq, B.jobs, max_jobs, B.scalars + VR2_N_JOBS + (round & 1u), shape, exists_waves, B.outs, B.scalars + VR2_QUEUE_ERR);
+        });
+        if (rc) return rc;
+        int const e2 = DeviceApi::vr2_apply(lane->stream, B, n, lane->vr_host_scalars);
+        if (e2) { set_error(std::string("verification round: ") + hipGetErrorString((hipError_t)e2)); return FLX_ERR_NO_DEVICE; }
+        if ((rc = lane->sync())) return rc;
+        u32 sc[VR2_SCALARS];
+        memcpy(sc, lane->vr_host_scalars, sizeof(sc));            // (left there by the last block of vr2_apply)
+        if (sc[VR2_QUEUE_ERR]) { set_error("existence tests: a window did not fit the row buffers"); return FLX_ERR_INTERNAL; }
+        u64 ws, by;
+        memcpy(&ws, &sc[VR2_WORD_STEPS], 8);
+        memcpy(&by, &sc[VR2_BYTES], 8);
+        if (ctx->timing) {        // the round's word-steps and sequence bytes were counted on the device: fold them into the kernel's accounting
+            std::lock_guard<std::mutex> g(ctx->mu);
+            auto it = ctx->stats.find("ed_align_exists");
+            if (it != ctx->stats.end()) { it->second.algorithmic_bytes += by - acc_bytes; it->second.work_units += ws - acc_steps; }
+        }
+        u64 const round_req = sc[VR2_N_REQ] - acc_req;
+        acc_steps = ws; acc_bytes = by; acc_req = sc[VR2_N_REQ];
+        S.n_inner_requested += round_req;
+        if (round_req == 0 && sc[VR2_N_CLIMBING] >= n_climbing) { set_error("verification rounds do not advance"); return FLX_ERR_INTERNAL; }
+        prev_jobs = sc[VR2_N_JOBS + (round & 1u)];
+        n_climbing = sc[VR2_N_CLIMBING];
+        smallest = sc[VR2_SMALLEST];
+        vprof.mark("round");
+    }
+    if ((rc = d2h(lane, h_status.data(), B.status, n))) return rc;
+    if ((rc = d2h(lane, h_node.data(), B.node, (size_t)n * 4))) return rc;
+    if ((rc = lane->sync())) return rc;
+    for (u32 i = 0; i < n; ++i) {
+        AnchorState& a = A[i];
+        if (h_status[i] == VR_DEAD && a.alive && !a.at_root) a.alive = false;
+        else if (h_status[i] == VR_AT_ROOT && !a.at_root) { a.at_root = true; a.node = h_node[i]; }
+    }
+    vprof.mark("read-back");
+    return FLX_OK;
+}
+
+int climb_on_host(Slice& S, Lane* lane, const flx_reads* RD, ExistsTimes& times) {
+    flx_ctx* ctx = lane->ctx;
+    HostIndex const& H = *ctx->hidx;
+    hvec<ReadState> const& reads = S.reads;
+    hvec<AnchorState>& A = S.A;
+    const u8* d_text = ctx->didx.text;
+    const u64* const d_peq = RD->d_peq.as<u64>();
+    int rc;
+    hvec<u32> climbing;                 // anchors that still have an inner node to test (in anchor order)
+    for (u32 ai = 0; ai < A.size(); ++ai) if (A[ai].alive && !A[ai].at_root) climbing.push_back(ai);
+    hvec<AlignRequest> reqs;
+    hvec<DevAlignOut> outs;
+    auto rows_of = [&](AnchorState const& a) { flx_pex_node const& nd = reads[a.read].tree_ref().inner[a.node]; return nd.to - nd.from + 1; };
+    // `climbing` carries each anchor's node size next to its index (the rounds scan it): {anchor, rows}
+    struct Climber { u32 anchor, rows; };
+    hvec<Climber> climbers, sel, wait, surv;
+    u32 smallest = 0xFFFFFFFFu;
+    climbers.reserve(climbing.size());
+    for (u32 ai : climbing) { u32 const r = rows_of(A[ai]); climbers.push_back(Climber{ai, r}); smallest = std::min(smallest, r); }
+    while (!climbers.empty()) {
+        u64 const limit = (u64)smallest * round_span_percent() / 100;
+        auto const tb0 = std::chrono::steady_clock::now();
+        sel.clear();
+        wait.clear();
+        surv.clear();
+        reqs.clear();
+        u32 next_smallest = 0xFFFFFFFFu;
+        for (Climber const& c : climbers) {                  // both parts stay in anchor order
+            if (c.rows <= limit) {
+                sel.push_back(c);
+                reqs.push_back(window_request(S, H, A[c.anchor], reads[A[c.anchor].read].tree_ref().inner[A[c.anchor].node], 0.0, nullptr));
+            } else { wait.push_back(c); next_smallest = std::min(next_smallest, c.rows); }
+        }
+        times.build_requests += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+        S.n_inner_requested += reqs.size();
+        // (statistics: the inner tests are counted per anchor in the interval pass below - under -I the reference never starts on an
+        // anchor whose root window is already verified, verification.cpp:45)
+        if ((rc = run_exists_jobs(lane, d_text, d_peq, reqs, outs, times))) return rc;
+        for (size_t i = 0; i < outs.size(); ++i) {
+            AnchorState& a = A[sel[i].anchor];
+            if (outs[i].score == 0xFFFFFFFFu) { a.alive = false; continue; }
+            a.node = reads[a.read].tree_ref().inner[a.node].parent_id;
+            if (reads[a.read].tree_ref().inner[a.node].parent_id == FLX_NULL_ID) a.at_root = true;
+            else { u32 const r = rows_of(a); surv.push_back(Climber{sel[i].anchor, r}); next_smallest = std::min(next_smallest, r); }
+        }
+        climbers.resize(wait.size() + surv.size());
+        std::merge(wait.begin(), wait.end(), surv.begin(), surv.end(), climbers.begin(), [](Climber const& x, Climber const& y) { return x.anchor < y.anchor; });
+        smallest = next_smallest;
+    }
+    return FLX_OK;
+}
+
+// ---- 6. interval pass in verification order (verification.cpp:45, 106-109, 119-136): decides which anchors align the root
+void interval_pass(Slice& S, const flx_params* P, HostIndex const& H) {
+    hvec<ReadState> const& reads = S.reads;
+    hvec<AnchorState>& A = S.A;
+    hvec<hvec<u32>> const& exec_order = S.exec_order;
+    Stats* const st_local = S.st_local.get();
+    hvec<AlignRequest>& root_reqs = S.root_reqs;
+    hvec<u32>& root_anchor = S.root_anchor;
+    hvec<Span>& root_spans = S.root_spans;
+    // statistics: the inner nodes an anchor tested (verification.cpp:241) - its leaf's parent, upwards, to the node it failed at or to
+    // the node below the root
+    auto add_inner_spans = [&](AnchorState const& a) {
+        auto const& tree = reads[a.read].tree_ref();
+        flx_pex_node const& leaf = tree.leaves[a.leaf];
+        if (P->direct_full_verification || leaf.parent_id == FLX_NULL_ID) return;
+        for (u32 nd = leaf.parent_id; tree.inner[nd].parent_id != FLX_NULL_ID; nd = tree.inner[nd].parent_id) {
+            st_local->at(Stats::SPAN_INNER).add(window_request(S, H, a, tree.inner[nd], 0.0, nullptr).n);
+            if (!a.alive && nd == a.node) break;
+        }
+    };
+    for (size_t r = 0; r < reads.size(); ++r) {
+        hvec<VerifiedIntervals> cache[2];
+        if (P->use_interval_optimization) { cache[0].resize(H.seq_len.size()); cache[1].resize(H.seq_len.size()); }
+        for (u32 ai : exec_order[r]) {
+            AnchorState& a = A[ai];
+            ReadState const& rs = reads[a.read];
+            Span sp;
+            AlignRequest const req = window_request(S, H, a, rs.tree_ref().root(), P->extra_verification_ratio, &sp);
+            if (P->use_interval_optimization) {
+                auto& ivs = cache[a.orientation][a.ref_id];
+                if (ivs.contains(trim_both({sp.offset, sp.offset + sp.length}, sp.extra))) {           // root_was_already_verified
+                    if (st_local) st_local->at(Stats::SPAN_ROOT_AVOIDED).add(sp.length);                // verification.cpp:130
+                    continue;
+                }
+                if (st_local) add_inner_spans(a);
+                if (!(a.alive && a.at_root)) continue;
+                ivs.insert({sp.offset, sp.offset + sp.length});
+            } else {
+                if (st_local) add_inner_spans(a);
+                if (!(a.alive && a.at_root)) continue;
+            }
+            a.wants_root = true;
+            if (st_local) st_local->at(Stats::SPAN_ROOT).add(sp.length);                               // verification.cpp:239
+            root_reqs.push_back(req);
+            root_anchor.push_back(ai);
+            root_spans.push_back(sp);
+        }
+    }
+}
+
+// ---- 7. root alignments (alignment.cpp:115-180)
+int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) {
+    flx_ctx* ctx = lane->ctx;
+    HostIndex const& H = *ctx->hidx;
+    hvec<u8> const& pool = RD->pool;
+    hvec<AlignRequest> const& root_reqs = S.root_reqs;
+    hvec<Span> const& root_spans = S.root_spans;
+    hvec<RootAlignment>& root_res = S.root_res;
+    root_res.assign(root_reqs.size(), RootAlignment{});
+    int rc;
+    if (P->without_cigar) {
+        if ((rc = ensure_reversed_text(lane))) return rc;
+        {
+            std::lock_guard<std::mutex> g(RD->peq_mu);
+            if (!RD->rev_built) {
+                hvec<u8> qrev(pool.rbegin(), pool.rend());
+                take_spare_read_buffer(ctx, 3, RD->d_pool_rev);
+                take_spare_read_buffer(ctx, 4, RD->d_peq_rev);
+                if ((rc = RD->d_pool_rev.ensure(qrev.size() + 256))) return rc;
+                FLX_HIP(hipMemcpyAsync(RD->d_pool_rev.ptr, qrev.data(), qrev.size(), hipMemcpyHostToDevice, lane->stream));
+                FLX_HIP(hipMemsetAsync((char*)RD->d_pool_rev.ptr + qrev.size(), 0, 192, lane->stream));
+                if ((rc = build_peq(lane, RD->d_pool_rev.as<u8>(), qrev.size(), RD->d_peq_rev))) return rc;
+                if (!RD->rev_event) FLX_HIP(hipEventCreateWithFlags(&RD->rev_event, hipEventDisableTiming));
+                FLX_HIP(hipEventRecord(RD->rev_event, lane->stream));
+                FLX_HIP(hipStreamSynchronize(lane->stream));        // qrev leaves scope
+                RD->rev_built = true;
+            }
+        }
+        FLX_HIP(hipStreamWaitEvent(lane->stream, RD->rev_event, 0));
+        hvec<AlignRequest> rev(root_reqs.size());
+        for (size_t i = 0; i < rev.size(); ++i)
+            rev[i] = AlignRequest{H.n - root_reqs[i].ref_off - root_reqs[i].n, pool.size() - root_reqs[i].q_off - root_reqs[i].m,
+                                  root_reqs[i].n, root_reqs[i].m, root_reqs[i].k};
+        hvec<DevAlignOut> outs;
+        if ((rc = run_score_jobs(lane, ctx->text_rev.as<u8>() + TEXT_PAD, RD->d_peq_rev.as<u64>(), rev, outs, "ed_align_exists"))) return rc;
+        for (size_t i = 0; i < outs.size(); ++i)
+            if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
+    } else {
+        hvec<TraceResult> tres;
+        if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_pool.as<u8>(), RD->d_peq.as<u64>(), root_reqs, tres, S.cig))) return rc;
+        for (size_t i = 0; i < tres.size(); ++i)
+            if (tres[i].exists) root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len};
+    }
+    return FLX_OK;
+}
+
+// the CIGAR words of the kept records only: records that shared (or overlapped in) words before share them afterwards
+void compact_cigars(flx_run* run, hvec<u32>& cig) {
+    hvec<u32> order;
+    for (u32 j = 0; j < run->records.size(); ++j) {
+        if (run->records[j].cigar_length) order.push_back(j);
+        else run->records[j].cigar_offset = 0;
+    }
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return run->records[a].cigar_offset < run->records[b].cigar_offset; });
+    hvec<u32> kept_words;
+    u64 seg_start = 0, seg_end = 0, seg_base = 0;
+    for (u32 j : order) {
+        flx_record& rec = run->records[j];
+        u64 const off = rec.cigar_offset, end = off + rec.cigar_length;
+        if (kept_words.empty() || off >= seg_end) {
+            seg_start = off; seg_end = end; seg_base = kept_words.size();
+            kept_words.insert(kept_words.end(), cig.begin() + (long)off, cig.begin() + (long)end);
+        } else if (end > seg_end) {
+            kept_words.insert(kept_words.end(), cig.begin() + (long)seg_end, cig.begin() + (long)end);
+            seg_end = end;
+        }
+        rec.cigar_offset = seg_base + (off - seg_start);
+    }
+    cig.swap(kept_words);
+}
+
+// ---- 8. records (alignment.cpp:37-79, output.cpp:49-108): per reference in id order, alignments in verification order
+void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_slice_reads, flx_run* run) {
+    HostIndex const& H = *ctx->hidx;
+    hvec<ReadState> const& reads = S.reads;
+    hvec<AnchorState> const& A = S.A;
+    hvec<u32> const& root_anchor = S.root_anchor;
+    hvec<RootAlignment> const& root_res = S.root_res;
+    hvec<u32>& cig = S.cig;
+    Stats* const st_local = S.st_local.get();
+    hvec<hvec<u32>> roots_of_read(reads.size());
+    for (u32 i = 0; i < root_anchor.size(); ++i) roots_of_read[A[root_anchor[i]].read].push_back(i);   // already in verification order
+    // output options (flx_select.hpp): a read's records are selected once they are formed and its statistics are taken
+    bool const select = output_options_active(O);
+    u64 n_dropped = 0;
+    std::vector<SelectKey> sel_keys;
+    std::vector<u8> sel_keep;
+    SelectScratch sel_scratch;
+    // mapping quality (flx_mapq.hpp): from all of a read's records, before any of them is dropped
+    bool const mapq = O && O->mapq;
+    std::vector<MapqKey> mq_keys;
+    std::vector<u8> mq_q;
+    MapqScratch mq_scratch;
+    for (size_t r = 0; r < reads.size(); ++r) {
+        size_t const rec0 = run->records.size();
+        bool have_best = false;
+        u32 best = 0;
+        for (u32 i : roots_of_read[r]) if (root_res[i].exists && (!have_best || root_res[i].nm < best)) { best = root_res[i].nm; have_best = true; }
+        bool primary_written = false;
+        for (u32 ref = 0; ref < H.seq_len.size(); ++ref)
+            for (u32 i : roots_of_read[r]) {
+                AnchorState const& a = A[root_anchor[i]];
+                if (a.ref_id != ref || !root_res[i].exists) continue;
+                u32 flag = a.orientation ? 16u : 0u;
+                bool const primary = !primary_written && root_res[i].nm == best;
+                if (primary) primary_written = true;
+                else flag |= 256u;
+                run->records.push_back(flx_record{reads[r].read_index, flag, (int32_t)ref, saturate_i32(root_res[i].start), root_res[i].nm,
+                                                  root_res[i].cigar_off, root_res[i].cigar_len, 0});
+                if (mapq) {
+                    if (mq_keys.empty()) mq_scratch.spans.clear();
+                    u64 const span = root_res[i].cigar_len ? cigar_reference_span_cached(cig.data() + root_res[i].cigar_off, root_res[i].cigar_len, mq_scratch)
+                                                           : reads[r].len;
+                    mq_keys.push_back(MapqKey{root_res[i].start, span, (int32_t)ref, flag, root_res[i].nm});
+                }
+            }
+        if (!primary_written) run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
+        if (mapq && !mq_keys.empty()) {
+            mq_q.resize(mq_keys.size());
+            read_mapq(mq_keys.data(), mq_keys.size(), mq_q.data(), mq_scratch);
+            for (size_t j = 0; j < mq_keys.size(); ++j) run->records[rec0 + j].reserved = mq_q[j];
+            mq_keys.clear();
+        }
+        if (select && run->records.size() - rec0 > 1) {
+            // (records in the loop's order: the read's mapped roots by reference, the start key unsaturated)
+            size_t const n = run->records.size() - rec0;
+            sel_keys.clear();
+            for (u32 ref = 0; ref < H.seq_len.size(); ++ref)
+                for (u32 i : roots_of_read[r]) {
+                    if (A[root_anchor[i]].ref_id != ref || !root_res[i].exists) continue;
+                    flx_record const& rec = run->records[rec0 + sel_keys.size()];
+                    sel_keys.push_back(SelectKey{root_res[i].start, rec.reference_id, rec.flag, rec.num_errors, rec.cigar_length,
+                                                 rec.cigar_length ? cig.data() + rec.cigar_offset : nullptr});
+                }
+            sel_keep.resize(n);
+            select_read_records(sel_keys.data(), n, O->drop_duplicates != 0, O->max_alignments_per_read, sel_keep.data(), sel_scratch);
+            size_t w = rec0;
+            for (size_t j = 0; j < n; ++j)
+                if (sel_keep[j]) run->records[w++] = run->records[rec0 + j];
+            n_dropped += run->records.size() - w;
+            run->records.resize(w);
+        }
+        if (st_local) {                                                                                  // parallelization.cpp:262-268
+            u64 n_al = 0;
+            for (u32 i : roots_of_read[r]) if (root_res[i].exists) { ++n_al; st_local->at(Stats::EDIT_DISTANCE).add(root_res[i].nm); }
+            st_local->at(Stats::ALIGNMENTS_PER_QUERY).add(n_al);
+        }
+    }
+    if (st_local) {
+        double const total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S.t_slice).count();
+        for (size_t r = 0; r < reads.size(); ++r) st_local->at(Stats::MS_VERIFICATION).add((u64)((total_ms - S.search_ms) / (double)std::max<size_t>(1, reads.size())));
+        stats_merge_locked(ctx->read_stats, *st_local);
+    }
+    if (select) compact_cigars(run, cig);
+    run->cigars = std::move(cig);
+    {
+        u64 found = 0;
+        for (auto const& rr : root_res) found += rr.exists;
+        std::lock_guard<std::mutex> g(ctx->mu);
+        flx_path_counters& pc = ctx->path;
+        pc.inner_tests_requested += S.n_inner_requested; pc.root_alignments_requested += S.root_reqs.size(); pc.root_alignments_found += found;
+        pc.records += run->records.size(); pc.reads += n_slice_reads; pc.reserved[0] += n_dropped;
+    }
+}
+
+}  // namespace
+
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run) {
+    flx_ctx* ctx = lane->ctx;
+    FLX_HIP(hipSetDevice(ctx->device));
+    HostIndex const& H = *ctx->hidx;
+    PhaseTimer prof;
+    Slice S;
+    int rc;
+    if ((rc = plan_reads(S, P, RD, first_read, end_read, run))) return rc;
+    if ((rc = plan_seeds(S, P, RD))) return rc;
+    prof.mark("pex+seeds");
+    if ((rc = search_seeds(S, lane, P, RD))) return rc;
+    prof.mark("search");
+    anchors_to_reads(S);
+    verification_order(S, P);
+    prof.mark("anchors+order");
+    FLX_HIP(hipStreamWaitEvent(lane->stream, RD->peq_event, 0));      // the DP launches start behind the Peq planes of the whole pool
+    u32 const n_climbing = start_climb(S, P);
+    static int const host_rounds = getenv("FLX_HOST_ROUNDS") ? 1 : 0;
+    ExistsTimes times;
+    if (!host_rounds && !S.st_local && n_climbing) rc = climb_on_device(S, lane, RD);
+    else rc = climb_on_host(S, lane, RD, times);
+    if (rc) return rc;
+    prof.mark("inner-levels");
+    if (prof.on)
+        fprintf(stderr, "[flx host profile] exists rounds: dedup=%.2f cluster=%.2f gpu-round-trip=%.2f scatter=%.2f build-requests=%.2f ms\n",
+                times.ms[0], times.ms[1], times.ms[2], times.ms[3], times.build_requests);
+    interval_pass(S, P, H);
+    prof.mark("interval-pass");
+    if ((rc = align_roots(S, lane, P, RD))) return rc;
+    prof.mark("root-align");
+    write_records(S, ctx, O, end_read - first_read, run);
+    prof.mark("records");
+    return FLX_OK;
+}
+
+}  // namespace flx
