@@ -25,10 +25,9 @@ u64 align_few_waves() {
 
 namespace {
 
-// word-steps the launch really performs for one job: the whole matrix, or only the band -k <= col-row <= n-m+k
+// word-steps the launch really performs for one job: only the band -k <= col-row <= n-m+k
 u64 job_word_steps(u32 n, u32 m, u32 k, AlignShape sh) {
     u64 const nw = (m + 63) / 64;
-    if (!sh.banded) return (u64)n * nw;
     i64 const W = sh.words_per_lane, band_hi = (i64)n - (i64)m + (i64)k;
     u64 total = 0;
     for (i64 g = 0; g * W < (i64)nw; ++g) {
@@ -40,8 +39,8 @@ u64 job_word_steps(u32 n, u32 m, u32 k, AlignShape sh) {
 }
 
 struct ShapeKey {
-    u32 w, g, banded;
-    bool operator<(ShapeKey const& o) const { return w != o.w ? w < o.w : g != o.g ? g < o.g : banded < o.banded; }
+    u32 w, g;
+    bool operator<(ShapeKey const& o) const { return w != o.w ? w < o.w : g < o.g; }
 };
 
 // Anchors of one locus produce many identical (window, node) jobs (sibling leaves share their parent's window, anchors with the
@@ -95,8 +94,8 @@ int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
     auto fits = [](AlignRequest const& r, AlignShape const& sh) {
         u32 const nw = (r.m + 63) / 64, W = sh.words_per_lane, R = sh.lanes_per_job;
         i64 const width = (i64)r.n - (i64)r.m + 2 * (i64)r.k;
-        if ((nw + W - 1) / W <= R || (sh.banded && (i64)64 * W * (R - 1) + R + 1 > width)) return true;
-        return sh.banded && sh.queue != 0 && ring_delay(r.n, r.m, r.k, W, R) + 1u <= RING_QUEUE_MAX;      // (a ring that waits: DeviceApi::align gives it the largest queue)
+        if ((nw + W - 1) / W <= R || (i64)64 * W * (R - 1) + R + 1 > width) return true;
+        return sh.queue != 0 && ring_delay(r.n, r.m, r.k, W, R) + 1u <= RING_QUEUE_MAX;      // (a ring that waits: DeviceApi::align gives it the largest queue)
     };
     if (!reqs.empty() && lanes / 64 >= align_few_waves()) {
         // A launch lasts at least as long as its longest job, and the jobs of a batch differ by a few columns (unions of a locus' windows): the
@@ -116,15 +115,15 @@ int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
         }
         // a handful of jobs with a shape of their own join the most common shape that can hold them instead of getting a launch
         std::map<ShapeKey, std::pair<u32, u32>> count;       // jobs, queue
-        for (auto const& sh : shapes) { auto& c = count[ShapeKey{sh.words_per_lane, sh.lanes_per_job, sh.banded}]; c.first++; c.second = std::max(c.second, sh.queue); }
+        for (auto const& sh : shapes) { auto& c = count[ShapeKey{sh.words_per_lane, sh.lanes_per_job}]; c.first++; c.second = std::max(c.second, sh.queue); }
         if (count.size() > 1) {
             for (size_t i = 0; i < reqs.size(); ++i) {
-                ShapeKey const mine{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded};
+                ShapeKey const mine{shapes[i].words_per_lane, shapes[i].lanes_per_job};
                 if (count[mine].first >= 64) continue;
                 u32 best_n = 0;
                 AlignShape best = shapes[i];
                 for (auto const& kv : count) {
-                    AlignShape const cand{kv.first.w, kv.first.g, kv.first.banded, kv.second.second};
+                    AlignShape const cand{kv.first.w, kv.first.g, kv.second.second};
                     if (kv.second.first >= 64 && kv.second.first > best_n && fits(reqs[i], cand)) { best_n = kv.second.first; best = cand; }
                 }
                 shapes[i] = best;
@@ -133,7 +132,7 @@ int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
         return FLX_OK;
     }
     if (reqs.empty()) return FLX_OK;
-    AlignShape common{0, 0, shapes[0].banded};
+    AlignShape common{0, 0};
     for (size_t i = 0; i < reqs.size(); ++i) {
         AlignShape const p = choose_align_shape(reqs[i].n, reqs[i].m, reqs[i].k, true);
         if (p.words_per_lane > common.words_per_lane) common.words_per_lane = p.words_per_lane;
@@ -143,7 +142,7 @@ int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
         u32 const nw = (reqs[i].m + 63) / 64, W = common.words_per_lane;
         i64 const width = (i64)reqs[i].n - (i64)reqs[i].m + 2 * (i64)reqs[i].k;
         u32 r = 1;
-        while (r < 64 && !((nw + W - 1) / W <= r || (common.banded && (i64)64 * W * (r - 1) + r + 1 > width))) r *= 2;
+        while (r < 64 && !((nw + W - 1) / W <= r || (i64)64 * W * (r - 1) + r + 1 > width)) r *= 2;
         if (r > common.lanes_per_job) common.lanes_per_job = r;
     }
     for (auto& sh : shapes) sh = common;
@@ -159,7 +158,7 @@ template <class PerJob>
 int launch_by_shape(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<AlignShape> const& shapes, size_t begin, size_t end,
                     const char* kernel_name, const char* what, bool trace, u16* d_lastrow, PerJob&& per_job) {
     std::map<ShapeKey, hvec<u32>> by_shape;
-    for (size_t i = begin; i < end; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job, shapes[i].banded}].push_back((u32)i);
+    for (size_t i = begin; i < end; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job}].push_back((u32)i);
     hvec<DevAlignJob> jobs;
     jobs.reserve(end - begin);
     hvec<ShapeLaunch> launches;
@@ -179,9 +178,9 @@ int launch_by_shape(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
     if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
     if ((rc = ctx->job_out.ensure((end - begin) * sizeof(DevAlignOut)))) return rc;
     for (auto const& l : launches) {
-        if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[%s]%s W %u R %u banded %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", kernel_name, what, l.key.w, l.key.g, l.key.banded, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
+        if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[%s]%s W %u R %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", kernel_name, what, l.key.w, l.key.g, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
         rc = timed_launch(ctx, kernel_name, l.bytes, l.word_steps, [&] {
-            return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count, AlignShape{l.key.w, l.key.g, l.key.banded}, trace,
+            return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count, AlignShape{l.key.w, l.key.g}, trace,
                                     trace ? ctx->trace.as<u64>() : nullptr, ctx->job_out.as<DevAlignOut>(), d_lastrow);
         });
         if (rc) return rc;
@@ -208,7 +207,7 @@ int run_score_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
 }
 
 // score, begin position and CIGAR for every (distinct) request
-int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                           hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
@@ -234,12 +233,11 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u8* d_query, const 
 
         hvec<u64> trace_off(count);
         u64 off = 0;
-        // (bytes: reference + query symbols read; trace written: full form 16 B per word-step, checkpointed form its carry and checkpoint regions)
+        // (bytes: reference + query symbols read; trace written: the checkpointed trace's carry and checkpoint regions)
         rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, begin, next, "ed_align_trace", "", true, nullptr, [&](u32 id, DevAlignJob& job) {
             AlignRequest const& r = reqs[id];
             job.trace_off = trace_off[id - begin] = off;
             off += slots[id];
-            if (!shapes[id].banded) return job_word_steps(r.n, r.m, r.k, shapes[id]) * 16;
             TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
             return (tl.carry_slots + tl.ckpt_slots) * 16;
         });
@@ -258,10 +256,8 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u8* d_query, const 
             size_t const id = begin + c;
             AlignRequest const& r = reqs[id];
             AlignShape const sh = shapes[id];
-            u32 const nw = (r.m + 63) / 64;
-            u32 const L = sh.banded ? sh.lanes_per_job : (nw + sh.words_per_lane - 1) / sh.words_per_lane;
             u32 const cap = 2 * outs[c].score + 2;      // runs <= 2*NM + 1
-            tjobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off[c], cigar_words, r.n, r.m, L, sh.words_per_lane, outs[c].end_col,
+            tjobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off[c], cigar_words, r.n, r.m, sh.lanes_per_job, sh.words_per_lane, outs[c].end_col,
                                         cap, (u32)tjob_req.size(), r.k});
             tjob_req.push_back((u32)id);
             cigar_words += cap;
@@ -272,8 +268,8 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u8* d_query, const 
             if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
             if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
             rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
-                return DeviceApi::traceback(ctx->stream, d_text, d_query, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(),
-                                            (u32)tjobs.size(), shapes[begin].banded != 0, ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
+                return DeviceApi::traceback(ctx->stream, d_text, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(), (u32)tjobs.size(),
+                                            ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
             });
             if (rc) return rc;
             tprof.mark("tb-prep");
@@ -315,13 +311,13 @@ int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequ
 }
 
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
-int run_trace_jobs(Lane* ctx, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                    hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
     hvec<AlignRequest> uniq;
     hvec<u32> uniq_of;
     dedup_requests(reqs, uniq, uniq_of);
     hvec<TraceResult> ures;
-    int rc = run_trace_jobs_unique(ctx, d_text, d_query, d_peq, uniq, ures, cigar_pool);
+    int rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool);
     if (rc) return rc;
     results.resize(reqs.size());
     for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
@@ -460,13 +456,13 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
 // The band of U contains the band of every member, and a banded value is exact whenever it is <= k.
 constexpr u64 UNION_MAX_SHIFT = 256;      // members start within this many columns of the first member of their union
 
-int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                          hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
     hvec<AlignRequest> uniq;
     hvec<u32> uniq_of;
     dedup_requests(reqs, uniq, uniq_of);
     hvec<TraceResult> ures(uniq.size());
-    bool usable = !uniq.empty() && choose_align_shape(uniq[0].n, uniq[0].m, uniq[0].k).banded != 0 && !getenv("FLX_NO_UNION");
+    bool usable = !uniq.empty() && !getenv("FLX_NO_UNION");
     for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
     // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
     struct Union { AlignRequest req; u32 first_member, n_members; };
@@ -499,7 +495,7 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u8* d_query, const u
         }
     }
     if (!usable || unions.size() == uniq.size()) {          // nothing to share: the plain path
-        int const rc = run_trace_jobs_unique(ctx, d_text, d_query, d_peq, uniq, ures, cigar_pool);
+        int const rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool);
         if (rc) return rc;
         results.resize(reqs.size());
         for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
@@ -601,8 +597,8 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u8* d_query, const u
             if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
             if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
             rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
-                return DeviceApi::traceback(ctx->stream, d_text, d_query, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(),
-                                            (u32)tjobs.size(), true, ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
+                return DeviceApi::traceback(ctx->stream, d_text, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(), (u32)tjobs.size(),
+                                            ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
             });
             if (rc) return rc;
             cigar_pool.resize(pool_base + cigar_words);
@@ -629,7 +625,7 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u8* d_query, const u
     }
     if (!fallback.empty()) {
         hvec<TraceResult> fres;
-        if ((rc = run_trace_jobs_unique(ctx, d_text, d_query, d_peq, fallback, fres, cigar_pool))) return rc;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
     if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", reqs.size(), uniq.size(), unions.size(), fallback.size());
@@ -736,7 +732,7 @@ extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t r
         }
     hvec<TraceResult> tres;
     hvec<u32> cig;
-    if ((rc = run_trace_jobs(L, d_text, L->seq.as<u8>(), L->peq.as<u64>(), trace_reqs, tres, cig))) return rc;
+    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig))) return rc;
     uint64_t const cap = cigar_pool_words ? *cigar_pool_words : 0;
     if (cigar_pool_words) *cigar_pool_words = cig.size();
     if (any_trace && (!cigar_pool || cig.size() > cap)) { set_error("cigar pool too small"); return FLX_ERR_CAPACITY; }

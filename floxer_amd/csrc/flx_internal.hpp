@@ -188,9 +188,9 @@ struct Vr2Buffers {
 };
 
 // launch geometry for one alignment job shape. queue: hand-over slots per job in LDS (a power of two; 0: the ring never waits, see ring_delay)
-struct AlignShape { u32 words_per_lane; u32 lanes_per_job; u32 banded; u32 queue = 0; };
+struct AlignShape { u32 words_per_lane; u32 lanes_per_job; u32 queue = 0; };
 
-// Banded TRACE launches (K4) do not store the trace itself. A lane computes its word group 16 columns (one block) per step, group g
+// TRACE launches (K4) do not store the trace itself. A lane computes its word group 16 columns (one block) per step, group g
 // takes block b at block-step T = b + g; per (block-step, ring lane, word) the launch keeps the 16 pairs of horizontal-delta bits
 // that enter the word from above (one u32) and the word's vertical delta vectors {vp, vn} before the block (one 16-byte slot). Any
 // word's trace bits over any block are recomputed from those by the traceback kernel (1.25 B instead of 16 B per column and word).
@@ -251,7 +251,8 @@ u64 align_trace_slots(u32 n, u32 m, u32 k, AlignShape sh);     // 16-byte trace 
 u32 align_supported_max_query();
 u32 fm_search_max_keyed_length();
 
-// ------------------------------------------------------------------------------------------------ device launchers (flx_device.hip)
+// ------------------------------------------------------------------------------------------------ device launchers (flx_index_build.hip,
+// flx_search_ordered.hip, flx_search.hip, flx_select.hip, flx_rounds.hip; the edit-distance kernels: flx_device.hip)
 struct KernelTimer;   // opaque, owned by the context
 
 struct DeviceApi {
@@ -300,7 +301,7 @@ struct DeviceApi {
                       bool erase, void* d_stat, u32* d_n_out, u32* d_out_offset, DevOutAnchor* d_out, u32 out_cap, u32* d_rows,
                       u32* d_row_offset, DevOutAnchor* d_sparse, u32 sparse_cap, void* d_scan_tmp, size_t scan_bytes, u32* d_lists);
     static int locate(void* stream, const DevIndex& idx, const u32* d_rows, u32 n, u32* d_out);
-    // d_lastrow (banded TRACE launches only, may be null): D[m][c] of every computed column c, 0xFFFF elsewhere (pre-filled by the caller)
+    // d_lastrow (TRACE launches only, may be null): D[m][c] of every computed column c, 0xFFFF elsewhere (pre-filled by the caller)
     static int align(void* stream, const u8* d_text, const u64* d_peq, const DevAlignJob* d_jobs, u32 n_jobs, AlignShape shape,
                      bool trace, u64* d_trace, DevAlignOut* d_out, u16* d_lastrow = nullptr);
     // flx_rounds.hip: a round = vr2_request (job list and count on the device), align_exists_counted on it, vr2_apply
@@ -311,8 +312,8 @@ struct DeviceApi {
     static AlignShape shape_holding(u32 nw, i64 width, bool parallel);
     static u64 shape_width_cap(u32 nw, AlignShape sh);       // the widest band (n - m + 2k) the shape holds for jobs of nw words
     static int lastrow_min(void* stream, const u16* d_lastrow, const DevRowWindow* d_windows, u32 n_windows, DevAlignOut* d_out);
-    static int traceback(void* stream, const u8* d_text, const u8* d_query, const u64* d_peq, const u64* d_trace,
-                         const DevTraceJob* d_jobs, u32 n_jobs, bool checkpointed, u32* d_cigar, DevTraceOut* d_out);
+    static int traceback(void* stream, const u8* d_text, const u64* d_peq, const u64* d_trace, const DevTraceJob* d_jobs, u32 n_jobs,
+                         u32* d_cigar, DevTraceOut* d_out);
 };
 
 // ------------------------------------------------------------------------------------------------ host logic

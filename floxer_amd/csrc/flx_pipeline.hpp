@@ -115,10 +115,10 @@ u64 align_few_waves();          // FLX_ALIGN_FEW_WAVES overrides the threshold (
 // score + end column for every request (no trace)
 int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, const char* kernel_name);
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
-int run_trace_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                    hvec<TraceResult>& results, hvec<u32>& cigar_pool);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
-int run_trace_jobs_union(Lane* lane, const u8* d_text, const u8* d_query, const u64* d_peq, hvec<AlignRequest> const& reqs,
+int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                          hvec<TraceResult>& results, hvec<u32>& cigar_pool);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
 int run_exists_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, ExistsTimes& times);

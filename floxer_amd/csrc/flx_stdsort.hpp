@@ -1,4 +1,4 @@
-// libstdc++'s std::sort reproduced step for step, for host and device (see seed_select_kernel in flx_device.hip: the reference orders
+// libstdc++'s std::sort reproduced step for step, for host and device (see seed_select_kernel in flx_select.hip: the reference orders
 // hit groups and anchor buckets with std::sort, its comparators tie, and what std::sort does with equal elements shows in the
 // output). tests/stdsort_check.cpp compares it with the real std::sort.
 #pragma once

@@ -565,7 +565,7 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) 
             if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
     } else {
         hvec<TraceResult> tres;
-        if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_pool.as<u8>(), RD->d_peq.as<u64>(), root_reqs, tres, S.cig))) return rc;
+        if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), root_reqs, tres, S.cig))) return rc;
         for (size_t i = 0; i < tres.size(); ++i)
             if (tres[i].exists) root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len};
     }

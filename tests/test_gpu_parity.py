@@ -613,24 +613,15 @@ def test_root_unions_and_their_fallback():
     assert forced == exp.records()
 
 
-def test_existence_kernel_forms_give_the_same_records():
-    """the existence tests run as a ring of lanes per job over the static band, 16 columns per step (ed_exists_block_kernel), by default;
-    one column per step with FLX_EXISTS_STEPWISE=1 (ed_band_kernel). The switch is read once per process, so the stepwise form runs in a
-    child: same records, both equal to the oracle's, on reads whose trees reach every launch shape of the lower levels and the
-    ring-scheduled upper ones"""
-    import subprocess, sys, json
+def test_existence_block_form_on_6kb_reads_matches_oracle():
+    """the existence tests run as a ring of lanes per job over the static band, 16 columns per step (ed_exists_block_kernel): records
+    equal to the oracle's on reads whose trees reach every launch shape of the lower levels and the ring-scheduled upper ones"""
     genome = S.make_genome(500000, 2, seed=161)
     reads, _, _ = S.make_reads(genome, 24, 6000, 0.08, seed=162)
     exp = O.Index(genome).run(reads, O.params(error_probability=0.08), threads=8)
     ctx = F.context(F.fmindex(genome))
     assert F.aligner(ctx, F.params(error_probability=0.08)).align_reads(reads).records() == exp.records()
     ctx.close()
-    code = ("import sys, json; sys.path.insert(0, %r); import floxer_amd as F; from floxer_amd import simulate as S;"
-            "g = S.make_genome(500000, 2, seed=161); r, _, _ = S.make_reads(g, 24, 6000, 0.08, seed=162);"
-            "c = F.context(F.fmindex(g)); print(json.dumps(F.aligner(c, F.params(error_probability=0.08)).align_reads(r).records()))"
-            % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, FLX_EXISTS_STEPWISE="1"), capture_output=True, text=True, check=True)
-    assert [tuple(r) for r in json.loads(out.stdout.strip().split("\n")[-1])] == exp.records()
 
 
 def test_existence_ring_form_on_the_hardest_corpus_matches_oracle(small_genome):
