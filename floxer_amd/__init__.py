@@ -10,6 +10,7 @@ libfloxer_amd.so:
     aligner(ctx, params).align_reads()     spawn_search_task + query_verifier::verify + write_alignments_for_query
     output_options(...), select_records()  not floxer's: duplicate alignments dropped / alignments per read capped (opt-in)
     output_options(mapq=True), assign_mapq()  not floxer's: mapping quality from a read's distinct loci (opt-in)
+    aligner(..., md=True), align(..., md=True)  not floxer's: MD strings, built on the device next to the CIGARs (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -299,9 +300,10 @@ class searcher:
 
 
 # ------------------------------------------------------------------------------------------------ seam 2: align
-def align_batch(ctx, query_pool, jobs, reference_pool=None):
+def align_batch(ctx, query_pool, jobs, reference_pool=None, md=False):
     """jobs: [(ref_offset, ref_length, query_offset, query_length, num_allowed_errors, mode)]. reference_pool None = the context's
-    reference text (offsets are then positions in the padded concatenated text). Returns a list of None | (nm, begin, cigar)."""
+    reference text (offsets are then positions in the padded concatenated text). Returns a list of None | (nm, begin, cigar);
+    md=True (flx_align_batch_md): None | (nm, begin, cigar, md) with md the MD string as bytes, None for a job without CIGAR."""
     q = as_u8(query_pool)
     arr = (capi.AlignJob * max(1, len(jobs)))()
     cap_words = 16
@@ -316,6 +318,18 @@ def align_batch(ctx, query_pool, jobs, reference_pool=None):
     else:
         ref = as_u8(reference_pool)
         rp, rl_ = ptr(ref, u8p), len(ref)
+    if md:
+        cap_md = 16 + sum(8 * k + 6 for (_, _, _, _, k, mode) in jobs if mode == MODE_WITH_CIGAR)
+        refs = (capi.MdRef * max(1, len(jobs)))()
+        mdp = np.zeros(cap_md, dtype=np.uint8)
+        md_bytes = C.c_uint64(cap_md)
+        check(lib().flx_align_batch_md(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words),
+                                       refs, ptr(mdp, u8p), C.byref(md_bytes)))
+        out = []
+        for r, m in zip(res[: len(jobs)], refs[: len(jobs)]):
+            out.append((r.num_errors, r.begin, cigar_string(cig[r.cigar_offset: r.cigar_offset + r.cigar_length]),
+                        mdp[m.offset: m.offset + m.length].tobytes() if m.length else None) if r.exists else None)
+        return out
     check(lib().flx_align_batch(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words)))
     out = []
     for r in res[: len(jobs)]:
@@ -323,9 +337,9 @@ def align_batch(ctx, query_pool, jobs, reference_pool=None):
     return out
 
 
-def align(ctx, reference, query, num_allowed_errors, mode=MODE_WITH_CIGAR):
-    """alignment::align for one (reference window, query) pair."""
-    return align_batch(ctx, query, [(0, len(reference), 0, len(query), num_allowed_errors, mode)], reference_pool=reference)[0]
+def align(ctx, reference, query, num_allowed_errors, mode=MODE_WITH_CIGAR, md=False):
+    """alignment::align for one (reference window, query) pair; md=True adds the MD string (see align_batch)."""
+    return align_batch(ctx, query, [(0, len(reference), 0, len(query), num_allowed_errors, mode)], reference_pool=reference, md=md)[0]
 
 
 # ------------------------------------------------------------------------------------------------ seam 3: whole path
@@ -354,13 +368,27 @@ def params(error_probability=None, query_errors=None, seed_errors=2, max_anchors
 
 class RunResult:
     """records of one flx_align_reads* call. `raw` is the flx_record array as the C ABI returns it; `rows` is the same as an (n,7)
-    int64 matrix {read_index, flag, ref_id, pos, nm, cigar_off, cigar_len}, made on first use."""
+    int64 matrix {read_index, flag, ref_id, pos, nm, cigar_off, cigar_len}, made on first use. A run made with md=True also has
+    `md_refs` ((n,2) uint64 {offset, length} into `md_bytes`) and `md`, a list of bytes / None per record, made on first use."""
 
-    def __init__(self, raw, cigars, skipped):
+    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None):
         self.raw = raw
         self.cigars = cigars
         self.skipped = skipped
+        self.md_refs = md_refs
+        self.md_bytes = md_bytes
         self._rows = None
+        self._md = None
+
+    @property
+    def md(self):
+        """the records' MD strings (bytes; None for a record without one); None for a run made without md=True"""
+        if self.md_refs is None:
+            return None
+        if self._md is None:
+            buf = self.md_bytes.tobytes()
+            self._md = [buf[int(o): int(o) + int(n)] if n else None for o, n in self.md_refs]
+        return self._md
 
     @property
     def n_records(self):
@@ -466,7 +494,17 @@ class resident_reads:
     __del__ = close
 
 
-def _collect_run(run, n):
+_MD_DTYPE = np.dtype([("off", np.uint64), ("len", np.uint32), ("res", np.uint32)])
+
+
+def tag_options(md=False):
+    """flx_tag_options (include/floxer_amd.h): optional tags, not floxer's; all off by default."""
+    t = capi.TagOptions()
+    t.md = int(bool(md))
+    return t
+
+
+def _collect_run(run, n, md=False):
     try:
         nr = lib().flx_run_num_records(run)
         nc = lib().flx_run_num_cigar_words(run)
@@ -475,20 +513,38 @@ def _collect_run(run, n):
         skipped = np.zeros(max(1, n), dtype=np.uint8)
         check(lib().flx_run_copy(run, raw.ctypes.data_as(C.POINTER(capi.Record)), ptr(cig, u32p), ptr(skipped, u8p)))
         raw = raw[:nr]
+        md_refs = md_bytes = None
+        if md:
+            nb = lib().flx_run_num_md_bytes(run)
+            refs = np.zeros(max(1, nr), dtype=_MD_DTYPE)
+            md_bytes = np.zeros(max(1, nb), dtype=np.uint8)
+            check(lib().flx_run_copy_md(run, refs.ctypes.data_as(C.POINTER(capi.MdRef)), ptr(md_bytes, u8p)))
+            md_refs = np.stack([refs["off"][:nr], refs["len"][:nr].astype(np.uint64)], axis=1) if nr else np.zeros((0, 2), dtype=np.uint64)
+            md_bytes = md_bytes[:nb]
     finally:
         lib().flx_run_free(run)
-    return RunResult(raw, cig[:nc], skipped[:n])
+    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes)
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None):
-        """output: output_options(...), None: every alignment is written (floxer's output)"""
-        self.ctx, self.params, self.output = ctx, p, output
+    def __init__(self, ctx, p, output=None, md=False):
+        """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
+        string (RunResult.md), built on the device; not together with without_cigar"""
+        self.ctx, self.params, self.output, self.md = ctx, p, output, bool(md)
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
         run = C.c_void_p()
         opt = C.byref(self.output) if self.output is not None else None
+        if self.md:
+            tags = tag_options(md=True)
+            if isinstance(reads, resident_reads):
+                check(lib().flx_align_reads_resident_with_tags(self.ctx.h, C.byref(self.params), reads.h, opt, C.byref(tags), C.byref(run)))
+                return _collect_run(run, reads.n, md=True)
+            pool, offs, n = _pool_and_offsets(reads)
+            check(lib().flx_align_reads_with_tags(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, opt, C.byref(tags),
+                                                  C.byref(run)))
+            return _collect_run(run, n, md=True)
         if isinstance(reads, resident_reads):
             if opt is None:
                 check(lib().flx_align_reads_resident(self.ctx.h, C.byref(self.params), reads.h, C.byref(run)))

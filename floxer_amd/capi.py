@@ -76,6 +76,14 @@ class OutputOptions(C.Structure):
                 ("reserved2", C.c_uint64 * 2)]
 
 
+class TagOptions(C.Structure):
+    _fields_ = [("md", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class MdRef(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PathCounters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("seeds", "seeds_with_anchors", "seeds_excluded_by_hard_cap", "seeds_selected_on_host", "anchors",
                                           "cursor_extensions", "inner_tests_requested", "root_alignments_requested",
@@ -101,6 +109,8 @@ EXPORTED = [
     "flx_ctx_set_stats", "flx_device_count", "flx_index_matches_reference", "flx_sam_set_threads", "flx_index_image_layout",
     "flx_index_image_upload", "flx_index_meta_export", "flx_index_meta_import", "flx_ctx_create_on_image",
     "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records", "flx_assign_mapq", "flx_sam_set_mapq",
+    "flx_align_reads_with_tags", "flx_align_reads_resident_with_tags", "flx_run_num_md_bytes", "flx_run_copy_md", "flx_align_batch_md",
+    "flx_sam_write_tagged",
 ]
 
 _lib = None
@@ -190,6 +200,17 @@ def lib():
                                                C.POINTER(C.c_void_p)]
     L.flx_align_reads_resident_with_options.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(OutputOptions),
                                                         C.POINTER(C.c_void_p)]
+    L.flx_align_reads_with_tags.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(OutputOptions),
+                                            C.POINTER(TagOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_with_tags.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(OutputOptions),
+                                                     C.POINTER(TagOptions), C.POINTER(C.c_void_p)]
+    L.flx_run_num_md_bytes.restype = C.c_uint64
+    L.flx_run_num_md_bytes.argtypes = [C.c_void_p]
+    L.flx_run_copy_md.argtypes = [C.c_void_p, C.POINTER(MdRef), u8p]
+    L.flx_align_batch_md.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(AlignJob), C.c_uint64,
+                                     C.POINTER(AlignResult), u32p, u64p, C.POINTER(MdRef), u8p, u64p]
+    L.flx_sam_write_tagged.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), u8p, u64p, C.POINTER(C.c_char_p), C.POINTER(Record), C.c_uint64, u32p,
+                                       C.POINTER(MdRef), u8p]
     L.flx_select_records.argtypes = [C.POINTER(Record), C.c_uint64, u32p, C.POINTER(OutputOptions), u8p]
     L.flx_assign_mapq.argtypes = [C.POINTER(Record), C.c_uint64, u32p, u64p, u8p]
     L.flx_run_num_records.restype = C.c_uint64

@@ -65,9 +65,10 @@ struct Options {
     bool drop_duplicate_alignments = false;
     uint64_t max_alignments = 0;                  // 0: no cap
     bool mapping_quality = false;
+    bool md_tag = false;
 };
 
-struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // note: printed by --help
+struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
 const OptDef OPTS[] = {
     {'r', "reference", false}, {'q', "queries", false}, {'o', "output", false}, {'i', "index", false}, {'l', "logfile", false},
     {'c', "console-debug-logs", true}, {'e', "query-errors", false}, {'p', "error-probability", false}, {'s', "seed-errors", false},
@@ -82,6 +83,8 @@ const OptDef OPTS[] = {
     {'D', "drop-duplicate-alignments", true}, {'N', "max-alignments", false},
     // nor this one: MAPQ from the read's distinct loci (flx_output_options.mapq, flx_mapq.hpp) instead of floxer's 255
     {'Q', "mapping-quality", true, "not floxer's: MAPQ from the read's distinct loci within its error budget instead of 255 (0..60; computed before -D / -N drop records)"},
+    // nor this one: an MD:Z tag on every mapped record (flx_tag_options.md), built on the GPU next to the CIGARs
+    {0, "md-tag", true, "not floxer's: MD:Z tag (reference bases at mismatches and deletions) on every mapped record; not with -w"},
 };
 
 struct CliError { std::string msg; };
@@ -127,11 +130,15 @@ Options parse_cli(int argc, char** argv) {
             if (eq != std::string::npos) { inline_value = name.substr(eq + 1); name = name.substr(0, eq); has_inline = true; }
             for (auto const& d : OPTS) if (name == d.long_id) def = &d;
         } else if (arg.size() == 2 && arg[0] == '-') {
-            for (auto const& d : OPTS) if (arg[1] == d.short_id) def = &d;
+            for (auto const& d : OPTS) if (d.short_id && arg[1] == d.short_id) def = &d;
         }
         if (arg == "-h" || arg == "--help") {
             fprintf(stderr, "floxer (MI355X-native path) - usage: ./floxer --reference hg38.fasta --queries reads.fastq --error-probability 0.07 --output mapped_reads.bam\n");
-            for (auto const& d : OPTS) fprintf(stderr, "  -%c, --%s%s%s%s\n", d.short_id, d.long_id, d.flag ? "" : " <value>", d.note ? "    " : "", d.note ? d.note : "");
+            for (auto const& d : OPTS) {
+                if (d.short_id) fprintf(stderr, "  -%c, ", d.short_id);
+                else fprintf(stderr, "      ");
+                fprintf(stderr, "--%s%s%s%s\n", d.long_id, d.flag ? "" : " <value>", d.note ? "    " : "", d.note ? d.note : "");
+            }
             exit(0);
         }
         if (arg == "--version") { fprintf(stderr, "%s\n", flx_version()); exit(0); }
@@ -173,6 +180,7 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "devices") o.devices = value;
         else if (n == "drop-duplicate-alignments") o.drop_duplicate_alignments = true;
         else if (n == "mapping-quality") o.mapping_quality = true;
+        else if (n == "md-tag") o.md_tag = true;
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -194,6 +202,7 @@ Options parse_cli(int argc, char** argv) {
     if (o.max_anchors_hard < o.max_anchors_soft)
         throw CliError{"The hard maximum number of anchors (" + std::to_string(o.max_anchors_hard) + ") should not be smaller than the soft maximum number of anchors (" + std::to_string(o.max_anchors_soft) + ")."};
     if (o.seed_sampling_step_size == 0) throw CliError{"Validation failed for option --seed-sampling-step-size: must be at least 1."};
+    if (o.md_tag && o.without_cigar) throw CliError{"The option --md-tag needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     return o;
 }
 
@@ -582,6 +591,9 @@ int main(int argc, char** argv) {
     out_opt.max_alignments_per_read = o.max_alignments;
     out_opt.mapq = o.mapping_quality;            // (the options go with every batch, whichever device context aligns it)
     flx_sam_set_mapq(out, o.mapping_quality);
+    flx_tag_options tag_opt;
+    memset(&tag_opt, 0, sizeof(tag_opt));
+    tag_opt.md = o.md_tag;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -595,7 +607,7 @@ int main(int argc, char** argv) {
     if (const char* env = getenv("FLX_BATCH_READS")) { size_t const v = strtoull(env, nullptr, 10); if (v) batch_reads = v; }
     // Batches are independent: up to three are in a context at a time (their chunks share its lanes), the next one is parsed
     // while they run, and results are written in input order.
-    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
+    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
     // FLX_CLI_PROFILE=1: seconds this run spent parsing (this thread), aligning (sum over the batches' tasks) and writing (the writer
     // thread) on stderr at the end: which of the three stages bounds the end-to-end rate
     std::atomic<uint64_t> us_parse{0}, us_align{0}, us_copy{0}, us_write{0}, us_records{0};
@@ -612,7 +624,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads_with_options(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &out_opt, &run);
+        f.rc = flx_align_reads_with_tags(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &out_opt, &tag_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));
@@ -620,6 +632,11 @@ int main(int argc, char** argv) {
         f.skipped.resize(b->ids.size());
         uint64_t const t1 = now_us();
         flx_run_copy(run, f.recs.data(), f.cig.data(), f.skipped.data());
+        if (o.md_tag) {
+            f.md_refs.resize(f.recs.size());
+            f.md.resize(flx_run_num_md_bytes(run) + 1);
+            flx_run_copy_md(run, f.md_refs.data(), f.md.data());
+        }
         flx_run_free(run);
         us_copy += now_us() - t1;
         f.batch = std::move(b);
@@ -647,7 +664,8 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < f.skipped.size(); ++i)
             if (f.skipped[i]) log_line("warning", "skipping query: %s due to bad configuration regarding the number of errors.", batch.ids[i]);
         uint64_t const t0 = now_us();
-        if (flx_sam_write(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data()) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+        if (flx_sam_write_tagged(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
+                                 o.md_tag ? f.md_refs.data() : nullptr, f.md.data()) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
         us_write += now_us() - t0;
         total_reads += batch.ids.size();
         total_records += f.recs.size();

@@ -206,9 +206,55 @@ int run_score_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
     return rc;
 }
 
-// score, begin position and CIGAR for every (distinct) request
+// The MD strings (flx_md.hip) of the trace jobs of one K5 launch, one MD job per trace job. The MD jobs go up with the trace jobs, the
+// kernel is queued directly behind K5 (it reads K5's DevTraceOut and CIGAR words on the device: no host synchronisation in between), and
+// the bytes come back with the CIGAR words. A job's slab holds md_slab_bytes(NM) bytes, NM being what K4 returned for it.
+struct MdBatch {
+    hvec<DevMdJob> jobs;
+    hvec<DevMdOut> outs;
+    u64 slab_bytes = 0;
+    size_t pool_base = 0;
+    void add(DevTraceJob const& t, u32 nm) {
+        u64 const cap = md_slab_bytes(nm);
+        jobs.push_back(DevMdJob{t.ref_off, t.cigar_off, slab_bytes, t.n, (u32)cap, t.out_index, 0});
+        slab_bytes += cap;
+    }
+    int upload(Lane* ctx) {
+        int rc;
+        if ((rc = h2d(ctx, ctx->md_jobs, jobs.data(), jobs.size() * sizeof(DevMdJob)))) return rc;
+        if ((rc = ctx->md_out.ensure(jobs.size() * sizeof(DevMdOut)))) return rc;
+        return ctx->md.ensure(slab_bytes + 16);
+    }
+    int launch(Lane* ctx, const u8* d_text) {
+        // (its algorithmic bytes depend on what K5 finds: they are added by account() once the lengths are back)
+        return timed_launch(ctx, "md_build", 0, jobs.size(), [&] {
+            return DeviceApi::md_build(ctx->stream, d_text, ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>(), ctx->md_jobs.as<DevMdJob>(), (u32)jobs.size(),
+                                       ctx->md.as<u8>(), ctx->md_out.as<DevMdOut>());
+        });
+    }
+    int fetch(Lane* ctx, hvec<u8>& pool) {                  // slabs are kept as they are (gaps included), like the CIGAR slabs
+        outs.resize(jobs.size());
+        pool_base = pool.size();
+        pool.resize(pool_base + slab_bytes);
+        int rc;
+        if ((rc = d2h(ctx, outs.data(), ctx->md_out.ptr, outs.size() * sizeof(DevMdOut)))) return rc;
+        return d2h(ctx, pool.data() + pool_base, ctx->md.ptr, slab_bytes);
+    }
+    // after the lane's sync: CIGAR words read + reference letters read (one per X / D column: at most NM) + MD bytes written
+    int account(Lane* ctx, hvec<DevTraceOut> const& touts) {
+        u64 bytes = 0;
+        for (size_t j = 0; j < jobs.size(); ++j) {
+            if (outs[j].len == 0xFFFFFFFFu) { set_error("md_build: MD slab overflow, or a path that leaves its window"); return FLX_ERR_INTERNAL; }
+            bytes += 4ull * touts[j].cigar_len + outs[j].len + (jobs[j].md_cap - 6u) / 8u;
+        }
+        ctx->ctx->account_more("md_build", bytes, 0);
+        return FLX_OK;
+    }
+};
+
+// score, begin position and CIGAR (and MD string, when md_pool is given) for every (distinct) request
 int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                          hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
+                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer tprof("trace-jobs");
@@ -250,6 +296,7 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         // ---- traceback for the jobs that have an alignment within k
         hvec<DevTraceJob> tjobs;
         hvec<u32> tjob_req;
+        MdBatch mdb;
         u64 cigar_words = 0, path_steps = 0;
         for (size_t c = 0; c < count; ++c) {
             if (outs[c].score == 0xFFFFFFFFu) continue;
@@ -260,6 +307,7 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
             tjobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off[c], cigar_words, r.n, r.m, sh.lanes_per_job, sh.words_per_lane, outs[c].end_col,
                                         cap, (u32)tjob_req.size(), r.k});
             tjob_req.push_back((u32)id);
+            if (md_pool) mdb.add(tjobs.back(), outs[c].score);
             cigar_words += cap;
             path_steps += (u64)r.m + outs[c].score;
         }
@@ -267,11 +315,13 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
             if ((rc = h2d(ctx, ctx->tjobs, tjobs.data(), tjobs.size() * sizeof(DevTraceJob)))) return rc;
             if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
             if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
+            if (md_pool && (rc = mdb.upload(ctx))) return rc;
             rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
                 return DeviceApi::traceback(ctx->stream, d_text, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(), (u32)tjobs.size(),
                                             ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
             });
             if (rc) return rc;
+            if (md_pool && (rc = mdb.launch(ctx, d_text))) return rc;
             tprof.mark("tb-prep");
             hvec<DevTraceOut> touts(tjobs.size());
             size_t const pool_base = cigar_pool.size();
@@ -279,16 +329,20 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
             tprof.mark("pool-resize");
             if ((rc = d2h(ctx, touts.data(), ctx->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
             if ((rc = d2h(ctx, cigar_pool.data() + pool_base, ctx->cigar.ptr, cigar_words * 4))) return rc;
+            if (md_pool && (rc = mdb.fetch(ctx, *md_pool))) return rc;
             if ((rc = ctx->sync())) return rc;
             tprof.mark("K5+d2h");
-            for (size_t j = 0; j < tjobs.size(); ++j) {
+            for (size_t j = 0; j < tjobs.size(); ++j)
                 if (touts[j].cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+            if (md_pool && (rc = mdb.account(ctx, touts))) return rc;
+            for (size_t j = 0; j < tjobs.size(); ++j) {
                 TraceResult& res = results[tjob_req[j]];
                 res.exists = true;
                 res.nm = outs[tjob_req[j] - begin].score;
                 res.begin = touts[j].begin;
                 res.cigar_off = pool_base + tjobs[j].cigar_off + touts[j].cigar_start;
                 res.cigar_len = touts[j].cigar_len;
+                if (md_pool) { res.md_off = mdb.pool_base + mdb.jobs[j].md_off; res.md_len = mdb.outs[j].len; }
             }
         }
     }
@@ -312,12 +366,12 @@ int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequ
 
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
 int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
     hvec<AlignRequest> uniq;
     hvec<u32> uniq_of;
     dedup_requests(reqs, uniq, uniq_of);
     hvec<TraceResult> ures;
-    int rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool);
+    int rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);
     if (rc) return rc;
     results.resize(reqs.size());
     for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
@@ -457,7 +511,7 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
 constexpr u64 UNION_MAX_SHIFT = 256;      // members start within this many columns of the first member of their union
 
 int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool) {
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
     hvec<AlignRequest> uniq;
     hvec<u32> uniq_of;
     dedup_requests(reqs, uniq, uniq_of);
@@ -495,7 +549,7 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
         }
     }
     if (!usable || unions.size() == uniq.size()) {          // nothing to share: the plain path
-        int const rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool);
+        int const rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);
         if (rc) return rc;
         results.resize(reqs.size());
         for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
@@ -565,6 +619,7 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
         // ---- one traceback per distinct (union, end column)
         hvec<DevTraceJob> tjobs;
         hvec<u32> win_tjob(wins.size(), 0xFFFFFFFFu);
+        MdBatch mdb;                                       // (the members of a union share its trace job's MD string as they share its CIGAR words)
         u64 cigar_words = 0, path_steps = 0;
         {
             size_t w0 = 0;
@@ -584,6 +639,7 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
                     win_tjob[w] = (u32)tjobs.size();
                     tjobs.push_back(DevTraceJob{ur.ref_off, ur.q_off, trace_off[ui - begin], cigar_words, ur.n, ur.m, sh.lanes_per_job, sh.words_per_lane,
                                                 end_in_union, cap, (u32)tjobs.size(), ur.k});
+                    if (md_pool) mdb.add(tjobs.back(), wouts[w].score);
                     cigar_words += cap;
                     path_steps += (u64)ur.m + wouts[w].score;
                 }
@@ -596,15 +652,21 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
             if ((rc = h2d(ctx, ctx->tjobs, tjobs.data(), tjobs.size() * sizeof(DevTraceJob)))) return rc;
             if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
             if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
+            if (md_pool && (rc = mdb.upload(ctx))) return rc;
             rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
                 return DeviceApi::traceback(ctx->stream, d_text, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(), (u32)tjobs.size(),
                                             ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
             });
             if (rc) return rc;
+            if (md_pool && (rc = mdb.launch(ctx, d_text))) return rc;
             cigar_pool.resize(pool_base + cigar_words);
             if ((rc = d2h(ctx, touts.data(), ctx->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
             if ((rc = d2h(ctx, cigar_pool.data() + pool_base, ctx->cigar.ptr, cigar_words * 4))) return rc;
+            if (md_pool && (rc = mdb.fetch(ctx, *md_pool))) return rc;
             if ((rc = ctx->sync())) return rc;
+            for (auto const& t : touts)
+                if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+            if (md_pool && (rc = mdb.account(ctx, touts))) return rc;
         }
         // ---- members take the union's alignment when its path starts inside their window
         for (size_t w = 0; w < wins.size(); ++w) {
@@ -621,11 +683,12 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
             res.begin = (u32)(t.begin - shift);
             res.cigar_off = pool_base + tjobs[win_tjob[w]].cigar_off + t.cigar_start;
             res.cigar_len = t.cigar_len;
+            if (md_pool) { res.md_off = mdb.pool_base + mdb.jobs[win_tjob[w]].md_off; res.md_len = mdb.outs[win_tjob[w]].len; }
         }
     }
     if (!fallback.empty()) {
         hvec<TraceResult> fres;
-        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool))) return rc;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
     if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", reqs.size(), uniq.size(), unions.size(), fallback.size());
@@ -668,7 +731,17 @@ using namespace flx;
 extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
                                uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                                uint32_t* cigar_pool, uint64_t* cigar_pool_words) {
-    if (!ctx || (n_jobs && (!jobs || !out || !query_pool))) { set_error("flx_align_batch: null argument"); return FLX_ERR_INVALID; }
+    return flx_align_batch_md(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, nullptr, nullptr, nullptr);
+}
+// out_md == NULL: no MD strings (flx_align_batch)
+extern "C" int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
+                                  uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
+                                  uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes) {
+    std::string const fn = out_md ? "flx_align_batch_md" : "flx_align_batch";        // (flx_align_batch forwards here)
+    if (out_md && !md_pool_bytes) { set_error(fn + ": null argument"); return FLX_ERR_INVALID; }
+    uint64_t const md_pool_cap = md_pool_bytes ? *md_pool_bytes : 0;
+    if (md_pool_bytes) *md_pool_bytes = 0;                                            // (out: bytes used, also on an early return)
+    if (!ctx || (n_jobs && (!jobs || !out || !query_pool))) { set_error(fn + ": null argument"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
     u64 const text_len = ref_pool ? ref_pool_len : ctx->hidx->n;
@@ -676,7 +749,7 @@ extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t r
     for (uint64_t i = 0; i < n_jobs; ++i) {
         flx_align_job const& j = jobs[i];
         if (j.query_length == 0 || j.query_offset + j.query_length > query_pool_len || j.ref_offset + j.ref_length > text_len || j.mode > 2) {
-            set_error("flx_align_batch: job outside its pools"); return FLX_ERR_INVALID;
+            set_error(fn + ": job outside its pools"); return FLX_ERR_INVALID;
         }
         if (j.query_length > align_supported_max_query()) { set_error("query longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
         any_rev |= j.mode == FLX_MODE_WITHOUT_CIGAR;
@@ -720,6 +793,7 @@ extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t r
         } else { trace_reqs.push_back({j.ref_offset, j.query_offset, j.ref_length, j.query_length, j.num_allowed_errors}); trace_ids.push_back((u32)i); }
     }
     for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_align_result{0, 0, 0, 0, 0, 0};
+    if (out_md) for (uint64_t i = 0; i < n_jobs; ++i) out_md[i] = flx_md_ref{0, 0, 0};
     hvec<DevAlignOut> outs;
     if ((rc = run_score_jobs(L, d_text, L->peq.as<u64>(), score_reqs, outs, "ed_align_exists"))) return rc;
     for (size_t i = 0; i < outs.size(); ++i)
@@ -732,15 +806,22 @@ extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t r
         }
     hvec<TraceResult> tres;
     hvec<u32> cig;
-    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig))) return rc;
+    hvec<u8> mdp;
+    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig, out_md ? &mdp : nullptr))) return rc;
     uint64_t const cap = cigar_pool_words ? *cigar_pool_words : 0;
     if (cigar_pool_words) *cigar_pool_words = cig.size();
     if (any_trace && (!cigar_pool || cig.size() > cap)) { set_error("cigar pool too small"); return FLX_ERR_CAPACITY; }
     if (!cig.empty()) memcpy(cigar_pool, cig.data(), cig.size() * 4);
+    if (out_md) {
+        *md_pool_bytes = mdp.size();
+        if (!mdp.empty() && (!md_pool || mdp.size() > md_pool_cap)) { set_error("md pool too small"); return FLX_ERR_CAPACITY; }
+        if (!mdp.empty()) memcpy(md_pool, mdp.data(), mdp.size());
+    }
     for (size_t i = 0; i < tres.size(); ++i)
         if (tres[i].exists) {
             flx_align_result& r = out[trace_ids[i]];
             r.exists = 1; r.num_errors = tres[i].nm; r.begin = tres[i].begin; r.cigar_offset = tres[i].cigar_off; r.cigar_length = tres[i].cigar_len;
+            if (out_md) out_md[trace_ids[i]] = flx_md_ref{tres[i].md_off, tres[i].md_len, 0};
         }
     return FLX_OK;
 }

@@ -52,7 +52,7 @@ struct Lane {
     int id = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     DeviceBuffer seq, seq_rev, peq, peq_rev, scheme, seeds, stack, hits, counters, rows, rows_out, qpack, items;
-    DeviceBuffer jobs, job_out, trace, tjobs, tjob_out, cigar, user_text, user_text_rev, lastrow, row_windows, row_out,
+    DeviceBuffer jobs, job_out, trace, tjobs, tjob_out, cigar, md, md_jobs, md_out, user_text, user_text_rev, lastrow, row_windows, row_out,
         seed_cnt, hit_off, grouped, sel_stat, sel_n, sel_off, sel_out, sel_tmp, sel_rows, sel_row_off, sel_sparse, sel_lists, vr, seed_gen, mailboxes;
     size_t trace_budget_bytes = 0;
     std::vector<PendingTiming> pending;
@@ -111,6 +111,9 @@ struct flx_ctx {
     flx::Lane* lane0() { return lanes[0].get(); }
     int sync_all();
     void account(const char* name, flx::u64 bytes, flx::u64 units, hipEvent_t start, hipEvent_t stop);   // caller holds mu
+    // bytes and units of launches already accounted that were only known once their results were back (takes mu; nothing when timing is off
+    // or the kernel has no entry)
+    void account_more(const char* name, flx::u64 bytes, flx::u64 units);
 };
 
 namespace flx {

@@ -160,6 +160,21 @@ struct DevTraceJob {
 };
 struct DevTraceOut { u32 begin; u32 cigar_start; u32 cigar_len; u32 pad; };   // cigar_start relative to the slab
 
+// ---- MD strings of traced paths (flx_md.hip), one job per trace job: the kernel reads that job's DevTraceOut and CIGAR words where K5
+// left them on the device
+struct DevMdJob {
+    u64 ref_off, cigar_off, md_off;                // the trace job's window in the text, its CIGAR slab (words), this job's MD slab (bytes)
+    u32 n;                                         // columns of the window: nothing is read beyond them
+    u32 md_cap;                                    // bytes of the MD slab
+    u32 out_index, pad;                            // the trace job's DevTraceOut and this job's DevMdOut
+};
+struct DevMdOut { u32 len; u32 pad; };             // len 0xFFFFFFFF: the slab was too small, or the CIGAR's path leaves the window
+// Bytes that hold the MD string of any alignment with nm errors. The string is numbers, letters and '^'. An X column and a D column
+// each count one error, so there are at most nm events (an X column, or a D op) and at most nm deleted or mismatched letters, and at most
+// one '^' per D op: letters + '^' <= 2 nm. Every event is preceded by one number and the end adds one: nm + 1 numbers, each the length
+// of a run of '=' columns, which is at most the number of query rows: <= 102 400 (align_supported_max_query), six digits. 8 nm + 6 in all.
+constexpr u64 md_slab_bytes(u64 nm) { return 8 * nm + 6; }
+
 // ------------------------------------------------------------------------------------------------ verification rounds on the device
 // The inner PEX levels as device-resident state: every anchor of a chunk with the node it is about to test (flx_rounds.hip).
 struct DevVrAnchor {            // 48 bytes
@@ -314,6 +329,9 @@ struct DeviceApi {
     static int lastrow_min(void* stream, const u16* d_lastrow, const DevRowWindow* d_windows, u32 n_windows, DevAlignOut* d_out);
     static int traceback(void* stream, const u8* d_text, const u64* d_peq, const u64* d_trace, const DevTraceJob* d_jobs, u32 n_jobs,
                          u32* d_cigar, DevTraceOut* d_out);
+    // flx_md.hip: the MD string of every job from the CIGAR words and DevTraceOut that `traceback` left at d_cigar / d_trace_out
+    static int md_build(void* stream, const u8* d_text, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevMdJob* d_jobs, u32 n_jobs,
+                        u8* d_md, DevMdOut* d_out);
 };
 
 // ------------------------------------------------------------------------------------------------ host logic

@@ -575,11 +575,23 @@ struct SpanCache { const uint32_t* of = nullptr; uint32_t len = 0; int64_t span 
 
 // one record as SAM text or as a BAM record, appended to `out`; false: the record cannot be represented (error set)
 // cigar_at (BAM): where in `out` the record's CIGAR array starts (SIZE_MAX: it has none of its own)
+// mdr (may be null): the record's MD string in md_bytes, written as MD:Z behind NM on a mapped record when its length is not 0; md_at (BAM):
+// where in `out` its bytes start (SIZE_MAX: none)
 bool format_record(flx_sam_writer const* w, flx_record const& r, const char* const* read_ids, const uint8_t* read_pool,
                    const uint64_t* read_offsets, const char* const* quals, const uint32_t* cigar_words, std::vector<uint8_t>& out, std::string& err,
-                   SpanCache& span_cache, size_t* cigar_at = nullptr) {
+                   SpanCache& span_cache, size_t* cigar_at = nullptr, const flx_md_ref* mdr = nullptr, const uint8_t* md_bytes = nullptr,
+                   size_t* md_at = nullptr) {
     static const char ops[] = "MIDNSHP=X";
     const char* id = read_ids[r.read_index];
+    if (md_at) *md_at = SIZE_MAX;
+    const uint8_t* md = nullptr;
+    if (mdr && mdr->length && !(r.flag & 4u)) {
+        if (!md_bytes) { err = "MD references without MD bytes"; return false; }
+        md = md_bytes + mdr->offset;
+        // (a tab or a line end would break the SAM line, a zero byte the BAM tag)
+        for (uint32_t b = 0; b < mdr->length; ++b)
+            if (!((md[b] >= '0' && md[b] <= '9') || (md[b] >= 'A' && md[b] <= 'Z') || md[b] == '^')) { err = std::string("MD string with a byte outside [0-9A-Z^] in a record of read ") + id; return false; }
+    }
     if (w->mapq_from_records && r.reserved > 254u) { err = std::string("mapping quality above 254 in the record of read ") + id; return false; }
     uint32_t const mapq = w->mapq_from_records ? r.reserved : 255u;
     bool const unmapped = (r.flag & 4u) != 0;
@@ -613,6 +625,7 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         if (slen == 0 || !qual || !*qual) out.push_back('*');
         else app(qual, slen);
         if (!unmapped) { app("\tNM:i:", 6); app_num(r.num_errors); }
+        if (md) { app("\tMD:Z:", 6); app((const char*)md, mdr->length); }
         out.push_back('\n');
         return true;
     }
@@ -673,6 +686,12 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         else if (r.num_errors < 65536) { out.push_back('S'); put16((uint16_t)r.num_errors); }
         else { out.push_back('I'); put32((int32_t)r.num_errors); }
     }
+    if (md) {
+        out.push_back('M'); out.push_back('D'); out.push_back('Z');
+        if (md_at) *md_at = out.size();
+        out.insert(out.end(), md, md + mdr->length);
+        out.push_back(0);
+    }
     if (long_cigar) {
         out.push_back('C'); out.push_back('G'); out.push_back('B'); out.push_back('I');
         put32((int32_t)r.cigar_length);
@@ -698,6 +717,12 @@ extern "C" int flx_sam_set_mapq(flx_sam_writer* w, int from_records) {
 
 extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
                              const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words) {
+    return flx_sam_write_tagged(w, read_ids, read_pool, read_offsets, quals, records, n_records, cigar_words, nullptr, nullptr);
+}
+
+extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
+                                    const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
+                                    const flx_md_ref* md, const uint8_t* md_bytes) {
     if (!w || (n_records && (!records || !read_ids || !read_pool || !read_offsets))) { set_error("flx_sam_write: null argument"); return FLX_ERR_INVALID; }
     if (w->failed) { set_error("write error on the alignment output"); return FLX_ERR_IO; }
     if (w->bam) {
@@ -750,11 +775,12 @@ extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, con
                 else if (done >= (4u << 20)) { base += done; raw.erase(raw.begin(), raw.begin() + (long)done); done = 0; }
             };
             size_t prev_cigar_at = SIZE_MAX;                   // stream position of the previous record's CIGAR array
+            size_t prev_md_at = SIZE_MAX;                      // and of its MD string
             SpanCache span_cache;
             for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i) {
-                size_t cigar_at = SIZE_MAX;
+                size_t cigar_at = SIZE_MAX, md_at = SIZE_MAX;
                 uint64_t const t_format = prof_ns();
-                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at)) break;
+                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at)) break;
                 if (writer_profile()) g_ns_format += prof_ns() - t_format;
                 if (cigar_at != SIZE_MAX) {
                     cigar_at += base;
@@ -762,6 +788,13 @@ extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, con
                     hints.push_back(StreamHint{cigar_at, 4 * (size_t)records[i].cigar_length, same ? cigar_at - prev_cigar_at : 0});
                 }
                 prev_cigar_at = cigar_at;
+                // the MD string repeats exactly when the CIGAR array does (records of one traced path): announced the same way, behind it
+                if (md_at != SIZE_MAX) {
+                    md_at += base;
+                    bool const same = prev_md_at != SIZE_MAX && i > r0 && md[i].offset == md[i - 1].offset && md[i].length == md[i - 1].length;
+                    hints.push_back(StreamHint{md_at, (size_t)md[i].length, same ? md_at - prev_md_at : 0});
+                }
+                prev_md_at = md_at;
                 deflate_full_blocks(false);
             }
             if (errs[p].empty()) deflate_full_blocks(true);
@@ -792,7 +825,7 @@ extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, con
         }
         SpanCache span_cache;
         for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i)
-            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache)) break;
+            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes)) break;
     });
     for (auto const& e : errs) if (!e.empty()) { set_error(e); return FLX_ERR_INVALID; }
     for (auto const& part : parts) {

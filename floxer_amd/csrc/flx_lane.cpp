@@ -44,7 +44,7 @@ struct Workspace { const char* name; DeviceBuffer Lane::*member; };
 #define FLX_WS(m) Workspace{#m, &Lane::m}
 constexpr Workspace WORKSPACES[] = {
     FLX_WS(seq), FLX_WS(seq_rev), FLX_WS(peq), FLX_WS(peq_rev), FLX_WS(scheme), FLX_WS(seeds), FLX_WS(stack), FLX_WS(hits), FLX_WS(counters), FLX_WS(rows),
-    FLX_WS(rows_out), FLX_WS(jobs), FLX_WS(job_out), FLX_WS(trace), FLX_WS(tjobs), FLX_WS(tjob_out), FLX_WS(cigar), FLX_WS(user_text), FLX_WS(user_text_rev),
+    FLX_WS(rows_out), FLX_WS(jobs), FLX_WS(job_out), FLX_WS(trace), FLX_WS(tjobs), FLX_WS(tjob_out), FLX_WS(cigar), FLX_WS(md), FLX_WS(md_jobs), FLX_WS(md_out), FLX_WS(user_text), FLX_WS(user_text_rev),
     FLX_WS(lastrow), FLX_WS(row_windows), FLX_WS(row_out), FLX_WS(seed_cnt), FLX_WS(hit_off), FLX_WS(grouped), FLX_WS(sel_stat), FLX_WS(sel_n), FLX_WS(sel_off),
     FLX_WS(sel_out), FLX_WS(sel_tmp), FLX_WS(sel_rows), FLX_WS(sel_row_off), FLX_WS(sel_sparse), FLX_WS(sel_lists), FLX_WS(vr), FLX_WS(qpack), FLX_WS(items),
     FLX_WS(seed_gen), FLX_WS(mailboxes)};
@@ -121,6 +121,14 @@ int Lane::sync() {
 
 using namespace flx;
 
+void flx_ctx::account_more(const char* name, u64 bytes, u64 units) {
+    if (!timing) return;
+    std::lock_guard<std::mutex> g(mu);
+    auto it = stats.find(name);
+    if (it == stats.end()) return;
+    it->second.algorithmic_bytes += bytes;
+    it->second.work_units += units;
+}
 void flx_ctx::account(const char* name, u64 bytes, u64 units, hipEvent_t start, hipEvent_t stop) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, start, stop);

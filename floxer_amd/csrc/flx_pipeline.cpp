@@ -134,11 +134,21 @@ extern "C" int flx_align_reads(flx_ctx* ctx, const flx_params* P, const uint8_t*
 }
 extern "C" int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets,
                                             uint64_t n_reads, const flx_output_options* O, flx_run** out) {
-    if (!output_options_valid(O)) return FLX_ERR_INVALID;
+    return flx_align_reads_with_tags(ctx, P, read_pool, read_offsets, n_reads, O, nullptr, out);
+}
+// md needs the trace: refused together with without_cigar, before any work
+static bool tags_fit_params(const flx_params* P, const flx_tag_options* T) {
+    if (!tag_options_valid(T)) return false;
+    if (T && T->md && P && P->without_cigar) { set_error("flx_tag_options.md needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
+    return true;
+}
+extern "C" int flx_align_reads_with_tags(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets,
+                                         uint64_t n_reads, const flx_output_options* O, const flx_tag_options* T, flx_run** out) {
+    if (!output_options_valid(O) || !tags_fit_params(P, T)) return FLX_ERR_INVALID;
     flx_reads* rd = nullptr;
     int rc = flx_reads_upload(ctx, read_pool, read_offsets, n_reads, &rd);
     if (rc) return rc;
-    rc = flx_align_reads_resident_with_options(ctx, P, rd, O, out);
+    rc = flx_align_reads_resident_with_tags(ctx, P, rd, O, T, out);
     flx_reads_free(rd);
     return rc;
 }
@@ -148,7 +158,11 @@ extern "C" int flx_align_reads_resident(flx_ctx* ctx, const flx_params* P, const
 }
 extern "C" int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_output_options* O,
                                                      flx_run** out) {
-    if (!output_options_valid(O)) return FLX_ERR_INVALID;
+    return flx_align_reads_resident_with_tags(ctx, P, RD, O, nullptr, out);
+}
+extern "C" int flx_align_reads_resident_with_tags(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_output_options* O,
+                                                  const flx_tag_options* T, flx_run** out) {
+    if (!output_options_valid(O) || !tags_fit_params(P, T)) return FLX_ERR_INVALID;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
@@ -158,6 +172,7 @@ extern "C" int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_par
     PhaseTimer dprof("dispatch");
     auto run = std::make_unique<flx_run>();
     run->skipped.assign(n_reads, 0);
+    run->has_md = T && T->md;
     if (n_reads == 0) { *out = run.release(); return FLX_OK; }       // an empty batch is an empty run
     // reads are independent units (parallelization.cpp:77-87): the batch is cut into contiguous chunks and every lane (a host
     // thread with its own stream and workspaces) takes the next chunk when it is done with its last one.
@@ -218,7 +233,7 @@ extern "C" int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_par
             u64 const a = chunk_first[c], b = chunk_first[c + 1];
             parts[c].skipped.assign(n_reads, 0);
             LaneLease lease(ctx, ctx->external_stream ? 0 : -1);      // waits while other calls on this context hold all lanes
-            rcs[c] = align_slice(lease.lane, P, O, RD, a, b, &parts[c]);
+            rcs[c] = align_slice(lease.lane, P, O, T, RD, a, b, &parts[c]);
             if (rcs[c]) { errs[c] = flx_last_error(); failed.store(true); }
             else { lease.lane->has_run = true; if (!ctx->external_stream) ctx->warm_one_cold_lane(lease.lane); }
         }
@@ -276,6 +291,27 @@ extern "C" int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* c
     }
     if (skipped && !run->skipped.empty()) memcpy(skipped, run->skipped.data(), run->skipped.size());
     cprof.mark("copy");
+    return FLX_OK;
+}
+extern "C" uint64_t flx_run_num_md_bytes(const flx_run* run) {
+    if (!run) return 0;
+    uint64_t n = run->md.size();
+    for (auto const& p : run->parts) n += p.md.size();
+    return n;
+}
+// the parts' MD offsets are rebased onto the concatenation of their pools, as flx_run_copy rebases the CIGAR offsets
+extern "C" int flx_run_copy_md(const flx_run* run, flx_md_ref* refs, uint8_t* md_bytes) {
+    if (!run) { set_error("null run"); return FLX_ERR_INVALID; }
+    if (!run->has_md) { set_error("flx_run_copy_md: the run was made without flx_tag_options.md"); return FLX_ERR_INVALID; }
+    uint64_t rb = 0, mb = 0;
+    auto emit = [&](flx_run const& part) {
+        if (refs) for (size_t r = 0; r < part.md_refs.size(); ++r) { refs[rb + r] = part.md_refs[r]; if (part.md_refs[r].length) refs[rb + r].offset += mb; }
+        if (md_bytes && !part.md.empty()) memcpy(md_bytes + mb, part.md.data(), part.md.size());
+        rb += part.records.size();
+        mb += part.md.size();
+    };
+    emit(*run);
+    for (auto const& p : run->parts) emit(p);
     return FLX_OK;
 }
 extern "C" void flx_run_free(flx_run* run) {

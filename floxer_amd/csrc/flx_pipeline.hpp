@@ -20,6 +20,9 @@ struct flx_run {
     flx::hvec<flx_record> records;     // cigar_offset relative to this object's `cigars`
     flx::hvec<flx::u32> cigars;
     flx::hvec<flx::u8> skipped;
+    bool has_md = false;               // made with flx_tag_options.md: md_refs is parallel to records, offsets relative to this object's `md`
+    flx::hvec<flx_md_ref> md_refs;
+    flx::hvec<flx::u8> md;
     flx::hvec<flx_run> parts;          // a batch result is the in-order list of its slices (no concatenation on the host)
 };
 
@@ -106,7 +109,7 @@ constexpr int SEARCH_NEEDS_HOST_SEEDS = 1;
 
 // ---- flx_align_jobs.cpp
 struct AlignRequest { u64 ref_off, q_off; u32 n, m, k; };
-struct TraceResult { bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; };
+struct TraceResult { bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; };
 // host milliseconds of the host-rounds form, summed over a chunk's rounds (FLX_HOST_PROFILE); owned by the chunk
 struct ExistsTimes { double ms[4] = {0, 0, 0, 0}; double build_requests = 0; };      // ms: dedup, cluster, GPU round trip, scatter
 
@@ -114,12 +117,13 @@ u64 round_span_percent();       // a round tests the nodes of [smallest, smalles
 u64 align_few_waves();          // FLX_ALIGN_FEW_WAVES overrides the threshold (tests force either form)
 // score + end column for every request (no trace)
 int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, const char* kernel_name);
-// score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
+// score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates).
+// md_pool != null: the MD string of every traced path as well (flx_md.hip), its bytes in md_pool (shared like the CIGAR words)
 int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool);
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
 int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool);
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
 int run_exists_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, ExistsTimes& times);
 int build_peq(Lane* lane, const u8* d_seq, u64 len, DeviceBuffer& peq);
@@ -149,7 +153,7 @@ struct AnchorState {
 };
 
 struct Span { u64 offset, length, extra; };
-struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; };
+struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; };
 
 struct Slice {
     // plan_reads
@@ -176,6 +180,8 @@ struct Slice {
     // align_roots
     hvec<RootAlignment> root_res;
     hvec<u32> cig;                                                            // CIGAR pool of root_res
+    bool want_md = false;                                                     // flx_tag_options.md: the traced paths' MD strings as well
+    hvec<u8> md;                                                              // MD pool of root_res
     // statistics in the reference's form (flx_stats.cpp), when the context has a statistics object attached, and their clock
     std::unique_ptr<Stats> st_local;
     std::chrono::steady_clock::time_point t_slice;
@@ -185,6 +191,9 @@ struct Slice {
 };
 
 // produces the slice's records (read_index relative to the whole batch)
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run);
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_reads* RD, u64 first_read, u64 end_read,
+                flx_run* run);
+// NULL or zeroed: no tags; md must be 0 or 1 and the reserved fields 0 (else the error is set)
+bool tag_options_valid(const flx_tag_options* t);
 
 }  // namespace flx

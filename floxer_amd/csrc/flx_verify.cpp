@@ -565,9 +565,10 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) 
             if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
     } else {
         hvec<TraceResult> tres;
-        if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), root_reqs, tres, S.cig))) return rc;
+        if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), root_reqs, tres, S.cig, S.want_md ? &S.md : nullptr))) return rc;
         for (size_t i = 0; i < tres.size(); ++i)
-            if (tres[i].exists) root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len};
+            if (tres[i].exists)
+                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len};
     }
     return FLX_OK;
 }
@@ -619,6 +620,9 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
     std::vector<MapqKey> mq_keys;
     std::vector<u8> mq_q;
     MapqScratch mq_scratch;
+    // MD (flx_tag_options.md): one {offset, length} per record, parallel to run->records; the selection moves it with the records it keeps
+    bool const md = S.want_md;
+    run->has_md = md;
     for (size_t r = 0; r < reads.size(); ++r) {
         size_t const rec0 = run->records.size();
         bool have_best = false;
@@ -635,6 +639,7 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
                 else flag |= 256u;
                 run->records.push_back(flx_record{reads[r].read_index, flag, (int32_t)ref, saturate_i32(root_res[i].start), root_res[i].nm,
                                                   root_res[i].cigar_off, root_res[i].cigar_len, 0});
+                if (md) run->md_refs.push_back(flx_md_ref{root_res[i].md_off, root_res[i].md_len, 0});
                 if (mapq) {
                     if (mq_keys.empty()) mq_scratch.spans.clear();
                     u64 const span = root_res[i].cigar_len ? cigar_reference_span_cached(cig.data() + root_res[i].cigar_off, root_res[i].cigar_len, mq_scratch)
@@ -642,7 +647,10 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
                     mq_keys.push_back(MapqKey{root_res[i].start, span, (int32_t)ref, flag, root_res[i].nm});
                 }
             }
-        if (!primary_written) run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
+        if (!primary_written) {
+            run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
+            if (md) run->md_refs.push_back(flx_md_ref{0, 0, 0});
+        }
         if (mapq && !mq_keys.empty()) {
             mq_q.resize(mq_keys.size());
             read_mapq(mq_keys.data(), mq_keys.size(), mq_q.data(), mq_scratch);
@@ -664,9 +672,13 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
             select_read_records(sel_keys.data(), n, O->drop_duplicates != 0, O->max_alignments_per_read, sel_keep.data(), sel_scratch);
             size_t w = rec0;
             for (size_t j = 0; j < n; ++j)
-                if (sel_keep[j]) run->records[w++] = run->records[rec0 + j];
+                if (sel_keep[j]) {
+                    if (md) run->md_refs[w] = run->md_refs[rec0 + j];
+                    run->records[w++] = run->records[rec0 + j];
+                }
             n_dropped += run->records.size() - w;
             run->records.resize(w);
+            if (md) run->md_refs.resize(w);
         }
         if (st_local) {                                                                                  // parallelization.cpp:262-268
             u64 n_al = 0;
@@ -681,6 +693,7 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
     }
     if (select) compact_cigars(run, cig);
     run->cigars = std::move(cig);
+    if (md) run->md = std::move(S.md);              // (not compacted under -D / -N: the dropped records' bytes stay, unreferenced)
     {
         u64 found = 0;
         for (auto const& rr : root_res) found += rr.exists;
@@ -693,12 +706,21 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
 
 }  // namespace
 
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run) {
+bool tag_options_valid(const flx_tag_options* t) {
+    if (!t) return true;
+    if (t->md > 1) { set_error("flx_tag_options: md must be 0 or 1"); return false; }
+    for (uint32_t r : t->reserved) if (r) { set_error("flx_tag_options: the reserved fields must be 0"); return false; }
+    return true;
+}
+
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_reads* RD, u64 first_read, u64 end_read,
+                flx_run* run) {
     flx_ctx* ctx = lane->ctx;
     FLX_HIP(hipSetDevice(ctx->device));
     HostIndex const& H = *ctx->hidx;
     PhaseTimer prof;
     Slice S;
+    S.want_md = T && T->md;
     int rc;
     if ((rc = plan_reads(S, P, RD, first_read, end_read, run))) return rc;
     if ((rc = plan_seeds(S, P, RD))) return rc;

@@ -8,4 +8,16 @@ namespace flx {
 
 __device__ __forceinline__ u32 lane_id() { return threadIdx.x & 63u; }
 
+// Inclusive prefix sum over the 64 lanes of a wave: lane l receives v[0] + ... + v[l]. Six __shfl_up steps, no LDS; every lane of the
+// wave must call it (the shuffles read inactive lanes otherwise). The wave's total is the value of lane 63.
+__device__ __forceinline__ u32 wave_inclusive_scan(u32 v) {
+    u32 const lane = lane_id();
+#pragma unroll
+    for (u32 d = 1; d < 64u; d <<= 1) {
+        u32 const below = __shfl_up(v, d);
+        if (lane >= d) v += below;
+    }
+    return v;
+}
+
 }  // namespace flx

@@ -176,6 +176,14 @@ int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len
                     uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                     uint32_t* cigar_pool, uint64_t* cigar_pool_words /* in: capacity, out: used */);
 
+/* flx_align_batch plus the MD string (see flx_tag_options) of every WITH_CIGAR job that exists: out_md[i] refers into md_pool, length 0 for
+ * every other job. md_pool_bytes: in = capacity, out = used (FLX_ERR_CAPACITY if larger than the capacity; 8 * num_allowed_errors + 6 bytes
+ * per WITH_CIGAR job always suffice). */
+typedef struct flx_md_ref { uint64_t offset; uint32_t length; uint32_t reserved; } flx_md_ref;   /* into the MD bytes; length 0: the record has no MD */
+int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
+                       uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
+                       uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes);
+
 /* ------------------------------------------------------------------------------------------------ seam 3: whole path
  * replaces parallelization::spawn_search_task + spawn_verification_task + query_verifier::verify +
  * alignment_output::write_alignments_for_query (parallelization.cpp:45-293, verification.hpp:22-48, output.cpp:49-108)
@@ -255,6 +263,26 @@ int flx_select_records(const flx_record* records, uint64_t n, const uint32_t* ci
  * read_lengths[read_index] reference symbols; read_lengths may be NULL: then the span comes from the CIGAR only (1 without one). */
 int flx_assign_mapq(const flx_record* records, uint64_t n, const uint32_t* cigar_words, const uint64_t* read_lengths, uint8_t* mapq);
 
+/* Optional tags: not floxer's, which writes NM only. All are off when the struct is zeroed (or NULL), and with all off nothing changes: no
+ * launch, no byte of any output.
+ *   md = 1 (0: off, anything else is refused): every mapped record of the run gets an MD string (SAM spec, the rule of samtools calmd on the
+ *     record's extended CIGAR): walk the reference-consuming columns from the record's position; '=' columns increment a counter; every X
+ *     column emits the counter (decimal, possibly 0), the reference letter, and resets the counter; every D op emits the counter, '^', the
+ *     op's reference letters, and resets the counter; I emits nothing; the end emits the counter ("10A5^AC6"; X X gives A0C, D then X gives
+ *     ^AC0T). Letters come from the index's ranks: 1..4 -> ACGT, anything else N: IUPAC and lower-case letters of the FASTA are not
+ *     recoverable. Reference-forward orientation for both strands. The strings are built on the device next to the CIGARs (a context made
+ *     on an index image has no host text). Records that share a CIGAR share their MD bytes. params->without_cigar has no trace: md together
+ *     with it is refused (FLX_ERR_INVALID) before any work. Output options select records together with their MD; the MD bytes of dropped
+ *     records stay in the pool (it is not compacted). The reserved fields must be 0. */
+typedef struct flx_tag_options { uint32_t md; uint32_t reserved[7]; } flx_tag_options;
+int flx_align_reads_with_tags(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets,
+                              uint64_t n_reads, const flx_output_options* options, const flx_tag_options* tags, flx_run** out);
+int flx_align_reads_resident_with_tags(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_output_options* options,
+                                       const flx_tag_options* tags, flx_run** out);
+uint64_t flx_run_num_md_bytes(const flx_run* run);                   /* 0 for a run made without md */
+/* refs: one per record, in record order; md_bytes: flx_run_num_md_bytes bytes (what lies between the strings is unspecified). Either may be NULL. A run made without md: FLX_ERR_INVALID. */
+int flx_run_copy_md(const flx_run* run, flx_md_ref* refs, uint8_t* md_bytes);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -306,6 +334,11 @@ int flx_sam_open(const char* path /* .sam or .bam */, const char* const* ref_ids
                  flx_sam_writer** out);
 int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
                   const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words);
+/* flx_sam_write with an MD:Z tag behind NM:i on every mapped record i with md[i].length > 0 (its bytes: md_bytes + md[i].offset). Bytes
+ * outside [0-9A-Z^] are refused with FLX_ERR_INVALID. md == NULL: exactly flx_sam_write. */
+int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
+                         const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
+                         const flx_md_ref* md, const uint8_t* md_bytes);
 int flx_sam_close(flx_sam_writer* w);
 /* record formatting and BGZF block compression of flx_sam_write on n_threads host threads (default 1; output bytes do not depend on it) */
 int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads);
