@@ -209,6 +209,8 @@ class context:
             check(lib().flx_ctx_reset_path_counters(self.h))
         out = {n: int(getattr(pc, n)) for n, _ in capi.PathCounters._fields_ if n != "reserved"}
         out["records_dropped"] = int(pc.reserved[0])          # records that output options left out (records: those written)
+        out["partial_records"] = int(pc.reserved[1])          # records of partial alignments written (partial_options), and
+        out["reads_rescued"] = int(pc.reserved[2])            # the reads that got them in place of their unmapped record
         return out
 
     def kernel_stats(self):
@@ -411,6 +413,28 @@ class RunResult:
     def records(self):
         return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), cigar_string(self.cigars[r[5]: r[5] + r[6]])) for r in self.rows]
 
+    @property
+    def clips(self):
+        """(n,2) int64 {leading, trailing} soft-clipped bases of every record, read off its CIGAR in the orientation SAM stores; not 0
+        only in the partial records of a run made with partial_options(...)"""
+        out = np.zeros((len(self.rows), 2), dtype=np.int64)
+        for i, r in enumerate(self.rows):
+            if r[6]:
+                first, last = int(self.cigars[r[5]]), int(self.cigars[r[5] + r[6] - 1])
+                out[i, 0] = first >> 4 if first & 15 == 4 else 0
+                out[i, 1] = last >> 4 if last & 15 == 4 and r[6] > 1 else 0
+        return out
+
+    def query_intervals(self, read_lengths):
+        """(n,2) int64 inclusive {from, to} of every mapped record's aligned part in read-forward coordinates ((-1,-1) for an unmapped
+        record or one without CIGAR): the clips turned round for the reverse strand"""
+        out = np.full((len(self.rows), 2), -1, dtype=np.int64)
+        for i, (r, (lead, trail)) in enumerate(zip(self.rows, self.clips)):
+            if r[6] and not r[1] & 4:
+                n = int(read_lengths[r[0]])
+                out[i] = (trail, n - 1 - lead) if r[1] & 16 else (lead, n - 1 - trail)
+        return out
+
 
 def output_options(drop_duplicates=False, max_alignments=0, mapq=False):
     """flx_output_options (include/floxer_amd.h); not floxer's options, all off by default (then the records are floxer's):
@@ -504,6 +528,31 @@ def tag_options(md=False):
     return t
 
 
+def partial_options(min_query_span=0, max_records=0, enable=True):
+    """flx_partial_options (include/floxer_amd.h): not floxer's. A read without a full alignment gets, in place of its unmapped record,
+    its largest verified parts as soft-clipped records: a primary and non-overlapping supplementaries (flag 2048). min_query_span: the
+    fewest query bases of such a part (0: 1000); max_records: the most records of a read (0: 4). Not together with without_cigar."""
+    if min_query_span < 0 or max_records < 0:
+        raise FloxerError("min_query_span and max_records must be >= 0 (0: the default)")
+    o = capi.PartialOptions()
+    o.enable, o.min_query_span, o.max_records = int(bool(enable)), int(min_query_span), int(max_records)
+    return o
+
+
+def choose_partials(candidates, cigars=None, options=None):
+    """flx_choose_partials: candidates = rows {read_index, q_from, q_to, orientation, reference_id, start, nm, cigar_offset, cigar_length}
+    (a read's rows contiguous, in verification order; forward query coordinates). Returns an int32 array: -1 for a candidate that is not
+    written, else its SAM flag."""
+    arr = (capi.PartialCandidate * max(1, len(candidates)))()
+    for a, c in zip(arr, candidates):
+        a.read_index, a.q_from, a.q_to, a.orientation, a.reference_id, a.start, a.nm, a.cigar_offset, a.cigar_length = [int(x) for x in c]
+    cig = np.ascontiguousarray(cigars, dtype=np.uint32) if cigars is not None and len(cigars) else None
+    out = np.zeros(max(1, len(candidates)), dtype=np.int32)
+    check(lib().flx_choose_partials(arr, len(candidates), ptr(cig, u32p) if cig is not None else None,
+                                    C.byref(options) if options is not None else None, out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out[: len(candidates)]
+
+
 def _collect_run(run, n, md=False):
     try:
         nr = lib().flx_run_num_records(run)
@@ -527,14 +576,28 @@ def _collect_run(run, n, md=False):
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None, md=False):
+    def __init__(self, ctx, p, output=None, md=False, partial=None):
         """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
-        string (RunResult.md), built on the device; not together with without_cigar"""
-        self.ctx, self.params, self.output, self.md = ctx, p, output, bool(md)
+        string (RunResult.md), built on the device; not together with without_cigar; partial: partial_options(...), None: a read
+        without a full alignment is written as unmapped (floxer's output)"""
+        self.ctx, self.params, self.output, self.md, self.partial = ctx, p, output, bool(md), partial
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
         run = C.c_void_p()
+        if self.partial is not None:
+            tags = tag_options(md=self.md)
+            bundle = capi.RunOptions()
+            if self.output is not None:
+                bundle.output = C.pointer(self.output)
+            bundle.tags = C.pointer(tags)
+            bundle.partial = C.pointer(self.partial)
+            if isinstance(reads, resident_reads):
+                check(lib().flx_align_reads_resident_opt(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), C.byref(run)))
+                return _collect_run(run, reads.n, md=self.md)
+            pool, offs, n = _pool_and_offsets(reads)
+            check(lib().flx_align_reads_opt(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), C.byref(run)))
+            return _collect_run(run, n, md=self.md)
         opt = C.byref(self.output) if self.output is not None else None
         if self.md:
             tags = tag_options(md=True)

@@ -80,6 +80,21 @@ class TagOptions(C.Structure):
     _fields_ = [("md", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
+class PartialOptions(C.Structure):
+    _fields_ = [("enable", C.c_uint32), ("min_query_span", C.c_uint32), ("max_records", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class RunOptions(C.Structure):
+    _fields_ = [("output", C.POINTER(OutputOptions)), ("tags", C.POINTER(TagOptions)), ("partial", C.POINTER(PartialOptions)),
+                ("reserved", C.c_void_p * 5)]
+
+
+class PartialCandidate(C.Structure):
+    _fields_ = [("read_index", C.c_uint64), ("q_from", C.c_uint32), ("q_to", C.c_uint32), ("orientation", C.c_uint32),
+                ("reference_id", C.c_int32), ("start", C.c_uint64), ("nm", C.c_uint32), ("cigar_length", C.c_uint32),
+                ("cigar_offset", C.c_uint64)]
+
+
 class MdRef(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -110,7 +125,7 @@ EXPORTED = [
     "flx_index_image_upload", "flx_index_meta_export", "flx_index_meta_import", "flx_ctx_create_on_image",
     "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records", "flx_assign_mapq", "flx_sam_set_mapq",
     "flx_align_reads_with_tags", "flx_align_reads_resident_with_tags", "flx_run_num_md_bytes", "flx_run_copy_md", "flx_align_batch_md",
-    "flx_sam_write_tagged",
+    "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
 ]
 
 _lib = None
@@ -204,6 +219,10 @@ def lib():
                                             C.POINTER(TagOptions), C.POINTER(C.c_void_p)]
     L.flx_align_reads_resident_with_tags.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(OutputOptions),
                                                      C.POINTER(TagOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_opt.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(RunOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_opt.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(RunOptions), C.POINTER(C.c_void_p)]
+    L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]
+    L.flx_partial_mapq.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(C.c_int32), u8p]
     L.flx_run_num_md_bytes.restype = C.c_uint64
     L.flx_run_num_md_bytes.argtypes = [C.c_void_p]
     L.flx_run_copy_md.argtypes = [C.c_void_p, C.POINTER(MdRef), u8p]

@@ -66,6 +66,8 @@ struct Options {
     uint64_t max_alignments = 0;                  // 0: no cap
     bool mapping_quality = false;
     bool md_tag = false;
+    bool partial_alignments = false;
+    uint64_t partial_min_span = 0, partial_max = 0;   // 0: the library's defaults
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -85,6 +87,10 @@ const OptDef OPTS[] = {
     {'Q', "mapping-quality", true, "not floxer's: MAPQ from the read's distinct loci within its error budget instead of 255 (0..60; computed before -D / -N drop records)"},
     // nor this one: an MD:Z tag on every mapped record (flx_tag_options.md), built on the GPU next to the CIGARs
     {0, "md-tag", true, "not floxer's: MD:Z tag (reference bases at mismatches and deletions) on every mapped record; not with -w"},
+    // nor these: soft-clipped partial alignments, primary + supplementary, for reads that would be unmapped (flx_partial_options, flx_partial.hpp)
+    {0, "partial-alignments", true, "not floxer's: a read without a full alignment gets its largest verified parts as soft-clipped records (primary, then flag 2048); not with -w"},
+    {0, "partial-min-span", false, "not floxer's: the fewest query bases of a partial alignment (default 1000)"},
+    {0, "partial-max", false, "not floxer's: the most partial records of a read (default 4)"},
 };
 
 struct CliError { std::string msg; };
@@ -181,6 +187,9 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "drop-duplicate-alignments") o.drop_duplicate_alignments = true;
         else if (n == "mapping-quality") o.mapping_quality = true;
         else if (n == "md-tag") o.md_tag = true;
+        else if (n == "partial-alignments") o.partial_alignments = true;
+        else if (n == "partial-min-span") { o.partial_min_span = parse_u64(n, value); range_check(n, (double)o.partial_min_span, 1, 100000); }
+        else if (n == "partial-max") { o.partial_max = parse_u64(n, value); range_check(n, (double)o.partial_max, 1, 65535); }
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -203,6 +212,8 @@ Options parse_cli(int argc, char** argv) {
         throw CliError{"The hard maximum number of anchors (" + std::to_string(o.max_anchors_hard) + ") should not be smaller than the soft maximum number of anchors (" + std::to_string(o.max_anchors_soft) + ")."};
     if (o.seed_sampling_step_size == 0) throw CliError{"Validation failed for option --seed-sampling-step-size: must be at least 1."};
     if (o.md_tag && o.without_cigar) throw CliError{"The option --md-tag needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.partial_alignments && o.without_cigar) throw CliError{"The option --partial-alignments needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (!o.partial_alignments && (o.partial_min_span || o.partial_max)) throw CliError{"The options --partial-min-span and --partial-max need --partial-alignments."};
     return o;
 }
 
@@ -594,6 +605,16 @@ int main(int argc, char** argv) {
     flx_tag_options tag_opt;
     memset(&tag_opt, 0, sizeof(tag_opt));
     tag_opt.md = o.md_tag;
+    flx_partial_options partial_opt;
+    memset(&partial_opt, 0, sizeof(partial_opt));
+    partial_opt.enable = o.partial_alignments;
+    partial_opt.min_query_span = (uint32_t)o.partial_min_span;
+    partial_opt.max_records = (uint32_t)o.partial_max;
+    flx_run_options run_opt;
+    memset(&run_opt, 0, sizeof(run_opt));
+    run_opt.output = &out_opt;
+    run_opt.tags = &tag_opt;
+    run_opt.partial = &partial_opt;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -624,7 +645,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads_with_tags(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &out_opt, &tag_opt, &run);
+        f.rc = flx_align_reads_opt(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));

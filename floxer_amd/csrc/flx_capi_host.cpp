@@ -7,6 +7,7 @@
 
 #include "flx_fm_core.hpp"
 #include "flx_mapq.hpp"
+#include "flx_partial.hpp"
 #include "flx_select.hpp"
 
 namespace flx {
@@ -196,6 +197,32 @@ int flx_assign_mapq(const flx_record* records, uint64_t n, const uint32_t* cigar
             keys[i - lo] = MapqKey{(u64)(uint32_t)r.position, span, r.reference_id, r.flag, r.num_errors};
         }
         read_mapq(keys.data(), keys.size(), mapq + lo, scratch);
+        lo = hi;
+    }
+    return FLX_OK;
+}
+
+int flx_choose_partials(const flx_partial_candidate* candidates, uint64_t n, const uint32_t* cigar_words, const flx_partial_options* options,
+                        int32_t* keep_flag) {
+    if ((n && (!candidates || !keep_flag))) { set_error("flx_choose_partials: null argument"); return FLX_ERR_INVALID; }
+    if (!partial_options_valid(options)) return FLX_ERR_INVALID;
+    PartialScratch scratch;
+    for (u64 lo = 0; lo < n;) {
+        u64 hi = lo + 1;
+        while (hi < n && candidates[hi].read_index == candidates[lo].read_index) ++hi;
+        choose_partials(candidates + lo, hi - lo, partial_max_records(options), cigar_words, keep_flag + lo, scratch);
+        lo = hi;
+    }
+    return FLX_OK;
+}
+
+int flx_partial_mapq(const flx_partial_candidate* candidates, uint64_t n, const uint32_t* cigar_words, const int32_t* keep_flag, uint8_t* mapq) {
+    if ((n && (!candidates || !keep_flag || !mapq))) { set_error("flx_partial_mapq: null argument"); return FLX_ERR_INVALID; }
+    PartialScratch scratch;
+    for (u64 lo = 0; lo < n;) {
+        u64 hi = lo + 1;
+        while (hi < n && candidates[hi].read_index == candidates[lo].read_index) ++hi;
+        partial_mapq(candidates + lo, hi - lo, cigar_words, keep_flag + lo, mapq + lo, scratch);
         lo = hi;
     }
     return FLX_OK;

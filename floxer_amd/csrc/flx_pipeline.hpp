@@ -155,6 +155,9 @@ struct AnchorState {
 struct Span { u64 offset, length, extra; };
 struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; };
 
+// a record rescue_partials leaves for write_records (flx_partial.hpp): a soft-clipped part of a read without a mapped record
+struct PartialRecord { u32 read; u32 flag; u32 ref_id; u64 start; u32 nm; u64 cigar_off; u32 cigar_len; u64 md_off; u32 md_len; u32 q_from, q_to; u32 mapq; };
+
 struct Slice {
     // plan_reads
     hvec<ReadState> reads;                                                    // the reads that are not skipped
@@ -182,6 +185,8 @@ struct Slice {
     hvec<u32> cig;                                                            // CIGAR pool of root_res
     bool want_md = false;                                                     // flx_tag_options.md: the traced paths' MD strings as well
     hvec<u8> md;                                                              // MD pool of root_res
+    // rescue_partials: the records of the reads it rescued, read by read in the order they are written in; {q_from, q_to} read-forward
+    hvec<PartialRecord> partials;
     // statistics in the reference's form (flx_stats.cpp), when the context has a statistics object attached, and their clock
     std::unique_ptr<Stats> st_local;
     std::chrono::steady_clock::time_point t_slice;
@@ -191,8 +196,8 @@ struct Slice {
 };
 
 // produces the slice's records (read_index relative to the whole batch)
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_reads* RD, u64 first_read, u64 end_read,
-                flx_run* run);
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_reads* RD,
+                u64 first_read, u64 end_read, flx_run* run);
 // NULL or zeroed: no tags; md must be 0 or 1 and the reserved fields 0 (else the error is set)
 bool tag_options_valid(const flx_tag_options* t);
 

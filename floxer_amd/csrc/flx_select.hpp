@@ -50,6 +50,8 @@ inline uint64_t select_hash(SelectKey const& k) {
 // keep[i] = 1 for the records of the read that are written, 0 for the others (rules of flx_output_options)
 inline void select_read_records(const SelectKey* k, size_t n, bool drop_duplicates, uint64_t max_per_read, uint8_t* keep, SelectScratch& s) {
     for (size_t i = 0; i < n; ++i) keep[i] = 1;
+    // (a read with a supplementary record carries partial alignments: they are selected already, flx_partial.hpp)
+    for (size_t i = 0; i < n; ++i) if (k[i].flag & 2048u) return;
     if (drop_duplicates && n > 1) {
         // records in (hash, index) order: a class of equal records lies in one run of equal hashes, its first record first
         s.hash.resize(n);

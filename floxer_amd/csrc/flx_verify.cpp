@@ -10,9 +10,11 @@
 #include <mutex>
 #include <queue>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "flx_mapq.hpp"
+#include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
 #include "flx_select.hpp"
 
@@ -417,7 +419,7 @@ int climb_on_device(Slice& S, Lane* lane, const flx_reads* RD) {
     if ((rc = lane->sync())) return rc;
     for (u32 i = 0; i < n; ++i) {
         AnchorState& a = A[i];
-        if (h_status[i] == VR_DEAD && a.alive && !a.at_root) a.alive = false;
+        if (h_status[i] == VR_DEAD && a.alive && !a.at_root) { a.alive = false; a.node = h_node[i]; }      // (the node it failed at, as climb_on_host leaves it)
         else if (h_status[i] == VR_AT_ROOT && !a.at_root) { a.at_root = true; a.node = h_node[i]; }
     }
     vprof.mark("read-back");
@@ -573,6 +575,92 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) 
     return FLX_OK;
 }
 
+// ---- 8. partial alignments of the reads that would be written as unmapped (flx_partial.hpp): every anchor's highest passed node,
+//      traced in the window it was tested in; does nothing, and launches nothing, when the option is off or no read is eligible
+int rescue_partials(Slice& S, Lane* lane, const flx_params* P, const flx_output_options* O, const flx_partial_options* PO, const flx_reads* RD) {
+    if (!partial_options_active(PO)) return FLX_OK;
+    flx_ctx* ctx = lane->ctx;
+    HostIndex const& H = *ctx->hidx;
+    hvec<ReadState> const& reads = S.reads;
+    hvec<AnchorState> const& A = S.A;
+    hvec<u8> mapped(reads.size(), 0);
+    for (u32 i = 0; i < S.root_anchor.size(); ++i) if (S.root_res[i].exists) mapped[A[S.root_anchor[i]].read] = 1;
+    u32 const min_span = partial_min_span(PO), max_records = partial_max_records(PO);
+    // ---- candidates, read by read in verification order; identical (orientation, node, reference, window) ones are one
+    struct Candidate { u32 read; u8 orientation; u32 ref_id; flx_pex_node node; Span span; };
+    hvec<Candidate> cands;
+    hvec<AlignRequest> reqs;
+    hvec<u32> read_first(reads.size() + 1, 0);
+    std::map<std::tuple<u64, u32, u32, u64, u32>, u32> seen;
+    for (size_t r = 0; r < reads.size(); ++r) {
+        read_first[r] = (u32)cands.size();
+        if (mapped[r]) continue;
+        PexTree const& tree = reads[r].tree_ref();
+        seen.clear();
+        for (u32 ai : S.exec_order[r]) {
+            AnchorState const& a = A[ai];
+            flx_pex_node const* node = &tree.leaves[a.leaf];
+            if (node->parent_id == FLX_NULL_ID) continue;                                        // a tree of one node: the leaf is the root
+            if (!P->direct_full_verification) {
+                if (a.alive && !a.at_root) { set_error("partial alignments: an anchor neither failed nor reached the root"); return FLX_ERR_INTERNAL; }
+                // the child of a.node (the node it failed at, or the root) on the anchor's path
+                u32 guard = 0;
+                for (u32 up = node->parent_id; up != a.node; up = node->parent_id) {
+                    if (up == FLX_NULL_ID || ++guard > tree.inner.size()) { set_error("partial alignments: an anchor's node is not on its path"); return FLX_ERR_INTERNAL; }
+                    node = &tree.inner[up];
+                }
+            }
+            if (node->to - node->from + 1 < min_span) continue;
+            Span sp;
+            AlignRequest const req = window_request(S, H, a, *node, 0.0, &sp);
+            if (!seen.emplace(std::make_tuple(req.q_off, req.m, req.k, req.ref_off, req.n), 0u).second) continue;
+            cands.push_back(Candidate{(u32)r, a.orientation, a.ref_id, *node, sp});
+            reqs.push_back(req);
+        }
+    }
+    read_first[reads.size()] = (u32)cands.size();
+    if (cands.empty()) return FLX_OK;
+    hvec<TraceResult> tres;
+    if (int const rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, S.cig, S.want_md ? &S.md : nullptr)) return rc;
+    // ---- selection per read, and the kept records with their clips
+    std::vector<flx_partial_candidate> pc;
+    std::vector<int32_t> flags;
+    std::vector<u8> quality;
+    PartialScratch scratch;
+    bool const mapq = O && O->mapq;
+    for (size_t r = 0; r < reads.size(); ++r) {
+        u32 const c0 = read_first[r], c1 = read_first[r + 1];
+        if (c0 == c1) continue;
+        u32 const len = reads[r].len;
+        pc.clear();
+        for (u32 c = c0; c < c1; ++c) {
+            if (!tres[c].exists) { set_error("partial alignments: no alignment in a window that verification passed"); return FLX_ERR_INTERNAL; }
+            flx_pex_node const& nd = cands[c].node;
+            u32 const q_from = cands[c].orientation ? len - 1 - nd.to : nd.from, q_to = cands[c].orientation ? len - 1 - nd.from : nd.to;
+            pc.push_back(flx_partial_candidate{reads[r].read_index, q_from, q_to, cands[c].orientation, (int32_t)cands[c].ref_id,
+                                               cands[c].span.offset + tres[c].begin, tres[c].nm, tres[c].cigar_len, tres[c].cigar_off});
+        }
+        flags.resize(pc.size());
+        choose_partials(pc.data(), pc.size(), max_records, S.cig.data(), flags.data(), scratch);
+        quality.assign(pc.size(), 0);
+        if (mapq) partial_mapq(pc.data(), pc.size(), S.cig.data(), flags.data(), quality.data(), scratch);
+        for (u32 j : scratch.kept) {
+            u32 const c = c0 + j;
+            flx_pex_node const& nd = cands[c].node;
+            // (new words behind the pool's: the traced words may be shared with other records)
+            u64 const off = S.cig.size();
+            if (nd.from) S.cig.push_back((nd.from << 4) | 4u);
+            size_t const at = S.cig.size();
+            S.cig.resize(at + tres[c].cigar_len);            // (grown first: the source lies in the same pool)
+            std::copy(S.cig.begin() + (long)tres[c].cigar_off, S.cig.begin() + (long)(tres[c].cigar_off + tres[c].cigar_len), S.cig.begin() + (long)at);
+            if (len - 1 - nd.to) S.cig.push_back(((len - 1 - nd.to) << 4) | 4u);
+            S.partials.push_back(PartialRecord{(u32)r, (u32)flags[j], cands[c].ref_id, pc[j].start, tres[c].nm, off, (u32)(S.cig.size() - off), tres[c].md_off,
+                                               tres[c].md_len, pc[j].q_from, pc[j].q_to, quality[j]});
+        }
+    }
+    return FLX_OK;
+}
+
 // the CIGAR words of the kept records only: records that shared (or overlapped in) words before share them afterwards
 void compact_cigars(flx_run* run, hvec<u32>& cig) {
     hvec<u32> order;
@@ -598,7 +686,7 @@ void compact_cigars(flx_run* run, hvec<u32>& cig) {
     cig.swap(kept_words);
 }
 
-// ---- 8. records (alignment.cpp:37-79, output.cpp:49-108): per reference in id order, alignments in verification order
+// ---- 9. records (alignment.cpp:37-79, output.cpp:49-108): per reference in id order, alignments in verification order
 void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_slice_reads, flx_run* run) {
     HostIndex const& H = *ctx->hidx;
     hvec<ReadState> const& reads = S.reads;
@@ -623,6 +711,8 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
     // MD (flx_tag_options.md): one {offset, length} per record, parallel to run->records; the selection moves it with the records it keeps
     bool const md = S.want_md;
     run->has_md = md;
+    size_t next_partial = 0;
+    u64 n_partial_records = 0, n_rescued = 0;
     for (size_t r = 0; r < reads.size(); ++r) {
         size_t const rec0 = run->records.size();
         bool have_best = false;
@@ -647,7 +737,16 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
                     mq_keys.push_back(MapqKey{root_res[i].start, span, (int32_t)ref, flag, root_res[i].nm});
                 }
             }
-        if (!primary_written) {
+        bool const rescued = next_partial < S.partials.size() && S.partials[next_partial].read == r;
+        if (rescued) {                                           // (only a read without a mapped record has partial records)
+            for (; next_partial < S.partials.size() && S.partials[next_partial].read == r; ++next_partial) {
+                PartialRecord const& p = S.partials[next_partial];
+                run->records.push_back(flx_record{reads[r].read_index, p.flag, (int32_t)p.ref_id, saturate_i32(p.start), p.nm, p.cigar_off, p.cigar_len, p.mapq});
+                if (md) run->md_refs.push_back(flx_md_ref{p.md_off, p.md_len, 0});
+                ++n_partial_records;
+            }
+            ++n_rescued;
+        } else if (!primary_written) {
             run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
             if (md) run->md_refs.push_back(flx_md_ref{0, 0, 0});
         }
@@ -657,7 +756,7 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
             for (size_t j = 0; j < mq_keys.size(); ++j) run->records[rec0 + j].reserved = mq_q[j];
             mq_keys.clear();
         }
-        if (select && run->records.size() - rec0 > 1) {
+        if (select && !rescued && run->records.size() - rec0 > 1) {
             // (records in the loop's order: the read's mapped roots by reference, the start key unsaturated)
             size_t const n = run->records.size() - rec0;
             sel_keys.clear();
@@ -701,6 +800,7 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
         flx_path_counters& pc = ctx->path;
         pc.inner_tests_requested += S.n_inner_requested; pc.root_alignments_requested += S.root_reqs.size(); pc.root_alignments_found += found;
         pc.records += run->records.size(); pc.reads += n_slice_reads; pc.reserved[0] += n_dropped;
+        pc.reserved[1] += n_partial_records; pc.reserved[2] += n_rescued;
     }
 }
 
@@ -713,8 +813,8 @@ bool tag_options_valid(const flx_tag_options* t) {
     return true;
 }
 
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_reads* RD, u64 first_read, u64 end_read,
-                flx_run* run) {
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_reads* RD,
+                u64 first_read, u64 end_read, flx_run* run) {
     flx_ctx* ctx = lane->ctx;
     FLX_HIP(hipSetDevice(ctx->device));
     HostIndex const& H = *ctx->hidx;
@@ -745,6 +845,8 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
     prof.mark("interval-pass");
     if ((rc = align_roots(S, lane, P, RD))) return rc;
     prof.mark("root-align");
+    if ((rc = rescue_partials(S, lane, P, O, PO, RD))) return rc;
+    prof.mark("partials");
     write_records(S, ctx, O, end_read - first_read, run);
     prof.mark("records");
     return FLX_OK;

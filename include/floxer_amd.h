@@ -12,7 +12,7 @@
  * flx_ctx_enable_kernel_timing, flx_ctx_reset_kernel_stats, flx_ctx_destroy) must not overlap anything else.
  *
  * Sequences are rank sequences as the reference stores them (input.cpp:165-176): $=0 A=1 C=2 G=3 T=4 N/other=5.
- * CIGARs are BAM words (len<<4|op) with ops I=1 D=2 '='=7 X=8 (extended CIGAR, alignment.cpp:178).
+ * CIGARs are BAM words (len<<4|op) with ops I=1 D=2 '='=7 X=8 (extended CIGAR, alignment.cpp:178), and S=4 in partial records only.
  */
 #ifndef FLOXER_AMD_H
 #define FLOXER_AMD_H
@@ -205,7 +205,7 @@ void flx_params_default(flx_params* p);
 
 typedef struct flx_record {          /* one SAM/BAM record, output.cpp:49-108 */
     uint64_t read_index;
-    uint32_t flag;                   /* 0 / 16 / 256 / 272 / 4 */
+    uint32_t flag;                   /* 0 / 16 / 256 / 272 / 4; 2048 / 2064 with flx_partial_options */
     int32_t reference_id;            /* -1 when unmapped */
     int32_t position;                /* 0-based, saturated to int32 (output.cpp:85) */
     uint32_t num_errors;             /* NM */
@@ -283,6 +283,66 @@ uint64_t flx_run_num_md_bytes(const flx_run* run);                   /* 0 for a 
 /* refs: one per record, in record order; md_bytes: flx_run_num_md_bytes bytes (what lies between the strings is unspecified). Either may be NULL. A run made without md: FLX_ERR_INVALID. */
 int flx_run_copy_md(const flx_run* run, flx_md_ref* refs, uint8_t* md_bytes);
 
+/* Partial alignments: not floxer's, which maps a read only when its whole length aligns within its errors (a chimeric read, or one
+ * across a structural break, is written as unmapped). Off when the struct is zeroed (or NULL), and then nothing changes: no launch, no
+ * byte of any output. With enable = 1 (anything else but 0 is refused) a read that is not skipped and that has no mapped record gets,
+ * in place of its unmapped record, the largest parts of it that verification proved to align, as soft-clipped records:
+ *   - candidate of an anchor: the highest PEX node on its leaf-to-root path that it passed - the child, on that path, of the node it
+ *     failed at (the leaf itself when its first inner node failed; a leaf counts as passed), or the child of the root when the anchor
+ *     reached the root and the root alignment failed. With params->direct_full_verification nothing climbs: the candidates are leaves;
+ *   - it counts when its node has at least min_query_span rows (0: the default 1000, a convention of this project, not fitted to
+ *     anything), and is traced in exactly the window it was tested in (no extension, k = the node's errors): an alignment exists.
+ *     Identical (orientation, node, reference, window) candidates are traced once, overlapping windows of a node share one DP as root
+ *     windows do, with MD strings when flx_tag_options.md is on;
+ *   - per read (query intervals in read-forward coordinates: node [from, to] of the reverse complement is [len-1-to, len-1-from]):
+ *     candidates equal to an earlier one in (orientation, reference, start, NM, CIGAR words) are dropped, the others ordered by (rows
+ *     descending, NM ascending, reference id, verification order) and taken greedily: the first is the primary (flag 0 / 16), a later
+ *     one is kept as supplementary (flag 2048 | strand) when its interval overlaps no kept one, until max_records (0: the default 4)
+ *     are kept. They are written primary first, then the supplementaries by forward query start;
+ *   - a kept record: position = the reference start of the aligned part, num_errors = its NM (clipped bases are not counted), CIGAR =
+ *     [from]S + the traced words + [rows behind the node]S in the oriented sequence (zero-length clips omitted), MD of the traced part.
+ * Output options: drop_duplicates and max_alignments_per_read leave a read's partial records alone (they are selected already;
+ * flx_select_records keeps all records of a read that has a flag-2048 record); mapq gives each kept record read_mapq's value over the
+ * read's traced candidates with exactly its forward query interval. params->without_cigar has no trace: refused together with enable
+ * (FLX_ERR_INVALID) before any work. --stats and every named flx_path_counters field keep describing verification; reserved[1] counts
+ * the partial records written and reserved[2] the reads that got them. No SA tag is written. The rule and its limits:
+ * floxer_amd/csrc/flx_partial.hpp. */
+typedef struct flx_partial_options {
+    uint32_t enable;
+    uint32_t min_query_span;     /* 0: 1000 */
+    uint32_t max_records;        /* 0: 4 */
+    uint32_t reserved[5];
+} flx_partial_options;
+/* Every option of a run in one bundle: each pointer may be NULL (that option off). A NULL bundle, or one of NULLs / zeroed structs, is
+ * exactly flx_align_reads / flx_align_reads_resident; the calls above forward here. The reserved pointers must be NULL. */
+typedef struct flx_run_options {
+    const flx_output_options* output;
+    const flx_tag_options* tags;
+    const flx_partial_options* partial;
+    const void* reserved[5];
+} flx_run_options;
+int flx_align_reads_opt(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                        const flx_run_options* options, flx_run** out);
+int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_run_options* options, flx_run** out);
+/* The selection on any candidate array (host only): the candidates of a read are contiguous and in verification order; q_from / q_to are
+ * inclusive read-forward coordinates. keep_flag[i] = -1 when candidate i is not written, else its SAM flag (0 / 16 / 2048 / 2064).
+ * cigar_words may be NULL: then CIGARs compare by (offset, length). options NULL: the defaults (enable is not read). */
+typedef struct flx_partial_candidate {
+    uint64_t read_index;
+    uint32_t q_from, q_to;
+    uint32_t orientation;        /* 0 forward, 1 reverse complement */
+    int32_t reference_id;
+    uint64_t start;              /* reference start of the aligned part */
+    uint32_t nm;
+    uint32_t cigar_length;
+    uint64_t cigar_offset;
+} flx_partial_candidate;
+int flx_choose_partials(const flx_partial_candidate* candidates, uint64_t n, const uint32_t* cigar_words, const flx_partial_options* options,
+                        int32_t* keep_flag);
+/* the mapping quality of the kept candidates (keep_flag as flx_choose_partials gave it), 0 for the others. cigar_words NULL: a
+ * candidate spans as many reference symbols as query rows. */
+int flx_partial_mapq(const flx_partial_candidate* candidates, uint64_t n, const uint32_t* cigar_words, const int32_t* keep_flag, uint8_t* mapq);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -307,7 +367,8 @@ typedef struct flx_path_counters {
     uint64_t seeds, seeds_with_anchors, seeds_excluded_by_hard_cap, seeds_selected_on_host, anchors, cursor_extensions;
     uint64_t inner_tests_requested, root_alignments_requested, root_alignments_found, records, reads;
     uint64_t search_reruns;      /* search launches repeated because a chunk's hits or queued subtrees outgrew their buffers */
-    uint64_t reserved[4];        /* reserved[0]: records_dropped, the records flx_output_options left out (records counts those written) */
+    uint64_t reserved[4];        /* reserved[0]: records_dropped, the records flx_output_options left out (records counts those written);
+                                    reserved[1]: partial records written, reserved[2]: reads they rescued (flx_partial_options) */
 } flx_path_counters;
 int flx_ctx_get_path_counters(flx_ctx* ctx, flx_path_counters* out);
 int flx_ctx_reset_path_counters(flx_ctx* ctx);
