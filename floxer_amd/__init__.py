@@ -11,6 +11,8 @@ libfloxer_amd.so:
     output_options(...), select_records()  not floxer's: duplicate alignments dropped / alignments per read capped (opt-in)
     output_options(mapq=True), assign_mapq()  not floxer's: mapping quality from a read's distinct loci (opt-in)
     aligner(..., md=True), align(..., md=True)  not floxer's: MD strings, built on the device next to the CIGARs (opt-in)
+    aligner(..., partial=partial_options())   not floxer's: soft-clipped partial alignments of reads without a full one (opt-in)
+    aligner(..., extend=extend_options()), extend_batch()  not floxer's: the partial records' ends extended to the break (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -539,6 +541,40 @@ def partial_options(min_query_span=0, max_records=0, enable=True):
     return o
 
 
+def extend_options(error_weight=0, x_drop=0, max_errors=0, enable=True):
+    """flx_extend_options (include/floxer_amd.h): not floxer's. Both ends of every partial record are extended to the break: an
+    extension keeps the rows R(d) reached with d errors that maximise R(d) - error_weight * d (0: 4), gives up once that score fell
+    x_drop (0: 100) below its maximum and never takes more than max_errors (0: 1024) errors. Needs partial_options(...)."""
+    if error_weight < 0 or x_drop < 0 or max_errors < 0:
+        raise FloxerError("error_weight, x_drop and max_errors must be >= 0 (0: the default)")
+    o = capi.ExtendOptions()
+    o.enable, o.error_weight, o.x_drop, o.max_errors = int(bool(enable)), int(error_weight), int(x_drop), int(max_errors)
+    return o
+
+
+EXTEND_STOP = {1: "x_drop", 2: "rows", 3: "max_errors"}
+
+
+def extend_batch(ctx, query_pool, jobs, reference_pool=None):
+    """flx_extend_batch, the extension kernel alone: jobs = [(text_pos, ref_limit, q_pos, row_limit, direction, error_weight, x_drop,
+    max_errors)] (the last three 0: the defaults). reference_pool None = the context's reference text. Returns an (n,4) int64 array
+    {rows, cols, errors, stop reason (EXTEND_STOP)}."""
+    q = as_u8(query_pool)
+    if len(q) == 0:
+        q = np.zeros(1, np.uint8)
+    arr = (capi.ExtendJob * max(1, len(jobs)))()
+    for i, (tp, rl, qp, il, direction, w, x, dm) in enumerate(jobs):
+        arr[i] = capi.ExtendJob(int(tp), int(qp), int(rl), int(il), int(direction), int(w), int(x), int(dm))
+    res = (capi.ExtendResult * max(1, len(jobs)))()
+    if reference_pool is None:
+        rp, rl_ = None, 0
+    else:
+        ref = as_u8(reference_pool)
+        rp, rl_ = ptr(ref, u8p), len(ref)
+    check(lib().flx_extend_batch(ctx.h, rp, rl_, ptr(q, u8p), len(query_pool), arr, len(jobs), res))
+    return np.array([(r.rows, r.cols, r.errors, r.stop_reason) for r in res[: len(jobs)]], dtype=np.int64).reshape(-1, 4)
+
+
 def choose_partials(candidates, cigars=None, options=None):
     """flx_choose_partials: candidates = rows {read_index, q_from, q_to, orientation, reference_id, start, nm, cigar_offset, cigar_length}
     (a read's rows contiguous, in verification order; forward query coordinates). Returns an int32 array: -1 for a candidate that is not
@@ -576,22 +612,26 @@ def _collect_run(run, n, md=False):
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None, md=False, partial=None):
+    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None):
         """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
         string (RunResult.md), built on the device; not together with without_cigar; partial: partial_options(...), None: a read
-        without a full alignment is written as unmapped (floxer's output)"""
-        self.ctx, self.params, self.output, self.md, self.partial = ctx, p, output, bool(md), partial
+        without a full alignment is written as unmapped (floxer's output); extend: extend_options(...), None: a partial record ends at
+        its PEX node's boundary (needs partial)"""
+        self.ctx, self.params, self.output, self.md, self.partial, self.extend = ctx, p, output, bool(md), partial, extend
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
         run = C.c_void_p()
-        if self.partial is not None:
+        if self.partial is not None or self.extend is not None:
             tags = tag_options(md=self.md)
             bundle = capi.RunOptions()
             if self.output is not None:
                 bundle.output = C.pointer(self.output)
             bundle.tags = C.pointer(tags)
-            bundle.partial = C.pointer(self.partial)
+            if self.partial is not None:
+                bundle.partial = C.pointer(self.partial)
+            if self.extend is not None:
+                bundle.extend = C.pointer(self.extend)
             if isinstance(reads, resident_reads):
                 check(lib().flx_align_reads_resident_opt(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), C.byref(run)))
                 return _collect_run(run, reads.n, md=self.md)

@@ -84,9 +84,23 @@ class PartialOptions(C.Structure):
     _fields_ = [("enable", C.c_uint32), ("min_query_span", C.c_uint32), ("max_records", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+class ExtendOptions(C.Structure):
+    _fields_ = [("enable", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32), ("max_errors", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class RunOptions(C.Structure):
     _fields_ = [("output", C.POINTER(OutputOptions)), ("tags", C.POINTER(TagOptions)), ("partial", C.POINTER(PartialOptions)),
-                ("reserved", C.c_void_p * 5)]
+                ("extend", C.POINTER(ExtendOptions)), ("reserved", C.c_void_p * 4)]
+
+
+class ExtendJob(C.Structure):
+    _fields_ = [("text_pos", C.c_uint64), ("q_pos", C.c_uint64), ("ref_limit", C.c_uint32), ("row_limit", C.c_uint32),
+                ("direction", C.c_int32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32), ("max_errors", C.c_uint32)]
+
+
+class ExtendResult(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("cols", C.c_uint32), ("errors", C.c_uint32), ("stop_reason", C.c_uint32)]
 
 
 class PartialCandidate(C.Structure):
@@ -126,6 +140,7 @@ EXPORTED = [
     "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records", "flx_assign_mapq", "flx_sam_set_mapq",
     "flx_align_reads_with_tags", "flx_align_reads_resident_with_tags", "flx_run_num_md_bytes", "flx_run_copy_md", "flx_align_batch_md",
     "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
+    "flx_extend_batch", "flx_sam_set_sa",
 ]
 
 _lib = None
@@ -255,6 +270,8 @@ def lib():
     L.flx_index_matches_reference.argtypes = [C.c_void_p, u8p, u64p, C.c_uint32]
     L.flx_sam_set_threads.argtypes = [C.c_void_p, C.c_uint32]
     L.flx_sam_set_mapq.argtypes = [C.c_void_p, C.c_int]
+    L.flx_sam_set_sa.argtypes = [C.c_void_p, C.c_int]
+    L.flx_extend_batch.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(ExtendJob), C.c_uint64, C.POINTER(ExtendResult)]
     L.flx_ctx_get_path_counters.argtypes = [C.c_void_p, C.POINTER(PathCounters)]
     L.flx_ctx_reset_path_counters.argtypes = [C.c_void_p]
     L.flx_sim_genome.argtypes = [C.c_uint64, C.c_uint64, u8p]

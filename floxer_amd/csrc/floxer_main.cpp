@@ -68,6 +68,8 @@ struct Options {
     bool md_tag = false;
     bool partial_alignments = false;
     uint64_t partial_min_span = 0, partial_max = 0;   // 0: the library's defaults
+    bool partial_extend = false, sa_tag = false;
+    uint64_t partial_extend_weight = 0, partial_extend_xdrop = 0, partial_extend_max_errors = 0;   // 0: the library's defaults
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -91,6 +93,12 @@ const OptDef OPTS[] = {
     {0, "partial-alignments", true, "not floxer's: a read without a full alignment gets its largest verified parts as soft-clipped records (primary, then flag 2048); not with -w"},
     {0, "partial-min-span", false, "not floxer's: the fewest query bases of a partial alignment (default 1000)"},
     {0, "partial-max", false, "not floxer's: the most partial records of a read (default 4)"},
+    // nor these: the partial records' ends extended to the break (flx_extend_options) and the SA:Z tag that ties a read's records together
+    {0, "partial-extend", true, "not floxer's: extend both ends of every partial record to the break (x-drop extension on the GPU); needs --partial-alignments"},
+    {0, "partial-extend-weight", false, "not floxer's: rows one more error must gain for the extension to go on (default 4); needs --partial-extend"},
+    {0, "partial-extend-xdrop", false, "not floxer's: the extension stops once its score fell this far below its maximum (default 100); needs --partial-extend"},
+    {0, "partial-extend-max-errors", false, "not floxer's: the most errors of one extension (default 1024, at most 4093); needs --partial-extend"},
+    {0, "sa-tag", true, "not floxer's: SA:Z tag on the records of every read that got supplementary records; needs --partial-alignments"},
 };
 
 struct CliError { std::string msg; };
@@ -190,6 +198,11 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "partial-alignments") o.partial_alignments = true;
         else if (n == "partial-min-span") { o.partial_min_span = parse_u64(n, value); range_check(n, (double)o.partial_min_span, 1, 100000); }
         else if (n == "partial-max") { o.partial_max = parse_u64(n, value); range_check(n, (double)o.partial_max, 1, 65535); }
+        else if (n == "partial-extend") o.partial_extend = true;
+        else if (n == "partial-extend-weight") { o.partial_extend_weight = parse_u64(n, value); range_check(n, (double)o.partial_extend_weight, 1, 65535); }
+        else if (n == "partial-extend-xdrop") { o.partial_extend_xdrop = parse_u64(n, value); range_check(n, (double)o.partial_extend_xdrop, 1, 1073741824); }
+        else if (n == "partial-extend-max-errors") { o.partial_extend_max_errors = parse_u64(n, value); range_check(n, (double)o.partial_extend_max_errors, 1, 4093); }
+        else if (n == "sa-tag") o.sa_tag = true;
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -214,6 +227,10 @@ Options parse_cli(int argc, char** argv) {
     if (o.md_tag && o.without_cigar) throw CliError{"The option --md-tag needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     if (o.partial_alignments && o.without_cigar) throw CliError{"The option --partial-alignments needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     if (!o.partial_alignments && (o.partial_min_span || o.partial_max)) throw CliError{"The options --partial-min-span and --partial-max need --partial-alignments."};
+    if (o.partial_extend && !o.partial_alignments) throw CliError{"The option --partial-extend needs --partial-alignments."};
+    if (!o.partial_extend && (o.partial_extend_weight || o.partial_extend_xdrop || o.partial_extend_max_errors))
+        throw CliError{"The options --partial-extend-weight, --partial-extend-xdrop and --partial-extend-max-errors need --partial-extend."};
+    if (o.sa_tag && !o.partial_alignments) throw CliError{"The option --sa-tag needs --partial-alignments."};
     return o;
 }
 
@@ -602,6 +619,7 @@ int main(int argc, char** argv) {
     out_opt.max_alignments_per_read = o.max_alignments;
     out_opt.mapq = o.mapping_quality;            // (the options go with every batch, whichever device context aligns it)
     flx_sam_set_mapq(out, o.mapping_quality);
+    flx_sam_set_sa(out, o.sa_tag);
     flx_tag_options tag_opt;
     memset(&tag_opt, 0, sizeof(tag_opt));
     tag_opt.md = o.md_tag;
@@ -614,7 +632,14 @@ int main(int argc, char** argv) {
     memset(&run_opt, 0, sizeof(run_opt));
     run_opt.output = &out_opt;
     run_opt.tags = &tag_opt;
+    flx_extend_options extend_opt;
+    memset(&extend_opt, 0, sizeof(extend_opt));
+    extend_opt.enable = o.partial_extend;
+    extend_opt.error_weight = (uint32_t)o.partial_extend_weight;
+    extend_opt.x_drop = (uint32_t)o.partial_extend_xdrop;
+    extend_opt.max_errors = (uint32_t)o.partial_extend_max_errors;
     run_opt.partial = &partial_opt;
+    run_opt.extend = &extend_opt;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);

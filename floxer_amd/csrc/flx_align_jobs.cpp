@@ -10,6 +10,7 @@
 #include <numeric>
 #include <string>
 
+#include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
 
 namespace flx {
@@ -697,6 +698,31 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
     return FLX_OK;
 }
 
+// One ed_extend launch over all jobs; the wavefront cells and the symbols walked are known once the results are back.
+int run_extend_jobs(Lane* lane, const u8* d_text, const u8* d_query, hvec<DevExtendJob>& jobs, hvec<DevExtendOut>& outs) {
+    outs.assign(jobs.size(), DevExtendOut{});
+    if (jobs.empty()) return FLX_OK;
+    u32 lds_d = 0;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        jobs[i].out_index = (u32)i;
+        if (jobs[i].d_max > EXTEND_MAX_ERRORS || jobs[i].row_limit > EXTEND_MAX_ROWS) { set_error("ed_extend: a job is larger than the kernel holds"); return FLX_ERR_INTERNAL; }
+        lds_d = std::max(lds_d, std::min(jobs[i].d_max, jobs[i].row_limit));
+    }
+    int rc;
+    if ((rc = h2d(lane, lane->ext_jobs, jobs.data(), jobs.size() * sizeof(DevExtendJob)))) return rc;
+    if ((rc = lane->ext_out.ensure(jobs.size() * sizeof(DevExtendOut)))) return rc;
+    rc = timed_launch(lane, "ed_extend", jobs.size() * (sizeof(DevExtendJob) + sizeof(DevExtendOut)), 0, [&] {
+        return DeviceApi::extend(lane->stream, d_text, d_query, lane->ext_jobs.as<DevExtendJob>(), (u32)jobs.size(), lds_d, lane->ext_out.as<DevExtendOut>());
+    });
+    if (rc) return rc;
+    if ((rc = d2h(lane, outs.data(), lane->ext_out.ptr, outs.size() * sizeof(DevExtendOut)))) return rc;
+    if ((rc = lane->sync())) return rc;
+    u64 cells = 0, symbols = 0;
+    for (auto const& o : outs) { cells += ((u64)o.last_d + 1) * ((u64)o.last_d + 1); symbols += (u64)o.rows + o.cols; }
+    lane->ctx->account_more("ed_extend", symbols, cells);
+    return FLX_OK;
+}
+
 int build_peq(Lane* ctx, const u8* d_seq, u64 len, DeviceBuffer& peq) {
     u64 const n_words = len / 64 + 2;
     int rc = peq.ensure(n_words * 6 * 8 + 64);
@@ -823,5 +849,39 @@ extern "C" int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_
             r.exists = 1; r.num_errors = tres[i].nm; r.begin = tres[i].begin; r.cigar_offset = tres[i].cigar_off; r.cigar_length = tres[i].cigar_len;
             if (out_md) out_md[trace_ids[i]] = flx_md_ref{tres[i].md_off, tres[i].md_len, 0};
         }
+    return FLX_OK;
+}
+
+// ================================================================================================ C ABI: the extension kernel alone
+extern "C" int flx_extend_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                                const flx_extend_job* jobs, uint64_t n_jobs, flx_extend_result* out) {
+    if (!ctx || (n_jobs && (!jobs || !out || !query_pool))) { set_error("flx_extend_batch: null argument"); return FLX_ERR_INVALID; }
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    u64 const text_len = ref_pool ? ref_pool_len : ctx->hidx->n;
+    hvec<DevExtendJob> dj(n_jobs);
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_extend_job const& j = jobs[i];
+        flx_extend_options const as_options{0, j.error_weight, j.x_drop, j.max_errors, {}};
+        if (!extend_options_valid(&as_options)) return FLX_ERR_INVALID;
+        if (j.direction != 1 && j.direction != -1) { set_error("flx_extend_batch: direction must be +1 or -1"); return FLX_ERR_INVALID; }
+        if (j.row_limit > EXTEND_MAX_ROWS || j.ref_limit >= (1u << 31)) { set_error("flx_extend_batch: row_limit must be below 2^19 and ref_limit below 2^31"); return FLX_ERR_INVALID; }
+        bool const inside = j.direction > 0 ? (j.text_pos <= text_len && j.ref_limit <= text_len - j.text_pos && j.q_pos <= query_pool_len && j.row_limit <= query_pool_len - j.q_pos)
+                                            : ((j.ref_limit == 0 || (j.text_pos < text_len && j.ref_limit <= j.text_pos + 1)) &&
+                                               (j.row_limit == 0 || (j.q_pos < query_pool_len && j.row_limit <= j.q_pos + 1)));
+        if (!inside) { set_error("flx_extend_batch: job outside its pools"); return FLX_ERR_INVALID; }
+        dj[i] = DevExtendJob{j.text_pos, j.q_pos, j.ref_limit, j.row_limit, j.direction, extend_weight(j.error_weight), extend_x_drop(j.x_drop),
+                             extend_max_errors(j.max_errors), (u32)i, 0};
+        if (j.ref_limit == 0 || j.row_limit == 0) { dj[i].text_pos = 0; dj[i].q_pos = 0; dj[i].ref_limit = 0; }      // nothing is read: R(0) = 0 (row_limit 0), or only D[i][0] = i (ref_limit 0)
+    }
+    FLX_HIP(hipSetDevice(ctx->device));
+    int rc;
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    Lane* L = lease.lane;
+    const u8* d_text = ctx->didx.text;
+    if (ref_pool && (rc = upload_padded(L, L->user_text, ref_pool, ref_pool_len, &d_text))) return rc;
+    if ((rc = h2d(L, L->seq, query_pool, query_pool_len, 192))) return rc;
+    hvec<DevExtendOut> outs;
+    if ((rc = run_extend_jobs(L, d_text, L->seq.as<u8>(), dj, outs))) return rc;
+    for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_extend_result{outs[i].rows, outs[i].cols, outs[i].errors, outs[i].reason};
     return FLX_OK;
 }

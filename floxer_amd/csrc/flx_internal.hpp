@@ -175,6 +175,19 @@ struct DevMdOut { u32 len; u32 pad; };             // len 0xFFFFFFFF: the slab w
 // of a run of '=' columns, which is at most the number of query rows: <= 102 400 (align_supported_max_query), six digits. 8 nm + 6 in all.
 constexpr u64 md_slab_bytes(u64 nm) { return 8 * nm + 6; }
 
+// ---- extension of a partial record's end (flx_extend.hip): one job per end, one wave per job
+struct DevExtendJob {
+    u64 text_pos, q_pos;        // the first column's symbol in the device text, the first row's symbol in the device query pool
+    u32 ref_limit, row_limit;
+    int direction;              // +1 / -1
+    u32 w, x_drop, d_max;
+    u32 out_index, pad;
+};
+struct DevExtendOut { u32 rows, cols, errors, reason; u32 last_d; u32 pad[3]; };      // last_d: the d the scan stopped at ((last_d + 1)^2 wavefront cells)
+constexpr u32 EXTEND_DEFAULT_WEIGHT = 4, EXTEND_DEFAULT_XDROP = 100, EXTEND_DEFAULT_MAX_ERRORS = 1024;
+constexpr u32 EXTEND_MAX_ERRORS = 4093;       // two wavefronts of 2 d + 5 words in 64 KiB of LDS (2 * (2 * 4093 + 5) * 4 = 65528); the packed (row, diagonal) maximum holds more
+constexpr u32 EXTEND_MAX_WEIGHT = 0xFFFFu, EXTEND_MAX_XDROP = 1u << 30, EXTEND_MAX_ROWS = (1u << 19) - 1;
+
 // ------------------------------------------------------------------------------------------------ verification rounds on the device
 // The inner PEX levels as device-resident state: every anchor of a chunk with the node it is about to test (flx_rounds.hip).
 struct DevVrAnchor {            // 48 bytes
@@ -332,6 +345,9 @@ struct DeviceApi {
     // flx_md.hip: the MD string of every job from the CIGAR words and DevTraceOut that `traceback` left at d_cigar / d_trace_out
     static int md_build(void* stream, const u8* d_text, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevMdJob* d_jobs, u32 n_jobs,
                         u8* d_md, DevMdOut* d_out);
+    // flx_extend.hip: lds_d = the largest min(d_max, row_limit) of the jobs (the launch's LDS: extend_lds_bytes(lds_d) <= 64 KiB)
+    static size_t extend_lds_bytes(u32 d_max);
+    static int extend(void* stream, const u8* d_text, const u8* d_query, const DevExtendJob* d_jobs, u32 n_jobs, u32 lds_d, DevExtendOut* d_out);
 };
 
 // ------------------------------------------------------------------------------------------------ host logic

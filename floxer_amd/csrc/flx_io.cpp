@@ -30,6 +30,7 @@ struct flx_sam_writer {
     std::vector<uint8_t> pending;    // BAM: uncompressed bytes that do not fill a BGZF block yet
     unsigned threads = 1;            // record formatting and BGZF compression run on this many threads (flx_sam_set_threads)
     bool mapq_from_records = false;  // MAPQ column: flx_record.reserved instead of 255 (flx_sam_set_mapq)
+    bool sa_tag = false;             // SA:Z on the records of reads that have a supplementary record (flx_sam_set_sa)
     bool failed = false;
 };
 
@@ -580,7 +581,7 @@ struct SpanCache { const uint32_t* of = nullptr; uint32_t len = 0; int64_t span 
 bool format_record(flx_sam_writer const* w, flx_record const& r, const char* const* read_ids, const uint8_t* read_pool,
                    const uint64_t* read_offsets, const char* const* quals, const uint32_t* cigar_words, std::vector<uint8_t>& out, std::string& err,
                    SpanCache& span_cache, size_t* cigar_at = nullptr, const flx_md_ref* mdr = nullptr, const uint8_t* md_bytes = nullptr,
-                   size_t* md_at = nullptr) {
+                   size_t* md_at = nullptr, const std::string* sa = nullptr) {
     static const char ops[] = "MIDNSHP=X";
     const char* id = read_ids[r.read_index];
     if (md_at) *md_at = SIZE_MAX;
@@ -626,6 +627,7 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         else app(qual, slen);
         if (!unmapped) { app("\tNM:i:", 6); app_num(r.num_errors); }
         if (md) { app("\tMD:Z:", 6); app((const char*)md, mdr->length); }
+        if (sa && !sa->empty()) { app("\tSA:Z:", 6); app(sa->data(), sa->size()); }
         out.push_back('\n');
         return true;
     }
@@ -692,6 +694,11 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         out.insert(out.end(), md, md + mdr->length);
         out.push_back(0);
     }
+    if (sa && !sa->empty()) {
+        out.push_back('S'); out.push_back('A'); out.push_back('Z');
+        out.insert(out.end(), sa->begin(), sa->end());
+        out.push_back(0);
+    }
     if (long_cigar) {
         out.push_back('C'); out.push_back('G'); out.push_back('B'); out.push_back('I');
         put32((int32_t)r.cigar_length);
@@ -701,7 +708,49 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
     memcpy(out.data() + start, &bs, 4);
     return true;
 }
+
+// SA strings (flx_sam_set_sa): sa[i] of every record of a read that has a flag-2048 record lists the read's other records in written
+// order as rname,pos,strand,CIGAR,mapQ,NM; (runs of = and X merged into M); empty for every other record
+void build_sa_strings(flx_sam_writer const* w, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words, std::vector<std::string>& sa) {
+    static const char ops[] = "MIDNSHP=X";
+    sa.assign(n_records, std::string());
+    std::vector<std::string> entries;
+    for (uint64_t r0 = 0; r0 < n_records;) {
+        uint64_t r1 = r0;
+        bool supplementary = false;
+        while (r1 < n_records && records[r1].read_index == records[r0].read_index) { supplementary |= (records[r1].flag & 2048u) != 0; ++r1; }
+        if (supplementary) {
+            entries.assign(r1 - r0, std::string());
+            for (uint64_t i = r0; i < r1; ++i) {
+                flx_record const& r = records[i];
+                if (r.flag & 4u) continue;
+                std::string& e = entries[i - r0];
+                e = w->ref_ids[(size_t)r.reference_id] + "," + std::to_string((long long)r.position + 1) + "," + ((r.flag & 16u) ? "-" : "+") + ",";
+                const uint32_t* cig = cigar_words ? cigar_words + r.cigar_offset : nullptr;
+                if (r.cigar_length == 0 || !cig) e += "*";
+                uint64_t m_run = 0;
+                for (uint32_t c = 0; cig && c < r.cigar_length; ++c) {
+                    uint32_t const op = cig[c] & 15, len = cig[c] >> 4;
+                    if (op == 0 || op == 7 || op == 8) { m_run += len; continue; }
+                    if (m_run) { e += std::to_string(m_run) + "M"; m_run = 0; }
+                    e += std::to_string(len) + ops[op < 9 ? op : 0];
+                }
+                if (m_run) e += std::to_string(m_run) + "M";
+                e += "," + std::to_string(w->mapq_from_records ? r.reserved : 255u) + "," + std::to_string(r.num_errors) + ";";
+            }
+            for (uint64_t i = r0; i < r1; ++i)
+                for (uint64_t j = r0; j < r1; ++j) if (j != i) sa[i] += entries[j - r0];
+        }
+        r0 = r1;
+    }
+}
 }  // namespace
+
+extern "C" int flx_sam_set_sa(flx_sam_writer* w, int on) {
+    if (!w) { set_error("null writer"); return FLX_ERR_INVALID; }
+    w->sa_tag = on != 0;
+    return FLX_OK;
+}
 
 extern "C" int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads) {
     if (!w) { set_error("null writer"); return FLX_ERR_INVALID; }
@@ -725,6 +774,8 @@ extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_i
                                     const flx_md_ref* md, const uint8_t* md_bytes) {
     if (!w || (n_records && (!records || !read_ids || !read_pool || !read_offsets))) { set_error("flx_sam_write: null argument"); return FLX_ERR_INVALID; }
     if (w->failed) { set_error("write error on the alignment output"); return FLX_ERR_IO; }
+    std::vector<std::string> sa;                               // (made once for the whole call: the parts below cut reads anywhere)
+    if (w->sa_tag) build_sa_strings(w, records, n_records, cigar_words, sa);
     if (w->bam) {
         // BAM: a worker formats a fixed number of records at a time into a small buffer and deflates every 64 KB of it into BGZF blocks as
         // it goes (the last block of a part is short: BGZF blocks need not be full), so the uncompressed records - 280 KB per read at default
@@ -780,7 +831,7 @@ extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_i
             for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i) {
                 size_t cigar_at = SIZE_MAX, md_at = SIZE_MAX;
                 uint64_t const t_format = prof_ns();
-                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at)) break;
+                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[i] : nullptr)) break;
                 if (writer_profile()) g_ns_format += prof_ns() - t_format;
                 if (cigar_at != SIZE_MAX) {
                     cigar_at += base;
@@ -825,7 +876,7 @@ extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_i
         }
         SpanCache span_cache;
         for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i)
-            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes)) break;
+            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes, nullptr, w->sa_tag ? &sa[i] : nullptr)) break;
     });
     for (auto const& e : errs) if (!e.empty()) { set_error(e); return FLX_ERR_INVALID; }
     for (auto const& part : parts) {

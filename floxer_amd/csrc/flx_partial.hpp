@@ -23,8 +23,33 @@
 //   6. Mapping quality (flx_output_options.mapq): read_mapq (flx_mapq.hpp) over the read's candidates (after the duplicates are dropped)
 //      with exactly the kept record's forward interval, the kept record as the primary.
 //
-// Limits: the clip boundary is a PEX node's boundary, not the true break; a read mapped in full that also carries a chimeric tail is
-// not touched; no SA tag is written.
+//   7. Extension to the break (flx_extend_options; the stage extend_partials of flx_verify.cpp, kernel ed_extend in flx_extend.hip),
+//      after the selection, on the kept records only; all coordinates in the record's oriented sequence. Each kept record has two
+//      ends, each end is one job, independent of every other:
+//      - start cell: right end - the query row behind the traced part's last row and the reference symbol behind its last reference
+//        column (start + the CIGAR's reference span); left end - the mirror image, both sequences walked backwards from the row and
+//        the symbol in front of the traced part;
+//      - limits: at most I_max rows, the rows up to the read's end, or, when another kept record of the read lies on that side
+//        (forward coordinates), the rows up to that record's original node interval; at most J_max symbols, up to the end of this
+//        reference sequence (never across a sequence boundary of the concatenated text). Two extensions may meet or overlap inside
+//        the gap between two records (microhomology at a break); an extension never enters another kept record's node interval;
+//      - score: D[i][j] = unit-cost edit distance between the first i rows and the first j symbols from the start cell, D[0][0] = 0,
+//        symbols match when their ranks are equal; m(i) = min_j D[i][j] (non-decreasing, at most +1 per row);
+//        R(d) = max{i <= I_max : m(i) <= d}; score(d) = R(d) - w d;
+//      - scan d = 0, 1, 2, .. keeping the running maximum G and the first d that reached it; stop at the first d with
+//        G - score(d) > X (x-drop), R(d) == I_max, or d == d_max;
+//      - result: d* = the first d that reached G, i* = R(d*), j* = the smallest j with D[i*][j] == d*; i* == 0: the end does not move;
+//      - defaults w = 4, X = 100, d_max = 1024: conventions of this project, not fitted to anything. A peak behind a valley deeper
+//        than X, or behind d_max errors, is not found;
+//      - a record whose ends moved by (iL, jL, dL) and (iR, jR, dR) is traced again by run_trace_jobs_union: query rows
+//        [from - iL, to + iR], reference window exactly [start - jL, end + jR], k = nm + dL + dR. An alignment exists by construction
+//        (FLX_ERR_INTERNAL otherwise); position, NM, the CIGAR core and the MD come from that trace (so NM <= nm + dL + dR), the soft
+//        clips are what remains of the read, q_from / q_to follow the new interval. Records whose ends did not move keep their
+//        words; the mapping quality keeps the value computed before the extension; flags, the order of a read's records and the
+//        counters do not change.
+//
+// Limits: without the extension a record ends at a PEX node's boundary, not at the break; a read mapped in full that also carries a
+// chimeric tail is not touched. The SA tag that ties a read's records together is the writer's (flx_sam_set_sa).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -48,6 +73,21 @@ inline bool partial_options_valid(const flx_partial_options* o) {
 inline bool partial_options_active(const flx_partial_options* o) { return o && o->enable; }
 inline uint32_t partial_min_span(const flx_partial_options* o) { return o && o->min_query_span ? o->min_query_span : PARTIAL_DEFAULT_MIN_SPAN; }
 inline uint32_t partial_max_records(const flx_partial_options* o) { return o && o->max_records ? o->max_records : PARTIAL_DEFAULT_MAX_RECORDS; }
+
+// flx_extend_options: NULL is no options; enable must be 0 or 1, the reserved fields 0 and the three values within what ed_extend holds
+inline bool extend_options_valid(const flx_extend_options* o) {
+    if (!o) return true;
+    if (o->enable > 1) { set_error("flx_extend_options: enable must be 0 or 1"); return false; }
+    for (uint32_t r : o->reserved) if (r) { set_error("flx_extend_options: the reserved fields must be 0"); return false; }
+    if (o->max_errors > EXTEND_MAX_ERRORS) { set_error("flx_extend_options: max_errors is larger than the 4093 the extension kernel's wavefronts hold in LDS"); return false; }
+    if (o->error_weight > EXTEND_MAX_WEIGHT) { set_error("flx_extend_options: error_weight must be at most 65535"); return false; }
+    if (o->x_drop > EXTEND_MAX_XDROP) { set_error("flx_extend_options: x_drop must be at most 2^30"); return false; }
+    return true;
+}
+inline bool extend_options_active(const flx_extend_options* o) { return o && o->enable; }
+inline uint32_t extend_weight(uint32_t v) { return v ? v : EXTEND_DEFAULT_WEIGHT; }
+inline uint32_t extend_x_drop(uint32_t v) { return v ? v : EXTEND_DEFAULT_XDROP; }
+inline uint32_t extend_max_errors(uint32_t v) { return v ? v : EXTEND_DEFAULT_MAX_ERRORS; }
 
 struct PartialScratch { std::vector<uint32_t> order, kept; std::vector<MapqKey> keys; std::vector<uint32_t> key_of; std::vector<uint8_t> q; MapqScratch mapq; };
 

@@ -141,14 +141,15 @@ extern "C" int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* P, c
 static bool run_options_valid(const flx_params* P, const flx_run_options* R) {
     if (!R) return true;
     for (const void* r : R->reserved) if (r) { set_error("flx_run_options: the reserved pointers must be NULL"); return false; }
-    if (!output_options_valid(R->output) || !tag_options_valid(R->tags) || !partial_options_valid(R->partial)) return false;
+    if (!output_options_valid(R->output) || !tag_options_valid(R->tags) || !partial_options_valid(R->partial) || !extend_options_valid(R->extend)) return false;
     if (R->tags && R->tags->md && P && P->without_cigar) { set_error("flx_tag_options.md needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (partial_options_active(R->partial) && P && P->without_cigar) { set_error("flx_partial_options.enable needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
+    if (extend_options_active(R->extend) && !partial_options_active(R->partial)) { set_error("flx_extend_options.enable extends partial records: it needs flx_partial_options.enable"); return false; }
     return true;
 }
 extern "C" int flx_align_reads_with_tags(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets,
                                          uint64_t n_reads, const flx_output_options* O, const flx_tag_options* T, flx_run** out) {
-    flx_run_options const R{O, T, nullptr, {}};
+    flx_run_options const R{O, T, nullptr, nullptr, {}};
     return flx_align_reads_opt(ctx, P, read_pool, read_offsets, n_reads, &R, out);
 }
 extern "C" int flx_align_reads_opt(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
@@ -171,7 +172,7 @@ extern "C" int flx_align_reads_resident_with_options(flx_ctx* ctx, const flx_par
 }
 extern "C" int flx_align_reads_resident_with_tags(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_output_options* O,
                                                   const flx_tag_options* T, flx_run** out) {
-    flx_run_options const R{O, T, nullptr, {}};
+    flx_run_options const R{O, T, nullptr, nullptr, {}};
     return flx_align_reads_resident_opt(ctx, P, RD, &R, out);
 }
 extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R, flx_run** out) {
@@ -179,6 +180,7 @@ extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, c
     const flx_output_options* const O = R ? R->output : nullptr;
     const flx_tag_options* const T = R ? R->tags : nullptr;
     const flx_partial_options* const PO = R ? R->partial : nullptr;
+    const flx_extend_options* const EO = R ? R->extend : nullptr;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
@@ -249,7 +251,7 @@ extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, c
             u64 const a = chunk_first[c], b = chunk_first[c + 1];
             parts[c].skipped.assign(n_reads, 0);
             LaneLease lease(ctx, ctx->external_stream ? 0 : -1);      // waits while other calls on this context hold all lanes
-            rcs[c] = align_slice(lease.lane, P, O, T, PO, RD, a, b, &parts[c]);
+            rcs[c] = align_slice(lease.lane, P, O, T, PO, EO, RD, a, b, &parts[c]);
             if (rcs[c]) { errs[c] = flx_last_error(); failed.store(true); }
             else { lease.lane->has_run = true; if (!ctx->external_stream) ctx->warm_one_cold_lane(lease.lane); }
         }

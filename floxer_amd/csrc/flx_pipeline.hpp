@@ -126,6 +126,8 @@ int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<Al
                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
 int run_exists_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, ExistsTimes& times);
+// extension jobs of partial records' ends (ed_extend, flx_extend.hip): one launch, outs[i] for jobs[i] (out_index is set here)
+int run_extend_jobs(Lane* lane, const u8* d_text, const u8* d_query, hvec<DevExtendJob>& jobs, hvec<DevExtendOut>& outs);
 int build_peq(Lane* lane, const u8* d_seq, u64 len, DeviceBuffer& peq);
 int ensure_reversed_text(Lane* lane);
 
@@ -156,7 +158,11 @@ struct Span { u64 offset, length, extra; };
 struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; };
 
 // a record rescue_partials leaves for write_records (flx_partial.hpp): a soft-clipped part of a read without a mapped record
-struct PartialRecord { u32 read; u32 flag; u32 ref_id; u64 start; u32 nm; u64 cigar_off; u32 cigar_len; u64 md_off; u32 md_len; u32 q_from, q_to; u32 mapq; };
+struct PartialRecord {
+    u32 read; u32 flag; u32 ref_id; u64 start; u32 nm; u64 cigar_off; u32 cigar_len; u64 md_off; u32 md_len; u32 q_from, q_to; u32 mapq;
+    u32 o_from, o_to;           // the traced rows in the oriented sequence (the node, before extend_partials moves them)
+    u64 core_off; u32 core_len; // the traced words without the clips
+};
 
 struct Slice {
     // plan_reads
@@ -196,7 +202,7 @@ struct Slice {
 };
 
 // produces the slice's records (read_index relative to the whole batch)
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_reads* RD,
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_extend_options* EO, const flx_reads* RD,
                 u64 first_read, u64 end_read, flx_run* run);
 // NULL or zeroed: no tags; md must be 0 or 1 and the reserved fields 0 (else the error is set)
 bool tag_options_valid(const flx_tag_options* t);

@@ -655,8 +655,103 @@ int rescue_partials(Slice& S, Lane* lane, const flx_params* P, const flx_output_
             std::copy(S.cig.begin() + (long)tres[c].cigar_off, S.cig.begin() + (long)(tres[c].cigar_off + tres[c].cigar_len), S.cig.begin() + (long)at);
             if (len - 1 - nd.to) S.cig.push_back(((len - 1 - nd.to) << 4) | 4u);
             S.partials.push_back(PartialRecord{(u32)r, (u32)flags[j], cands[c].ref_id, pc[j].start, tres[c].nm, off, (u32)(S.cig.size() - off), tres[c].md_off,
-                                               tres[c].md_len, pc[j].q_from, pc[j].q_to, quality[j]});
+                                               tres[c].md_len, pc[j].q_from, pc[j].q_to, quality[j], nd.from, nd.to, tres[c].cigar_off, tres[c].cigar_len});
         }
+    }
+    return FLX_OK;
+}
+
+// ---- 8b. the kept partial records' ends extended to the break (flx_extend_options; the rule: flx_partial.hpp): one ed_extend launch
+//      over both ends of every kept record of the slice, then one trace of the records that moved; does nothing, and launches nothing,
+//      when the option is off or no record is kept
+int extend_partials(Slice& S, Lane* lane, const flx_extend_options* EO, const flx_reads* RD) {
+    if (!extend_options_active(EO) || S.partials.empty()) return FLX_OK;
+    flx_ctx* ctx = lane->ctx;
+    HostIndex const& H = *ctx->hidx;
+    u32 const w = extend_weight(EO->error_weight), x_drop = extend_x_drop(EO->x_drop), d_max = extend_max_errors(EO->max_errors);
+    struct End { u32 record; bool right; };
+    hvec<DevExtendJob> jobs;
+    hvec<End> ends;
+    hvec<u64> spans(S.partials.size());
+    for (size_t p0 = 0; p0 < S.partials.size();) {
+        size_t p1 = p0;
+        while (p1 < S.partials.size() && S.partials[p1].read == S.partials[p0].read) ++p1;
+        ReadState const& rs = S.reads[S.partials[p0].read];
+        for (size_t i = p0; i < p1; ++i) {
+            PartialRecord const& p = S.partials[i];
+            // rows free on either side in forward coordinates: up to the read's end, or to the nearest kept record's node interval
+            u32 fwd_left = p.q_from, fwd_right = rs.len - 1 - p.q_to;
+            for (size_t j = p0; j < p1; ++j) {
+                PartialRecord const& o = S.partials[j];
+                if (j == i) continue;
+                if (o.q_to < p.q_from) fwd_left = std::min(fwd_left, p.q_from - 1 - o.q_to);
+                else if (o.q_from > p.q_to) fwd_right = std::min(fwd_right, o.q_from - 1 - p.q_to);
+            }
+            bool const rc_strand = (p.flag & 16u) != 0;
+            u32 const rows_right = rc_strand ? fwd_left : fwd_right, rows_left = rc_strand ? fwd_right : fwd_left;
+            u64 const span = spans[i] = cigar_reference_span(S.cig.data() + p.core_off, p.core_len);
+            u64 const seq_start = H.seq_start[p.ref_id], seq_len = H.seq_len[p.ref_id], q_base = rs.pool_off[rc_strand ? 1 : 0];
+            u64 const cols_right = seq_len - std::min(seq_len, p.start + span), cols_left = p.start;
+            if (rows_right && cols_right) {
+                jobs.push_back(DevExtendJob{seq_start + p.start + span, q_base + p.o_to + 1, (u32)std::min<u64>(cols_right, 0x7FFFFFFFu), rows_right, 1, w, x_drop, d_max, 0, 0});
+                ends.push_back(End{(u32)i, true});
+            }
+            if (rows_left && cols_left) {
+                jobs.push_back(DevExtendJob{seq_start + p.start - 1, q_base + p.o_from - 1, (u32)std::min<u64>(cols_left, 0x7FFFFFFFu), rows_left, -1, w, x_drop, d_max, 0, 0});
+                ends.push_back(End{(u32)i, false});
+            }
+        }
+        p0 = p1;
+    }
+    hvec<DevExtendOut> outs;
+    int rc;
+    if ((rc = run_extend_jobs(lane, ctx->didx.text, RD->d_pool.as<u8>(), jobs, outs))) return rc;
+    // ---- the records that moved, traced again over exactly the longer interval
+    struct Move { u32 rows[2] = {0, 0}, cols[2] = {0, 0}, errors[2] = {0, 0}; };      // [0] left, [1] right
+    hvec<Move> moves(S.partials.size());
+    for (size_t e = 0; e < ends.size(); ++e) {
+        if (outs[e].rows == 0) continue;
+        Move& m = moves[ends[e].record];
+        int const side = ends[e].right ? 1 : 0;
+        m.rows[side] = outs[e].rows; m.cols[side] = outs[e].cols; m.errors[side] = outs[e].errors;
+    }
+    hvec<AlignRequest> reqs;
+    hvec<u32> req_record;
+    for (size_t i = 0; i < S.partials.size(); ++i) {
+        Move const& m = moves[i];
+        if (!m.rows[0] && !m.rows[1]) continue;
+        PartialRecord const& p = S.partials[i];
+        ReadState const& rs = S.reads[p.read];
+        reqs.push_back(AlignRequest{H.seq_start[p.ref_id] + p.start - m.cols[0], rs.pool_off[(p.flag & 16u) ? 1 : 0] + p.o_from - m.rows[0],
+                                    (u32)(spans[i] + m.cols[0] + m.cols[1]), p.o_to - p.o_from + 1 + m.rows[0] + m.rows[1], p.nm + m.errors[0] + m.errors[1]});
+        req_record.push_back((u32)i);
+    }
+    if (reqs.empty()) return FLX_OK;
+    hvec<TraceResult> tres;
+    if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, S.cig, S.want_md ? &S.md : nullptr))) return rc;
+    for (size_t j = 0; j < reqs.size(); ++j) {
+        if (!tres[j].exists) { set_error("partial extension: no alignment over an interval the extension reached"); return FLX_ERR_INTERNAL; }
+        PartialRecord& p = S.partials[req_record[j]];
+        Move const& m = moves[req_record[j]];
+        u32 const len = S.reads[p.read].len;
+        p.o_from -= m.rows[0];
+        p.o_to += m.rows[1];
+        if (p.flag & 16u) { p.q_from -= m.rows[1]; p.q_to += m.rows[0]; }
+        else { p.q_from -= m.rows[0]; p.q_to += m.rows[1]; }
+        p.start = p.start - m.cols[0] + tres[j].begin;
+        p.nm = tres[j].nm;
+        p.core_off = tres[j].cigar_off;
+        p.core_len = tres[j].cigar_len;
+        p.md_off = tres[j].md_off;
+        p.md_len = tres[j].md_len;
+        u64 const off = S.cig.size();
+        if (p.o_from) S.cig.push_back((p.o_from << 4) | 4u);
+        size_t const at = S.cig.size();
+        S.cig.resize(at + tres[j].cigar_len);              // (grown first: the source lies in the same pool)
+        std::copy(S.cig.begin() + (long)tres[j].cigar_off, S.cig.begin() + (long)(tres[j].cigar_off + tres[j].cigar_len), S.cig.begin() + (long)at);
+        if (len - 1 - p.o_to) S.cig.push_back(((len - 1 - p.o_to) << 4) | 4u);
+        p.cigar_off = off;
+        p.cigar_len = (u32)(S.cig.size() - off);
     }
     return FLX_OK;
 }
@@ -813,7 +908,7 @@ bool tag_options_valid(const flx_tag_options* t) {
     return true;
 }
 
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_reads* RD,
+int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_extend_options* EO, const flx_reads* RD,
                 u64 first_read, u64 end_read, flx_run* run) {
     flx_ctx* ctx = lane->ctx;
     FLX_HIP(hipSetDevice(ctx->device));
@@ -847,6 +942,8 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
     prof.mark("root-align");
     if ((rc = rescue_partials(S, lane, P, O, PO, RD))) return rc;
     prof.mark("partials");
+    if ((rc = extend_partials(S, lane, EO, RD))) return rc;
+    if (extend_options_active(EO)) prof.mark("extend");
     write_records(S, ctx, O, end_read - first_read, run);
     prof.mark("records");
     return FLX_OK;

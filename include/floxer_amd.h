@@ -305,7 +305,8 @@ int flx_run_copy_md(const flx_run* run, flx_md_ref* refs, uint8_t* md_bytes);
  * flx_select_records keeps all records of a read that has a flag-2048 record); mapq gives each kept record read_mapq's value over the
  * read's traced candidates with exactly its forward query interval. params->without_cigar has no trace: refused together with enable
  * (FLX_ERR_INVALID) before any work. --stats and every named flx_path_counters field keep describing verification; reserved[1] counts
- * the partial records written and reserved[2] the reads that got them. No SA tag is written. The rule and its limits:
+ * the partial records written and reserved[2] the reads that got them. Each record ends at a PEX node's boundary unless
+ * flx_extend_options moves its ends to the break; the SA tag is the writer's (flx_sam_set_sa). The rule and its limits:
  * floxer_amd/csrc/flx_partial.hpp. */
 typedef struct flx_partial_options {
     uint32_t enable;
@@ -313,13 +314,40 @@ typedef struct flx_partial_options {
     uint32_t max_records;        /* 0: 4 */
     uint32_t reserved[5];
 } flx_partial_options;
+/* Extension of the partial records to the break: not floxer's. Off when the struct is zeroed (or NULL), and then nothing changes: no
+ * launch, no byte of any output. With enable = 1 (anything else but 0 is refused; it needs flx_partial_options.enable, else
+ * FLX_ERR_INVALID before any work) both ends of every kept partial record are extended from the cell behind its traced part, as far
+ * as the sequence keeps aligning (kernel ed_extend, one score-only wavefront job per end), and the records that moved are traced
+ * again over the longer interval:
+ *   - a job walks at most the rows up to the read's end, or up to the original node interval of the read's next kept record on that
+ *     side, and at most the symbols up to the end of its reference sequence;
+ *   - with D the unit-cost edit distance from the start cell, m(i) = min_j D[i][j], R(d) = max{i : m(i) <= d} and
+ *     score(d) = R(d) - error_weight * d, it scans d = 0, 1, .. and stops at the first d with (running maximum - score(d)) > x_drop,
+ *     R(d) = the row limit, or d = max_errors; the end moves by R(d*) rows and j* symbols at d* errors, d* the first d of the maximum
+ *     and j* the smallest j with D[R(d*)][j] = d*;
+ *   - error_weight (0: 4), x_drop (0: 100) and max_errors (0: 1024) are conventions of this project, not fitted to anything; a peak
+ *     behind a valley deeper than x_drop, or behind max_errors errors, is not found. max_errors above 4093 (what the kernel's two
+ *     wavefronts hold in LDS), error_weight above 65535 and x_drop above 2^30 are refused.
+ * A record that moved: query rows [from - iL, to + iR], reference window exactly [start - jL, end + jR], traced with nm + dL + dR
+ * allowed errors; position, NM, CIGAR and MD come from that trace, the soft clips are what remains of the read; its mapping quality
+ * (flx_output_options.mapq) keeps the value computed before the extension. Records that did not move keep their words. Flags, the
+ * order of a read's records and the counters do not change. The full rule: floxer_amd/csrc/flx_partial.hpp. The reserved fields
+ * must be 0. */
+typedef struct flx_extend_options {
+    uint32_t enable;
+    uint32_t error_weight;       /* 0: 4 */
+    uint32_t x_drop;             /* 0: 100 */
+    uint32_t max_errors;         /* 0: 1024 */
+    uint32_t reserved[4];
+} flx_extend_options;
 /* Every option of a run in one bundle: each pointer may be NULL (that option off). A NULL bundle, or one of NULLs / zeroed structs, is
  * exactly flx_align_reads / flx_align_reads_resident; the calls above forward here. The reserved pointers must be NULL. */
 typedef struct flx_run_options {
     const flx_output_options* output;
     const flx_tag_options* tags;
     const flx_partial_options* partial;
-    const void* reserved[5];
+    const flx_extend_options* extend;
+    const void* reserved[4];
 } flx_run_options;
 int flx_align_reads_opt(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
                         const flx_run_options* options, flx_run** out);
@@ -342,6 +370,27 @@ int flx_choose_partials(const flx_partial_candidate* candidates, uint64_t n, con
 /* the mapping quality of the kept candidates (keep_flag as flx_choose_partials gave it), 0 for the others. cigar_words NULL: a
  * candidate spans as many reference symbols as query rows. */
 int flx_partial_mapq(const flx_partial_candidate* candidates, uint64_t n, const uint32_t* cigar_words, const int32_t* keep_flag, uint8_t* mapq);
+
+/* The extension kernel alone (ed_extend), in the style of seam 2: one job per end. ref_pool == NULL: the context's reference text
+ * (text_pos is then a position in the padded concatenated text). A job starts at reference symbol text_pos and query symbol q_pos
+ * (the first column and row of its matrix) and walks both sequences upwards (direction +1) or downwards (-1) for at most ref_limit
+ * symbols and row_limit rows, which must lie in their pools (row_limit < 2^19). error_weight, x_drop, max_errors: 0 takes the
+ * defaults of flx_extend_options, with the same bounds. out[i]: the rows and columns the end moves by and the errors of that
+ * extension (0, 0, 0: it does not move), and why the scan stopped. */
+typedef struct flx_extend_job {
+    uint64_t text_pos;
+    uint64_t q_pos;
+    uint32_t ref_limit;
+    uint32_t row_limit;
+    int32_t direction;           /* +1 or -1 */
+    uint32_t error_weight;
+    uint32_t x_drop;
+    uint32_t max_errors;
+} flx_extend_job;
+enum { FLX_EXTEND_STOP_XDROP = 1, FLX_EXTEND_STOP_ROWS = 2, FLX_EXTEND_STOP_MAX_ERRORS = 3 };
+typedef struct flx_extend_result { uint32_t rows, cols, errors, stop_reason; } flx_extend_result;
+int flx_extend_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                     const flx_extend_job* jobs, uint64_t n_jobs, flx_extend_result* out);
 
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
@@ -406,6 +455,12 @@ int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads);
 /* MAPQ column: from_records = 0 (default) writes 255, "not available", as floxer does; != 0 writes records[i].reserved (what a run made
  * with flx_output_options.mapq stores there; a value above 254 makes flx_sam_write fail with FLX_ERR_INVALID) */
 int flx_sam_set_mapq(flx_sam_writer* w, int from_records);
+/* SA:Z tag (not floxer's): on != 0 gives every record of a read that has a flag-2048 record (the partial records of flx_partial_options)
+ * the tag behind NM / MD (SAZ...\0 in BAM). It lists the read's other records in written order, each as
+ * rname,pos,strand,CIGAR,mapQ,NM; with pos 1-based, strand + or -, the record's own CIGAR with runs of = and X merged into M (ops S, M,
+ * I, D) and mapQ what the writer puts into that record's MAPQ column. A read's records must be contiguous within one flx_sam_write
+ * call, as in every flx_run. Default off: then no byte changes. */
+int flx_sam_set_sa(flx_sam_writer* w, int on);
 
 /* ------------------------------------------------------------------------------------------------ synthetic inputs
  * The reference's simulator (src/main/simulated_dataset.cpp:30-49, 81-223), multi-threaded and with a portable generator:
