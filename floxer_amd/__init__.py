@@ -622,42 +622,16 @@ class aligner:
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
         run = C.c_void_p()
-        if self.partial is not None or self.extend is not None:
-            tags = tag_options(md=self.md)
-            bundle = capi.RunOptions()
-            if self.output is not None:
-                bundle.output = C.pointer(self.output)
-            bundle.tags = C.pointer(tags)
-            if self.partial is not None:
-                bundle.partial = C.pointer(self.partial)
-            if self.extend is not None:
-                bundle.extend = C.pointer(self.extend)
-            if isinstance(reads, resident_reads):
-                check(lib().flx_align_reads_resident_opt(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), C.byref(run)))
-                return _collect_run(run, reads.n, md=self.md)
+        tags = tag_options(md=self.md)
+        bundle = capi.RunOptions()
+        bundle.tags = C.pointer(tags)
+        for name in ("output", "partial", "extend"):
+            if getattr(self, name) is not None:
+                setattr(bundle, name, C.pointer(getattr(self, name)))
+        if isinstance(reads, resident_reads):
+            n = reads.n
+            check(lib().flx_align_reads_resident_opt(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), C.byref(run)))
+        else:
             pool, offs, n = _pool_and_offsets(reads)
             check(lib().flx_align_reads_opt(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), C.byref(run)))
-            return _collect_run(run, n, md=self.md)
-        opt = C.byref(self.output) if self.output is not None else None
-        if self.md:
-            tags = tag_options(md=True)
-            if isinstance(reads, resident_reads):
-                check(lib().flx_align_reads_resident_with_tags(self.ctx.h, C.byref(self.params), reads.h, opt, C.byref(tags), C.byref(run)))
-                return _collect_run(run, reads.n, md=True)
-            pool, offs, n = _pool_and_offsets(reads)
-            check(lib().flx_align_reads_with_tags(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, opt, C.byref(tags),
-                                                  C.byref(run)))
-            return _collect_run(run, n, md=True)
-        if isinstance(reads, resident_reads):
-            if opt is None:
-                check(lib().flx_align_reads_resident(self.ctx.h, C.byref(self.params), reads.h, C.byref(run)))
-            else:
-                check(lib().flx_align_reads_resident_with_options(self.ctx.h, C.byref(self.params), reads.h, opt, C.byref(run)))
-            return _collect_run(run, reads.n)
-        pool, offs, n = _pool_and_offsets(reads)
-        if opt is None:
-            check(lib().flx_align_reads(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(run)))
-        else:
-            check(lib().flx_align_reads_with_options(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, opt,
-                                                     C.byref(run)))
-        return _collect_run(run, n)
+        return _collect_run(run, n, md=self.md)

@@ -46,39 +46,39 @@ struct ShapeKey {
 
 // Anchors of one locus produce many identical (window, node) jobs (sibling leaves share their parent's window, anchors with the
 // same indel drift share the root window). Identical inputs give identical outputs, so each distinct job runs once.
-struct ReqKey {
-    u64 ref_off, q_off; u32 n, m, k;
-    bool operator==(ReqKey const& o) const { return ref_off == o.ref_off && q_off == o.q_off && n == o.n && m == o.m && k == o.k; }
-};
-struct ReqKeyHash {
-    size_t operator()(ReqKey const& r) const {
-        u64 h = r.ref_off * 0x9E3779B97F4A7C15ull ^ (r.q_off + 0x7F4A7C15ull) * 0xC2B2AE3D27D4EB4Full;
-        h ^= ((u64)r.n << 40) ^ ((u64)r.m << 20) ^ r.k;
-        h ^= h >> 29;
-        return (size_t)(h * 0xBF58476D1CE4E5B9ull);
-    }
-};
+bool same_request(AlignRequest const& a, AlignRequest const& b) { return a.ref_off == b.ref_off && a.q_off == b.q_off && a.n == b.n && a.m == b.m && a.k == b.k; }
+size_t request_hash(AlignRequest const& r) {
+    u64 h = r.ref_off * 0x9E3779B97F4A7C15ull ^ (r.q_off + 0x7F4A7C15ull) * 0xC2B2AE3D27D4EB4Full;
+    h ^= ((u64)r.n << 40) ^ ((u64)r.m << 20) ^ r.k;
+    h ^= h >> 29;
+    return (size_t)(h * 0xBF58476D1CE4E5B9ull);
+}
 void dedup_requests(hvec<AlignRequest> const& reqs, hvec<AlignRequest>& uniq, hvec<u32>& uniq_of) {
     // open-addressing table of indices into `uniq` (power-of-two size, linear probing)
     size_t cap = 16;
     while (cap < reqs.size() * 2 + 1) cap <<= 1;
     hvec<u32> table(cap, 0xFFFFFFFFu);
-    ReqKeyHash const hasher;
     uniq.clear();
     uniq.reserve(reqs.size());
     uniq_of.resize(reqs.size());
     for (size_t i = 0; i < reqs.size(); ++i) {
-        AlignRequest const& r = reqs[i];
-        ReqKey const key{r.ref_off, r.q_off, r.n, r.m, r.k};
-        size_t h = hasher(key) & (cap - 1);
-        while (true) {
-            u32 const e = table[h];
-            if (e == 0xFFFFFFFFu) { table[h] = (u32)uniq.size(); uniq_of[i] = (u32)uniq.size(); uniq.push_back(r); break; }
-            AlignRequest const& u = uniq[e];
-            if (u.ref_off == r.ref_off && u.q_off == r.q_off && u.n == r.n && u.m == r.m && u.k == r.k) { uniq_of[i] = e; break; }
-            h = (h + 1) & (cap - 1);
-        }
+        size_t h = request_hash(reqs[i]) & (cap - 1);
+        while (table[h] != 0xFFFFFFFFu && !same_request(uniq[table[h]], reqs[i])) h = (h + 1) & (cap - 1);
+        if (table[h] == 0xFFFFFFFFu) { table[h] = (u32)uniq.size(); uniq.push_back(reqs[i]); }
+        uniq_of[i] = table[h];
     }
+}
+// a form for distinct requests, run over the distinct ones of `reqs`: every request gets the result of its like
+template <class Out, class RunUnique>
+int run_deduplicated(hvec<AlignRequest> const& reqs, hvec<Out>& outs, RunUnique&& run_unique) {
+    hvec<AlignRequest> uniq;
+    hvec<u32> uniq_of;
+    dedup_requests(reqs, uniq, uniq_of);
+    hvec<Out> uouts;
+    if (int const rc = run_unique(uniq, uouts)) return rc;
+    outs.resize(reqs.size());
+    for (size_t i = 0; i < reqs.size(); ++i) outs[i] = uouts[uniq_of[i]];
+    return FLX_OK;
 }
 
 // Shapes for the jobs of one call. Many jobs: each gets the shape that costs the fewest wave slots. Few jobs (they would leave
@@ -207,49 +207,125 @@ int run_score_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
     return rc;
 }
 
-// The MD strings (flx_md.hip) of the trace jobs of one K5 launch, one MD job per trace job. The MD jobs go up with the trace jobs, the
-// kernel is queued directly behind K5 (it reads K5's DevTraceOut and CIGAR words on the device: no host synchronisation in between), and
-// the bytes come back with the CIGAR words. A job's slab holds md_slab_bytes(NM) bytes, NM being what K4 returned for it.
-struct MdBatch {
-    hvec<DevMdJob> jobs;
-    hvec<DevMdOut> outs;
-    u64 slab_bytes = 0;
-    size_t pool_base = 0;
-    void add(DevTraceJob const& t, u32 nm) {
-        u64 const cap = md_slab_bytes(nm);
-        jobs.push_back(DevMdJob{t.ref_off, t.cigar_off, slab_bytes, t.n, (u32)cap, t.out_index, 0});
-        slab_bytes += cap;
-    }
-    int upload(Lane* ctx) {
-        int rc;
-        if ((rc = h2d(ctx, ctx->md_jobs, jobs.data(), jobs.size() * sizeof(DevMdJob)))) return rc;
-        if ((rc = ctx->md_out.ensure(jobs.size() * sizeof(DevMdOut)))) return rc;
-        return ctx->md.ensure(slab_bytes + 16);
-    }
-    int launch(Lane* ctx, const u8* d_text) {
-        // (its algorithmic bytes depend on what K5 finds: they are added by account() once the lengths are back)
-        return timed_launch(ctx, "md_build", 0, jobs.size(), [&] {
-            return DeviceApi::md_build(ctx->stream, d_text, ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>(), ctx->md_jobs.as<DevMdJob>(), (u32)jobs.size(),
-                                       ctx->md.as<u8>(), ctx->md_out.as<DevMdOut>());
-        });
-    }
-    int fetch(Lane* ctx, hvec<u8>& pool) {                  // slabs are kept as they are (gaps included), like the CIGAR slabs
-        outs.resize(jobs.size());
-        pool_base = pool.size();
-        pool.resize(pool_base + slab_bytes);
-        int rc;
-        if ((rc = d2h(ctx, outs.data(), ctx->md_out.ptr, outs.size() * sizeof(DevMdOut)))) return rc;
-        return d2h(ctx, pool.data() + pool_base, ctx->md.ptr, slab_bytes);
-    }
-    // after the lane's sync: CIGAR words read + reference letters read (one per X / D column: at most NM) + MD bytes written
-    int account(Lane* ctx, hvec<DevTraceOut> const& touts) {
-        u64 bytes = 0;
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            if (outs[j].len == 0xFFFFFFFFu) { set_error("md_build: MD slab overflow, or a path that leaves its window"); return FLX_ERR_INTERNAL; }
-            bytes += 4ull * touts[j].cigar_len + outs[j].len + (jobs[j].md_cap - 6u) / 8u;
+// The trace arena of one call: the launch shape and the trace slots (16 bytes each) of every request, and the cut of the requests into
+// chunks whose trace planes fit the lane's budget together.
+struct TracePlan {
+    hvec<AlignShape> shapes;
+    hvec<u64> slots;
+    u64 budget_slots = 0;
+    size_t next = 0;                                           // the first request of the next chunk
+    int make(Lane* lane, hvec<AlignRequest> const& reqs) {
+        if (int const rc = choose_shapes(reqs, shapes)) return rc;
+        slots.resize(reqs.size());
+        budget_slots = std::max<u64>(lane->trace_budget_bytes / 16, 1);
+        for (size_t i = 0; i < reqs.size(); ++i) {
+            slots[i] = align_trace_slots(reqs[i].n, reqs[i].m, reqs[i].k, shapes[i]);
+            if (slots[i] > budget_slots) { set_error("one alignment needs more trace memory than the configured budget (FLX_TRACE_ARENA_MB)"); return FLX_ERR_CAPACITY; }
         }
-        ctx->ctx->account_more("md_build", bytes, 0);
         return FLX_OK;
+    }
+    bool done() const { return next == slots.size(); }
+    // the next chunk [begin, end); the lane's arena holds its planes afterwards
+    int next_chunk(Lane* lane, size_t& begin, size_t& end) {
+        begin = next;
+        u64 used = 0;
+        while (next < slots.size() && used + slots[next] <= budget_slots) { used += slots[next]; ++next; }
+        end = next;
+        // the arena is taken whole on first use (its size is the configured budget): no reallocation between batches
+        return lane->trace.ensure(std::max<size_t>(used * 16 + 64, lane->trace.ptr ? 0 : std::min<size_t>(lane->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2));
+    }
+};
+
+// K5 over the paths of one arena chunk, and their MD strings (flx_md.hip) when wanted: one MD job per trace job. The MD jobs go up with
+// the trace jobs, md_build is queued directly behind K5 (it reads K5's DevTraceOut and CIGAR words on the device: no host synchronisation
+// in between), and the bytes come back with the CIGAR words. A job's CIGAR slab holds 2 NM + 2 words and its MD slab md_slab_bytes(NM)
+// bytes, NM being what K4 returned for it; the slabs are kept as they are (gaps included): no host repacking.
+struct Traceback {
+    bool const want_md;
+    PhaseTimer* const prof;
+    hvec<DevTraceJob> jobs;
+    hvec<DevTraceOut> outs;
+    hvec<DevMdJob> md_jobs;
+    hvec<DevMdOut> md_outs;
+    u64 cigar_words = 0, path_steps = 0, md_bytes = 0;
+    size_t cigar_base = 0, md_base = 0;                        // where this batch's slabs start in the host pools
+    explicit Traceback(bool md, PhaseTimer* prof_ = nullptr) : want_md(md), prof(prof_) {}
+    // the path that ends at end_col of the last row of r's DP, whose trace planes lie at trace_off; returns the trace job's index
+    u32 add(AlignRequest const& r, u64 trace_off, AlignShape sh, u32 end_col, u32 nm) {
+        u32 const j = (u32)jobs.size(), cap = 2 * nm + 2;      // runs <= 2*NM + 1
+        jobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off, cigar_words, r.n, r.m, sh.lanes_per_job, sh.words_per_lane, end_col, cap, j, r.k});
+        if (want_md) {
+            u64 const slab = md_slab_bytes(nm);
+            md_jobs.push_back(DevMdJob{r.ref_off, cigar_words, md_bytes, r.n, (u32)slab, j, 0});
+            md_bytes += slab;
+        }
+        cigar_words += cap;
+        path_steps += (u64)r.m + nm;
+        return j;
+    }
+    int run(Lane* lane, const u8* d_text, const u64* d_peq, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
+        cigar_base = cigar_pool.size();
+        if (jobs.empty()) return FLX_OK;
+        int rc;
+        if ((rc = h2d(lane, lane->tjobs, jobs.data(), jobs.size() * sizeof(DevTraceJob)))) return rc;
+        if ((rc = lane->tjob_out.ensure(jobs.size() * sizeof(DevTraceOut)))) return rc;
+        if ((rc = lane->cigar.ensure(cigar_words * 4 + 16))) return rc;
+        if (want_md) {
+            if ((rc = h2d(lane, lane->md_jobs, md_jobs.data(), md_jobs.size() * sizeof(DevMdJob)))) return rc;
+            if ((rc = lane->md_out.ensure(md_jobs.size() * sizeof(DevMdOut)))) return rc;
+            if ((rc = lane->md.ensure(md_bytes + 16))) return rc;
+        }
+        rc = timed_launch(lane, "ed_traceback", path_steps * 18, path_steps, [&] {
+            return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), lane->tjobs.as<DevTraceJob>(), (u32)jobs.size(),
+                                        lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>());
+        });
+        if (rc) return rc;
+        if (want_md) {
+            // (its algorithmic bytes depend on what K5 finds: they are added below once the lengths are back)
+            rc = timed_launch(lane, "md_build", 0, md_jobs.size(), [&] {
+                return DeviceApi::md_build(lane->stream, d_text, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->md_jobs.as<DevMdJob>(), (u32)md_jobs.size(),
+                                           lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
+            });
+            if (rc) return rc;
+        }
+        if (prof) prof->mark("tb-prep");
+        outs.resize(jobs.size());
+        cigar_pool.resize(cigar_base + cigar_words);
+        if (prof) prof->mark("pool-resize");
+        if ((rc = d2h(lane, outs.data(), lane->tjob_out.ptr, outs.size() * sizeof(DevTraceOut)))) return rc;
+        if ((rc = d2h(lane, cigar_pool.data() + cigar_base, lane->cigar.ptr, cigar_words * 4))) return rc;
+        if (want_md) {
+            md_outs.resize(md_jobs.size());
+            md_base = md_pool->size();
+            md_pool->resize(md_base + md_bytes);
+            if ((rc = d2h(lane, md_outs.data(), lane->md_out.ptr, md_outs.size() * sizeof(DevMdOut)))) return rc;
+            if ((rc = d2h(lane, md_pool->data() + md_base, lane->md.ptr, md_bytes))) return rc;
+        }
+        if ((rc = lane->sync())) return rc;
+        if (prof) prof->mark("K5+d2h");
+        for (auto const& t : outs)
+            if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+        if (want_md) {
+            // CIGAR words read + reference letters read (one per X / D column: at most NM) + MD bytes written
+            u64 bytes = 0;
+            for (size_t j = 0; j < md_jobs.size(); ++j) {
+                if (md_outs[j].len == 0xFFFFFFFFu) { set_error("md_build: MD slab overflow, or a path that leaves its window"); return FLX_ERR_INTERNAL; }
+                bytes += 4ull * outs[j].cigar_len + md_outs[j].len + (md_jobs[j].md_cap - 6u) / 8u;
+            }
+            lane->ctx->account_more("md_build", bytes, 0);
+        }
+        return FLX_OK;
+    }
+    // trace job j as the result of a request whose K4 score was nm (begin: relative to the job's window)
+    TraceResult result(u32 j, u32 nm) const {
+        TraceResult res;
+        res.exists = true;
+        res.nm = nm;
+        res.begin = outs[j].begin;
+        res.cigar_off = cigar_base + jobs[j].cigar_off + outs[j].cigar_start;
+        res.cigar_len = outs[j].cigar_len;
+        if (want_md) { res.md_off = md_base + md_jobs[j].md_off; res.md_len = md_outs[j].len; }
+        return res;
     }
 };
 
@@ -259,33 +335,21 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer tprof("trace-jobs");
-    hvec<AlignShape> shapes;
-    if (int const src = choose_shapes(reqs, shapes)) return src;
-    hvec<u64> slots(reqs.size());
-    u64 const budget_slots = std::max<u64>(ctx->trace_budget_bytes / 16, 1);
-    for (size_t i = 0; i < reqs.size(); ++i) {
-        slots[i] = align_trace_slots(reqs[i].n, reqs[i].m, reqs[i].k, shapes[i]);
-        if (slots[i] > budget_slots) { set_error("one alignment needs more trace memory than the configured budget (FLX_TRACE_ARENA_MB)"); return FLX_ERR_CAPACITY; }
-    }
+    TracePlan plan;
     int rc;
-    size_t next = 0;
-    while (next < reqs.size()) {
-        // ---- chunk of jobs whose trace planes fit the arena
-        size_t begin = next;
-        u64 used = 0;
-        while (next < reqs.size() && used + slots[next] <= budget_slots) { used += slots[next]; ++next; }
-        size_t const count = next - begin;
-        // the arena is taken whole on first use (its size is the configured budget): no reallocation between batches
-        if ((rc = ctx->trace.ensure(std::max<size_t>(used * 16 + 64, ctx->trace.ptr ? 0 : std::min<size_t>(ctx->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2)))) return rc;
-
+    if ((rc = plan.make(ctx, reqs))) return rc;
+    while (!plan.done()) {
+        size_t begin, end;
+        if ((rc = plan.next_chunk(ctx, begin, end))) return rc;
+        size_t const count = end - begin;
         hvec<u64> trace_off(count);
         u64 off = 0;
         // (bytes: reference + query symbols read; trace written: the checkpointed trace's carry and checkpoint regions)
-        rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, begin, next, "ed_align_trace", "", true, nullptr, [&](u32 id, DevAlignJob& job) {
+        rc = launch_by_shape(ctx, d_text, d_peq, reqs, plan.shapes, begin, end, "ed_align_trace", "", true, nullptr, [&](u32 id, DevAlignJob& job) {
             AlignRequest const& r = reqs[id];
             job.trace_off = trace_off[id - begin] = off;
-            off += slots[id];
-            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
+            off += plan.slots[id];
+            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, plan.shapes[id].words_per_lane, plan.shapes[id].lanes_per_job);
             return (tl.carry_slots + tl.ckpt_slots) * 16;
         });
         if (rc) return rc;
@@ -295,57 +359,15 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         tprof.mark("K4");
 
         // ---- traceback for the jobs that have an alignment within k
-        hvec<DevTraceJob> tjobs;
+        Traceback tb(md_pool != nullptr, &tprof);
         hvec<u32> tjob_req;
-        MdBatch mdb;
-        u64 cigar_words = 0, path_steps = 0;
         for (size_t c = 0; c < count; ++c) {
             if (outs[c].score == 0xFFFFFFFFu) continue;
-            size_t const id = begin + c;
-            AlignRequest const& r = reqs[id];
-            AlignShape const sh = shapes[id];
-            u32 const cap = 2 * outs[c].score + 2;      // runs <= 2*NM + 1
-            tjobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off[c], cigar_words, r.n, r.m, sh.lanes_per_job, sh.words_per_lane, outs[c].end_col,
-                                        cap, (u32)tjob_req.size(), r.k});
-            tjob_req.push_back((u32)id);
-            if (md_pool) mdb.add(tjobs.back(), outs[c].score);
-            cigar_words += cap;
-            path_steps += (u64)r.m + outs[c].score;
+            tb.add(reqs[begin + c], trace_off[c], plan.shapes[begin + c], outs[c].end_col, outs[c].score);
+            tjob_req.push_back((u32)(begin + c));
         }
-        if (!tjobs.empty()) {
-            if ((rc = h2d(ctx, ctx->tjobs, tjobs.data(), tjobs.size() * sizeof(DevTraceJob)))) return rc;
-            if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
-            if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
-            if (md_pool && (rc = mdb.upload(ctx))) return rc;
-            rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
-                return DeviceApi::traceback(ctx->stream, d_text, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(), (u32)tjobs.size(),
-                                            ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
-            });
-            if (rc) return rc;
-            if (md_pool && (rc = mdb.launch(ctx, d_text))) return rc;
-            tprof.mark("tb-prep");
-            hvec<DevTraceOut> touts(tjobs.size());
-            size_t const pool_base = cigar_pool.size();
-            cigar_pool.resize(pool_base + cigar_words);          // slabs are kept as they are (gaps included): no host repacking
-            tprof.mark("pool-resize");
-            if ((rc = d2h(ctx, touts.data(), ctx->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
-            if ((rc = d2h(ctx, cigar_pool.data() + pool_base, ctx->cigar.ptr, cigar_words * 4))) return rc;
-            if (md_pool && (rc = mdb.fetch(ctx, *md_pool))) return rc;
-            if ((rc = ctx->sync())) return rc;
-            tprof.mark("K5+d2h");
-            for (size_t j = 0; j < tjobs.size(); ++j)
-                if (touts[j].cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
-            if (md_pool && (rc = mdb.account(ctx, touts))) return rc;
-            for (size_t j = 0; j < tjobs.size(); ++j) {
-                TraceResult& res = results[tjob_req[j]];
-                res.exists = true;
-                res.nm = outs[tjob_req[j] - begin].score;
-                res.begin = touts[j].begin;
-                res.cigar_off = pool_base + tjobs[j].cigar_off + touts[j].cigar_start;
-                res.cigar_len = touts[j].cigar_len;
-                if (md_pool) { res.md_off = mdb.pool_base + mdb.jobs[j].md_off; res.md_len = mdb.outs[j].len; }
-            }
-        }
+        if ((rc = tb.run(ctx, d_text, d_peq, cigar_pool, md_pool))) return rc;
+        for (u32 j = 0; j < tjob_req.size(); ++j) results[tjob_req[j]] = tb.result(j, outs[tjob_req[j] - begin].score);
     }
     return FLX_OK;
 }
@@ -354,29 +376,17 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
 
 int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                    hvec<DevAlignOut>& outs, const char* kernel_name) {
-    hvec<AlignRequest> uniq;
-    hvec<u32> uniq_of;
-    dedup_requests(reqs, uniq, uniq_of);
-    hvec<DevAlignOut> uouts;
-    int rc = run_score_jobs_unique(ctx, d_text, d_peq, uniq, uouts, kernel_name);
-    if (rc) return rc;
-    outs.resize(reqs.size());
-    for (size_t i = 0; i < reqs.size(); ++i) outs[i] = uouts[uniq_of[i]];
-    return FLX_OK;
+    return run_deduplicated(reqs, outs, [&](hvec<AlignRequest> const& uniq, hvec<DevAlignOut>& uouts) {
+        return run_score_jobs_unique(ctx, d_text, d_peq, uniq, uouts, kernel_name);
+    });
 }
 
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
 int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                    hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
-    hvec<AlignRequest> uniq;
-    hvec<u32> uniq_of;
-    dedup_requests(reqs, uniq, uniq_of);
-    hvec<TraceResult> ures;
-    int rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);
-    if (rc) return rc;
-    results.resize(reqs.size());
-    for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
-    return FLX_OK;
+    return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
+        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);
+    });
 }
 
 // Existence tests of one locus. Anchors of the same read at the same locus test the same node in windows shifted by their indel
@@ -395,7 +405,6 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
     static int const disabled = (getenv("FLX_NO_UNION") || getenv("FLX_NO_EXISTS_CLUSTERS")) ? 1 : 0;
     hvec<AlignRequest> uniq;
     hvec<u32> uniq_of(reqs.size());
-    hvec<u32> order;                                          // position in `uniq` (identity: kept for the code below)
     struct Cluster { u32 first, count; u64 lo_start, hi_start, lo_end, hi_end; };     // members = uniq[first .. first+count)
     hvec<Cluster> clusters;
     uniq.reserve(reqs.size());
@@ -429,8 +438,6 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
         }
         i0 = i1;
     }
-    order.resize(uniq.size());
-    std::iota(order.begin(), order.end(), 0u);
     lap(0);
     hvec<DevAlignOut> uouts(uniq.size(), DevAlignOut{0xFFFFFFFFu, 0});
     // ---- one launch: single windows on their own, clusters on their intersection and (speculatively: a separate round trip
@@ -439,7 +446,7 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
     hvec<u32> job_cluster;                                   // cluster index, bit 31 set for the union job
     for (u32 ci = 0; ci < clusters.size(); ++ci) {
         Cluster const& c = clusters[ci];
-        AlignRequest r = uniq[order[c.first]];
+        AlignRequest r = uniq[c.first];
         if (c.count == 1) { jobs.push_back(r); job_cluster.push_back(ci); continue; }
         if (c.lo_end > c.hi_start) {                         // the common columns (none: straight to the union and the members)
             AlignRequest i = r;
@@ -475,7 +482,7 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
     for (u32 ci = 0; ci < clusters.size(); ++ci) {
         Cluster const& c = clusters[ci];
         if (state[ci] != 0) continue;
-        for (u32 j = 0; j < c.count; ++j) { jobs.push_back(uniq[order[c.first + j]]); job_member.push_back(order[c.first + j]); }
+        for (u32 j = 0; j < c.count; ++j) { jobs.push_back(uniq[c.first + j]); job_member.push_back(c.first + j); }
     }
     if (!jobs.empty()) {
         if ((rc = run_score_jobs_unique(ctx, d_text, d_peq, jobs, jouts, "ed_align_exists"))) return rc;
@@ -484,7 +491,7 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
     for (u32 ci = 0; ci < clusters.size(); ++ci) {
         if (state[ci] == 0) continue;
         Cluster const& c = clusters[ci];
-        for (u32 j = 0; j < c.count; ++j) uouts[order[c.first + j]] = DevAlignOut{state[ci] == 1 ? pass_score[ci] : 0xFFFFFFFFu, 0};
+        for (u32 j = 0; j < c.count; ++j) uouts[c.first + j] = DevAlignOut{state[ci] == 1 ? pass_score[ci] : 0xFFFFFFFFu, 0};
     }
     if (getenv("FLX_ALIGN_DEBUG")) {
         size_t multi = 0, decided_a = 0;
@@ -511,12 +518,11 @@ int run_exists_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
 // The band of U contains the band of every member, and a banded value is exact whenever it is <= k.
 constexpr u64 UNION_MAX_SHIFT = 256;      // members start within this many columns of the first member of their union
 
-int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
-    hvec<AlignRequest> uniq;
-    hvec<u32> uniq_of;
-    dedup_requests(reqs, uniq, uniq_of);
-    hvec<TraceResult> ures(uniq.size());
+namespace {
+
+// the union form over distinct requests (n_requests: with their duplicates, for the debug line)
+int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& uniq, size_t n_requests,
+                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
     bool usable = !uniq.empty() && !getenv("FLX_NO_UNION");
     for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
     // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
@@ -549,34 +555,20 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
             members.push_back(id);
         }
     }
-    if (!usable || unions.size() == uniq.size()) {          // nothing to share: the plain path
-        int const rc = run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);
-        if (rc) return rc;
-        results.resize(reqs.size());
-        for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
-        return FLX_OK;
-    }
+    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);      // nothing to share: the plain path
 
+    ures.assign(uniq.size(), TraceResult{});
     hvec<AlignRequest> ureqs(unions.size());
     for (size_t i = 0; i < unions.size(); ++i) ureqs[i] = unions[i].req;
-    hvec<AlignShape> shapes;
-    if (int const src = choose_shapes(ureqs, shapes)) return src;
-    hvec<u64> slots(ureqs.size());
-    u64 const budget_slots = std::max<u64>(ctx->trace_budget_bytes / 16, 1);
-    for (size_t i = 0; i < ureqs.size(); ++i) {
-        slots[i] = align_trace_slots(ureqs[i].n, ureqs[i].m, ureqs[i].k, shapes[i]);
-        if (slots[i] > budget_slots) { set_error("one alignment needs more trace memory than the configured budget (FLX_TRACE_ARENA_MB)"); return FLX_ERR_CAPACITY; }
-    }
+    TracePlan plan;
+    int rc;
+    if ((rc = plan.make(ctx, ureqs))) return rc;
     hvec<AlignRequest> fallback;
     hvec<u32> fallback_of;                   // uniq index of each fallback request
-    int rc;
-    size_t next = 0;
-    while (next < ureqs.size()) {
-        size_t const begin = next;
-        u64 used = 0;
-        while (next < ureqs.size() && used + slots[next] <= budget_slots) { used += slots[next]; ++next; }
+    while (!plan.done()) {
+        size_t begin, next;
+        if ((rc = plan.next_chunk(ctx, begin, next))) return rc;
         size_t const count = next - begin;
-        if ((rc = ctx->trace.ensure(std::max<size_t>(used * 16 + 64, ctx->trace.ptr ? 0 : std::min<size_t>(ctx->trace_budget_bytes, (size_t)budget_slots * 16) / 3 * 2)))) return rc;
 
         // ---- K4 over the unions of this arena chunk, with their last rows
         hvec<u64> trace_off(count), row_off(count);
@@ -585,13 +577,13 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
         if ((rc = ctx->lastrow.ensure(rows * 2 + 64))) return rc;
         FLX_HIP(hipMemsetAsync(ctx->lastrow.ptr, 0xFF, rows * 2, ctx->stream));
         rows = 0;
-        rc = launch_by_shape(ctx, d_text, d_peq, ureqs, shapes, begin, next, "ed_align_trace", " unions", true, ctx->lastrow.as<u16>(), [&](u32 id, DevAlignJob& job) {
+        rc = launch_by_shape(ctx, d_text, d_peq, ureqs, plan.shapes, begin, next, "ed_align_trace", " unions", true, ctx->lastrow.as<u16>(), [&](u32 id, DevAlignJob& job) {
             AlignRequest const& r = ureqs[id];
             job.trace_off = trace_off[id - begin] = off;
             job.lastrow_off = row_off[id - begin] = rows;
-            off += slots[id];
+            off += plan.slots[id];
             rows += ((u64)r.n + 15) / 16 * 16;
-            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, shapes[id].words_per_lane, shapes[id].lanes_per_job);
+            TraceLayout const tl = ckpt_trace_layout(r.n, r.m, r.k, plan.shapes[id].words_per_lane, plan.shapes[id].lanes_per_job);
             return (tl.carry_slots + tl.ckpt_slots) * 16 + 2ull * r.n;
         });
         if (rc) return rc;
@@ -617,74 +609,33 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
         if ((rc = d2h(ctx, wouts.data(), ctx->row_out.ptr, wins.size() * sizeof(DevAlignOut)))) return rc;
         if ((rc = ctx->sync())) return rc;
 
-        // ---- one traceback per distinct (union, end column)
-        hvec<DevTraceJob> tjobs;
+        // ---- one traceback per distinct (union, end column); the members of a union share its trace job's CIGAR words and MD string
+        Traceback tb(md_pool != nullptr);
         hvec<u32> win_tjob(wins.size(), 0xFFFFFFFFu);
-        MdBatch mdb;                                       // (the members of a union share its trace job's MD string as they share its CIGAR words)
-        u64 cigar_words = 0, path_steps = 0;
-        {
-            size_t w0 = 0;
-            while (w0 < wins.size()) {                     // windows of one union are consecutive
-                size_t w1 = w0;
-                while (w1 < wins.size() && win_union[w1] == win_union[w0]) ++w1;
-                u32 const ui = win_union[w0];
-                AlignRequest const& ur = ureqs[ui];
-                AlignShape const sh = shapes[ui];
-                for (size_t w = w0; w < w1; ++w) {
-                    if (wouts[w].score == 0xFFFFFFFFu) continue;
-                    u32 const end_in_union = (u32)(uniq[win_member[w]].ref_off - ur.ref_off) + wouts[w].end_col;
-                    for (size_t v = w0; v < w; ++v)
-                        if (win_tjob[v] != 0xFFFFFFFFu && tjobs[win_tjob[v]].end_col == end_in_union) { win_tjob[w] = win_tjob[v]; break; }
-                    if (win_tjob[w] != 0xFFFFFFFFu) continue;
-                    u32 const cap = 2 * wouts[w].score + 2;
-                    win_tjob[w] = (u32)tjobs.size();
-                    tjobs.push_back(DevTraceJob{ur.ref_off, ur.q_off, trace_off[ui - begin], cigar_words, ur.n, ur.m, sh.lanes_per_job, sh.words_per_lane,
-                                                end_in_union, cap, (u32)tjobs.size(), ur.k});
-                    if (md_pool) mdb.add(tjobs.back(), wouts[w].score);
-                    cigar_words += cap;
-                    path_steps += (u64)ur.m + wouts[w].score;
-                }
-                w0 = w1;
+        for (size_t w0 = 0; w0 < wins.size();) {                     // windows of one union are consecutive
+            size_t w1 = w0;
+            while (w1 < wins.size() && win_union[w1] == win_union[w0]) ++w1;
+            u32 const ui = win_union[w0];
+            for (size_t w = w0; w < w1; ++w) {
+                if (wouts[w].score == 0xFFFFFFFFu) continue;
+                u32 const end_in_union = (u32)(uniq[win_member[w]].ref_off - ureqs[ui].ref_off) + wouts[w].end_col;
+                for (size_t v = w0; v < w; ++v)
+                    if (win_tjob[v] != 0xFFFFFFFFu && tb.jobs[win_tjob[v]].end_col == end_in_union) { win_tjob[w] = win_tjob[v]; break; }
+                if (win_tjob[w] == 0xFFFFFFFFu) win_tjob[w] = tb.add(ureqs[ui], trace_off[ui - begin], plan.shapes[ui], end_in_union, wouts[w].score);
             }
+            w0 = w1;
         }
-        hvec<DevTraceOut> touts(tjobs.size());
-        size_t const pool_base = cigar_pool.size();
-        if (!tjobs.empty()) {
-            if ((rc = h2d(ctx, ctx->tjobs, tjobs.data(), tjobs.size() * sizeof(DevTraceJob)))) return rc;
-            if ((rc = ctx->tjob_out.ensure(tjobs.size() * sizeof(DevTraceOut)))) return rc;
-            if ((rc = ctx->cigar.ensure(cigar_words * 4 + 16))) return rc;
-            if (md_pool && (rc = mdb.upload(ctx))) return rc;
-            rc = timed_launch(ctx, "ed_traceback", path_steps * 18, path_steps, [&] {
-                return DeviceApi::traceback(ctx->stream, d_text, d_peq, ctx->trace.as<u64>(), ctx->tjobs.as<DevTraceJob>(), (u32)tjobs.size(),
-                                            ctx->cigar.as<u32>(), ctx->tjob_out.as<DevTraceOut>());
-            });
-            if (rc) return rc;
-            if (md_pool && (rc = mdb.launch(ctx, d_text))) return rc;
-            cigar_pool.resize(pool_base + cigar_words);
-            if ((rc = d2h(ctx, touts.data(), ctx->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
-            if ((rc = d2h(ctx, cigar_pool.data() + pool_base, ctx->cigar.ptr, cigar_words * 4))) return rc;
-            if (md_pool && (rc = mdb.fetch(ctx, *md_pool))) return rc;
-            if ((rc = ctx->sync())) return rc;
-            for (auto const& t : touts)
-                if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
-            if (md_pool && (rc = mdb.account(ctx, touts))) return rc;
-        }
+        if ((rc = tb.run(ctx, d_text, d_peq, cigar_pool, md_pool))) return rc;
         // ---- members take the union's alignment when its path starts inside their window
         for (size_t w = 0; w < wins.size(); ++w) {
             u32 const id = win_member[w];
             if (wouts[w].score == 0xFFFFFFFFu) continue;                       // no alignment within k in this window
-            DevTraceOut const& t = touts[win_tjob[w]];
-            if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+            TraceResult res = tb.result(win_tjob[w], wouts[w].score);
             u64 const shift = uniq[id].ref_off - ureqs[win_union[w]].ref_off;
             static int const force_own = getenv("FLX_UNION_ALIGN_OWN") ? 1 : 0;        // test hook: as if every path left its window
-            if (t.begin < shift || force_own) { fallback_of.push_back(id); fallback.push_back(uniq[id]); continue; }
-            TraceResult& res = ures[id];
-            res.exists = true;
-            res.nm = wouts[w].score;
-            res.begin = (u32)(t.begin - shift);
-            res.cigar_off = pool_base + tjobs[win_tjob[w]].cigar_off + t.cigar_start;
-            res.cigar_len = t.cigar_len;
-            if (md_pool) { res.md_off = mdb.pool_base + mdb.jobs[win_tjob[w]].md_off; res.md_len = mdb.outs[win_tjob[w]].len; }
+            if (res.begin < shift || force_own) { fallback_of.push_back(id); fallback.push_back(uniq[id]); continue; }
+            res.begin = (u32)(res.begin - shift);
+            ures[id] = res;
         }
     }
     if (!fallback.empty()) {
@@ -692,10 +643,17 @@ int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Ali
         if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
-    if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", reqs.size(), uniq.size(), unions.size(), fallback.size());
-    results.resize(reqs.size());
-    for (size_t i = 0; i < reqs.size(); ++i) results[i] = ures[uniq_of[i]];
+    if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", n_requests, uniq.size(), unions.size(), fallback.size());
     return FLX_OK;
+}
+
+}  // namespace
+
+int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
+    return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
+        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool);
+    });
 }
 
 // One ed_extend launch over all jobs; the wavefront cells and the symbols walked are known once the results are back.

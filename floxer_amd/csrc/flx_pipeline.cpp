@@ -177,10 +177,11 @@ extern "C" int flx_align_reads_resident_with_tags(flx_ctx* ctx, const flx_params
 }
 extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R, flx_run** out) {
     if (!run_options_valid(P, R)) return FLX_ERR_INVALID;
-    const flx_output_options* const O = R ? R->output : nullptr;
-    const flx_tag_options* const T = R ? R->tags : nullptr;
-    const flx_partial_options* const PO = R ? R->partial : nullptr;
-    const flx_extend_options* const EO = R ? R->extend : nullptr;
+    RunOptions opt{};                            // (a NULL bundle, a NULL member and a zeroed struct are the same: that option is off)
+    if (R && R->output) opt.output = *R->output;
+    if (R && R->tags) opt.tags = *R->tags;
+    if (R && R->partial) opt.partial = *R->partial;
+    if (R && R->extend) opt.extend = *R->extend;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
@@ -190,7 +191,7 @@ extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, c
     PhaseTimer dprof("dispatch");
     auto run = std::make_unique<flx_run>();
     run->skipped.assign(n_reads, 0);
-    run->has_md = T && T->md;
+    run->has_md = opt.tags.md;
     if (n_reads == 0) { *out = run.release(); return FLX_OK; }       // an empty batch is an empty run
     // reads are independent units (parallelization.cpp:77-87): the batch is cut into contiguous chunks and every lane (a host
     // thread with its own stream and workspaces) takes the next chunk when it is done with its last one.
@@ -251,7 +252,7 @@ extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, c
             u64 const a = chunk_first[c], b = chunk_first[c + 1];
             parts[c].skipped.assign(n_reads, 0);
             LaneLease lease(ctx, ctx->external_stream ? 0 : -1);      // waits while other calls on this context hold all lanes
-            rcs[c] = align_slice(lease.lane, P, O, T, PO, EO, RD, a, b, &parts[c]);
+            rcs[c] = align_slice(lease.lane, P, opt, RD, a, b, &parts[c]);
             if (rcs[c]) { errs[c] = flx_last_error(); failed.store(true); }
             else { lease.lane->has_run = true; if (!ctx->external_stream) ctx->warm_one_cold_lane(lease.lane); }
         }

@@ -199,12 +199,16 @@ struct Slice {
     double search_ms = 0;
 
     u32 n_sampled(ReadState const& r) const { return (u32)((r.tree_ref().leaves.size() + step - 1) / step); }      // seeds per orientation
+    // traces windows of the slice's reads (root windows, partial records): CIGAR words into cig, MD strings into md when wanted
+    int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres) {
+        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr);
+    }
 };
 
+// the options of a run by value (flx_run_options, validated): an option that is off is a zeroed member
+struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; };
+
 // produces the slice's records (read_index relative to the whole batch)
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_extend_options* EO, const flx_reads* RD,
-                u64 first_read, u64 end_read, flx_run* run);
-// NULL or zeroed: no tags; md must be 0 or 1 and the reserved fields 0 (else the error is set)
-bool tag_options_valid(const flx_tag_options* t);
+int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run);
 
 }  // namespace flx

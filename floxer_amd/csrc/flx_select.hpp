@@ -29,6 +29,13 @@ inline bool output_options_valid(const flx_output_options* o) {
     return true;
 }
 inline bool output_options_active(const flx_output_options* o) { return o && (o->drop_duplicates || o->max_alignments_per_read); }
+// flx_tag_options: NULL or zeroed is no tags; md must be 0 or 1 and the reserved fields 0 (set_error otherwise)
+inline bool tag_options_valid(const flx_tag_options* t) {
+    if (!t) return true;
+    if (t->md > 1) { set_error("flx_tag_options: md must be 0 or 1"); return false; }
+    for (uint32_t r : t->reserved) if (r) { set_error("flx_tag_options: the reserved fields must be 0"); return false; }
+    return true;
+}
 
 // (records of one union share their CIGAR words: the same words compare equal without reading them)
 inline bool select_same(SelectKey const& a, SelectKey const& b) {

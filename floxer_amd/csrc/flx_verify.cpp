@@ -567,7 +567,7 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) 
             if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
     } else {
         hvec<TraceResult> tres;
-        if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), root_reqs, tres, S.cig, S.want_md ? &S.md : nullptr))) return rc;
+        if ((rc = S.trace_windows(lane, RD, root_reqs, tres))) return rc;
         for (size_t i = 0; i < tres.size(); ++i)
             if (tres[i].exists)
                 root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len};
@@ -575,17 +575,28 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) 
     return FLX_OK;
 }
 
+// [left]S + the core words + [right]S as new words behind the pool's (the core's words may be shared with other records); {offset, length}
+std::pair<u64, u32> append_clipped(hvec<u32>& cig, u32 left, u64 core_off, u32 core_len, u32 right) {
+    u64 const off = cig.size();
+    auto clip = [&](u32 rows) { if (rows) cig.push_back((rows << 4) | 4u); };
+    clip(left);
+    size_t const at = cig.size();
+    cig.resize(at + core_len);                             // (grown first: the source lies in the same pool)
+    std::copy(cig.begin() + (long)core_off, cig.begin() + (long)(core_off + core_len), cig.begin() + (long)at);
+    clip(right);
+    return {off, (u32)(cig.size() - off)};
+}
+
 // ---- 8. partial alignments of the reads that would be written as unmapped (flx_partial.hpp): every anchor's highest passed node,
 //      traced in the window it was tested in; does nothing, and launches nothing, when the option is off or no read is eligible
-int rescue_partials(Slice& S, Lane* lane, const flx_params* P, const flx_output_options* O, const flx_partial_options* PO, const flx_reads* RD) {
-    if (!partial_options_active(PO)) return FLX_OK;
-    flx_ctx* ctx = lane->ctx;
-    HostIndex const& H = *ctx->hidx;
+int rescue_partials(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD) {
+    if (!R.partial.enable) return FLX_OK;
+    HostIndex const& H = *lane->ctx->hidx;
     hvec<ReadState> const& reads = S.reads;
     hvec<AnchorState> const& A = S.A;
     hvec<u8> mapped(reads.size(), 0);
     for (u32 i = 0; i < S.root_anchor.size(); ++i) if (S.root_res[i].exists) mapped[A[S.root_anchor[i]].read] = 1;
-    u32 const min_span = partial_min_span(PO), max_records = partial_max_records(PO);
+    u32 const min_span = partial_min_span(&R.partial), max_records = partial_max_records(&R.partial);
     // ---- candidates, read by read in verification order; identical (orientation, node, reference, window) ones are one
     struct Candidate { u32 read; u8 orientation; u32 ref_id; flx_pex_node node; Span span; };
     hvec<Candidate> cands;
@@ -621,13 +632,13 @@ int rescue_partials(Slice& S, Lane* lane, const flx_params* P, const flx_output_
     read_first[reads.size()] = (u32)cands.size();
     if (cands.empty()) return FLX_OK;
     hvec<TraceResult> tres;
-    if (int const rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, S.cig, S.want_md ? &S.md : nullptr)) return rc;
+    if (int const rc = S.trace_windows(lane, RD, reqs, tres)) return rc;
     // ---- selection per read, and the kept records with their clips
     std::vector<flx_partial_candidate> pc;
     std::vector<int32_t> flags;
     std::vector<u8> quality;
     PartialScratch scratch;
-    bool const mapq = O && O->mapq;
+    bool const mapq = R.output.mapq;
     for (size_t r = 0; r < reads.size(); ++r) {
         u32 const c0 = read_first[r], c1 = read_first[r + 1];
         if (c0 == c1) continue;
@@ -647,14 +658,8 @@ int rescue_partials(Slice& S, Lane* lane, const flx_params* P, const flx_output_
         for (u32 j : scratch.kept) {
             u32 const c = c0 + j;
             flx_pex_node const& nd = cands[c].node;
-            // (new words behind the pool's: the traced words may be shared with other records)
-            u64 const off = S.cig.size();
-            if (nd.from) S.cig.push_back((nd.from << 4) | 4u);
-            size_t const at = S.cig.size();
-            S.cig.resize(at + tres[c].cigar_len);            // (grown first: the source lies in the same pool)
-            std::copy(S.cig.begin() + (long)tres[c].cigar_off, S.cig.begin() + (long)(tres[c].cigar_off + tres[c].cigar_len), S.cig.begin() + (long)at);
-            if (len - 1 - nd.to) S.cig.push_back(((len - 1 - nd.to) << 4) | 4u);
-            S.partials.push_back(PartialRecord{(u32)r, (u32)flags[j], cands[c].ref_id, pc[j].start, tres[c].nm, off, (u32)(S.cig.size() - off), tres[c].md_off,
+            auto const clipped = append_clipped(S.cig, nd.from, tres[c].cigar_off, tres[c].cigar_len, len - 1 - nd.to);
+            S.partials.push_back(PartialRecord{(u32)r, (u32)flags[j], cands[c].ref_id, pc[j].start, tres[c].nm, clipped.first, clipped.second, tres[c].md_off,
                                                tres[c].md_len, pc[j].q_from, pc[j].q_to, quality[j], nd.from, nd.to, tres[c].cigar_off, tres[c].cigar_len});
         }
     }
@@ -664,11 +669,11 @@ int rescue_partials(Slice& S, Lane* lane, const flx_params* P, const flx_output_
 // ---- 8b. the kept partial records' ends extended to the break (flx_extend_options; the rule: flx_partial.hpp): one ed_extend launch
 //      over both ends of every kept record of the slice, then one trace of the records that moved; does nothing, and launches nothing,
 //      when the option is off or no record is kept
-int extend_partials(Slice& S, Lane* lane, const flx_extend_options* EO, const flx_reads* RD) {
-    if (!extend_options_active(EO) || S.partials.empty()) return FLX_OK;
-    flx_ctx* ctx = lane->ctx;
-    HostIndex const& H = *ctx->hidx;
-    u32 const w = extend_weight(EO->error_weight), x_drop = extend_x_drop(EO->x_drop), d_max = extend_max_errors(EO->max_errors);
+int extend_partials(Slice& S, Lane* lane, RunOptions const& R, const flx_reads* RD) {
+    flx_extend_options const& EO = R.extend;
+    if (!EO.enable || S.partials.empty()) return FLX_OK;
+    HostIndex const& H = *lane->ctx->hidx;
+    u32 const w = extend_weight(EO.error_weight), x_drop = extend_x_drop(EO.x_drop), d_max = extend_max_errors(EO.max_errors);
     struct End { u32 record; bool right; };
     hvec<DevExtendJob> jobs;
     hvec<End> ends;
@@ -705,7 +710,7 @@ int extend_partials(Slice& S, Lane* lane, const flx_extend_options* EO, const fl
     }
     hvec<DevExtendOut> outs;
     int rc;
-    if ((rc = run_extend_jobs(lane, ctx->didx.text, RD->d_pool.as<u8>(), jobs, outs))) return rc;
+    if ((rc = run_extend_jobs(lane, lane->ctx->didx.text, RD->d_pool.as<u8>(), jobs, outs))) return rc;
     // ---- the records that moved, traced again over exactly the longer interval
     struct Move { u32 rows[2] = {0, 0}, cols[2] = {0, 0}, errors[2] = {0, 0}; };      // [0] left, [1] right
     hvec<Move> moves(S.partials.size());
@@ -728,7 +733,7 @@ int extend_partials(Slice& S, Lane* lane, const flx_extend_options* EO, const fl
     }
     if (reqs.empty()) return FLX_OK;
     hvec<TraceResult> tres;
-    if ((rc = run_trace_jobs_union(lane, ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, S.cig, S.want_md ? &S.md : nullptr))) return rc;
+    if ((rc = S.trace_windows(lane, RD, reqs, tres))) return rc;
     for (size_t j = 0; j < reqs.size(); ++j) {
         if (!tres[j].exists) { set_error("partial extension: no alignment over an interval the extension reached"); return FLX_ERR_INTERNAL; }
         PartialRecord& p = S.partials[req_record[j]];
@@ -744,14 +749,7 @@ int extend_partials(Slice& S, Lane* lane, const flx_extend_options* EO, const fl
         p.core_len = tres[j].cigar_len;
         p.md_off = tres[j].md_off;
         p.md_len = tres[j].md_len;
-        u64 const off = S.cig.size();
-        if (p.o_from) S.cig.push_back((p.o_from << 4) | 4u);
-        size_t const at = S.cig.size();
-        S.cig.resize(at + tres[j].cigar_len);              // (grown first: the source lies in the same pool)
-        std::copy(S.cig.begin() + (long)tres[j].cigar_off, S.cig.begin() + (long)(tres[j].cigar_off + tres[j].cigar_len), S.cig.begin() + (long)at);
-        if (len - 1 - p.o_to) S.cig.push_back(((len - 1 - p.o_to) << 4) | 4u);
-        p.cigar_off = off;
-        p.cigar_len = (u32)(S.cig.size() - off);
+        std::tie(p.cigar_off, p.cigar_len) = append_clipped(S.cig, p.o_from, p.core_off, p.core_len, len - 1 - p.o_to);
     }
     return FLX_OK;
 }
@@ -782,7 +780,8 @@ void compact_cigars(flx_run* run, hvec<u32>& cig) {
 }
 
 // ---- 9. records (alignment.cpp:37-79, output.cpp:49-108): per reference in id order, alignments in verification order
-void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_slice_reads, flx_run* run) {
+void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_reads, flx_run* run) {
+    flx_output_options const& O = R.output;
     HostIndex const& H = *ctx->hidx;
     hvec<ReadState> const& reads = S.reads;
     hvec<AnchorState> const& A = S.A;
@@ -793,13 +792,13 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
     hvec<hvec<u32>> roots_of_read(reads.size());
     for (u32 i = 0; i < root_anchor.size(); ++i) roots_of_read[A[root_anchor[i]].read].push_back(i);   // already in verification order
     // output options (flx_select.hpp): a read's records are selected once they are formed and its statistics are taken
-    bool const select = output_options_active(O);
+    bool const select = output_options_active(&O);
     u64 n_dropped = 0;
     std::vector<SelectKey> sel_keys;
     std::vector<u8> sel_keep;
     SelectScratch sel_scratch;
     // mapping quality (flx_mapq.hpp): from all of a read's records, before any of them is dropped
-    bool const mapq = O && O->mapq;
+    bool const mapq = O.mapq;
     std::vector<MapqKey> mq_keys;
     std::vector<u8> mq_q;
     MapqScratch mq_scratch;
@@ -863,7 +862,7 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
                                                  rec.cigar_length ? cig.data() + rec.cigar_offset : nullptr});
                 }
             sel_keep.resize(n);
-            select_read_records(sel_keys.data(), n, O->drop_duplicates != 0, O->max_alignments_per_read, sel_keep.data(), sel_scratch);
+            select_read_records(sel_keys.data(), n, O.drop_duplicates != 0, O.max_alignments_per_read, sel_keep.data(), sel_scratch);
             size_t w = rec0;
             for (size_t j = 0; j < n; ++j)
                 if (sel_keep[j]) {
@@ -901,21 +900,13 @@ void write_records(Slice& S, flx_ctx* ctx, const flx_output_options* O, u64 n_sl
 
 }  // namespace
 
-bool tag_options_valid(const flx_tag_options* t) {
-    if (!t) return true;
-    if (t->md > 1) { set_error("flx_tag_options: md must be 0 or 1"); return false; }
-    for (uint32_t r : t->reserved) if (r) { set_error("flx_tag_options: the reserved fields must be 0"); return false; }
-    return true;
-}
-
-int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, const flx_tag_options* T, const flx_partial_options* PO, const flx_extend_options* EO, const flx_reads* RD,
-                u64 first_read, u64 end_read, flx_run* run) {
+int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run) {
     flx_ctx* ctx = lane->ctx;
     FLX_HIP(hipSetDevice(ctx->device));
     HostIndex const& H = *ctx->hidx;
     PhaseTimer prof;
     Slice S;
-    S.want_md = T && T->md;
+    S.want_md = R.tags.md;
     int rc;
     if ((rc = plan_reads(S, P, RD, first_read, end_read, run))) return rc;
     if ((rc = plan_seeds(S, P, RD))) return rc;
@@ -940,11 +931,11 @@ int align_slice(Lane* lane, const flx_params* P, const flx_output_options* O, co
     prof.mark("interval-pass");
     if ((rc = align_roots(S, lane, P, RD))) return rc;
     prof.mark("root-align");
-    if ((rc = rescue_partials(S, lane, P, O, PO, RD))) return rc;
+    if ((rc = rescue_partials(S, lane, P, R, RD))) return rc;
     prof.mark("partials");
-    if ((rc = extend_partials(S, lane, EO, RD))) return rc;
-    if (extend_options_active(EO)) prof.mark("extend");
-    write_records(S, ctx, O, end_read - first_read, run);
+    if ((rc = extend_partials(S, lane, R, RD))) return rc;
+    if (R.extend.enable) prof.mark("extend");
+    write_records(S, ctx, R, end_read - first_read, run);
     prof.mark("records");
     return FLX_OK;
 }

@@ -613,6 +613,50 @@ def test_root_unions_and_their_fallback():
     assert forced == exp.records()
 
 
+ARENA_SPLIT_READS = 500
+
+
+def _trace_runs_in_default_and_small_arena(n_reads, env):
+    """in a child (the arena budget and the lanes are read when a context is made, the hooks once per process): the same md=True call
+    on a context with the default trace arena and on one with FLX_TRACE_ARENA_MB=1 (128 MB for the one lane that works: the floor of
+    make_context); per context the records (as rows) and MD refs, digests of the CIGAR words and of the MD bytes they refer to, the ed_traceback launches"""
+    import subprocess, sys, json
+    code = ("import sys, json, os, hashlib; sys.path.insert(0, %r); import numpy as np, floxer_amd as F; from floxer_amd import simulate as S;"
+            "g = S.make_genome(800000, 1, seed=51); r, _, _ = S.make_reads(g, %d, 5000, 0.08, seed=52); idx = F.fmindex(g); out = []\n"
+            "def referenced(pool, refs):\n"          # what lies between the strings of a pool is unspecified: zeroed before the digest
+            "    used = np.zeros(len(pool), dtype=bool)\n"
+            "    for off, n in np.unique(refs, axis=0): used[int(off): int(off) + int(n)] = True\n"
+            "    return hashlib.sha256(np.where(used, pool, 0).tobytes()).hexdigest()\n"
+            "for mb in (None, '1'):\n"
+            "    if mb: os.environ['FLX_TRACE_ARENA_MB'] = mb\n"
+            "    c = F.context(idx); c.enable_kernel_timing(True)\n"
+            "    res = F.aligner(c, F.params(error_probability=0.08), md=True).align_reads(r)\n"
+            "    out.append(dict(skipped=res.skipped.tolist(), rows=res.rows.tolist(), md_refs=res.md_refs.tolist(),\n"
+            "                    cigars=referenced(res.cigars, res.rows[:, 5:7]), md=referenced(res.md_bytes, res.md_refs),\n"
+            "                    tracebacks=c.kernel_stats()['ed_traceback']['launches']))\n"
+            "    c.close()\n"
+            "print(json.dumps(out))" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), n_reads))
+    child_env = {k: v for k, v in os.environ.items() if k not in ("FLX_TRACE_ARENA_MB", "FLX_NO_UNION")}
+    child_env.update(FLX_LANES="2", FLX_CHUNK_READS="1000000", **env)
+    out = subprocess.run([sys.executable, "-c", code], env=child_env, capture_output=True, text=True, check=True)
+    return json.loads(out.stdout.strip().split("\n")[-1])
+
+
+@pytest.mark.parametrize("env", [dict(), dict(FLX_NO_UNION="1")], ids=["unions", "plain"])
+def test_trace_arena_split_gives_the_same_run(env):
+    """a batch whose trace planes do not fit the arena together is traced in several arena chunks, by the union form and (FLX_NO_UNION)
+    by the plain form: records, CIGAR words, MD refs and MD bytes equal those of the default arena, which holds the batch at once.
+    That the split happened is read off the ed_traceback launches (one per arena chunk that has a path). 500 reads is the smallest
+    hundred at which the union form makes three launches in the small arena, one more than the assertion needs; measured on an MI355X
+    (default arena / small arena): 300 reads 1 / 2 (unions) and 1 / 14 (plain), 400 reads 1 / 2 and 1 / 19, 500 reads 1 / 3 and 1 / 12,
+    600 reads 1 / 3 and 1 / 14; under a second per form."""
+    default, small = _trace_runs_in_default_and_small_arena(ARENA_SPLIT_READS, env)
+    print("ed_traceback launches: default arena %d, small arena %d" % (default["tracebacks"], small["tracebacks"]))
+    assert small["tracebacks"] > default["tracebacks"]
+    for key in ("skipped", "rows", "md_refs", "cigars", "md"):
+        assert small[key] == default[key], key
+
+
 def test_existence_block_form_on_6kb_reads_matches_oracle():
     """the existence tests run as a ring of lanes per job over the static band, 16 columns per step (ed_exists_block_kernel): records
     equal to the oracle's on reads whose trees reach every launch shape of the lower levels and the ring-scheduled upper ones"""
