@@ -87,9 +87,14 @@ static void exclusive_sum(hipStream_t s, const u32* in, u32* out, u32 n, u32* ti
 constexpr u32 SEL_MAX = 64;
 struct SelStat { u8 useful, raw, flag, excluded; u32 excluded_soft; };      // flag 1: the host selects this seed's anchors; = DevSelStat
 
+// A search that outgrew the hit buffer (more slots asked for, counters[0], than it has) counted hits in seed_cnt that have no slot:
+// the offsets then run past `grouped`. Such a pass is repeated with a larger buffer; nothing of it is scattered and nothing selected.
+// With every hit in its slot the last offset is at most counters[0] <= hit_cap.
+__device__ __forceinline__ bool hits_fit(const u32* __restrict__ counters, u32 hit_cap) { return counters[0] <= hit_cap; }
+
 __global__ void __launch_bounds__(256) hit_scatter_kernel(const DevHit* __restrict__ hits, const u32* __restrict__ counters, u32 hit_cap,
                                                           const u32* __restrict__ offset, DevHit* __restrict__ grouped) {
-    u32 const n_slots = min(counters[0], hit_cap);
+    u32 const n_slots = hits_fit(counters, hit_cap) ? counters[0] : 0u;
     for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += gridDim.x * blockDim.x) {
         DevHit h = hits[i];
         if (h.seed == 0xFFFFFFFFu) continue;
@@ -196,12 +201,14 @@ __device__ __forceinline__ bool select_seed(const DevHit* __restrict__ groups, u
 constexpr u32 SEL_LIGHT = 8;
 constexpr u32 SELW_MAX_GROUPS = 512, SELW_FEW_GROUPS = 64;
 __global__ void __launch_bounds__(256) seed_rows_kernel(const DevHit* __restrict__ grouped, const u32* __restrict__ hit_offset, u32 n_seeds,
-                                                        u32 hard_cap, u32 soft_cap, u32* __restrict__ rows, SelStat* __restrict__ stat,
-                                                        u32* __restrict__ n_out, u32* __restrict__ lists, u32* __restrict__ list_counts) {
+                                                        const u32* __restrict__ counters, u32 hit_cap, u32 hard_cap, u32 soft_cap,
+                                                        u32* __restrict__ rows, SelStat* __restrict__ stat, u32* __restrict__ n_out,
+                                                        u32* __restrict__ lists, u32* __restrict__ list_counts) {
     u32 const sid = blockIdx.x * blockDim.x + threadIdx.x;
     u32 cls = 0;                                             // 1 light, 2 heavy (a wave, up to SELW_FEW_GROUPS groups), 3 heavy with more groups
     if (sid < n_seeds) {
-        u32 const g0 = hit_offset[sid], cnt = hit_offset[sid + 1] - g0;
+        // (a pass whose hits did not fit: every seed counts as one without hits, so no kernel behind this one reads `grouped`)
+        u32 const g0 = hit_offset[sid], cnt = hits_fit(counters, hit_cap) ? hit_offset[sid + 1] - g0 : 0u;
         SelStat st{0, 0, 0, 0, 0};
         u32 total = 0;
         if (cnt > hard_cap) st.excluded = 1;                // every group has at least one row: over the hard cap whatever the rows are
@@ -331,6 +338,8 @@ __global__ void __launch_bounds__(64, MAXG <= 64 ? 4 : 2) seed_select_wave_kerne
         __syncthreads();
         // ---- rows round robin over the groups (search.cpp:239-272): row lb + round of every group that still has one, until
         //      `total` are kept
+        //      (with more than 64 groups round 0 ends at its first ballot: all 64 lanes are alive and total <= SEL_MAX = 64 rows are
+        //      kept, so the later bases only ever run with 64 groups or fewer, where there are none)
         u32 kept = 0;
         for (u32 round = 0; kept < total; ++round) {
             bool any = false;
@@ -414,11 +423,13 @@ __global__ void __launch_bounds__(64, MAXG <= 64 ? 4 : 2) seed_select_wave_kerne
 
 __global__ void __launch_bounds__(256) seed_compact_kernel(const DevOutAnchor* __restrict__ sparse, const u32* __restrict__ row_offset,
                                                            const u32* __restrict__ n_out, const u32* __restrict__ out_offset, u32 n_seeds,
-                                                           DevOutAnchor* __restrict__ out, u32 out_cap) {
+                                                           DevOutAnchor* __restrict__ out, u32 out_cap, u32 sparse_cap) {
     u32 const sid = blockIdx.x * blockDim.x + threadIdx.x;
     if (sid >= n_seeds) return;
     u32 const n = n_out[sid], from = row_offset[sid], to = out_offset[sid];
-    for (u32 i = 0; i < n; ++i) if (to + i < out_cap) out[to + i] = sparse[from + i];
+    // (a seed's slots of the sparse list lie past its end when the list was outgrown: those anchors were never stored, and the pass
+    // is repeated)
+    for (u32 i = 0; i < n; ++i) if (from + i < sparse_cap && to + i < out_cap) out[to + i] = sparse[from + i];
 }
 
 size_t DeviceApi::select_scan_bytes(u32 n_seeds) {
@@ -438,8 +449,8 @@ int DeviceApi::select(void* stream, const DevHit* d_hits, const u32* d_counters,
     SelStat* const stat = reinterpret_cast<SelStat*>(d_stat);
     u32* const list_counts = d_lists + 3 * (size_t)n_seeds;
     if ((e = hipMemsetAsync(list_counts, 0, 12, s)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(seed_rows_kernel, dim3((n_seeds + 255) / 256), dim3(256), 0, s, d_grouped, d_hit_offset, n_seeds, hard_cap, soft_cap, d_rows,
-                       stat, d_n_out, d_lists, list_counts);
+    hipLaunchKernelGGL(seed_rows_kernel, dim3((n_seeds + 255) / 256), dim3(256), 0, s, d_grouped, d_hit_offset, n_seeds, d_counters, hit_cap,
+                       hard_cap, soft_cap, d_rows, stat, d_n_out, d_lists, list_counts);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     exclusive_sum(s, d_rows, d_row_offset, n_seeds + 1, (u32*)d_scan_tmp);
     // grids sized for the usual shares (a quarter of the seeds light, a per cent heavy); the kernels loop over their lists
@@ -453,7 +464,7 @@ int DeviceApi::select(void* stream, const DevHit* d_hits, const u32* d_counters,
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     exclusive_sum(s, d_n_out, d_out_offset, n_seeds + 1, (u32*)d_scan_tmp);
     hipLaunchKernelGGL(seed_compact_kernel, dim3((n_seeds + 255) / 256), dim3(256), 0, s, d_sparse, d_row_offset, d_n_out, d_out_offset, n_seeds,
-                       d_out, out_cap);
+                       d_out, out_cap, sparse_cap);
     return (int)hipGetLastError();
 }
 
