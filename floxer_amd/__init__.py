@@ -13,6 +13,7 @@ libfloxer_amd.so:
     aligner(..., md=True), align(..., md=True)  not floxer's: MD strings, built on the device next to the CIGARs (opt-in)
     aligner(..., partial=partial_options())   not floxer's: soft-clipped partial alignments of reads without a full one (opt-in)
     aligner(..., extend=extend_options()), extend_batch()  not floxer's: the partial records' ends extended to the break (opt-in)
+    aligner(..., split=split_options()), cigar_tails()  not floxer's: reads mapped in full that carry a chimeric tail are split (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -213,6 +214,7 @@ class context:
         out["records_dropped"] = int(pc.reserved[0])          # records that output options left out (records: those written)
         out["partial_records"] = int(pc.reserved[1])          # records of partial alignments written (partial_options), and
         out["reads_rescued"] = int(pc.reserved[2])            # the reads that got them in place of their unmapped record
+        out["reads_split"] = int(pc.reserved[3])              # the reads mapped in full that split_options split at a chimeric tail
         return out
 
     def kernel_stats(self):
@@ -552,6 +554,53 @@ def extend_options(error_weight=0, x_drop=0, max_errors=0, enable=True):
     return o
 
 
+def split_options(error_weight=0, x_drop=0, min_tail_rows=0, enable=True):
+    """flx_split_options (include/floxer_amd.h): not floxer's. A read mapped in full whose primary's score rows - error_weight * errors
+    (0: 4) falls more than x_drop (0: 100) below its maximum towards an end, over at least min_tail_rows (0: 100) query bases, is
+    written as a soft-clipped primary plus the supplementaries its anchors proved inside the tail. Needs partial_options(...) and
+    output_options(max_alignments=1); not together with without_cigar."""
+    if error_weight < 0 or x_drop < 0 or min_tail_rows < 0:
+        raise FloxerError("error_weight, x_drop and min_tail_rows must be >= 0 (0: the default)")
+    o = capi.SplitOptions()
+    o.enable, o.error_weight, o.x_drop, o.min_tail_rows = int(bool(enable)), int(error_weight), int(x_drop), int(min_tail_rows)
+    return o
+
+
+TAIL_FIELDS = ("left_rows", "left_cols", "left_errors", "left_words", "right_rows", "right_cols", "right_errors", "right_words")
+
+
+def _tail_jobs(words, jobs):
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    n_words = len(w)
+    if n_words == 0:
+        w = np.zeros(1, np.uint32)
+    arr = (capi.TailJob * max(1, len(jobs)))()
+    for i, j in enumerate(jobs):
+        off, ln, ew, x, mr = (list(j) + [0, 0, 0])[:5]
+        arr[i] = capi.TailJob(int(off), int(ln), int(ew), int(x), int(mr))
+    return w, n_words, arr, (capi.TailResult * max(1, len(jobs)))()
+
+
+def _tail_rows(res, n):
+    return np.array([[getattr(r, f) for f in TAIL_FIELDS] for r in res[:n]], dtype=np.int64).reshape(-1, 8)
+
+
+def cigar_tails(words, jobs):
+    """flx_cigar_tails, the tail rule on the host: words = BAM CIGAR words (ops = X I D), jobs = [(cigar_offset, cigar_length[,
+    error_weight, x_drop, min_tail_rows])] (the last three 0 or left out: the defaults). Returns an (n,8) int64 array {left_rows,
+    left_cols, left_errors, left_words, right_rows, right_cols, right_errors, right_words} (TAIL_FIELDS); an absent tail is zeros."""
+    w, n_words, arr, res = _tail_jobs(words, jobs)
+    check(lib().flx_cigar_tails(ptr(w, u32p), n_words, arr, len(jobs), res))
+    return _tail_rows(res, len(jobs))
+
+
+def cigar_tails_batch(ctx, words, jobs):
+    """flx_cigar_tails_batch: the same numbers from the kernel cigar_tails"""
+    w, n_words, arr, res = _tail_jobs(words, jobs)
+    check(lib().flx_cigar_tails_batch(ctx.h, ptr(w, u32p), n_words, arr, len(jobs), res))
+    return _tail_rows(res, len(jobs))
+
+
 EXTEND_STOP = {1: "x_drop", 2: "rows", 3: "max_errors"}
 
 
@@ -612,12 +661,13 @@ def _collect_run(run, n, md=False):
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None):
+    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None):
         """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
         string (RunResult.md), built on the device; not together with without_cigar; partial: partial_options(...), None: a read
         without a full alignment is written as unmapped (floxer's output); extend: extend_options(...), None: a partial record ends at
-        its PEX node's boundary (needs partial)"""
-        self.ctx, self.params, self.output, self.md, self.partial, self.extend = ctx, p, output, bool(md), partial, extend
+        its PEX node's boundary (needs partial); split: split_options(...), None: a read mapped in full is one record whatever its
+        ends look like (needs partial and output_options(max_alignments=1))"""
+        self.ctx, self.params, self.output, self.md, self.partial, self.extend, self.split = ctx, p, output, bool(md), partial, extend, split
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
@@ -628,10 +678,11 @@ class aligner:
         for name in ("output", "partial", "extend"):
             if getattr(self, name) is not None:
                 setattr(bundle, name, C.pointer(getattr(self, name)))
+        split = C.byref(self.split) if self.split is not None else None
         if isinstance(reads, resident_reads):
             n = reads.n
-            check(lib().flx_align_reads_resident_opt(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), C.byref(run)))
+            check(lib().flx_align_reads_resident_split(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, C.byref(run)))
         else:
             pool, offs, n = _pool_and_offsets(reads)
-            check(lib().flx_align_reads_opt(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), C.byref(run)))
+            check(lib().flx_align_reads_split(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, C.byref(run)))
         return _collect_run(run, n, md=self.md)

@@ -94,6 +94,21 @@ class RunOptions(C.Structure):
                 ("extend", C.POINTER(ExtendOptions)), ("reserved", C.c_void_p * 4)]
 
 
+class SplitOptions(C.Structure):
+    _fields_ = [("enable", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32), ("min_tail_rows", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class TailJob(C.Structure):
+    _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
+                ("min_tail_rows", C.c_uint32)]
+
+
+class TailResult(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("left_rows", "left_cols", "left_errors", "left_words", "right_rows", "right_cols", "right_errors",
+                                          "right_words")]
+
+
 class ExtendJob(C.Structure):
     _fields_ = [("text_pos", C.c_uint64), ("q_pos", C.c_uint64), ("ref_limit", C.c_uint32), ("row_limit", C.c_uint32),
                 ("direction", C.c_int32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32), ("max_errors", C.c_uint32)]
@@ -140,7 +155,7 @@ EXPORTED = [
     "flx_align_reads_with_options", "flx_align_reads_resident_with_options", "flx_select_records", "flx_assign_mapq", "flx_sam_set_mapq",
     "flx_align_reads_with_tags", "flx_align_reads_resident_with_tags", "flx_run_num_md_bytes", "flx_run_copy_md", "flx_align_batch_md",
     "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
-    "flx_extend_batch", "flx_sam_set_sa",
+    "flx_extend_batch", "flx_sam_set_sa", "flx_align_reads_split", "flx_align_reads_resident_split", "flx_cigar_tails", "flx_cigar_tails_batch",
 ]
 
 _lib = None
@@ -236,6 +251,12 @@ def lib():
                                                      C.POINTER(TagOptions), C.POINTER(C.c_void_p)]
     L.flx_align_reads_opt.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(RunOptions), C.POINTER(C.c_void_p)]
     L.flx_align_reads_resident_opt.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(RunOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_split.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(RunOptions), C.POINTER(SplitOptions),
+                                        C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_split.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(RunOptions), C.POINTER(SplitOptions),
+                                                 C.POINTER(C.c_void_p)]
+    L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
+    L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]
     L.flx_partial_mapq.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(C.c_int32), u8p]
     L.flx_run_num_md_bytes.restype = C.c_uint64

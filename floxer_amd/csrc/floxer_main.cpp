@@ -70,6 +70,8 @@ struct Options {
     uint64_t partial_min_span = 0, partial_max = 0;   // 0: the library's defaults
     bool partial_extend = false, sa_tag = false;
     uint64_t partial_extend_weight = 0, partial_extend_xdrop = 0, partial_extend_max_errors = 0;   // 0: the library's defaults
+    bool split_tails = false;
+    uint64_t split_tails_weight = 0, split_tails_xdrop = 0, split_tails_min_rows = 0;               // 0: the library's defaults
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -99,6 +101,11 @@ const OptDef OPTS[] = {
     {0, "partial-extend-xdrop", false, "not floxer's: the extension stops once its score fell this far below its maximum (default 100); needs --partial-extend"},
     {0, "partial-extend-max-errors", false, "not floxer's: the most errors of one extension (default 1024, at most 4093); needs --partial-extend"},
     {0, "sa-tag", true, "not floxer's: SA:Z tag on the records of every read that got supplementary records; needs --partial-alignments"},
+    // nor these: reads mapped in full whose primary carries a chimeric tail are split into a clipped primary and supplementaries (flx_split_options)
+    {0, "split-tails", true, "not floxer's: split a read mapped in full whose primary ends in a chimeric tail (clipped primary + supplementaries); needs --partial-alignments and -N 1, not with -w"},
+    {0, "split-tails-weight", false, "not floxer's: rows one error costs in the tail score (default 4); needs --split-tails"},
+    {0, "split-tails-xdrop", false, "not floxer's: a tail exists once the score fell this far below its maximum (default 100); needs --split-tails"},
+    {0, "split-tails-min-rows", false, "not floxer's: the fewest query bases of a tail (default 100); needs --split-tails"},
 };
 
 struct CliError { std::string msg; };
@@ -203,6 +210,10 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "partial-extend-xdrop") { o.partial_extend_xdrop = parse_u64(n, value); range_check(n, (double)o.partial_extend_xdrop, 1, 1073741824); }
         else if (n == "partial-extend-max-errors") { o.partial_extend_max_errors = parse_u64(n, value); range_check(n, (double)o.partial_extend_max_errors, 1, 4093); }
         else if (n == "sa-tag") o.sa_tag = true;
+        else if (n == "split-tails") o.split_tails = true;
+        else if (n == "split-tails-weight") { o.split_tails_weight = parse_u64(n, value); range_check(n, (double)o.split_tails_weight, 1, 65535); }
+        else if (n == "split-tails-xdrop") { o.split_tails_xdrop = parse_u64(n, value); range_check(n, (double)o.split_tails_xdrop, 1, 1073741824); }
+        else if (n == "split-tails-min-rows") { o.split_tails_min_rows = parse_u64(n, value); range_check(n, (double)o.split_tails_min_rows, 1, 524287); }
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -231,6 +242,11 @@ Options parse_cli(int argc, char** argv) {
     if (!o.partial_extend && (o.partial_extend_weight || o.partial_extend_xdrop || o.partial_extend_max_errors))
         throw CliError{"The options --partial-extend-weight, --partial-extend-xdrop and --partial-extend-max-errors need --partial-extend."};
     if (o.sa_tag && !o.partial_alignments) throw CliError{"The option --sa-tag needs --partial-alignments."};
+    if (o.split_tails && !o.partial_alignments) throw CliError{"The option --split-tails needs --partial-alignments."};
+    if (o.split_tails && o.max_alignments != 1) throw CliError{"The option --split-tails judges the primary alignment and needs -N/--max-alignments 1."};
+    if (o.split_tails && o.without_cigar) throw CliError{"The option --split-tails needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (!o.split_tails && (o.split_tails_weight || o.split_tails_xdrop || o.split_tails_min_rows))
+        throw CliError{"The options --split-tails-weight, --split-tails-xdrop and --split-tails-min-rows need --split-tails."};
     return o;
 }
 
@@ -640,6 +656,12 @@ int main(int argc, char** argv) {
     extend_opt.max_errors = (uint32_t)o.partial_extend_max_errors;
     run_opt.partial = &partial_opt;
     run_opt.extend = &extend_opt;
+    flx_split_options split_opt;
+    memset(&split_opt, 0, sizeof(split_opt));
+    split_opt.enable = o.split_tails;
+    split_opt.error_weight = (uint32_t)o.split_tails_weight;
+    split_opt.x_drop = (uint32_t)o.split_tails_xdrop;
+    split_opt.min_tail_rows = (uint32_t)o.split_tails_min_rows;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -670,7 +692,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads_opt(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &run);
+        f.rc = flx_align_reads_split(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));

@@ -12,6 +12,7 @@
 
 #include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
+#include "flx_tails.hpp"
 
 namespace flx {
 
@@ -239,17 +240,22 @@ struct TracePlan {
 // K5 over the paths of one arena chunk, and their MD strings (flx_md.hip) when wanted: one MD job per trace job. The MD jobs go up with
 // the trace jobs, md_build is queued directly behind K5 (it reads K5's DevTraceOut and CIGAR words on the device: no host synchronisation
 // in between), and the bytes come back with the CIGAR words. A job's CIGAR slab holds 2 NM + 2 words and its MD slab md_slab_bytes(NM)
-// bytes, NM being what K4 returned for it; the slabs are kept as they are (gaps included): no host repacking.
+// bytes, NM being what K4 returned for it; the slabs are kept as they are (gaps included): no host repacking. The paths' tails
+// (flx_tails.hip) when wanted: one tail job per trace job as well, cigar_tails queued behind K5 (behind md_build if both are on), its
+// 32-byte results back with the CIGAR words.
 struct Traceback {
     bool const want_md;
+    const TailParams* const want_tails;
     PhaseTimer* const prof;
     hvec<DevTraceJob> jobs;
     hvec<DevTraceOut> outs;
     hvec<DevMdJob> md_jobs;
     hvec<DevMdOut> md_outs;
+    hvec<DevTailJob> tail_jobs;
+    hvec<DevTailOut> tail_outs;
     u64 cigar_words = 0, path_steps = 0, md_bytes = 0;
     size_t cigar_base = 0, md_base = 0;                        // where this batch's slabs start in the host pools
-    explicit Traceback(bool md, PhaseTimer* prof_ = nullptr) : want_md(md), prof(prof_) {}
+    explicit Traceback(bool md, const TailParams* tails, PhaseTimer* prof_ = nullptr) : want_md(md), want_tails(tails), prof(prof_) {}
     // the path that ends at end_col of the last row of r's DP, whose trace planes lie at trace_off; returns the trace job's index
     u32 add(AlignRequest const& r, u64 trace_off, AlignShape sh, u32 end_col, u32 nm) {
         u32 const j = (u32)jobs.size(), cap = 2 * nm + 2;      // runs <= 2*NM + 1
@@ -259,6 +265,7 @@ struct Traceback {
             md_jobs.push_back(DevMdJob{r.ref_off, cigar_words, md_bytes, r.n, (u32)slab, j, 0});
             md_bytes += slab;
         }
+        if (want_tails) tail_jobs.push_back(DevTailJob{cigar_words, j, want_tails->w, want_tails->x_drop, want_tails->min_rows});
         cigar_words += cap;
         path_steps += (u64)r.m + nm;
         return j;
@@ -275,6 +282,10 @@ struct Traceback {
             if ((rc = lane->md_out.ensure(md_jobs.size() * sizeof(DevMdOut)))) return rc;
             if ((rc = lane->md.ensure(md_bytes + 16))) return rc;
         }
+        if (want_tails) {
+            if ((rc = h2d(lane, lane->tail_jobs, tail_jobs.data(), tail_jobs.size() * sizeof(DevTailJob)))) return rc;
+            if ((rc = lane->tail_out.ensure(tail_jobs.size() * sizeof(DevTailOut)))) return rc;
+        }
         rc = timed_launch(lane, "ed_traceback", path_steps * 18, path_steps, [&] {
             return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), lane->tjobs.as<DevTraceJob>(), (u32)jobs.size(),
                                         lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>());
@@ -285,6 +296,14 @@ struct Traceback {
             rc = timed_launch(lane, "md_build", 0, md_jobs.size(), [&] {
                 return DeviceApi::md_build(lane->stream, d_text, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->md_jobs.as<DevMdJob>(), (u32)md_jobs.size(),
                                            lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
+            });
+            if (rc) return rc;
+        }
+        if (want_tails) {
+            // (the CIGAR words it reads are known once K5's lengths are back: they are added below)
+            rc = timed_launch(lane, "cigar_tails", tail_jobs.size() * (sizeof(DevTailJob) + sizeof(DevTraceOut) + sizeof(DevTailOut)), tail_jobs.size(), [&] {
+                return DeviceApi::cigar_tails(lane->stream, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->tail_jobs.as<DevTailJob>(), (u32)tail_jobs.size(),
+                                              lane->tail_out.as<DevTailOut>());
             });
             if (rc) return rc;
         }
@@ -301,6 +320,10 @@ struct Traceback {
             if ((rc = d2h(lane, md_outs.data(), lane->md_out.ptr, md_outs.size() * sizeof(DevMdOut)))) return rc;
             if ((rc = d2h(lane, md_pool->data() + md_base, lane->md.ptr, md_bytes))) return rc;
         }
+        if (want_tails) {
+            tail_outs.resize(tail_jobs.size());
+            if ((rc = d2h(lane, tail_outs.data(), lane->tail_out.ptr, tail_outs.size() * sizeof(DevTailOut)))) return rc;
+        }
         if ((rc = lane->sync())) return rc;
         if (prof) prof->mark("K5+d2h");
         for (auto const& t : outs)
@@ -314,6 +337,11 @@ struct Traceback {
             }
             lane->ctx->account_more("md_build", bytes, 0);
         }
+        if (want_tails) {
+            u64 bytes = 0;
+            for (auto const& t : outs) bytes += 4ull * t.cigar_len;
+            lane->ctx->account_more("cigar_tails", bytes, 0);
+        }
         return FLX_OK;
     }
     // trace job j as the result of a request whose K4 score was nm (begin: relative to the job's window)
@@ -325,13 +353,14 @@ struct Traceback {
         res.cigar_off = cigar_base + jobs[j].cigar_off + outs[j].cigar_start;
         res.cigar_len = outs[j].cigar_len;
         if (want_md) { res.md_off = md_base + md_jobs[j].md_off; res.md_len = md_outs[j].len; }
+        if (want_tails) res.tail = tail_outs[j];
         return res;
     }
 };
 
 // score, begin position and CIGAR (and MD string, when md_pool is given) for every (distinct) request
 int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
+                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer tprof("trace-jobs");
@@ -359,7 +388,7 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         tprof.mark("K4");
 
         // ---- traceback for the jobs that have an alignment within k
-        Traceback tb(md_pool != nullptr, &tprof);
+        Traceback tb(md_pool != nullptr, tails, &tprof);
         hvec<u32> tjob_req;
         for (size_t c = 0; c < count; ++c) {
             if (outs[c].score == 0xFFFFFFFFu) continue;
@@ -383,9 +412,9 @@ int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequ
 
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
 int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);
+        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails);
     });
 }
 
@@ -522,7 +551,7 @@ namespace {
 
 // the union form over distinct requests (n_requests: with their duplicates, for the debug line)
 int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& uniq, size_t n_requests,
-                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
+                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
     bool usable = !uniq.empty() && !getenv("FLX_NO_UNION");
     for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
     // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
@@ -555,7 +584,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
             members.push_back(id);
         }
     }
-    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool);      // nothing to share: the plain path
+    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails);      // nothing to share: the plain path
 
     ures.assign(uniq.size(), TraceResult{});
     hvec<AlignRequest> ureqs(unions.size());
@@ -610,7 +639,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         if ((rc = ctx->sync())) return rc;
 
         // ---- one traceback per distinct (union, end column); the members of a union share its trace job's CIGAR words and MD string
-        Traceback tb(md_pool != nullptr);
+        Traceback tb(md_pool != nullptr, tails);
         hvec<u32> win_tjob(wins.size(), 0xFFFFFFFFu);
         for (size_t w0 = 0; w0 < wins.size();) {                     // windows of one union are consecutive
             size_t w1 = w0;
@@ -640,7 +669,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
     }
     if (!fallback.empty()) {
         hvec<TraceResult> fres;
-        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool))) return rc;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
     if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", n_requests, uniq.size(), unions.size(), fallback.size());
@@ -650,9 +679,9 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
 }  // namespace
 
 int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool) {
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool);
+        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails);
     });
 }
 
@@ -679,6 +708,26 @@ int run_extend_jobs(Lane* lane, const u8* d_text, const u8* d_query, hvec<DevExt
     for (auto const& o : outs) { cells += ((u64)o.last_d + 1) * ((u64)o.last_d + 1); symbols += (u64)o.rows + o.cols; }
     lane->ctx->account_more("ed_extend", symbols, cells);
     return FLX_OK;
+}
+
+// One cigar_tails launch over CIGAR words and DevTraceOuts made on the host: the kernel alone (the pipeline queues it behind K5).
+int run_tail_jobs(Lane* lane, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevTailJob> const& jobs, hvec<DevTailOut>& outs) {
+    outs.assign(jobs.size(), DevTailOut{});
+    if (jobs.empty()) return FLX_OK;
+    int rc;
+    if ((rc = h2d(lane, lane->cigar, words, n_words * 4))) return rc;
+    if ((rc = h2d(lane, lane->tjob_out, touts.data(), touts.size() * sizeof(DevTraceOut)))) return rc;
+    if ((rc = h2d(lane, lane->tail_jobs, jobs.data(), jobs.size() * sizeof(DevTailJob)))) return rc;
+    if ((rc = lane->tail_out.ensure(jobs.size() * sizeof(DevTailOut)))) return rc;
+    u64 bytes = jobs.size() * (sizeof(DevTailJob) + sizeof(DevTraceOut) + sizeof(DevTailOut));
+    for (auto const& t : touts) bytes += 4ull * t.cigar_len;
+    rc = timed_launch(lane, "cigar_tails", bytes, jobs.size(), [&] {
+        return DeviceApi::cigar_tails(lane->stream, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->tail_jobs.as<DevTailJob>(), (u32)jobs.size(),
+                                      lane->tail_out.as<DevTailOut>());
+    });
+    if (rc) return rc;
+    if ((rc = d2h(lane, outs.data(), lane->tail_out.ptr, outs.size() * sizeof(DevTailOut)))) return rc;
+    return lane->sync();
 }
 
 int build_peq(Lane* ctx, const u8* d_seq, u64 len, DeviceBuffer& peq) {
@@ -841,5 +890,25 @@ extern "C" int flx_extend_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t 
     hvec<DevExtendOut> outs;
     if ((rc = run_extend_jobs(L, d_text, L->seq.as<u8>(), dj, outs))) return rc;
     for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_extend_result{outs[i].rows, outs[i].cols, outs[i].errors, outs[i].reason};
+    return FLX_OK;
+}
+
+// ================================================================================================ C ABI: the tail kernel alone
+extern "C" int flx_cigar_tails_batch(flx_ctx* ctx, const uint32_t* cigar_words, uint64_t n_words, const flx_tail_job* jobs, uint64_t n_jobs, flx_tail_result* out) {
+    if (!ctx || (n_jobs && (!jobs || !out)) || (n_words && !cigar_words)) { set_error("flx_cigar_tails_batch: null argument"); return FLX_ERR_INVALID; }
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    if (!tail_jobs_valid(cigar_words, n_words, jobs, n_jobs, "flx_cigar_tails_batch")) return FLX_ERR_INVALID;      // (before any launch)
+    hvec<DevTraceOut> touts(n_jobs);
+    hvec<DevTailJob> dj(n_jobs);
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_tail_job const& j = jobs[i];
+        touts[i] = DevTraceOut{0, 0, j.cigar_length, 0};
+        dj[i] = DevTailJob{j.cigar_offset, (u32)i, split_weight(j.error_weight), split_x_drop(j.x_drop), split_min_tail_rows(j.min_tail_rows)};
+    }
+    FLX_HIP(hipSetDevice(ctx->device));
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    hvec<DevTailOut> outs;
+    if (int const rc = run_tail_jobs(lease.lane, cigar_words, n_words, touts, dj, outs)) return rc;
+    for (uint64_t i = 0; i < n_jobs; ++i) memcpy(&out[i], &outs[i], sizeof(flx_tail_result));
     return FLX_OK;
 }

@@ -9,6 +9,7 @@
 #include "flx_mapq.hpp"
 #include "flx_partial.hpp"
 #include "flx_select.hpp"
+#include "flx_tails.hpp"
 
 namespace flx {
 const char* last_error_cstr();
@@ -224,6 +225,19 @@ int flx_partial_mapq(const flx_partial_candidate* candidates, uint64_t n, const 
         while (hi < n && candidates[hi].read_index == candidates[lo].read_index) ++hi;
         partial_mapq(candidates + lo, hi - lo, cigar_words, keep_flag + lo, mapq + lo, scratch);
         lo = hi;
+    }
+    return FLX_OK;
+}
+
+int flx_cigar_tails(const uint32_t* cigar_words, uint64_t n_words, const flx_tail_job* jobs, uint64_t n_jobs, flx_tail_result* out) {
+    if ((n_jobs && (!jobs || !out)) || (n_words && !cigar_words)) { set_error("flx_cigar_tails: null argument"); return FLX_ERR_INVALID; }
+    if (!tail_jobs_valid(cigar_words, n_words, jobs, n_jobs, "flx_cigar_tails")) return FLX_ERR_INVALID;
+    for (u64 i = 0; i < n_jobs; ++i) {
+        flx_tail_job const& j = jobs[i];
+        if (!cigar_tails(cigar_words + j.cigar_offset, j.cigar_length, split_weight(j.error_weight), split_x_drop(j.x_drop), split_min_tail_rows(j.min_tail_rows), &out[i])) {
+            set_error("flx_cigar_tails: invalid CIGAR");      // (tail_jobs_valid has judged the same words)
+            return FLX_ERR_INVALID;
+        }
     }
     return FLX_OK;
 }

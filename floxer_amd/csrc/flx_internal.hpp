@@ -175,6 +175,16 @@ struct DevMdOut { u32 len; u32 pad; };             // len 0xFFFFFFFF: the slab w
 // of a run of '=' columns, which is at most the number of query rows: <= 102 400 (align_supported_max_query), six digits. 8 nm + 6 in all.
 constexpr u64 md_slab_bytes(u64 nm) { return 8 * nm + 6; }
 
+// ---- chimeric tails of traced paths (flx_tails.hip; the rule: flx_tails.hpp), one job per trace job: the kernel reads that job's
+// DevTraceOut and CIGAR words where K5 left them on the device
+struct DevTailJob {
+    u64 cigar_off;                                 // the trace job's CIGAR slab (words)
+    u32 out_index;                                 // the trace job's DevTraceOut and this job's DevTailOut
+    u32 w, x_drop, min_rows;
+};
+struct DevTailOut { u32 left_rows, left_cols, left_errors, left_words, right_rows, right_cols, right_errors, right_words; };   // = flx_tail_result
+static_assert(sizeof(DevTailOut) == 32 && sizeof(DevTailOut) == sizeof(flx_tail_result), "one 32-byte result per job");
+
 // ---- extension of a partial record's end (flx_extend.hip): one job per end, one wave per job
 struct DevExtendJob {
     u64 text_pos, q_pos;        // the first column's symbol in the device text, the first row's symbol in the device query pool
@@ -345,6 +355,8 @@ struct DeviceApi {
     // flx_md.hip: the MD string of every job from the CIGAR words and DevTraceOut that `traceback` left at d_cigar / d_trace_out
     static int md_build(void* stream, const u8* d_text, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevMdJob* d_jobs, u32 n_jobs,
                         u8* d_md, DevMdOut* d_out);
+    // flx_tails.hip: the tails of every job's path (flx_tails.hpp) from the CIGAR words and DevTraceOut that `traceback` left
+    static int cigar_tails(void* stream, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevTailJob* d_jobs, u32 n_jobs, DevTailOut* d_out);
     // flx_extend.hip: lds_d = the largest min(d_max, row_limit) of the jobs (the launch's LDS: extend_lds_bytes(lds_d) <= 64 KiB)
     static size_t extend_lds_bytes(u32 d_max);
     static int extend(void* stream, const u8* d_text, const u8* d_query, const DevExtendJob* d_jobs, u32 n_jobs, u32 lds_d, DevExtendOut* d_out);

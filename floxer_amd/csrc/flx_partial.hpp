@@ -48,8 +48,9 @@
 //        words; the mapping quality keeps the value computed before the extension; flags, the order of a read's records and the
 //        counters do not change.
 //
-// Limits: without the extension a record ends at a PEX node's boundary, not at the break; a read mapped in full that also carries a
-// chimeric tail is not touched. The SA tag that ties a read's records together is the writer's (flx_sam_set_sa).
+// Limits: without the extension a record ends at a PEX node's boundary, not at the break. A read mapped in full that also carries a
+// chimeric tail is the business of flx_split_options (flx_tails.hpp, the stage split_tails): its records come through choose_partials,
+// extend_partials and the writer like the ones made here. The SA tag that ties a read's records together is the writer's (flx_sam_set_sa).
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -109,7 +109,9 @@ constexpr int SEARCH_NEEDS_HOST_SEEDS = 1;
 
 // ---- flx_align_jobs.cpp
 struct AlignRequest { u64 ref_off, q_off; u32 n, m, k; };
-struct TraceResult { bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; };
+struct TraceResult { bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; };
+// the values of the tail rule (flx_tails.hpp) for the traces that want it, defaults resolved
+struct TailParams { u32 w, x_drop, min_rows; };
 // host milliseconds of the host-rounds form, summed over a chunk's rounds (FLX_HOST_PROFILE); owned by the chunk
 struct ExistsTimes { double ms[4] = {0, 0, 0, 0}; double build_requests = 0; };      // ms: dedup, cluster, GPU round trip, scatter
 
@@ -118,12 +120,15 @@ u64 align_few_waves();          // FLX_ALIGN_FEW_WAVES overrides the threshold (
 // score + end column for every request (no trace)
 int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, const char* kernel_name);
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates).
-// md_pool != null: the MD string of every traced path as well (flx_md.hip), its bytes in md_pool (shared like the CIGAR words)
+// md_pool != null: the MD string of every traced path as well (flx_md.hip), its bytes in md_pool (shared like the CIGAR words);
+// tails != null: the tails of every traced path as well (flx_tails.hip), in TraceResult::tail
 int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr);
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
 int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr);
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr);
+// one cigar_tails launch over words and DevTraceOuts made on the host (flx_cigar_tails_batch)
+int run_tail_jobs(Lane* lane, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevTailJob> const& jobs, hvec<DevTailOut>& outs);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
 int run_exists_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, ExistsTimes& times);
 // extension jobs of partial records' ends (ed_extend, flx_extend.hip): one launch, outs[i] for jobs[i] (out_index is set here)
@@ -155,13 +160,15 @@ struct AnchorState {
 };
 
 struct Span { u64 offset, length, extra; };
-struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; };
+struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; };
 
-// a record rescue_partials leaves for write_records (flx_partial.hpp): a soft-clipped part of a read without a mapped record
+// a record rescue_partials (flx_partial.hpp: a soft-clipped part of a read without a mapped record) or split_tails (flx_tails.hpp: the
+// kept part and the tails of a read mapped in full) leaves for write_records
 struct PartialRecord {
     u32 read; u32 flag; u32 ref_id; u64 start; u32 nm; u64 cigar_off; u32 cigar_len; u64 md_off; u32 md_len; u32 q_from, q_to; u32 mapq;
     u32 o_from, o_to;           // the traced rows in the oriented sequence (the node, before extend_partials moves them)
     u64 core_off; u32 core_len; // the traced words without the clips
+    bool split = false;         // a record of a split read: written instead of the read's root records
 };
 
 struct Slice {
@@ -191,7 +198,8 @@ struct Slice {
     hvec<u32> cig;                                                            // CIGAR pool of root_res
     bool want_md = false;                                                     // flx_tag_options.md: the traced paths' MD strings as well
     hvec<u8> md;                                                              // MD pool of root_res
-    // rescue_partials: the records of the reads it rescued, read by read in the order they are written in; {q_from, q_to} read-forward
+    // split_tails, rescue_partials: the records of the reads they split / rescued, read by read in the order they are written in;
+    // {q_from, q_to} read-forward
     hvec<PartialRecord> partials;
     // statistics in the reference's form (flx_stats.cpp), when the context has a statistics object attached, and their clock
     std::unique_ptr<Stats> st_local;
@@ -200,13 +208,14 @@ struct Slice {
 
     u32 n_sampled(ReadState const& r) const { return (u32)((r.tree_ref().leaves.size() + step - 1) / step); }      // seeds per orientation
     // traces windows of the slice's reads (root windows, partial records): CIGAR words into cig, MD strings into md when wanted
-    int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres) {
-        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr);
+    // tails: the paths' tails as well (align_roots alone asks for them)
+    int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres, const TailParams* tails = nullptr) {
+        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails);
     }
 };
 
 // the options of a run by value (flx_run_options, validated): an option that is off is a zeroed member
-struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; };
+struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; };
 
 // produces the slice's records (read_index relative to the whole batch)
 int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run);

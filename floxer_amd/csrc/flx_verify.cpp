@@ -17,6 +17,7 @@
 #include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
 #include "flx_select.hpp"
+#include "flx_tails.hpp"
 
 namespace flx {
 
@@ -529,7 +530,7 @@ void interval_pass(Slice& S, const flx_params* P, HostIndex const& H) {
 }
 
 // ---- 7. root alignments (alignment.cpp:115-180)
-int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) {
+int align_roots(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD) {
     flx_ctx* ctx = lane->ctx;
     HostIndex const& H = *ctx->hidx;
     hvec<u8> const& pool = RD->pool;
@@ -567,10 +568,12 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, const flx_reads* RD) 
             if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
     } else {
         hvec<TraceResult> tres;
-        if ((rc = S.trace_windows(lane, RD, root_reqs, tres))) return rc;
+        // (flx_split_options: the tails of every root path come back with its CIGAR words; no other trace of the slice asks for them)
+        TailParams const tails{split_weight(R.split.error_weight), split_x_drop(R.split.x_drop), split_min_tail_rows(R.split.min_tail_rows)};
+        if ((rc = S.trace_windows(lane, RD, root_reqs, tres, R.split.enable ? &tails : nullptr))) return rc;
         for (size_t i = 0; i < tres.size(); ++i)
             if (tres[i].exists)
-                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len};
+                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len, tres[i].tail};
     }
     return FLX_OK;
 }
@@ -585,6 +588,136 @@ std::pair<u64, u32> append_clipped(hvec<u32>& cig, u32 left, u64 core_off, u32 c
     std::copy(cig.begin() + (long)core_off, cig.begin() + (long)(core_off + core_len), cig.begin() + (long)at);
     clip(right);
     return {off, (u32)(cig.size() - off)};
+}
+
+// ---- 7b. reads mapped in full whose primary carries a chimeric tail (flx_split_options; the rule: flx_tails.hpp, its numbers came back
+//      with the root CIGARs): the primary is traced again over the kept part, and the nodes that the read's anchors passed inside a
+//      tail are traced as rescue_partials traces them; one trace over both for the whole slice. Does nothing, and launches nothing,
+//      when the option is off or no primary has a tail
+int split_tails(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD) {
+    if (!R.split.enable) return FLX_OK;
+    HostIndex const& H = *lane->ctx->hidx;
+    hvec<ReadState> const& reads = S.reads;
+    hvec<AnchorState> const& A = S.A;
+    hvec<RootAlignment> const& root_res = S.root_res;
+    hvec<hvec<u32>> roots_of_read(reads.size());
+    for (u32 i = 0; i < S.root_anchor.size(); ++i) roots_of_read[A[S.root_anchor[i]].read].push_back(i);
+    u32 const min_span = partial_min_span(&R.partial), max_records = partial_max_records(&R.partial);
+    struct Split { u32 read, root, req; u32 cand_first, cand_end; };
+    struct Candidate { u8 orientation; u32 ref_id; flx_pex_node node; Span span; };
+    hvec<Split> splits;
+    hvec<Candidate> cands;
+    hvec<AlignRequest> reqs;
+    hvec<u32> cand_req;
+    std::map<std::tuple<u64, u32, u32, u64, u32>, u32> seen;
+    for (size_t r = 0; r < reads.size(); ++r) {
+        // the primary, as write_records finds it: the first record with the best NM, references in id order
+        bool have = false;
+        u32 best = 0, prim = 0;
+        for (u32 i : roots_of_read[r]) if (root_res[i].exists && (!have || root_res[i].nm < best)) { best = root_res[i].nm; have = true; }
+        if (!have) continue;
+        have = false;
+        for (u32 ref = 0; ref < H.seq_len.size() && !have; ++ref)
+            for (u32 i : roots_of_read[r])
+                if (A[S.root_anchor[i]].ref_id == ref && root_res[i].exists && root_res[i].nm == best) { prim = i; have = true; break; }
+        RootAlignment const& pr = root_res[prim];
+        DevTailOut const& t = pr.tail;
+        if (!t.left_rows && !t.right_rows) continue;
+        ReadState const& rs = reads[r];
+        AnchorState const& pa = A[S.root_anchor[prim]];
+        u32 const len = rs.len;
+        u64 const span = cigar_reference_span(S.cig.data() + pr.cigar_off, pr.cigar_len);
+        if ((u64)t.left_rows + t.right_rows >= len) continue;             // (error rates beyond 1 / w: the score never rises, nothing would be kept)
+        if ((u64)t.left_cols + t.right_cols > span || (u64)t.left_errors + t.right_errors > pr.nm) {
+            set_error("split tails: a tail larger than its alignment"); return FLX_ERR_INTERNAL;
+        }
+        Split sp{(u32)r, prim, (u32)reqs.size(), (u32)cands.size(), 0};
+        reqs.push_back(AlignRequest{H.seq_start[pa.ref_id] + pr.start + t.left_cols, rs.pool_off[pa.orientation] + t.left_rows,
+                                    (u32)(span - t.left_cols - t.right_cols), len - t.left_rows - t.right_rows, pr.nm - t.left_errors - t.right_errors});
+        // the tails' read-forward intervals, half-open: [0] the oriented left tail, [1] the right one
+        u32 tail_lo[2] = {0, len - t.right_rows}, tail_hi[2] = {t.left_rows, len};
+        if (pa.orientation) { tail_lo[0] = len - t.left_rows; tail_hi[0] = len; tail_lo[1] = 0; tail_hi[1] = t.right_rows; }
+        PexTree const& tree = rs.tree_ref();
+        seen.clear();
+        for (u32 ai : S.exec_order[r]) {
+            AnchorState const& a = A[ai];
+            flx_pex_node const* node = &tree.leaves[a.leaf];
+            if (node->parent_id == FLX_NULL_ID) continue;                                        // a tree of one node: the leaf is the root
+            auto inside = [&](flx_pex_node const& nd) {
+                u32 const f = a.orientation ? len - 1 - nd.to : nd.from, e = (a.orientation ? len - 1 - nd.from : nd.to) + 1;
+                return (tail_lo[0] < tail_hi[0] && f >= tail_lo[0] && e <= tail_hi[0]) || (tail_lo[1] < tail_hi[1] && f >= tail_lo[1] && e <= tail_hi[1]);
+            };
+            if (!inside(*node)) continue;
+            if (!P->direct_full_verification) {
+                if (a.alive && !a.at_root) { set_error("split tails: an anchor neither failed nor reached the root"); return FLX_ERR_INTERNAL; }
+                // upwards over the nodes it passed (those below a.node: the node it failed at, or the root) while they stay inside the tail
+                u32 guard = 0;
+                for (u32 up = node->parent_id; up != a.node; up = node->parent_id) {
+                    if (up == FLX_NULL_ID || ++guard > tree.inner.size()) { set_error("split tails: an anchor's node is not on its path"); return FLX_ERR_INTERNAL; }
+                    if (!inside(tree.inner[up])) break;
+                    node = &tree.inner[up];
+                }
+            }
+            if (node->to - node->from + 1 < min_span) continue;
+            Span wsp;
+            AlignRequest const req = window_request(S, H, a, *node, 0.0, &wsp);
+            if (!seen.emplace(std::make_tuple(req.q_off, req.m, req.k, req.ref_off, req.n), 0u).second) continue;
+            cands.push_back(Candidate{a.orientation, a.ref_id, *node, wsp});
+            cand_req.push_back((u32)reqs.size());
+            reqs.push_back(req);
+        }
+        sp.cand_end = (u32)cands.size();
+        splits.push_back(sp);
+    }
+    if (splits.empty()) return FLX_OK;
+    hvec<TraceResult> tres;
+    if (int const rc = S.trace_windows(lane, RD, reqs, tres)) return rc;
+    std::vector<flx_partial_candidate> pc;
+    std::vector<int32_t> flags;
+    std::vector<u8> quality;
+    PartialScratch scratch;
+    for (Split const& sp : splits) {
+        ReadState const& rs = reads[sp.read];
+        RootAlignment const& pr = root_res[sp.root];
+        AnchorState const& pa = A[S.root_anchor[sp.root]];
+        DevTailOut const& t = pr.tail;
+        u32 const len = rs.len, o_from = t.left_rows, o_to = len - 1 - t.right_rows;
+        TraceResult const& kt = tres[sp.req];
+        if (!kt.exists) { set_error("split tails: no alignment over the kept part of a path"); return FLX_ERR_INTERNAL; }
+        auto const clipped = append_clipped(S.cig, o_from, kt.cigar_off, kt.cigar_len, len - 1 - o_to);
+        u32 const q_from = pa.orientation ? len - 1 - o_to : o_from, q_to = pa.orientation ? len - 1 - o_from : o_to;
+        PartialRecord kept{sp.read, pa.orientation ? 16u : 0u, pa.ref_id, pr.start + t.left_cols + kt.begin, kt.nm, clipped.first, clipped.second, kt.md_off, kt.md_len,
+                           q_from, q_to, 0, o_from, o_to, kt.cigar_off, kt.cigar_len};
+        kept.split = true;
+        S.partials.push_back(kept);
+        // the supplementaries: choose_partials over the tail candidates
+        pc.clear();
+        for (u32 c = sp.cand_first; c < sp.cand_end; ++c) {
+            TraceResult const& ct = tres[cand_req[c]];
+            if (!ct.exists) { set_error("split tails: no alignment in a window that verification passed"); return FLX_ERR_INTERNAL; }
+            flx_pex_node const& nd = cands[c].node;
+            u32 const f = cands[c].orientation ? len - 1 - nd.to : nd.from, e = cands[c].orientation ? len - 1 - nd.from : nd.to;
+            pc.push_back(flx_partial_candidate{rs.read_index, f, e, cands[c].orientation, (int32_t)cands[c].ref_id, cands[c].span.offset + ct.begin, ct.nm, ct.cigar_len, ct.cigar_off});
+        }
+        if (pc.empty() || max_records < 2) continue;
+        flags.resize(pc.size());
+        choose_partials(pc.data(), pc.size(), max_records - 1, S.cig.data(), flags.data(), scratch);
+        quality.assign(pc.size(), 0);
+        if (R.output.mapq) partial_mapq(pc.data(), pc.size(), S.cig.data(), flags.data(), quality.data(), scratch);
+        std::vector<uint32_t> order(scratch.kept);
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return pc[x].q_from < pc[y].q_from; });
+        for (u32 j : order) {
+            u32 const c = sp.cand_first + j;
+            flx_pex_node const& nd = cands[c].node;
+            TraceResult const& ct = tres[cand_req[c]];
+            auto const cl = append_clipped(S.cig, nd.from, ct.cigar_off, ct.cigar_len, len - 1 - nd.to);
+            PartialRecord sup{sp.read, 2048u | (cands[c].orientation ? 16u : 0u), cands[c].ref_id, pc[j].start, ct.nm, cl.first, cl.second, ct.md_off, ct.md_len,
+                              pc[j].q_from, pc[j].q_to, quality[j], nd.from, nd.to, ct.cigar_off, ct.cigar_len};
+            sup.split = true;
+            S.partials.push_back(sup);
+        }
+    }
+    return FLX_OK;
 }
 
 // ---- 8. partial alignments of the reads that would be written as unmapped (flx_partial.hpp): every anchor's highest passed node,
@@ -663,6 +796,8 @@ int rescue_partials(Slice& S, Lane* lane, const flx_params* P, RunOptions const&
                                                tres[c].md_len, pc[j].q_from, pc[j].q_to, quality[j], nd.from, nd.to, tres[c].cigar_off, tres[c].cigar_len});
         }
     }
+    // (split_tails has left its records in front of these: read by read again, a read's records in the order they were made in)
+    if (R.split.enable) std::stable_sort(S.partials.begin(), S.partials.end(), [](PartialRecord const& x, PartialRecord const& y) { return x.read < y.read; });
     return FLX_OK;
 }
 
@@ -806,7 +941,7 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
     bool const md = S.want_md;
     run->has_md = md;
     size_t next_partial = 0;
-    u64 n_partial_records = 0, n_rescued = 0;
+    u64 n_partial_records = 0, n_rescued = 0, n_split = 0;
     for (size_t r = 0; r < reads.size(); ++r) {
         size_t const rec0 = run->records.size();
         bool have_best = false;
@@ -832,14 +967,29 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
                 }
             }
         bool const rescued = next_partial < S.partials.size() && S.partials[next_partial].read == r;
-        if (rescued) {                                           // (only a read without a mapped record has partial records)
+        bool const split = rescued && S.partials[next_partial].split;
+        u32 split_mapq = 0;
+        if (split) {
+            // a split read's partial records are written instead of its root records; with -Q its primary keeps their value
+            if (mapq && !mq_keys.empty()) {
+                mq_q.resize(mq_keys.size());
+                read_mapq(mq_keys.data(), mq_keys.size(), mq_q.data(), mq_scratch);
+                for (size_t j = 0; j < mq_keys.size(); ++j) if (!(mq_keys[j].flag & 256u)) split_mapq = mq_q[j];
+                mq_keys.clear();
+            }
+            n_dropped += run->records.size() - rec0;
+            run->records.resize(rec0);
+            if (md) run->md_refs.resize(rec0);
+        }
+        if (rescued) {                                           // (a read without a mapped record, or a split one)
             for (; next_partial < S.partials.size() && S.partials[next_partial].read == r; ++next_partial) {
                 PartialRecord const& p = S.partials[next_partial];
-                run->records.push_back(flx_record{reads[r].read_index, p.flag, (int32_t)p.ref_id, saturate_i32(p.start), p.nm, p.cigar_off, p.cigar_len, p.mapq});
+                run->records.push_back(flx_record{reads[r].read_index, p.flag, (int32_t)p.ref_id, saturate_i32(p.start), p.nm, p.cigar_off, p.cigar_len,
+                                                  split && !(p.flag & 2048u) ? split_mapq : p.mapq});
                 if (md) run->md_refs.push_back(flx_md_ref{p.md_off, p.md_len, 0});
                 ++n_partial_records;
             }
-            ++n_rescued;
+            if (split) ++n_split; else ++n_rescued;
         } else if (!primary_written) {
             run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
             if (md) run->md_refs.push_back(flx_md_ref{0, 0, 0});
@@ -894,7 +1044,7 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
         flx_path_counters& pc = ctx->path;
         pc.inner_tests_requested += S.n_inner_requested; pc.root_alignments_requested += S.root_reqs.size(); pc.root_alignments_found += found;
         pc.records += run->records.size(); pc.reads += n_slice_reads; pc.reserved[0] += n_dropped;
-        pc.reserved[1] += n_partial_records; pc.reserved[2] += n_rescued;
+        pc.reserved[1] += n_partial_records; pc.reserved[2] += n_rescued; pc.reserved[3] += n_split;
     }
 }
 
@@ -929,8 +1079,10 @@ int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_
                 times.ms[0], times.ms[1], times.ms[2], times.ms[3], times.build_requests);
     interval_pass(S, P, H);
     prof.mark("interval-pass");
-    if ((rc = align_roots(S, lane, P, RD))) return rc;
+    if ((rc = align_roots(S, lane, P, R, RD))) return rc;
     prof.mark("root-align");
+    if ((rc = split_tails(S, lane, P, R, RD))) return rc;
+    if (R.split.enable) prof.mark("split-tails");
     if ((rc = rescue_partials(S, lane, P, R, RD))) return rc;
     prof.mark("partials");
     if ((rc = extend_partials(S, lane, R, RD))) return rc;

@@ -19,5 +19,15 @@ __device__ __forceinline__ u32 wave_inclusive_scan(u32 v) {
     }
     return v;
 }
+// the same over signed 64-bit values (every shuffle moves two words)
+__device__ __forceinline__ i64 wave_inclusive_scan(i64 v) {
+    u32 const lane = lane_id();
+#pragma unroll
+    for (u32 d = 1; d < 64u; d <<= 1) {
+        i64 const below = __shfl_up(v, d);
+        if (lane >= d) v += below;
+    }
+    return v;
+}
 
 }  // namespace flx

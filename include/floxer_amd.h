@@ -392,6 +392,61 @@ typedef struct flx_extend_result { uint32_t rows, cols, errors, stop_reason; } f
 int flx_extend_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
                      const flx_extend_job* jobs, uint64_t n_jobs, flx_extend_result* out);
 
+/* Chimeric tails of reads that are mapped in full: not floxer's. A read whose whole length fits its errors is written as one record
+ * even when its last few hundred bases belong elsewhere; the break then shows only as a run of X / I / D at one end of the CIGAR. Off
+ * when the struct is zeroed (or NULL), and then nothing changes: no launch, no byte of any output. With enable = 1 (anything else but
+ * 0 is refused) the rule below is applied to every root alignment's CIGAR on the device, behind the traceback (kernel cigar_tails), and
+ * a read whose primary (the first record with the best NM in output order) has a tail is split:
+ *   - the rule, on a CIGAR core of T words (ops = X I D): boundary t = 0..T lies behind word t; rows_t / cols_t count the query /
+ *     reference consumed, err_t the lengths of X, I and D, S_t = rows_t - error_weight * err_t (signed 64-bit, S_0 = 0). Right tail:
+ *     G = max S_t, t_R the smallest t with S_t = G; it exists iff G - S_T > x_drop and rows_T - rows_{t_R} >= min_tail_rows. Left
+ *     tail: g = min S_t, t_L the largest t with S_t = g; it exists iff -g > x_drop and rows_{t_L} >= min_tail_rows. Both and
+ *     t_L >= t_R: neither. Cuts fall on word boundaries. error_weight (0: 4) and x_drop (0: 100) are the extension's conventions,
+ *     min_tail_rows (0: 100) is one of this project; none is fitted to anything. Bounds: error_weight <= 65535, x_drop <= 2^30,
+ *     min_tail_rows < 2^19;
+ *   - the kept part is traced again over the oriented rows [left_rows, len - 1 - right_rows] in exactly the reference window
+ *     [start + left_cols, start + span - right_cols) with nm - left_errors - right_errors allowed errors; it is the primary (flag
+ *     0 / 16) with the tails soft-clipped; position, NM, CIGAR and MD come from that trace;
+ *   - tail candidates: for every anchor of the read in verification order the highest node on its leaf-to-root path that it passed
+ *     (flx_partial_options; every node below the root for an anchor whose root alignment exists) and whose read-forward interval lies
+ *     inside one tail's, with at least partial.min_query_span rows, traced in the window it was tested in. flx_choose_partials' rule
+ *     over them with max_records - 1 keeps the supplementaries (flag 2048 | strand), written behind the primary by forward query
+ *     start. A split read without candidate is its clipped primary alone;
+ *   - flx_extend_options then carries every end of these records to the break under its own limits, the primary's cut ends included;
+ *   - the read's root records are not written (they count in flx_path_counters.reserved[0]); with flx_output_options.mapq the
+ *     primary keeps the value of the read's root records and the supplementaries get flx_partial_mapq's over the tail candidates.
+ * It needs flx_partial_options.enable and flx_output_options.max_alignments_per_read == 1 (a tail is judged on the primary; full-length
+ * secondaries beside a clipped primary would contradict it) and is refused with params->without_cigar: FLX_ERR_INVALID before any
+ * work. Limits: a tail that holds a second good region behind a second break is cut once; a structural indel inside a read whose
+ * score recovers afterwards is not a break. flx_path_counters.reserved[1] counts these records too, reserved[3] the reads split.
+ * The rule: floxer_amd/csrc/flx_tails.hpp. The reserved fields must be 0. */
+typedef struct flx_split_options {
+    uint32_t enable;
+    uint32_t error_weight;       /* 0: 4 */
+    uint32_t x_drop;             /* 0: 100 */
+    uint32_t min_tail_rows;      /* 0: 100 */
+    uint32_t reserved[4];
+} flx_split_options;
+/* flx_align_reads_opt / flx_align_reads_resident_opt with the split options (NULL or zeroed: exactly those calls, which forward here) */
+int flx_align_reads_split(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                          const flx_run_options* options, const flx_split_options* split, flx_run** out);
+int flx_align_reads_resident_split(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_run_options* options,
+                                   const flx_split_options* split, flx_run** out);
+/* The rule alone on any CIGAR words: job i covers words [cigar_offset, cigar_offset + cigar_length) of the pool; a zero in any of the
+ * last three fields takes the default. An absent tail reports zeros. A job outside the pool, an op other than = X I D, op lengths that
+ * sum to 2^32 or more, or a value beyond its bound is refused (FLX_ERR_INVALID; flx_cigar_tails_batch: before any launch).
+ * flx_cigar_tails runs on the host, flx_cigar_tails_batch runs the kernel; both give the same numbers. */
+typedef struct flx_tail_job {
+    uint64_t cigar_offset;
+    uint32_t cigar_length;
+    uint32_t error_weight;
+    uint32_t x_drop;
+    uint32_t min_tail_rows;
+} flx_tail_job;
+typedef struct flx_tail_result { uint32_t left_rows, left_cols, left_errors, left_words, right_rows, right_cols, right_errors, right_words; } flx_tail_result;
+int flx_cigar_tails(const uint32_t* cigar_words, uint64_t n_words, const flx_tail_job* jobs, uint64_t n_jobs, flx_tail_result* out);
+int flx_cigar_tails_batch(flx_ctx* ctx, const uint32_t* cigar_words, uint64_t n_words, const flx_tail_job* jobs, uint64_t n_jobs, flx_tail_result* out);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -417,7 +472,8 @@ typedef struct flx_path_counters {
     uint64_t inner_tests_requested, root_alignments_requested, root_alignments_found, records, reads;
     uint64_t search_reruns;      /* search launches repeated because a chunk's hits or queued subtrees outgrew their buffers */
     uint64_t reserved[4];        /* reserved[0]: records_dropped, the records flx_output_options left out (records counts those written);
-                                    reserved[1]: partial records written, reserved[2]: reads they rescued (flx_partial_options) */
+                                    reserved[1]: partial records written (those of split reads included), reserved[2]: reads they rescued
+                                    (flx_partial_options); reserved[3]: reads split (flx_split_options) */
 } flx_path_counters;
 int flx_ctx_get_path_counters(flx_ctx* ctx, flx_path_counters* out);
 int flx_ctx_reset_path_counters(flx_ctx* ctx);
