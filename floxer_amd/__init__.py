@@ -343,6 +343,17 @@ def align_batch(ctx, query_pool, jobs, reference_pool=None, md=False):
     return out
 
 
+def align_shapes(jobs):
+    """the launch shape align_batch would give every job of a call with these jobs (flx_align_shapes; no context, no GPU):
+    [(words_per_lane, lanes_per_job, queue)], queue = the hand-over slots the job's ring occupies, 0 for a ring that never waits."""
+    arr = (capi.AlignJob * max(1, len(jobs)))()
+    for i, (ro, rl, qo, ql, k, mode) in enumerate(jobs):
+        arr[i] = capi.AlignJob(ro, qo, rl, ql, k, mode)
+    out = (capi.AlignShape * max(1, len(jobs)))()
+    check(lib().flx_align_shapes(arr, len(jobs), out))
+    return [(s.words_per_lane, s.lanes_per_job, s.queue) for s in out[: len(jobs)]]
+
+
 def align(ctx, reference, query, num_allowed_errors, mode=MODE_WITH_CIGAR, md=False):
     """alignment::align for one (reference window, query) pair; md=True adds the MD string (see align_batch)."""
     return align_batch(ctx, query, [(0, len(reference), 0, len(query), num_allowed_errors, mode)], reference_pool=reference, md=md)[0]

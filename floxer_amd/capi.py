@@ -53,6 +53,10 @@ class AlignJob(C.Structure):
                 ("num_allowed_errors", C.c_uint32), ("mode", C.c_uint32)]
 
 
+class AlignShape(C.Structure):
+    _fields_ = [("words_per_lane", C.c_uint32), ("lanes_per_job", C.c_uint32), ("queue", C.c_uint32)]
+
+
 class AlignResult(C.Structure):
     _fields_ = [("exists", C.c_uint32), ("num_errors", C.c_uint32), ("begin", C.c_uint64), ("cigar_offset", C.c_uint64),
                 ("cigar_length", C.c_uint32), ("reserved", C.c_uint32)]
@@ -156,6 +160,7 @@ EXPORTED = [
     "flx_align_reads_with_tags", "flx_align_reads_resident_with_tags", "flx_run_num_md_bytes", "flx_run_copy_md", "flx_align_batch_md",
     "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
     "flx_extend_batch", "flx_sam_set_sa", "flx_align_reads_split", "flx_align_reads_resident_split", "flx_cigar_tails", "flx_cigar_tails_batch",
+    "flx_align_shapes",
 ]
 
 _lib = None
@@ -236,6 +241,7 @@ def lib():
     L.flx_search_groups.argtypes = [C.c_void_p, u8p, C.c_uint64, C.POINTER(Seed), C.c_uint64, C.c_uint64, C.POINTER(HitGroup), u64p]
     L.flx_align_batch.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(AlignJob), C.c_uint64,
                                   C.POINTER(AlignResult), u32p, u64p]
+    L.flx_align_shapes.argtypes = [C.POINTER(AlignJob), C.c_uint64, C.POINTER(AlignShape)]
     L.flx_params_default.argtypes = [C.POINTER(Params)]
     L.flx_align_reads.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(C.c_void_p)]
     L.flx_reads_upload.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64, C.POINTER(C.c_void_p)]

@@ -761,6 +761,49 @@ int ensure_reversed_text(Lane* lane) {
 using namespace flx;
 
 // ================================================================================================ C ABI: seam 2
+// The jobs of one flx_align_batch call as the three request lists it runs, by mode (ids: the job of every request). WITHOUT_CIGAR jobs
+// run on the reversed pools: their offsets are mirrored in text_len / query_pool_len.
+struct BatchRequests { hvec<AlignRequest> reqs[3]; hvec<u32> ids[3]; };
+static void split_batch_jobs(const flx_align_job* jobs, uint64_t n_jobs, u64 text_len, u64 query_pool_len, BatchRequests& B) {
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_align_job const& j = jobs[i];
+        if (j.mode == FLX_MODE_WITHOUT_CIGAR) B.reqs[j.mode].push_back({text_len - j.ref_offset - j.ref_length, query_pool_len - j.query_offset - j.query_length, j.ref_length, j.query_length, j.num_allowed_errors});
+        else B.reqs[j.mode].push_back({j.ref_offset, j.query_offset, j.ref_length, j.query_length, j.num_allowed_errors});
+        B.ids[j.mode].push_back((u32)i);
+    }
+}
+
+// The launch shape flx_align_batch gives every job: the same three lists, their distinct requests (run_deduplicated) and choose_shapes on
+// each. queue: the hand-over slots the job's own ring occupies in that shape (0: it never waits; more than RING_QUEUE_MAX would mean a
+// shape that does not hold the job). Host arithmetic only: no context, no device.
+extern "C" int flx_align_shapes(const flx_align_job* jobs, uint64_t n_jobs, flx_align_shape* out) {
+    if (n_jobs && (!jobs || !out)) { set_error("flx_align_shapes: null argument"); return FLX_ERR_INVALID; }
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    u64 text_len = 0, query_pool_len = 0;                 // (any pool that holds every job mirrors the offsets one to one)
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_align_job const& j = jobs[i];
+        if (j.query_length == 0 || j.mode > 2) { set_error("flx_align_shapes: job without query rows, or of an unknown mode"); return FLX_ERR_INVALID; }
+        if (j.query_length > align_supported_max_query()) { set_error("query longer than the supported maximum"); return FLX_ERR_UNSUPPORTED; }
+        text_len = std::max<u64>(text_len, j.ref_offset + j.ref_length);
+        query_pool_len = std::max<u64>(query_pool_len, j.query_offset + j.query_length);
+    }
+    BatchRequests B;
+    split_batch_jobs(jobs, n_jobs, text_len, query_pool_len, B);
+    for (int mode = 0; mode < 3; ++mode) {
+        hvec<AlignRequest> uniq;
+        hvec<u32> uniq_of;
+        hvec<AlignShape> shapes;
+        dedup_requests(B.reqs[mode], uniq, uniq_of);
+        if (int const rc = choose_shapes(uniq, shapes)) return rc;
+        for (size_t i = 0; i < B.reqs[mode].size(); ++i) {
+            AlignRequest const& r = B.reqs[mode][i];
+            AlignShape const sh = shapes[uniq_of[i]];
+            out[B.ids[mode][i]] = flx_align_shape{sh.words_per_lane, sh.lanes_per_job, ring_queue_for(ring_delay(r.n, r.m, r.k, sh.words_per_lane, sh.lanes_per_job))};
+        }
+    }
+    return FLX_OK;
+}
+
 extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
                                uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                                uint32_t* cigar_pool, uint64_t* cigar_pool_words) {
@@ -815,16 +858,10 @@ extern "C" int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_
         if ((rc = h2d(L, L->seq_rev, qrev.data(), qrev.size(), 64))) return rc;
         if ((rc = build_peq(L, L->seq_rev.as<u8>(), query_pool_len, L->peq_rev))) return rc;
     }
-    hvec<AlignRequest> score_reqs, rev_reqs, trace_reqs;
-    hvec<u32> score_ids, rev_ids, trace_ids;
-    for (uint64_t i = 0; i < n_jobs; ++i) {
-        flx_align_job const& j = jobs[i];
-        if (j.mode == FLX_MODE_EXISTS) { score_reqs.push_back({j.ref_offset, j.query_offset, j.ref_length, j.query_length, j.num_allowed_errors}); score_ids.push_back((u32)i); }
-        else if (j.mode == FLX_MODE_WITHOUT_CIGAR) {
-            rev_reqs.push_back({text_len - j.ref_offset - j.ref_length, query_pool_len - j.query_offset - j.query_length, j.ref_length, j.query_length, j.num_allowed_errors});
-            rev_ids.push_back((u32)i);
-        } else { trace_reqs.push_back({j.ref_offset, j.query_offset, j.ref_length, j.query_length, j.num_allowed_errors}); trace_ids.push_back((u32)i); }
-    }
+    BatchRequests B;
+    split_batch_jobs(jobs, n_jobs, text_len, query_pool_len, B);
+    hvec<AlignRequest> const &score_reqs = B.reqs[FLX_MODE_EXISTS], &rev_reqs = B.reqs[FLX_MODE_WITHOUT_CIGAR], &trace_reqs = B.reqs[FLX_MODE_WITH_CIGAR];
+    hvec<u32> const &score_ids = B.ids[FLX_MODE_EXISTS], &rev_ids = B.ids[FLX_MODE_WITHOUT_CIGAR], &trace_ids = B.ids[FLX_MODE_WITH_CIGAR];
     for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_align_result{0, 0, 0, 0, 0, 0};
     if (out_md) for (uint64_t i = 0; i < n_jobs; ++i) out_md[i] = flx_md_ref{0, 0, 0};
     hvec<DevAlignOut> outs;

@@ -347,13 +347,6 @@ __global__ void __launch_bounds__(64, (W <= 4 ? 3 : W <= 6 ? 2 : 1)) ed_trace_bl
     ed_block_body<W, true>(text, peq, jobs, n_jobs, log2_r, out, blockIdx.x, lds_eq, trace, lastrow, queue, nullptr);
 }
 
-// hand-over slots a job with this delay needs (a power of two; 0: none)
-static u32 ring_queue_for(u32 delay) {
-    if (delay == 0) return 0;
-    u32 q = 32;
-    while (q < delay + 1u) q *= 2;
-    return q;
-}
 // the widest band (diagonals - 1 = n - m + 2k) a shape holds: any when every group has a lane; else the one whose ring_delay still fits
 // `queue` hand-over slots (three blocks of slack for the roundings of ring_group_blocks; a job beyond it is reported by the kernel)
 static u64 shape_width_cap(u32 nw, AlignShape sh) {

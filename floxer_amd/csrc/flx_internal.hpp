@@ -247,6 +247,13 @@ struct TraceLayout { u64 steps, carry_words, carry_slots, ckpt_slots; };   // st
 // could start: every revolution of the ring then begins `delay` block-steps later than the one above it would allow, offset(g) =
 // g + (g / R) delay, the lanes work back to back, and what lane R - 1 hands down to lane 0 waits those steps in a queue in LDS.
 constexpr u32 RING_QUEUE_MAX = 128;          // most hand-over slots per job: delay + 1 of them are in use
+// hand-over slots a job with this delay needs (a power of two; 0: none)
+inline u32 ring_queue_for(u32 delay) {
+    if (delay == 0) return 0;
+    u32 q = 32;
+    while (q < delay + 1u) q *= 2;
+    return q;
+}
 FLX_HD inline void ring_group_blocks(int n, int m, int k, int W, int Lg, int pad, int g, int& b_lo, int& b_hi) {
     int const band_hi = n - m + k;
     int const r0 = 64 * W * g - pad > 0 ? 64 * W * g - pad : 0, r1 = 64 * W * (g + 1) - pad;

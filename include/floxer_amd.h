@@ -176,6 +176,12 @@ int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len
                     uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                     uint32_t* cigar_pool, uint64_t* cigar_pool_words /* in: capacity, out: used */);
 
+/* The launch shape flx_align_batch would give every job of a call with these jobs (a diagnostic and test hook; host arithmetic only: no
+ * context, no GPU). The kernels run a job on a ring of lanes_per_job lanes, words_per_lane 64-row words of the query per lane;
+ * queue = the hand-over slots the job's ring occupies in LDS, 0 for a ring that never waits for a lane. */
+typedef struct flx_align_shape { uint32_t words_per_lane, lanes_per_job, queue; } flx_align_shape;
+int flx_align_shapes(const flx_align_job* jobs, uint64_t n_jobs, flx_align_shape* out);
+
 /* flx_align_batch plus the MD string (see flx_tag_options) of every WITH_CIGAR job that exists: out_md[i] refers into md_pool, length 0 for
  * every other job. md_pool_bytes: in = capacity, out = used (FLX_ERR_CAPACITY if larger than the capacity; 8 * num_allowed_errors + 6 bytes
  * per WITH_CIGAR job always suffice). */

@@ -9,6 +9,7 @@ import floxer_amd as F
 from floxer_amd import capi
 from floxer_amd import simulate as S
 import oracle_lib as O
+import align_corpus as AC
 
 pytestmark = pytest.mark.gpu
 
@@ -201,13 +202,7 @@ def test_align_batch_random_all_shapes(small_genome):
         assert g == exp, (ql, rl, k, mode)
 
 
-@pytest.mark.parametrize("shape", ["1,2", "1,8", "2,4", "3,4", "5,2", "5,8", "8,2"])
-def test_align_batch_on_rings_that_wait(small_genome, monkeypatch, shape):
-    """launch shapes with fewer lanes than a job's band asks for: every revolution of the ring waits (flx_internal.hpp: ring_delay), what the
-    last lane hands to the first goes through the queue in LDS; existence, score / end and traced alignments (K4's slots, K5's reading of
-    them) against the oracle, sizes from one word group to 26 000 rows"""
-    _, _, ctx, _ = small_genome
-    monkeypatch.setenv("FLX_FORCE_SHAPE", shape)
+def _ring_jobs():
     rng = np.random.default_rng(33)
     refs, queries, jobs = [], [], []
     ro = qo = 0
@@ -222,7 +217,40 @@ def test_align_batch_on_rings_that_wait(small_genome, monkeypatch, shape):
             queries.append(q)
             ro += len(ref)
             qo += len(q)
-    rpool, qpool = np.concatenate(refs), np.concatenate(queries)
+    return np.concatenate(refs), np.concatenate(queries), jobs
+
+
+@pytest.mark.parametrize("shape", ["1,2", "1,8", "2,4", "3,4", "5,2", "5,8", "8,2"])
+def test_align_batch_on_rings_that_wait(small_genome, monkeypatch, shape):
+    """launch shapes with fewer lanes than a job's band asks for: every revolution of the ring waits (flx_internal.hpp: ring_delay), what the
+    last lane hands to the first goes through the queue in LDS; existence, score / end and traced alignments (K4's slots, K5's reading of
+    them) against the oracle, sizes from one word group to 26 000 rows. FLX_ALIGN_FEW_WAVES=0: shapes per job (a batch this small would
+    otherwise get one common shape whose ring never waits); align_shapes shows the shape every job really gets: the forced one for every job
+    it can hold. (The widest jobs here would wait more than the 127 block-steps a launch has hand-over slots for: FLX_FORCE_SHAPE leaves
+    those their default shape, in which the wide ones wait as well.)"""
+    _, _, ctx, _ = small_genome
+    monkeypatch.setenv("FLX_FORCE_SHAPE", shape)
+    monkeypatch.setenv("FLX_ALIGN_FEW_WAVES", "0")
+    rpool, qpool, jobs = _ring_jobs()
+    forced = tuple(int(x) for x in shape.split(","))
+    shapes = F.align_shapes(jobs)
+    for (_, rl, _, ql, k, mode), (w, r, q) in zip(jobs, shapes):
+        # (a job the forced shape holds may still take the shape of the widest job of its class of query words: choose_shapes)
+        assert (w, r) != forced or AC.shape_holds(rl, ql, k, *forced), (shape, ql, rl, k, mode, (w, r, q))
+        assert (w, r) == forced or ql >= 5000, (shape, ql, rl, k, mode, (w, r, q))
+        assert q <= AC.RING_QUEUE_MAX
+    assert 2 * sum(1 for w, r, _ in shapes if (w, r) == forced) > len(jobs)
+    # the widest job of a class of query words decides for its class (choose_shapes): it has the forced shape iff that shape holds it
+    widest = {}
+    for job, sh in zip(jobs, shapes):
+        _, rl, _, ql, k, mode = job
+        key = ((ql + 63) // 64, mode)
+        if key not in widest or rl - ql + 2 * k > widest[key][0]:
+            widest[key] = (rl - ql + 2 * k, job, sh)
+    for _, (_, rl, _, ql, k, mode), (w, r, q) in widest.values():
+        assert ((w, r) == forced) == AC.shape_holds(rl, ql, k, *forced), (shape, ql, rl, k, mode, (w, r, q))
+    for mode in (0, 1, 2):
+        assert any(q > 0 and (w, r) == forced for (*_, md), (w, r, q) in zip(jobs, shapes) if md == mode), (shape, mode)
     got = F.align_batch(ctx, qpool, jobs, reference_pool=rpool)
     for (ro_, rl, qo_, ql, k, mode), g in zip(jobs, got):
         exp = O.align(rpool[ro_:ro_ + rl], qpool[qo_:qo_ + ql], k, mode=mode, algo=1)
