@@ -158,7 +158,7 @@ int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes) {
 struct ShapeLaunch { ShapeKey key; u32 first, count; u64 word_steps, bytes; };
 template <class PerJob>
 int launch_by_shape(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<AlignShape> const& shapes, size_t begin, size_t end,
-                    const char* kernel_name, const char* what, bool trace, u16* d_lastrow, PerJob&& per_job) {
+                    const char* kernel_name, const char* what, bool trace, u16* d_lastrow, DevAlignOut** d_out, PerJob&& per_job) {
     std::map<ShapeKey, hvec<u32>> by_shape;
     for (size_t i = begin; i < end; ++i) by_shape[ShapeKey{shapes[i].words_per_lane, shapes[i].lanes_per_job}].push_back((u32)i);
     hvec<DevAlignJob> jobs;
@@ -178,16 +178,32 @@ int launch_by_shape(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignReq
     }
     int rc;
     if ((rc = h2d(ctx, ctx->jobs, jobs.data(), jobs.size() * sizeof(DevAlignJob)))) return rc;
-    if ((rc = ctx->job_out.ensure((end - begin) * sizeof(DevAlignOut)))) return rc;
+    // the results: into the lane's mapped result block when it has room (read in place after the stream wait), else on the device
+    // (*d_out tells the caller where)
+    *d_out = (DevAlignOut*)ctx->result_slot((end - begin) * sizeof(DevAlignOut));
+    if (!*d_out) {
+        if ((rc = ctx->job_out.ensure((end - begin) * sizeof(DevAlignOut)))) return rc;
+        *d_out = ctx->job_out.as<DevAlignOut>();
+    }
+    DevAlignOut* const out = *d_out;
     for (auto const& l : launches) {
         if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[%s]%s W %u R %u jobs %u word-steps %llu n0 %u m0 %u k0 %u\n", kernel_name, what, l.key.w, l.key.g, l.count, (unsigned long long)l.word_steps, jobs[l.first].n, jobs[l.first].m, jobs[l.first].k);
         rc = timed_launch(ctx, kernel_name, l.bytes, l.word_steps, [&] {
             return DeviceApi::align(ctx->stream, d_text, d_peq, ctx->jobs.as<DevAlignJob>() + l.first, l.count, AlignShape{l.key.w, l.key.g}, trace,
-                                    trace ? ctx->trace.as<u64>() : nullptr, ctx->job_out.as<DevAlignOut>(), d_lastrow);
+                                    trace ? ctx->trace.as<u64>() : nullptr, out, d_lastrow);
         });
         if (rc) return rc;
     }
     return FLX_OK;
+}
+
+// a result table that a launch left at `src`: read in place when it is in the lane's mapped block (after the wait the caller makes
+// next), copied when it is on the device
+template <class T>
+int fetch_results(Lane* lane, hvec<T>& dst, const T* src, bool& in_place) {
+    char const* const lo = (char const*)lane->results.ptr;
+    in_place = lo && (char const*)src >= lo && (char const*)src < lo + lane->results.cap;
+    return in_place ? FLX_OK : d2h(lane, dst.data(), src, dst.size() * sizeof(T));
 }
 
 // score + end column for every (distinct) request (no trace)
@@ -200,10 +216,14 @@ int run_score_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
     int rc;
     if ((rc = choose_shapes(reqs, shapes))) return rc;
     jprof.mark("shapes");
-    if ((rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, 0, reqs.size(), kernel_name, "", false, nullptr, [](u32, DevAlignJob&) { return (u64)0; }))) return rc;
-    if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, reqs.size() * sizeof(DevAlignOut)))) return rc;
+    ResultScope const scope(ctx);
+    DevAlignOut* d_out = nullptr;
+    bool in_place = false;
+    if ((rc = launch_by_shape(ctx, d_text, d_peq, reqs, shapes, 0, reqs.size(), kernel_name, "", false, nullptr, &d_out, [](u32, DevAlignJob&) { return (u64)0; }))) return rc;
+    if ((rc = fetch_results(ctx, outs, d_out, in_place))) return rc;
     jprof.mark("launch");
     rc = ctx->sync();
+    if (!rc && in_place) memcpy(outs.data(), d_out, outs.size() * sizeof(DevAlignOut));
     jprof.mark("wait");
     return rc;
 }
@@ -274,57 +294,83 @@ struct Traceback {
         cigar_base = cigar_pool.size();
         if (jobs.empty()) return FLX_OK;
         int rc;
-        if ((rc = h2d(lane, lane->tjobs, jobs.data(), jobs.size() * sizeof(DevTraceJob)))) return rc;
+        // the job tables (trace, MD, tails) up in one copy, packed in the lane's staging block
+        auto const up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+        size_t const b_jobs = jobs.size() * sizeof(DevTraceJob), b_md = md_jobs.size() * sizeof(DevMdJob), b_tail = tail_jobs.size() * sizeof(DevTailJob);
+        size_t const o_md = up(b_jobs), o_tail = o_md + up(b_md), b_tables = o_tail + b_tail;
+        if ((rc = lane->tjobs.ensure(b_tables + 16))) return rc;
+        char* const h = (char*)lane->stage_begin(b_tables);
+        if (!h) return FLX_ERR_NO_DEVICE;
+        memcpy(h, jobs.data(), b_jobs);
+        if (b_md) memcpy(h + o_md, md_jobs.data(), b_md);
+        if (b_tail) memcpy(h + o_tail, tail_jobs.data(), b_tail);
+        FLX_HIP(hipMemcpyAsync(lane->tjobs.ptr, h, b_tables, hipMemcpyHostToDevice, lane->stream));
+        const DevTraceJob* const d_jobs = lane->tjobs.as<DevTraceJob>();
+        const DevMdJob* const d_md_jobs = (const DevMdJob*)((char*)lane->tjobs.ptr + o_md);
+        const DevTailJob* const d_tail_jobs = (const DevTailJob*)((char*)lane->tjobs.ptr + o_tail);
         if ((rc = lane->tjob_out.ensure(jobs.size() * sizeof(DevTraceOut)))) return rc;
         if ((rc = lane->cigar.ensure(cigar_words * 4 + 16))) return rc;
         if (want_md) {
-            if ((rc = h2d(lane, lane->md_jobs, md_jobs.data(), md_jobs.size() * sizeof(DevMdJob)))) return rc;
             if ((rc = lane->md_out.ensure(md_jobs.size() * sizeof(DevMdOut)))) return rc;
             if ((rc = lane->md.ensure(md_bytes + 16))) return rc;
         }
-        if (want_tails) {
-            if ((rc = h2d(lane, lane->tail_jobs, tail_jobs.data(), tail_jobs.size() * sizeof(DevTailJob)))) return rc;
-            if ((rc = lane->tail_out.ensure(tail_jobs.size() * sizeof(DevTailOut)))) return rc;
-        }
+        if (want_tails && (rc = lane->tail_out.ensure(tail_jobs.size() * sizeof(DevTailOut)))) return rc;
+        // The small result tables (16 bytes per path, MD lengths, tails) come back through the lane's mapped result block when it holds them
+        // all: K5 stores its DevTraceOuts there itself when nothing on the device reads them; md_build and cigar_tails read them, so with
+        // either they stay on the device and one publish_stage launch behind the stage hands all the tables over.
+        outs.resize(jobs.size());
+        md_outs.resize(md_jobs.size());
+        tail_outs.resize(tail_jobs.size());
+        DevTraceOut* r_outs = (DevTraceOut*)lane->result_slot(outs.size() * sizeof(DevTraceOut));
+        DevMdOut* r_md = want_md ? (DevMdOut*)lane->result_slot(md_outs.size() * sizeof(DevMdOut)) : nullptr;
+        DevTailOut* r_tail = want_tails ? (DevTailOut*)lane->result_slot(tail_outs.size() * sizeof(DevTailOut)) : nullptr;
+        bool const mapped = r_outs && (!want_md || r_md) && (!want_tails || r_tail);
+        bool const direct = mapped && !want_md && !want_tails;
+        DevTraceOut* const d_outs = direct ? r_outs : lane->tjob_out.as<DevTraceOut>();
         rc = timed_launch(lane, "ed_traceback", path_steps * 18, path_steps, [&] {
-            return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), lane->tjobs.as<DevTraceJob>(), (u32)jobs.size(),
-                                        lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>());
+            return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), d_jobs, (u32)jobs.size(), lane->cigar.as<u32>(), d_outs);
         });
         if (rc) return rc;
         if (want_md) {
             // (its algorithmic bytes depend on what K5 finds: they are added below once the lengths are back)
             rc = timed_launch(lane, "md_build", 0, md_jobs.size(), [&] {
-                return DeviceApi::md_build(lane->stream, d_text, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->md_jobs.as<DevMdJob>(), (u32)md_jobs.size(),
-                                           lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
+                return DeviceApi::md_build(lane->stream, d_text, lane->cigar.as<u32>(), d_outs, d_md_jobs, (u32)md_jobs.size(), lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
             });
             if (rc) return rc;
         }
         if (want_tails) {
             // (the CIGAR words it reads are known once K5's lengths are back: they are added below)
             rc = timed_launch(lane, "cigar_tails", tail_jobs.size() * (sizeof(DevTailJob) + sizeof(DevTraceOut) + sizeof(DevTailOut)), tail_jobs.size(), [&] {
-                return DeviceApi::cigar_tails(lane->stream, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->tail_jobs.as<DevTailJob>(), (u32)tail_jobs.size(),
-                                              lane->tail_out.as<DevTailOut>());
+                return DeviceApi::cigar_tails(lane->stream, lane->cigar.as<u32>(), d_outs, d_tail_jobs, (u32)tail_jobs.size(), lane->tail_out.as<DevTailOut>());
             });
             if (rc) return rc;
         }
+        if (mapped && !direct) {
+            PublishList pub;
+            pub.add(lane->tjob_out.ptr, r_outs, outs.size() * sizeof(DevTraceOut) / 4);
+            if (want_md) pub.add(lane->md_out.ptr, r_md, md_outs.size() * sizeof(DevMdOut) / 4);
+            if (want_tails) pub.add(lane->tail_out.ptr, r_tail, tail_outs.size() * sizeof(DevTailOut) / 4);
+            int const e = DeviceApi::publish_stage(lane->stream, pub);
+            if (e) { set_error(std::string("publish_stage: ") + hipGetErrorString((hipError_t)e)); return FLX_ERR_NO_DEVICE; }
+        }
         if (prof) prof->mark("tb-prep");
-        outs.resize(jobs.size());
         cigar_pool.resize(cigar_base + cigar_words);
         if (prof) prof->mark("pool-resize");
-        if ((rc = d2h(lane, outs.data(), lane->tjob_out.ptr, outs.size() * sizeof(DevTraceOut)))) return rc;
+        if (!mapped && (rc = d2h(lane, outs.data(), lane->tjob_out.ptr, outs.size() * sizeof(DevTraceOut)))) return rc;
         if ((rc = d2h(lane, cigar_pool.data() + cigar_base, lane->cigar.ptr, cigar_words * 4))) return rc;
         if (want_md) {
-            md_outs.resize(md_jobs.size());
             md_base = md_pool->size();
             md_pool->resize(md_base + md_bytes);
-            if ((rc = d2h(lane, md_outs.data(), lane->md_out.ptr, md_outs.size() * sizeof(DevMdOut)))) return rc;
+            if (!mapped && (rc = d2h(lane, md_outs.data(), lane->md_out.ptr, md_outs.size() * sizeof(DevMdOut)))) return rc;
             if ((rc = d2h(lane, md_pool->data() + md_base, lane->md.ptr, md_bytes))) return rc;
         }
-        if (want_tails) {
-            tail_outs.resize(tail_jobs.size());
-            if ((rc = d2h(lane, tail_outs.data(), lane->tail_out.ptr, tail_outs.size() * sizeof(DevTailOut)))) return rc;
-        }
+        if (want_tails && !mapped && (rc = d2h(lane, tail_outs.data(), lane->tail_out.ptr, tail_outs.size() * sizeof(DevTailOut)))) return rc;
         if ((rc = lane->sync())) return rc;
+        if (mapped) {
+            memcpy(outs.data(), r_outs, outs.size() * sizeof(DevTraceOut));
+            if (want_md) memcpy(md_outs.data(), r_md, md_outs.size() * sizeof(DevMdOut));
+            if (want_tails) memcpy(tail_outs.data(), r_tail, tail_outs.size() * sizeof(DevTailOut));
+        }
         if (prof) prof->mark("K5+d2h");
         for (auto const& t : outs)
             if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
@@ -374,7 +420,10 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         hvec<u64> trace_off(count);
         u64 off = 0;
         // (bytes: reference + query symbols read; trace written: the checkpointed trace's carry and checkpoint regions)
-        rc = launch_by_shape(ctx, d_text, d_peq, reqs, plan.shapes, begin, end, "ed_align_trace", "", true, nullptr, [&](u32 id, DevAlignJob& job) {
+        ResultScope const scope(ctx);
+        DevAlignOut* d_out = nullptr;
+        bool in_place = false;
+        rc = launch_by_shape(ctx, d_text, d_peq, reqs, plan.shapes, begin, end, "ed_align_trace", "", true, nullptr, &d_out, [&](u32 id, DevAlignJob& job) {
             AlignRequest const& r = reqs[id];
             job.trace_off = trace_off[id - begin] = off;
             off += plan.slots[id];
@@ -383,8 +432,9 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         });
         if (rc) return rc;
         hvec<DevAlignOut> outs(count);
-        if ((rc = d2h(ctx, outs.data(), ctx->job_out.ptr, count * sizeof(DevAlignOut)))) return rc;
+        if ((rc = fetch_results(ctx, outs, d_out, in_place))) return rc;
         if ((rc = ctx->sync())) return rc;
+        if (in_place) memcpy(outs.data(), d_out, count * sizeof(DevAlignOut));
         tprof.mark("K4");
 
         // ---- traceback for the jobs that have an alignment within k
@@ -594,6 +644,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
     if ((rc = plan.make(ctx, ureqs))) return rc;
     hvec<AlignRequest> fallback;
     hvec<u32> fallback_of;                   // uniq index of each fallback request
+    size_t n_tjobs = 0, n_unions_several_jobs = 0;      // (FLX_ALIGN_DEBUG: traceback jobs, unions whose members end at more than one column)
     while (!plan.done()) {
         size_t begin, next;
         if ((rc = plan.next_chunk(ctx, begin, next))) return rc;
@@ -604,9 +655,13 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         u64 off = 0, rows = 0;
         for (size_t i = begin; i < next; ++i) rows += ((u64)ureqs[i].n + 15) / 16 * 16;      // K4 stores a block's 16 last-row values as two 16-byte words
         if ((rc = ctx->lastrow.ensure(rows * 2 + 64))) return rc;
-        FLX_HIP(hipMemsetAsync(ctx->lastrow.ptr, 0xFF, rows * 2, ctx->stream));
+        // (No fill of the last-row region: K4's last group writes whole blocks from the job's block b_lo to its last, 0xFFFF past column n,
+        // and lastrow_min does not read a window's columns in front of that - lastrow_first_written, proved from enter_group's b_lo / b_hi of
+        // the last group: DevRowWindow::skip below.)
         rows = 0;
-        rc = launch_by_shape(ctx, d_text, d_peq, ureqs, plan.shapes, begin, next, "ed_align_trace", " unions", true, ctx->lastrow.as<u16>(), [&](u32 id, DevAlignJob& job) {
+        ResultScope const scope(ctx);
+        DevAlignOut* d_union_out = nullptr;      // (the unions' own scores are not read: every member's comes from its window of the last row)
+        rc = launch_by_shape(ctx, d_text, d_peq, ureqs, plan.shapes, begin, next, "ed_align_trace", " unions", true, ctx->lastrow.as<u16>(), &d_union_out, [&](u32 id, DevAlignJob& job) {
             AlignRequest const& r = ureqs[id];
             job.trace_off = trace_off[id - begin] = off;
             job.lastrow_off = row_off[id - begin] = rows;
@@ -617,34 +672,50 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         });
         if (rc) return rc;
         // ---- every member's rightmost minimum over its own columns
-        hvec<DevRowWindow> wins;
+        // (the window table is read once, by one wave per window: lastrow_min reads it where the host builds it, in the lane's staging
+        // block, and leaves its results in the lane's mapped result block; a copy each way when the block has no room)
+        size_t n_wins = 0;
+        for (size_t ui = begin; ui < next; ++ui) n_wins += unions[ui].n_members;
+        DevRowWindow* const wins = (DevRowWindow*)ctx->stage_begin(n_wins * sizeof(DevRowWindow));
+        if (!wins) return FLX_ERR_NO_DEVICE;
         hvec<u32> win_member;                // uniq index per window
         hvec<u32> win_union;                 // union index (absolute) per window
-        for (size_t ui = begin; ui < next; ++ui)
+        for (size_t ui = begin; ui < next; ++ui) {
+            AlignRequest const& u = ureqs[ui];
+            u64 const first_written = lastrow_first_written(u.n, u.m, u.k, plan.shapes[ui].words_per_lane);
             for (u32 j = 0; j < unions[ui].n_members; ++j) {
                 u32 const id = members[unions[ui].first_member + j];
                 AlignRequest const& r = uniq[id];
-                wins.push_back(DevRowWindow{row_off[ui - begin] + (r.ref_off - ureqs[ui].ref_off), r.n, r.k, (u32)wins.size(), 0});
+                u64 const shift = r.ref_off - u.ref_off;
+                u32 const skip = (u32)std::min<u64>(first_written > shift ? first_written - shift : 0, r.n);
+                wins[win_member.size()] = DevRowWindow{row_off[ui - begin] + shift, r.n, r.k, (u32)win_member.size(), skip};
                 win_member.push_back(id);
                 win_union.push_back((u32)ui);
             }
-        if ((rc = h2d(ctx, ctx->row_windows, wins.data(), wins.size() * sizeof(DevRowWindow)))) return rc;
-        if ((rc = ctx->row_out.ensure(wins.size() * sizeof(DevAlignOut)))) return rc;
-        rc = timed_launch(ctx, "ed_lastrow_min", rows * 2, wins.size(), [&] {
-            return DeviceApi::lastrow_min(ctx->stream, ctx->lastrow.as<u16>(), ctx->row_windows.as<DevRowWindow>(), (u32)wins.size(), ctx->row_out.as<DevAlignOut>());
+        }
+        hvec<DevAlignOut> wouts(n_wins);
+        DevAlignOut* d_wouts = (DevAlignOut*)ctx->result_slot(n_wins * sizeof(DevAlignOut));
+        bool const wouts_in_place = d_wouts != nullptr;
+        if (!wouts_in_place) {
+            if ((rc = ctx->row_out.ensure(n_wins * sizeof(DevAlignOut)))) return rc;
+            d_wouts = ctx->row_out.as<DevAlignOut>();
+        }
+        rc = timed_launch(ctx, "ed_lastrow_min", rows * 2, n_wins, [&] {
+            return DeviceApi::lastrow_min(ctx->stream, ctx->lastrow.as<u16>(), wins, (u32)n_wins, d_wouts);
         });
         if (rc) return rc;
-        hvec<DevAlignOut> wouts(wins.size());
-        if ((rc = d2h(ctx, wouts.data(), ctx->row_out.ptr, wins.size() * sizeof(DevAlignOut)))) return rc;
+        if (!wouts_in_place && (rc = d2h(ctx, wouts.data(), d_wouts, n_wins * sizeof(DevAlignOut)))) return rc;
         if ((rc = ctx->sync())) return rc;
+        if (wouts_in_place) memcpy(wouts.data(), d_wouts, n_wins * sizeof(DevAlignOut));
 
         // ---- one traceback per distinct (union, end column); the members of a union share its trace job's CIGAR words and MD string
         Traceback tb(md_pool != nullptr, tails);
-        hvec<u32> win_tjob(wins.size(), 0xFFFFFFFFu);
-        for (size_t w0 = 0; w0 < wins.size();) {                     // windows of one union are consecutive
+        hvec<u32> win_tjob(n_wins, 0xFFFFFFFFu);
+        for (size_t w0 = 0; w0 < n_wins;) {                     // windows of one union are consecutive
             size_t w1 = w0;
-            while (w1 < wins.size() && win_union[w1] == win_union[w0]) ++w1;
+            while (w1 < n_wins && win_union[w1] == win_union[w0]) ++w1;
             u32 const ui = win_union[w0];
+            size_t const jobs_before = tb.jobs.size();
             for (size_t w = w0; w < w1; ++w) {
                 if (wouts[w].score == 0xFFFFFFFFu) continue;
                 u32 const end_in_union = (u32)(uniq[win_member[w]].ref_off - ureqs[ui].ref_off) + wouts[w].end_col;
@@ -652,11 +723,13 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
                     if (win_tjob[v] != 0xFFFFFFFFu && tb.jobs[win_tjob[v]].end_col == end_in_union) { win_tjob[w] = win_tjob[v]; break; }
                 if (win_tjob[w] == 0xFFFFFFFFu) win_tjob[w] = tb.add(ureqs[ui], trace_off[ui - begin], plan.shapes[ui], end_in_union, wouts[w].score);
             }
+            n_unions_several_jobs += tb.jobs.size() - jobs_before > 1;
             w0 = w1;
         }
+        n_tjobs += tb.jobs.size();
         if ((rc = tb.run(ctx, d_text, d_peq, cigar_pool, md_pool))) return rc;
         // ---- members take the union's alignment when its path starts inside their window
-        for (size_t w = 0; w < wins.size(); ++w) {
+        for (size_t w = 0; w < n_wins; ++w) {
             u32 const id = win_member[w];
             if (wouts[w].score == 0xFFFFFFFFu) continue;                       // no alignment within k in this window
             TraceResult res = tb.result(win_tjob[w], wouts[w].score);
@@ -672,7 +745,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
-    if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu\n", n_requests, uniq.size(), unions.size(), fallback.size());
+    if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu traceback jobs %zu unions with several jobs %zu\n", n_requests, uniq.size(), unions.size(), fallback.size(), n_tjobs, n_unions_several_jobs);
     return FLX_OK;
 }
 

@@ -192,6 +192,8 @@ int make_context(int hip_device, const flx_index* index, void* const image[5], b
     if (const char* env = getenv("FLX_TRACE_ARENA_MB")) { size_t const mb = strtoull(env, nullptr, 10); if (mb) budget = mb << 20; }
     budget = std::max<size_t>(budget, (size_t)256 << 20);
     for (auto& lane : ctx->lanes) lane->trace_budget_bytes = std::max<size_t>(budget / n_lanes, (size_t)128 << 20);
+    // (test hook: FLX_TRACE_ARENA_KB = every lane's budget in KB, below the floors: a batch of a few short reads in several arena chunks)
+    if (const char* env = getenv("FLX_TRACE_ARENA_KB")) { size_t const kb = strtoull(env, nullptr, 10); if (kb) for (auto& lane : ctx->lanes) lane->trace_budget_bytes = kb << 10; }
     *out = ctx.release();
     return FLX_OK;
 }
@@ -238,7 +240,16 @@ flx_ctx::~flx_ctx() {
     if (upload_stream) (void)hipStreamDestroy(upload_stream);
 }
 
-void flx_ctx_destroy(flx_ctx* ctx) { delete ctx; }
+int flx_ctx_destroy(flx_ctx* ctx) {
+    if (!ctx) return FLX_OK;
+    {
+        // a live read batch hands its device buffers back to this context when it is freed (flx_reads_free): the context stays until then
+        std::lock_guard<std::mutex> g(ctx->spare_mu);
+        if (ctx->live_reads > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_reads) + " read batch(es) of this context are still alive (flx_reads_free them first)"); return FLX_ERR_INVALID; }
+    }
+    delete ctx;
+    return FLX_OK;
+}
 
 int flx_ctx_set_stream(flx_ctx* ctx, void* hip_stream) {
     if (!ctx) { set_error("null context"); return FLX_ERR_INVALID; }

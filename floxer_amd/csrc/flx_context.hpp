@@ -36,6 +36,18 @@ struct DeviceBuffer {
     template <class T> T* as() const { return reinterpret_cast<T*>(ptr); }
 };
 
+// Page-locked host memory that the device reads and writes in place (mapped), grow-only.
+struct PinnedBuffer {
+    void* ptr = nullptr;
+    size_t cap = 0;
+    PinnedBuffer() = default;
+    PinnedBuffer(PinnedBuffer const&) = delete;
+    PinnedBuffer& operator=(PinnedBuffer const&) = delete;
+    ~PinnedBuffer() { release(); }
+    int ensure(size_t bytes);        // contents are NOT preserved; the caller makes sure the device is done with the old block
+    void release();
+};
+
 struct PendingTiming { std::string name; hipEvent_t start, stop; u64 bytes, units; };
 
 }  // namespace flx
@@ -59,6 +71,18 @@ struct Lane {
     std::vector<hipEvent_t> event_pool;
     hipEvent_t sync_event = nullptr;
     u32* vr_host_scalars = nullptr;  // page-locked, mapped: a round's scalars, written by the device (flx_rounds.hip)
+    // A stage's small tables go up packed: built in place in `staging`, one copy per stage (or read in place by a kernel that reads a
+    // table once). stage_begin returns the block for the stage that starts now: every stage ends with a wait for the stream before its
+    // host code goes on, so the previous stage's copies have left the block. Null: out of page-locked memory (an error is set).
+    PinnedBuffer staging;
+    void* stage_begin(size_t bytes);
+    // Small per-chunk results (counters, job counts, result tables of a few KB) come back without a copy: the producing kernel stores
+    // them into this mapped block and the host reads them after the stream wait it makes anyway. Every use takes its own range
+    // (result_slot), written in full by its producer: nothing is ever cleared. A ResultScope gives the ranges taken inside it back.
+    PinnedBuffer results;
+    size_t results_used = 0;
+    static constexpr size_t RESULT_BLOCK_BYTES = 1u << 20;
+    void* result_slot(size_t bytes); // null: no room (the caller copies instead)
     bool has_run = false;            // a chunk has run here (its workspaces have their working sizes)
     double hits_per_seed = 0, items_per_seed = 0, sel_rows_per_seed = 0;      // of the last search here: the next one's buffers are sized for that and a margin
     int wait_idle();                 // the stream has drained (the thread sleeps on a blocking event unless FLX_SPIN_SYNC is set)
@@ -86,6 +110,7 @@ struct flx_ctx {
     // host memory (flx_align_reads: three buffers made and freed per batch) used to stall every lane three times per batch.
     std::mutex spare_mu;
     std::vector<std::unique_ptr<flx::DeviceBuffer>> spare_read_buffers[5];
+    int live_reads = 0;              // read batches made on this context and not yet freed (guarded by spare_mu): flx_ctx_destroy refuses while > 0
     bool external_stream = false;    // a caller-owned stream is installed on lane 0: run on that lane only
     // accounting
     bool timing = false;
@@ -125,6 +150,15 @@ struct LaneLease {
     ~LaneLease() { ctx->release_lane(lane); }
     LaneLease(LaneLease const&) = delete;
     LaneLease& operator=(LaneLease const&) = delete;
+};
+
+struct ResultScope {
+    Lane* lane;
+    size_t mark;
+    explicit ResultScope(Lane* l) : lane(l), mark(l->results_used) {}
+    ~ResultScope() { lane->results_used = mark; }
+    ResultScope(ResultScope const&) = delete;
+    ResultScope& operator=(ResultScope const&) = delete;
 };
 
 // brackets a launch with events when timing is enabled

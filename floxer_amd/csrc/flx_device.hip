@@ -514,8 +514,10 @@ __global__ void __launch_bounds__(64) lastrow_min_kernel(const u16* __restrict__
     u32 const lane = threadIdx.x & 63u;
     const u16* __restrict__ row = lastrow + w.first;
     u32 best = 0xFFFFu, col = 0;
+    // (the first w.skip columns lie in blocks the job's last group never wrote: they count as 0xFFFF unread, so the last-row region
+    // needs no fill in front of K4)
     for (u32 c = lane; c < w.n; c += 64u) {
-        u32 const v = row[c];
+        u32 const v = c < w.skip ? 0xFFFFu : row[c];
         if (v <= best) { best = v; col = c + 1u; }
     }
     // wave reduction on (value ascending, column descending): key = value << 32 | ~column

@@ -150,7 +150,9 @@ struct DevAlignJob {
 struct DevAlignOut { u32 score; u32 end_col; };    // score 0xFFFFFFFF: no alignment within k
 
 // one window inside a job's column range: its best end column is the rightmost minimum of the job's last row over [first, first+n)
-struct DevRowWindow { u64 first; u32 n, k; u32 out_index, pad; };
+// skip: the window's first `skip` columns lie in blocks the job's last group never computes (lastrow_first_written): they are not read and
+// count as 0xFFFF
+struct DevRowWindow { u64 first; u32 n, k; u32 out_index, skip; };
 
 struct DevTraceJob {
     u64 ref_off, q_off, trace_off, cigar_off;      // cigar_off: first word of this job's CIGAR slab
@@ -275,6 +277,17 @@ FLX_HD inline u32 ring_delay(u32 n, u32 m, u32 k, u32 W, u32 R) {
     }
     return (u32)delay;
 }
+// The first column of a job's last-row region that a TRACE launch writes. Only the job's last group stores last-row values, one whole
+// block (16 columns, 0xFFFF past column n) for every block b_lo .. b_hi of its band (ed_block_body's flush), and b_hi of the last group
+// is the window's last block: the columns in front of block b_lo are never written, and a job without any column in its band (n == 0 or
+// n + k < m: ed_block_body leaves before its first block) writes none of its n columns.
+FLX_HD inline u32 lastrow_first_written(u32 n, u32 m, u32 k, u32 W) {
+    if (n == 0 || m == 0 || (u64)n + k < m) return n;
+    int const nw = (int)((m + 63u) / 64u), Lg = (nw + (int)W - 1) / (int)W, pad = Lg * 64 * (int)W - (int)m;
+    int lo, hi;
+    ring_group_blocks((int)n, (int)m, (int)k, (int)W, Lg, pad, Lg - 1, lo, hi);
+    return (u32)lo * 16u;
+}
 FLX_HD inline u64 ring_offset(u32 g, u32 R, u32 delay) { return (u64)g + (u64)(g / R) * delay; }
 // block-steps of a job: the last group's last block is the window's last
 FLX_HD inline u64 ring_steps(u32 n, u32 m, u32 k, u32 W, u32 R) {
@@ -300,8 +313,38 @@ u32 fm_search_max_keyed_length();
 // flx_search_ordered.hip, flx_search.hip, flx_select.hip, flx_rounds.hip; the edit-distance kernels: flx_device.hip)
 struct KernelTimer;   // opaque, owned by the context
 
+// ---- what a stage's launches want set or handed back, as kernel arguments (flx_stage.hip): one clear_stage launch in front of a stage
+// instead of one fill per buffer, one publish_stage launch behind it instead of one copy per small result
+struct ClearItem { u32* ptr; u32 words; u32 value; };
+struct ClearList {
+    static constexpr u32 MAX = 8;
+    ClearItem item[MAX];
+    u32 n = 0;
+    bool add(void* p, size_t words, u32 value = 0) {
+        if (n == MAX || words > 0xFFFFFFFFull) return false;
+        if (words) item[n++] = ClearItem{(u32*)p, (u32)words, value};
+        return true;
+    }
+};
+struct PublishItem { const u32* src; u32* dst; u32 words; };
+struct PublishList {
+    static constexpr u32 MAX = 4;
+    PublishItem item[MAX];
+    u32 n = 0;
+    bool add(const void* src, void* dst, size_t words) {
+        if (n == MAX || words > 0xFFFFFFFFull) return false;
+        if (words) item[n++] = PublishItem{(const u32*)src, (u32*)dst, (u32)words};
+        return true;
+    }
+};
+
 struct DeviceApi {
     // all return 0 or a hipError_t (non-zero)
+    // flx_stage.hip: every item's words set to its value (one launch; nothing when the list is empty)
+    static int clear_stage(void* stream, ClearList const& L);
+    // flx_stage.hip: every item's words copied from device memory to where the host reads them (page-locked mapped memory), with ordinary
+    // vector stores (one launch)
+    static int publish_stage(void* stream, PublishList const& L);
     // suffix array of text[0, n) on the device (a suffix that is a prefix of another sorts first); out: n entries on the host
     static int suffix_array(int hip_device, const u8* text, u64 n, u32* out);
     // suffix array, BWT of the text and of the reversed text and both occurrence tables (n / 64 + 1 blocks each), built on the
@@ -316,13 +359,15 @@ struct DeviceApi {
                       u32* d_counters, u32* d_seed_cnt = nullptr);
     // flx_search.hip: the walk with its stack in LDS plus the presence filter (d_qpack: 2-bit form of d_seq, null: no filter) and the
     // text walk of one-row subtrees (d_items: room for item_cap queued subtrees, null: none are queued). d_counters: 32 zeroed words.
+    // clears: what the caller still wants cleared in front of the walk (d_counters, d_seed_rows, ...); the mailboxes' control words are added
+    // and one clear_stage launch does them all
     // d_seed_rows (n_seeds zeroed words, or null): rows reported per seed over all lanes; with it the lanes of a wave share the subtrees
     // of heavy seeds once the seed queue is dry, and busy waves hand subtrees to waves that have run out of work through d_mailboxes
     // (see fm_search_filter_kernel)
     static int search_filtered(void* stream, const DevIndex& idx, const u8* d_seq, const u32* d_qpack, const u64* d_scheme, const DevSeed* d_seeds,
                                u32 n_seeds, u32 max_hits_per_seed, u32 frame_levels, DevHit* d_hits, u32 hit_cap, DevHit* d_items, u32 item_cap,
                                u32* d_counters, u32* d_seed_cnt, u32* d_seed_rows, void* d_mailboxes, u32 mailbox_waves, u32 concurrent_launches,
-                               bool long_seeds = false);
+                               bool long_seeds, ClearList clears);
     // long_seeds: most seeds of the launch have more than 64 symbols (the text walk then takes its larger LDS windows: up to 160 symbols)
     // the mailboxes through which the waves of one launch of the filter walk hand subtrees to each other (room for `waves` waves; may be null)
     static size_t mailbox_bytes(u32 waves);
@@ -337,7 +382,7 @@ struct DeviceApi {
     // 2-bit form of a sequence pool (pack_words_for(len) words, flx_fm_core.hpp)
     static int pack_pool(void* stream, const u8* d_seq, u64 len, u32* d_qpack);
     // anchor selection on the device (see seed_select_kernel). d_seed_cnt, d_hit_offset, d_n_out, d_out_offset: n_seeds + 1 entries
-    // (the caller zeroes the last entry of d_seed_cnt and d_n_out); d_stat: one DevSelStat per seed;
+    // (the caller zeroes the last entry of d_seed_cnt and d_n_out, and the three list lengths d_lists[3 n_seeds ..]); d_stat: one DevSelStat per seed;
     // d_grouped: as many entries as d_hits; d_out: one entry per selected anchor (at most the number of rows of the handled seeds);
     // d_lists: 3 * n_seeds + 3 entries (the lists of light, heavy and many-group seeds and their lengths)
     static size_t select_scan_bytes(u32 n_seeds);
@@ -346,7 +391,8 @@ struct DeviceApi {
                       bool erase, void* d_stat, u32* d_n_out, u32* d_out_offset, DevOutAnchor* d_out, u32 out_cap, u32* d_rows,
                       u32* d_row_offset, DevOutAnchor* d_sparse, u32 sparse_cap, void* d_scan_tmp, size_t scan_bytes, u32* d_lists);
     static int locate(void* stream, const DevIndex& idx, const u32* d_rows, u32 n, u32* d_out);
-    // d_lastrow (TRACE launches only, may be null): D[m][c] of every computed column c, 0xFFFF elsewhere (pre-filled by the caller)
+    // d_lastrow (TRACE launches only, may be null): D[m][c] of every column from lastrow_first_written on (whole blocks: 0xFFFF past column n);
+    // the columns in front of it are left as they were
     static int align(void* stream, const u8* d_text, const u64* d_peq, const DevAlignJob* d_jobs, u32 n_jobs, AlignShape shape,
                      bool trace, u64* d_trace, DevAlignOut* d_out, u16* d_lastrow = nullptr);
     // flx_rounds.hip: a round = vr2_request (job list and count on the device), align_exists_counted on it, vr2_apply

@@ -32,6 +32,40 @@ void DeviceBuffer::release() {
     cap = 0;
 }
 
+int PinnedBuffer::ensure(size_t bytes) {
+    if (bytes <= cap && ptr) return FLX_OK;
+    release();
+    size_t const want = std::max<size_t>(bytes + bytes / 2, 4096);
+    void* p = nullptr;
+    hipError_t e = hipHostMalloc(&p, want, hipHostMallocMapped);
+    size_t got = want;
+    if (e != hipSuccess) { (void)hipGetLastError(); got = bytes; e = hipHostMalloc(&p, bytes, hipHostMallocMapped); }   // retry without slack
+    if (e != hipSuccess) { set_error(std::string("hipHostMalloc of ") + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e)); return FLX_ERR_NO_DEVICE; }
+    ptr = p;
+    cap = got;
+    return FLX_OK;
+}
+void PinnedBuffer::release() {
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+}
+
+void* Lane::stage_begin(size_t bytes) {
+    if (bytes > staging.cap || !staging.ptr) {
+        if (wait_idle()) return nullptr;                 // (nothing of this lane reads the old block any more)
+        if (staging.ensure(bytes)) return nullptr;
+    }
+    return staging.ptr;
+}
+void* Lane::result_slot(size_t bytes) {
+    if (!results.ptr && results.ensure(RESULT_BLOCK_BYTES)) { (void)hipGetLastError(); return nullptr; }
+    size_t const at = (results_used + 63) & ~(size_t)63;
+    if (bytes == 0 || at + bytes > results.cap) return nullptr;
+    results_used = at + bytes;
+    return (char*)results.ptr + at;
+}
+
 hipEvent_t Lane::get_event() {
     if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -83,6 +117,9 @@ void Lane::release_all() {
     if (own_stream) (void)hipStreamDestroy(own_stream);
     own_stream = stream = nullptr;
     if (vr_host_scalars) { (void)hipHostFree(vr_host_scalars); vr_host_scalars = nullptr; }
+    staging.release();
+    results.release();
+    results_used = 0;
 }
 int Lane::wait_idle() {
     // hipStreamSynchronize and hipEventSynchronize keep the calling core busy for as long as the GPU works (also with

@@ -106,14 +106,18 @@ extern "C" int flx_reads_upload(flx_ctx* ctx, const uint8_t* read_pool, const ui
     if (total) FLX_HIP(hipMemcpyAsync(rd->d_pool.ptr, rd->pool.data(), total, hipMemcpyHostToDevice, s0));
     FLX_HIP(hipMemsetAsync((char*)rd->d_pool.ptr + total, 0, 192, s0));
     FLX_HIP(hipStreamSynchronize(s0));
+    { std::lock_guard<std::mutex> g(ctx->spare_mu); ++ctx->live_reads; }
     *out = rd.release();
     return FLX_OK;
 }
 
+// (the batch's device buffers go back to the context for the next batch without a device-wide wait: every run on the batch must have
+// returned before it is freed, and the context outlives it - flx_ctx_destroy refuses while a batch is alive)
 extern "C" void flx_reads_free(flx_reads* reads) {
     if (!reads) return;
     if (reads->ctx) (void)hipSetDevice(reads->ctx->device);
     if (reads->ctx) {
+        { std::lock_guard<std::mutex> g(reads->ctx->spare_mu); --reads->ctx->live_reads; }
         keep_spare_read_buffer(reads->ctx, 0, reads->d_pool);
         keep_spare_read_buffer(reads->ctx, 1, reads->d_pack);
         keep_spare_read_buffer(reads->ctx, 2, reads->d_peq);

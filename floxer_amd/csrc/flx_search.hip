@@ -643,8 +643,9 @@ static u32 env_u32(const char* name, u32 dflt) {
 // queued). frame_levels = largest error count of a seed. d_counters: 32 words, zeroed by the caller.
 int DeviceApi::search_filtered(void* stream, const DevIndex& idx, const u8* d_seq, const u32* d_qpack, const u64* d_scheme, const DevSeed* d_seeds,
                                u32 n_seeds, u32 max_hits_per_seed, u32 frame_levels, DevHit* d_hits, u32 hit_cap, DevHit* d_items, u32 item_cap,
-                               u32* d_counters, u32* d_seed_cnt, u32* d_seed_rows, void* d_mailboxes, u32 mailbox_waves, u32 concurrent_launches, bool long_seeds) {
-    if (n_seeds == 0) return 0;
+                               u32* d_counters, u32* d_seed_cnt, u32* d_seed_rows, void* d_mailboxes, u32 mailbox_waves, u32 concurrent_launches, bool long_seeds,
+                               ClearList clears) {
+    if (n_seeds == 0) return clear_stage(stream, clears);
     static u32 const spw = env_u32("FLX_FM_SEEDS_PER_WAVE", 256);
     static u32 const forced_waves = env_u32("FLX_FM_MAX_WAVES", 0);
     u32 const no_filter = env_u32("FLX_FM_NO_FILTER", 0), no_text = env_u32("FLX_FM_NO_TEXT", 0);      // (read per call: tests switch them)
@@ -677,12 +678,12 @@ int DeviceApi::search_filtered(void* stream, const DevIndex& idx, const u8* d_se
     if (seed_rows && d_mailboxes && mailbox_waves >= grid.x && env_u32("FLX_FM_NO_MAILBOXES", 0) == 0) {
         u32* const words = (u32*)d_mailboxes;
         size_t const zeroed = ((size_t)MB_CTRL_WORDS + (size_t)grid.x * (2 + MB_HUNGRY_PER_WAVE)) * 4;
-        hipError_t const e = hipMemsetAsync(words, 0, zeroed, s);
-        if (e != hipSuccess) return (int)e;
+        if (!clears.add(words, zeroed / 4)) return (int)hipErrorInvalidValue;
         MB.ctrl = words; MB.state = words + MB_CTRL_WORDS; MB.count = MB.state + grid.x; MB.hungry = MB.count + grid.x;
         MB.n_hungry = grid.x * MB_HUNGRY_PER_WAVE;
         MB.items = reinterpret_cast<FrameItem*>((char*)d_mailboxes + (zeroed + 255) / 256 * 256);
     }
+    if (int const e = clear_stage(stream, clears)) return e;
     auto const kernel = stats ? fm_search_filter_kernel<true> : fm_search_filter_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, dim3(64), lds_bytes, s, C, n_seeds, d_hits, hit_cap, d_items, item_cap, d_counters, d_seed_cnt, seed_rows, MB, refill_a, fm_prio, std::max(1u, steal_min), steal_after, cap_look);
     if (C.text_min_remain) {

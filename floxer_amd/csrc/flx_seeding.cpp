@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <numeric>
@@ -139,18 +140,29 @@ int search_seeds_device(Lane* ctx, const u8* d_seq_pool_or_null, const u8* h_seq
         if ((rc = h2d(ctx, ctx->seq, h_seq_pool, pool_len, 64))) return rc;
         d_seq = ctx->seq.as<u8>();
     }
-    if ((rc = h2d(ctx, ctx->scheme, scheme_table.data(), scheme_table.size() * 8))) return rc;
-    if (!gen) { if ((rc = h2d(ctx, ctx->seeds, dseeds.data(), dseeds.size() * sizeof(DevSeed)))) return rc; }
-    else {
-        // the chunk's description (a few hundred KB) up, the DevSeeds written where the search reads them
-        size_t const b_reads = gen->reads.size() * sizeof(DevSeedRead), b_leaves = gen->leaves.size() * sizeof(DevSeedLeaf), b_classes = gen->classes.size() * sizeof(DevSeedClass);
-        size_t const o_leaves = (b_reads + 255) / 256 * 256, o_classes = o_leaves + (b_leaves + 255) / 256 * 256;
-        if ((rc = ctx->seed_gen.ensure(o_classes + b_classes + 256))) return rc;
+    const u64* d_scheme = nullptr;
+    if (!gen) {
+        if ((rc = h2d(ctx, ctx->scheme, scheme_table.data(), scheme_table.size() * 8))) return rc;
+        d_scheme = ctx->scheme.as<u64>();
+        if ((rc = h2d(ctx, ctx->seeds, dseeds.data(), dseeds.size() * sizeof(DevSeed)))) return rc;
+    } else {
+        // the chunk's description (a few hundred KB) and the scheme table up in one copy, packed in the lane's staging block; the DevSeeds
+        // written where the search reads them
+        size_t const b_reads = gen->reads.size() * sizeof(DevSeedRead), b_leaves = gen->leaves.size() * sizeof(DevSeedLeaf), b_classes = gen->classes.size() * sizeof(DevSeedClass),
+                     b_scheme = scheme_table.size() * 8;
+        auto const up = [](size_t b) { return (b + 255) / 256 * 256; };
+        size_t const o_leaves = up(b_reads), o_classes = o_leaves + up(b_leaves), o_scheme = o_classes + up(b_classes), total = o_scheme + b_scheme;
+        if ((rc = ctx->seed_gen.ensure(total + 256))) return rc;
         if ((rc = ctx->seeds.ensure(n_seeds * sizeof(DevSeed)))) return rc;
+        char* const h = (char*)ctx->stage_begin(total);
+        if (!h) return FLX_ERR_NO_DEVICE;
+        memcpy(h, gen->reads.data(), b_reads);
+        memcpy(h + o_leaves, gen->leaves.data(), b_leaves);
+        memcpy(h + o_classes, gen->classes.data(), b_classes);
+        memcpy(h + o_scheme, scheme_table.data(), b_scheme);
         char* const g = (char*)ctx->seed_gen.ptr;
-        FLX_HIP(hipMemcpyAsync(g, gen->reads.data(), b_reads, hipMemcpyHostToDevice, ctx->stream));
-        FLX_HIP(hipMemcpyAsync(g + o_leaves, gen->leaves.data(), b_leaves, hipMemcpyHostToDevice, ctx->stream));
-        FLX_HIP(hipMemcpyAsync(g + o_classes, gen->classes.data(), b_classes, hipMemcpyHostToDevice, ctx->stream));
+        FLX_HIP(hipMemcpyAsync(g, h, total, hipMemcpyHostToDevice, ctx->stream));
+        d_scheme = (const u64*)(g + o_scheme);
         int const e = DeviceApi::build_seeds(ctx->stream, (const DevSeedRead*)g, (u32)gen->reads.size(), (const DevSeedLeaf*)(g + o_leaves), (const DevSeedClass*)(g + o_classes),
                                              ctx->seeds.as<DevSeed>());
         if (e) { set_error(std::string("seed_build: ") + hipGetErrorString((hipError_t)e)); return FLX_ERR_NO_DEVICE; }
@@ -213,7 +225,9 @@ int search_seeds_device(Lane* ctx, const u8* d_seq_pool_or_null, const u8* h_seq
         sel_cap = std::max(sel_cap, hit_cap);
         if ((rc = ctx->hits.ensure(hit_cap * sizeof(DevHit)))) return rc;
         if (item_cap && (rc = ctx->items.ensure(item_cap * sizeof(DevHit)))) return rc;
-        FLX_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 128, ctx->stream));
+        // what the stage's kernels want zeroed, in one clear_stage launch in front of the walk
+        ClearList clears;
+        clears.add(ctx->counters.ptr, 32);
         if (device_select) {
             // one selected anchor per hit row at most; rows <= hits * SEL_MAX would be the hard bound, the seeds the device
             // handles have at most soft-cap rows each and nearly all hits have one row: hit_cap entries, checked after the run
@@ -221,20 +235,22 @@ int search_seeds_device(Lane* ctx, const u8* d_seq_pool_or_null, const u8* h_seq
             if ((rc = ctx->sel_out.ensure(sel_cap * sizeof(DevOutAnchor)))) return rc;
             if ((rc = ctx->sel_sparse.ensure(sel_cap * sizeof(DevOutAnchor)))) return rc;
             // (the search counts a seed's rows here while it runs; seed_rows_kernel then writes every entry but the last)
-            FLX_HIP(hipMemsetAsync(ctx->sel_rows.ptr, 0, (n_seeds + 1) * 4, ctx->stream));
-            FLX_HIP(hipMemsetAsync(ctx->seed_cnt.ptr, 0, (n_seeds + 1) * 4, ctx->stream));
-            FLX_HIP(hipMemsetAsync((char*)ctx->sel_n.ptr + n_seeds * 4, 0, 4, ctx->stream));
+            clears.add(ctx->sel_rows.ptr, n_seeds + 1);
+            clears.add(ctx->seed_cnt.ptr, n_seeds + 1);
+            clears.add(ctx->sel_n.as<u32>() + n_seeds, 1);
+            clears.add(ctx->sel_lists.as<u32>() + 3 * n_seeds, 3);      // (the lengths of the selection's three seed lists)
         }
         if (alloc_debug) { dump_lane_buffers(*ctx, "search"); fprintf(stderr, "[flx alloc] lane %d search: seeds %llu hit_cap %llu item_cap %llu pool %p qpack %p\n", ctx->id, (unsigned long long)n_seeds, (unsigned long long)hit_cap, (unsigned long long)item_cap, (const void*)d_seq, (const void*)d_qpack); }
         rc = timed_launch(ctx, "fm_search", 0, n_seeds, [&] {
             u32 const concurrent = ctx->ctx->external_stream ? 1u : (u32)ctx->ctx->lanes.size();
             if (filtered)
-                return DeviceApi::search_filtered(ctx->stream, ctx->ctx->didx, d_seq, d_qpack, ctx->scheme.as<u64>(), ctx->seeds.as<DevSeed>(), (u32)n_seeds,
+                return DeviceApi::search_filtered(ctx->stream, ctx->ctx->didx, d_seq, d_qpack, d_scheme, ctx->seeds.as<DevSeed>(), (u32)n_seeds,
                                                   max_hits, max_errors, ctx->hits.as<DevHit>(), (u32)std::min<u64>(hit_cap, 0xFFFFFFFFu),
                                                   item_cap ? ctx->items.as<DevHit>() : nullptr, (u32)std::min<u64>(item_cap, 0xFFFFFFFFu),
                                                   ctx->counters.as<u32>(), device_select ? ctx->seed_cnt.as<u32>() : nullptr,
-                                                  device_select ? ctx->sel_rows.as<u32>() : nullptr, device_select ? ctx->mailboxes.ptr : nullptr, mailbox_waves, concurrent, long_seeds);
-            return DeviceApi::search(ctx->stream, ctx->ctx->didx, d_seq, ctx->scheme.as<u64>(), ctx->seeds.as<DevSeed>(), (u32)n_seeds,
+                                                  device_select ? ctx->sel_rows.as<u32>() : nullptr, device_select ? ctx->mailboxes.ptr : nullptr, mailbox_waves, concurrent, long_seeds, clears);
+            if (int const e = DeviceApi::clear_stage(ctx->stream, clears)) return e;
+            return DeviceApi::search(ctx->stream, ctx->ctx->didx, d_seq, d_scheme, ctx->seeds.as<DevSeed>(), (u32)n_seeds,
                                      max_hits, ctx->stack.as<DevFrame>(), ctx->hits.as<DevHit>(), (u32)std::min<u64>(hit_cap, 0xFFFFFFFFu),
                                      ctx->counters.as<u32>(), device_select ? ctx->seed_cnt.as<u32>() : nullptr);
         });
@@ -251,13 +267,32 @@ int search_seeds_device(Lane* ctx, const u8* d_seq_pool_or_null, const u8* h_seq
             });
             if (rc) return rc;
         }
-        if ((rc = d2h(ctx, counters, ctx->counters.ptr, 128))) return rc;
-        if (device_select) {
-            if ((rc = d2h(ctx, &sel_total, (char*)ctx->sel_off.ptr + n_seeds * 4, 4))) return rc;
-            if ((rc = d2h(ctx, &sel_rows_total, (char*)ctx->sel_row_off.ptr + n_seeds * 4, 4))) return rc;
-            if ((rc = d2h(ctx, sel_stat.data(), ctx->sel_stat.ptr, n_seeds * sizeof(DevSelStat)))) return rc;
+        // the counters and the selection's two totals come back through the lane's mapped result block: one publish_stage launch behind the
+        // stage's kernels, read after the stream wait (a copy each when the block has no room)
+        ResultScope const scope(ctx);
+        u32* const r_small = (u32*)ctx->result_slot(34 * 4);
+        if (r_small) {
+            PublishList pub;
+            pub.add(ctx->counters.ptr, r_small, 32);
+            if (device_select) {
+                pub.add(ctx->sel_off.as<u32>() + n_seeds, r_small + 32, 1);
+                pub.add(ctx->sel_row_off.as<u32>() + n_seeds, r_small + 33, 1);
+            }
+            int const e = DeviceApi::publish_stage(ctx->stream, pub);
+            if (e) { set_error(std::string("publish_stage: ") + hipGetErrorString((hipError_t)e)); return FLX_ERR_NO_DEVICE; }
+        } else {
+            if ((rc = d2h(ctx, counters, ctx->counters.ptr, 128))) return rc;
+            if (device_select) {
+                if ((rc = d2h(ctx, &sel_total, (char*)ctx->sel_off.ptr + n_seeds * 4, 4))) return rc;
+                if ((rc = d2h(ctx, &sel_rows_total, (char*)ctx->sel_row_off.ptr + n_seeds * 4, 4))) return rc;
+            }
         }
+        if (device_select && (rc = d2h(ctx, sel_stat.data(), ctx->sel_stat.ptr, n_seeds * sizeof(DevSelStat)))) return rc;
         if ((rc = ctx->sync())) return rc;
+        if (r_small) {
+            memcpy(counters, r_small, 128);
+            if (device_select) { sel_total = r_small[32]; sel_rows_total = r_small[33]; }
+        }
         if (getenv("FLX_SEARCH_DEBUG")) fprintf(stderr, "[fm_search] seeds %llu ext %u (of single-row intervals %u) wave-iterations %u (max per wave %u) busy pair-iterations %u, after the queue ran dry %u (max %u), subtrees handed over %u, from wave to wave %u, walks abandoned over the cap %u\n", (unsigned long long)n_seeds, counters[2], counters[3], counters[4], counters[5], counters[6], counters[8], counters[9], counters[14], counters[15], counters[20]);
         if (getenv("FLX_SEARCH_DEBUG") && filtered) fprintf(stderr, "[fm_search filtered] subtrees queued %u (slots %u of %llu), filter words asked %u, children dropped %u, searches ended by the prefix lookup %u; text walk: lane-steps %u, wave-iterations %u in %u waves (longest %u)\n", counters[3], counters[16], (unsigned long long)item_cap, counters[10], counters[11], counters[12], counters[18], counters[19], counters[22], counters[21]);
         if (counters[1]) { set_error(counters[1] & 2u ? "fm_search: a subtree handed between waves was not taken" : "fm_search: DFS stack reservation exceeded"); return FLX_ERR_INTERNAL; }

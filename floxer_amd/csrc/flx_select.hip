@@ -448,7 +448,6 @@ int DeviceApi::select(void* stream, const DevHit* d_hits, const u32* d_counters,
     hipLaunchKernelGGL(hit_scatter_kernel, dim3(2048), dim3(256), 0, s, d_hits, d_counters, hit_cap, d_hit_offset, d_grouped);
     SelStat* const stat = reinterpret_cast<SelStat*>(d_stat);
     u32* const list_counts = d_lists + 3 * (size_t)n_seeds;
-    if ((e = hipMemsetAsync(list_counts, 0, 12, s)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(seed_rows_kernel, dim3((n_seeds + 255) / 256), dim3(256), 0, s, d_grouped, d_hit_offset, n_seeds, d_counters, hit_cap,
                        hard_cap, soft_cap, d_rows, stat, d_n_out, d_lists, list_counts);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;

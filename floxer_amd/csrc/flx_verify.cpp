@@ -318,10 +318,24 @@ int climb_on_device(Slice& S, Lane* lane, const flx_reads* RD) {
     }
     if (nodes.empty()) nodes.push_back(DevVrNode{0xFFFFFFFFu, 0, 1, 0});
     u32 const n_queries = (u32)(2 * reads.size());
-    hvec<u32> q_first(n_queries + 1, 0);
-    hvec<DevVrAnchor> da(n);
-    hvec<u32> h_node(n);
-    hvec<u8> h_status(n);
+    // ---- one device buffer cut into the arrays of Vr2Buffers. What the host fills (anchors, nodes, the queries' first anchors, every
+    //      anchor's node and status) and what starts from a constant (the job slots: ~0, the scalars: 0) lie in front, in one image that is
+    //      built in the lane's staging block and goes up in one copy; node and status, next to each other, come back in one
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t const at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    size_t const o_anchors = take((size_t)n * sizeof(DevVrAnchor)), o_nodes = take(nodes.size() * sizeof(DevVrNode)), o_qfirst = take(((size_t)n_queries + 1) * 4),
+                 o_node = take((size_t)n * 4), o_status = take(n), o_slot = take((size_t)n * 4), o_scalars = take(VR2_SCALARS * 4), image_bytes = off,
+                 o_jobs = take((size_t)n * 2 * sizeof(DevAlignJob)), o_outs = take((size_t)n * 2 * sizeof(DevAlignOut));
+    if ((rc = lane->vr.ensure(off))) return rc;
+    char* const image = (char*)lane->stage_begin(image_bytes);
+    if (!image) return FLX_ERR_NO_DEVICE;
+    memset(image, 0, image_bytes);                              // (the gaps between the arrays as well)
+    DevVrAnchor* const da = (DevVrAnchor*)(image + o_anchors);
+    u32* const q_first = (u32*)(image + o_qfirst);
+    u32* const h_node = (u32*)(image + o_node);
+    u8* const h_status = (u8*)(image + o_status);
+    memcpy(image + o_nodes, nodes.data(), nodes.size() * sizeof(DevVrNode));
+    memset(image + o_slot, 0xFF, (size_t)n * 4);
     u32 n_climbing = 0, smallest = 0xFFFFFFFFu;
     for (u32 i = 0; i < n; ++i) {
         AnchorState const& a = A[i];
@@ -338,26 +352,13 @@ int climb_on_device(Slice& S, Lane* lane, const flx_reads* RD) {
         if (i > 0 && 2u * A[i - 1].read + A[i - 1].orientation > query) { set_error("verification rounds: anchors out of query order"); return FLX_ERR_INTERNAL; }
     }
     for (u32 qi = 0; qi < n_queries; ++qi) q_first[qi + 1] += q_first[qi];
-    // ---- one device buffer cut into the arrays of Vr2Buffers
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t const at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-    size_t const o_anchors = take((size_t)n * sizeof(DevVrAnchor)), o_nodes = take(nodes.size() * sizeof(DevVrNode)), o_qfirst = take(((size_t)n_queries + 1) * 4),
-                 o_node = take((size_t)n * 4), o_status = take(n), o_slot = take((size_t)n * 4), o_jobs = take((size_t)n * 2 * sizeof(DevAlignJob)),
-                 o_outs = take((size_t)n * 2 * sizeof(DevAlignOut)), o_scalars = take(VR2_SCALARS * 4);
     vprof.mark("anchor-table");
-    if ((rc = lane->vr.ensure(off))) return rc;
     char* const base = (char*)lane->vr.ptr;
     Vr2Buffers B{};
     B.anchors = (const DevVrAnchor*)(base + o_anchors); B.nodes = (const DevVrNode*)(base + o_nodes); B.q_first = (const u32*)(base + o_qfirst);
     B.node = (u32*)(base + o_node); B.status = (u8*)(base + o_status); B.a_slot = (u32*)(base + o_slot);
     B.jobs = (DevAlignJob*)(base + o_jobs); B.outs = (DevAlignOut*)(base + o_outs); B.scalars = (u32*)(base + o_scalars);
-    FLX_HIP(hipMemcpyAsync(base + o_anchors, da.data(), (size_t)n * sizeof(DevVrAnchor), hipMemcpyHostToDevice, lane->stream));
-    FLX_HIP(hipMemcpyAsync(base + o_nodes, nodes.data(), nodes.size() * sizeof(DevVrNode), hipMemcpyHostToDevice, lane->stream));
-    FLX_HIP(hipMemcpyAsync(base + o_qfirst, q_first.data(), ((size_t)n_queries + 1) * 4, hipMemcpyHostToDevice, lane->stream));
-    FLX_HIP(hipMemcpyAsync(base + o_node, h_node.data(), (size_t)n * 4, hipMemcpyHostToDevice, lane->stream));
-    FLX_HIP(hipMemcpyAsync(base + o_status, h_status.data(), n, hipMemcpyHostToDevice, lane->stream));
-    FLX_HIP(hipMemsetAsync(base + o_slot, 0xFF, (size_t)n * 4, lane->stream));
-    FLX_HIP(hipMemsetAsync(B.scalars, 0, VR2_SCALARS * 4, lane->stream));
+    FLX_HIP(hipMemcpyAsync(base, image, image_bytes, hipMemcpyHostToDevice, lane->stream));
     if (!lane->vr_host_scalars) FLX_HIP(hipHostMalloc((void**)&lane->vr_host_scalars, VR2_SCALARS * 4, hipHostMallocMapped));
     vprof.mark("upload");
     u64 const few_waves = align_few_waves();
@@ -415,8 +416,9 @@ int climb_on_device(Slice& S, Lane* lane, const flx_reads* RD) {
         smallest = sc[VR2_SMALLEST];
         vprof.mark("round");
     }
-    if ((rc = d2h(lane, h_status.data(), B.status, n))) return rc;
-    if ((rc = d2h(lane, h_node.data(), B.node, (size_t)n * 4))) return rc;
+    // (node and status back in one copy, over the image's own copy of them: the rounds' last wait is long past the upload)
+    if ((rc = lane->wait_idle())) return rc;
+    if (n) FLX_HIP(hipMemcpyAsync(image + o_node, base + o_node, o_status + n - o_node, hipMemcpyDeviceToHost, lane->stream));
     if ((rc = lane->sync())) return rc;
     for (u32 i = 0; i < n; ++i) {
         AnchorState& a = A[i];

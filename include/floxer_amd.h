@@ -87,7 +87,9 @@ int flx_index_copy_bwt(const flx_index* index, int reversed, uint8_t* out);
 typedef struct flx_ctx flx_ctx;
 int flx_device_count(void);                                  /* HIP devices visible to the process (0: none / no runtime) */
 int flx_ctx_create(int hip_device, const flx_index* index, flx_ctx** out);   /* uploads index + reference text to HBM */
-void flx_ctx_destroy(flx_ctx* ctx);
+/* Refused (FLX_ERR_INVALID, the context stays as it is and usable) while a read batch made on it with flx_reads_upload has not been
+ * freed: a batch hands its device buffers back to its context when it is freed. NULL: FLX_OK. */
+int flx_ctx_destroy(flx_ctx* ctx);
 /* Index replicas across the GPUs of a job (the FM index is replicated per GPU). The HBM image of an index is five
  * device buffers (occurrence table of the text, of the reversed text, suffix array, text with its guard bytes, k-mer table). A rank
  * that built or loaded the index uploads the image into buffers it owns (flx_index_image_upload), sends them to the other ranks
@@ -228,6 +230,8 @@ int flx_align_reads(flx_ctx* ctx, const flx_params* params, const uint8_t* read_
 /* The same with the reads already resident in HBM (the measured configuration of bench.py): upload once, align many times. */
 typedef struct flx_reads flx_reads;
 int flx_reads_upload(flx_ctx* ctx, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads, flx_reads** out);
+/* Free a batch only after every run on it has returned (its device buffers are reused by the next batch without a device-wide wait),
+ * and before its context is destroyed. */
 void flx_reads_free(flx_reads* reads);
 int flx_align_reads_resident(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, flx_run** out);
 

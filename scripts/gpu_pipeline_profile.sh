@@ -9,7 +9,7 @@ python3 $R/scripts/host_profile_summary.py $R/bench_out/${T}_hostprof.err 32 > $
 python3 -c "import json; d=json.load(open('$R/bench_out/${T}_hostprof.json')); print('host-profile run:', d['value'], 'reads/s')" >> $R/bench_out/${T}_host_profile.txt
 head -40 $R/bench_out/${T}_host_profile.txt
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kt
-timeout -k 10 400 rocprofv3 --kernel-trace -d /tmp/kt -o kt --output-format csv -- python3 $R/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-isolated-pass "$@" > $R/bench_out/${T}_traced.json 2> /dev/null
+timeout -k 10 400 rocprofv3 --kernel-trace -d /tmp/kt -o kt --output-format csv -- python3 $R/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-isolated-pass --no-repeat-rich-leg --no-host-inputs-leg "$@" > $R/bench_out/${T}_traced.json 2> /dev/null
 F=$(find /tmp/kt -name '*kernel_trace.csv' | head -1)
 head -1 $F > $R/bench_out/${T}_trace_header.txt; python3 $R/scripts/trace_concurrency.py $F 28 > $R/bench_out/${T}_concurrency.txt
 python3 -c "import json; d=json.load(open('$R/bench_out/${T}_traced.json')); print('traced run:', d['value'], 'reads/s')" >> $R/bench_out/${T}_concurrency.txt
