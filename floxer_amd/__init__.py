@@ -14,6 +14,7 @@ libfloxer_amd.so:
     aligner(..., partial=partial_options())   not floxer's: soft-clipped partial alignments of reads without a full one (opt-in)
     aligner(..., extend=extend_options()), extend_batch()  not floxer's: the partial records' ends extended to the break (opt-in)
     aligner(..., split=split_options()), cigar_tails()  not floxer's: reads mapped in full that carry a chimeric tail are split (opt-in)
+    aligner(..., gaps=gap_options()), left_align()  not floxer's: indels left-aligned on the device behind the traceback (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -306,10 +307,12 @@ class searcher:
 
 
 # ------------------------------------------------------------------------------------------------ seam 2: align
-def align_batch(ctx, query_pool, jobs, reference_pool=None, md=False):
+def align_batch(ctx, query_pool, jobs, reference_pool=None, md=False, gaps=None):
     """jobs: [(ref_offset, ref_length, query_offset, query_length, num_allowed_errors, mode)]. reference_pool None = the context's
     reference text (offsets are then positions in the padded concatenated text). Returns a list of None | (nm, begin, cigar);
-    md=True (flx_align_batch_md): None | (nm, begin, cigar, md) with md the MD string as bytes, None for a job without CIGAR."""
+    md=True (flx_align_batch_md): None | (nm, begin, cigar, md) with md the MD string as bytes, None for a job without CIGAR.
+    gaps: gap_options(...) (flx_align_batch_gaps): the traced paths' gaps left-aligned before the MD strings are built; None: the
+    calls above, unchanged."""
     q = as_u8(query_pool)
     arr = (capi.AlignJob * max(1, len(jobs)))()
     cap_words = 16
@@ -329,14 +332,22 @@ def align_batch(ctx, query_pool, jobs, reference_pool=None, md=False):
         refs = (capi.MdRef * max(1, len(jobs)))()
         mdp = np.zeros(cap_md, dtype=np.uint8)
         md_bytes = C.c_uint64(cap_md)
-        check(lib().flx_align_batch_md(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words),
-                                       refs, ptr(mdp, u8p), C.byref(md_bytes)))
+        if gaps is not None:
+            check(lib().flx_align_batch_gaps(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words),
+                                             refs, ptr(mdp, u8p), C.byref(md_bytes), C.byref(gaps)))
+        else:
+            check(lib().flx_align_batch_md(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words),
+                                           refs, ptr(mdp, u8p), C.byref(md_bytes)))
         out = []
         for r, m in zip(res[: len(jobs)], refs[: len(jobs)]):
             out.append((r.num_errors, r.begin, cigar_string(cig[r.cigar_offset: r.cigar_offset + r.cigar_length]),
                         mdp[m.offset: m.offset + m.length].tobytes() if m.length else None) if r.exists else None)
         return out
-    check(lib().flx_align_batch(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words)))
+    if gaps is not None:
+        check(lib().flx_align_batch_gaps(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words),
+                                         None, None, None, C.byref(gaps)))
+    else:
+        check(lib().flx_align_batch(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words)))
     out = []
     for r in res[: len(jobs)]:
         out.append((r.num_errors, r.begin, cigar_string(cig[r.cigar_offset: r.cigar_offset + r.cigar_length])) if r.exists else None)
@@ -577,6 +588,54 @@ def split_options(error_weight=0, x_drop=0, min_tail_rows=0, enable=True):
     return o
 
 
+def gap_options(left_align=True):
+    """flx_gap_options (include/floxer_amd.h): not floxer's. Every traced path's gaps are moved to the leftmost column they reach without
+    crossing an X or a gap of the other kind (the convention of VCF, minimap2 and bwa; floxer's and the default here is right-aligned),
+    on the device, before MD strings and tails are computed. Not together with without_cigar."""
+    o = capi.GapOptions()
+    o.left_align = int(bool(left_align))
+    return o
+
+
+def _left_align_call(fn, head, reference_pool, query_pool, words, jobs):
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    n_words = len(w)
+    if n_words == 0:
+        w = np.zeros(1, np.uint32)
+    q = as_u8(query_pool)
+    n_q = len(q)
+    if n_q == 0:
+        q = np.zeros(1, np.uint8)
+    if reference_pool is None:
+        rp, rl_ = None, 0
+    else:
+        ref = as_u8(reference_pool)
+        rp, rl_ = ptr(ref, u8p), len(ref)
+    arr = (capi.LeftAlignJob * max(1, len(jobs)))()
+    cap = 16
+    for i, (co, cl, ro, rl, begin, qo, ql) in enumerate(jobs):
+        arr[i] = capi.LeftAlignJob(int(co), int(cl), 0, int(ro), int(rl), int(begin), int(qo), int(ql), 0)
+        cap += 2 * int(cl)
+    out = np.zeros(cap, dtype=np.uint32)
+    n_out = C.c_uint64(cap)
+    refs = (capi.CigarRef * max(1, len(jobs)))()
+    check(fn(*head, rp, rl_, ptr(q, u8p), n_q, ptr(w, u32p), n_words, arr, len(jobs), ptr(out, u32p), C.byref(n_out), refs))
+    return [out[r.offset: r.offset + r.length].copy() for r in refs[: len(jobs)]]
+
+
+def left_align(reference_pool, query_pool, words, jobs):
+    """flx_left_align, the left-align rule on the host (floxer_amd/csrc/flx_leftalign.hpp): words = BAM CIGAR words (ops = X I D), jobs
+    = [(cigar_offset, cigar_length, ref_offset, ref_length, begin, query_offset, query_length)]: the words of the job in the word
+    pool, its reference window in reference_pool (column `begin` of it is the path's first) and its query in query_pool. Returns
+    the normalised words of every job as a list of uint32 arrays."""
+    return _left_align_call(lib().flx_left_align, (), reference_pool, query_pool, words, jobs)
+
+
+def left_align_batch(ctx, query_pool, words, jobs, reference_pool=None):
+    """flx_left_align_batch: the same words from the kernel cigar_left_align. reference_pool None = the context's reference text."""
+    return _left_align_call(lib().flx_left_align_batch, (ctx.h,), reference_pool, query_pool, words, jobs)
+
+
 TAIL_FIELDS = ("left_rows", "left_cols", "left_errors", "left_words", "right_rows", "right_cols", "right_errors", "right_words")
 
 
@@ -672,13 +731,15 @@ def _collect_run(run, n, md=False):
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None):
+    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None, gaps=None):
         """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
         string (RunResult.md), built on the device; not together with without_cigar; partial: partial_options(...), None: a read
         without a full alignment is written as unmapped (floxer's output); extend: extend_options(...), None: a partial record ends at
         its PEX node's boundary (needs partial); split: split_options(...), None: a read mapped in full is one record whatever its
-        ends look like (needs partial and output_options(max_alignments=1))"""
+        ends look like (needs partial and output_options(max_alignments=1)); gaps: gap_options(...), None: gaps stay right-aligned
+        (floxer's output)"""
         self.ctx, self.params, self.output, self.md, self.partial, self.extend, self.split = ctx, p, output, bool(md), partial, extend, split
+        self.gaps = gaps
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
@@ -690,10 +751,12 @@ class aligner:
             if getattr(self, name) is not None:
                 setattr(bundle, name, C.pointer(getattr(self, name)))
         split = C.byref(self.split) if self.split is not None else None
+        gaps = C.byref(self.gaps) if self.gaps is not None else None
         if isinstance(reads, resident_reads):
             n = reads.n
-            check(lib().flx_align_reads_resident_split(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, C.byref(run)))
+            check(lib().flx_align_reads_resident_gaps(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, gaps, C.byref(run)))
         else:
             pool, offs, n = _pool_and_offsets(reads)
-            check(lib().flx_align_reads_split(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, C.byref(run)))
+            check(lib().flx_align_reads_gaps(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, gaps,
+                                             C.byref(run)))
         return _collect_run(run, n, md=self.md)

@@ -103,6 +103,20 @@ class SplitOptions(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class GapOptions(C.Structure):
+    _fields_ = [("left_align", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class LeftAlignJob(C.Structure):
+    _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("reserved", C.c_uint32), ("ref_offset", C.c_uint64),
+                ("ref_length", C.c_uint32), ("begin", C.c_uint32), ("query_offset", C.c_uint64), ("query_length", C.c_uint32),
+                ("reserved2", C.c_uint32)]
+
+
+class CigarRef(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -160,7 +174,7 @@ EXPORTED = [
     "flx_align_reads_with_tags", "flx_align_reads_resident_with_tags", "flx_run_num_md_bytes", "flx_run_copy_md", "flx_align_batch_md",
     "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
     "flx_extend_batch", "flx_sam_set_sa", "flx_align_reads_split", "flx_align_reads_resident_split", "flx_cigar_tails", "flx_cigar_tails_batch",
-    "flx_align_shapes",
+    "flx_align_shapes", "flx_align_reads_gaps", "flx_align_reads_resident_gaps", "flx_align_batch_gaps", "flx_left_align", "flx_left_align_batch",
 ]
 
 _lib = None
@@ -261,6 +275,15 @@ def lib():
                                         C.POINTER(C.c_void_p)]
     L.flx_align_reads_resident_split.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(RunOptions), C.POINTER(SplitOptions),
                                                  C.POINTER(C.c_void_p)]
+    L.flx_align_reads_gaps.argtypes = [C.c_void_p, C.POINTER(Params), u8p, u64p, C.c_uint64, C.POINTER(RunOptions), C.POINTER(SplitOptions),
+                                       C.POINTER(GapOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_gaps.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(RunOptions), C.POINTER(SplitOptions),
+                                                C.POINTER(GapOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_batch_gaps.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(AlignJob), C.c_uint64,
+                                       C.POINTER(AlignResult), u32p, u64p, C.POINTER(MdRef), u8p, u64p, C.POINTER(GapOptions)]
+    L.flx_left_align.argtypes = [u8p, C.c_uint64, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(LeftAlignJob), C.c_uint64, u32p, u64p,
+                                 C.POINTER(CigarRef)]
+    L.flx_left_align_batch.argtypes = [C.c_void_p] + L.flx_left_align.argtypes
     L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]

@@ -72,6 +72,7 @@ struct Options {
     uint64_t partial_extend_weight = 0, partial_extend_xdrop = 0, partial_extend_max_errors = 0;   // 0: the library's defaults
     bool split_tails = false;
     uint64_t split_tails_weight = 0, split_tails_xdrop = 0, split_tails_min_rows = 0;               // 0: the library's defaults
+    bool left_align_indels = false;
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -106,6 +107,8 @@ const OptDef OPTS[] = {
     {0, "split-tails-weight", false, "not floxer's: rows one error costs in the tail score (default 4); needs --split-tails"},
     {0, "split-tails-xdrop", false, "not floxer's: a tail exists once the score fell this far below its maximum (default 100); needs --split-tails"},
     {0, "split-tails-min-rows", false, "not floxer's: the fewest query bases of a tail (default 100); needs --split-tails"},
+    // nor this: every CIGAR's gaps moved to the first copy of a homopolymer or repeat instead of the last (flx_gap_options)
+    {0, "left-align-indels", true, "opt-in, not floxer's: left-align the indels of every CIGAR (on the GPU behind the traceback; MD and split tails follow), as VCF, minimap2 and bwa do; not with -w"},
 };
 
 struct CliError { std::string msg; };
@@ -211,6 +214,7 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "partial-extend-max-errors") { o.partial_extend_max_errors = parse_u64(n, value); range_check(n, (double)o.partial_extend_max_errors, 1, 4093); }
         else if (n == "sa-tag") o.sa_tag = true;
         else if (n == "split-tails") o.split_tails = true;
+        else if (n == "left-align-indels") o.left_align_indels = true;
         else if (n == "split-tails-weight") { o.split_tails_weight = parse_u64(n, value); range_check(n, (double)o.split_tails_weight, 1, 65535); }
         else if (n == "split-tails-xdrop") { o.split_tails_xdrop = parse_u64(n, value); range_check(n, (double)o.split_tails_xdrop, 1, 1073741824); }
         else if (n == "split-tails-min-rows") { o.split_tails_min_rows = parse_u64(n, value); range_check(n, (double)o.split_tails_min_rows, 1, 524287); }
@@ -247,6 +251,7 @@ Options parse_cli(int argc, char** argv) {
     if (o.split_tails && o.without_cigar) throw CliError{"The option --split-tails needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     if (!o.split_tails && (o.split_tails_weight || o.split_tails_xdrop || o.split_tails_min_rows))
         throw CliError{"The options --split-tails-weight, --split-tails-xdrop and --split-tails-min-rows need --split-tails."};
+    if (o.left_align_indels && o.without_cigar) throw CliError{"The option --left-align-indels needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     return o;
 }
 
@@ -662,6 +667,9 @@ int main(int argc, char** argv) {
     split_opt.error_weight = (uint32_t)o.split_tails_weight;
     split_opt.x_drop = (uint32_t)o.split_tails_xdrop;
     split_opt.min_tail_rows = (uint32_t)o.split_tails_min_rows;
+    flx_gap_options gap_opt;
+    memset(&gap_opt, 0, sizeof(gap_opt));
+    gap_opt.left_align = o.left_align_indels;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -692,7 +700,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads_split(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &run);
+        f.rc = flx_align_reads_gaps(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &gap_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));

@@ -13,6 +13,7 @@
 #include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
 #include "flx_tails.hpp"
+#include "flx_leftalign.hpp"
 
 namespace flx {
 
@@ -262,10 +263,14 @@ struct TracePlan {
 // in between), and the bytes come back with the CIGAR words. A job's CIGAR slab holds 2 NM + 2 words and its MD slab md_slab_bytes(NM)
 // bytes, NM being what K4 returned for it; the slabs are kept as they are (gaps included): no host repacking. The paths' tails
 // (flx_tails.hip) when wanted: one tail job per trace job as well, cigar_tails queued behind K5 (behind md_build if both are on), its
-// 32-byte results back with the CIGAR words.
+// 32-byte results back with the CIGAR words. Left-aligned gaps (flx_leftalign.hip) when wanted: one job per trace job again,
+// cigar_left_align queued between K5 and md_build; it writes the normalised words into a second slab buffer of the same layout and
+// rewrites K5's DevTraceOuts, and everything behind it (md_build, cigar_tails, the copy back) takes that buffer instead of K5's.
 struct Traceback {
     bool const want_md;
     const TailParams* const want_tails;
+    const u8* const d_la_query;                                // null: gaps stay where K5 put them
+    bool const want_left_align;
     PhaseTimer* const prof;
     hvec<DevTraceJob> jobs;
     hvec<DevTraceOut> outs;
@@ -273,9 +278,12 @@ struct Traceback {
     hvec<DevMdOut> md_outs;
     hvec<DevTailJob> tail_jobs;
     hvec<DevTailOut> tail_outs;
+    hvec<DevLeftAlignJob> la_jobs;
+    hvec<DevLeftAlignStat> la_stats;
     u64 cigar_words = 0, path_steps = 0, md_bytes = 0;
     size_t cigar_base = 0, md_base = 0;                        // where this batch's slabs start in the host pools
-    explicit Traceback(bool md, const TailParams* tails, PhaseTimer* prof_ = nullptr) : want_md(md), want_tails(tails), prof(prof_) {}
+    explicit Traceback(bool md, const TailParams* tails, const u8* d_la_query_, PhaseTimer* prof_ = nullptr)
+        : want_md(md), want_tails(tails), d_la_query(d_la_query_), want_left_align(d_la_query_ != nullptr), prof(prof_) {}
     // the path that ends at end_col of the last row of r's DP, whose trace planes lie at trace_off; returns the trace job's index
     u32 add(AlignRequest const& r, u64 trace_off, AlignShape sh, u32 end_col, u32 nm) {
         u32 const j = (u32)jobs.size(), cap = 2 * nm + 2;      // runs <= 2*NM + 1
@@ -286,6 +294,7 @@ struct Traceback {
             md_bytes += slab;
         }
         if (want_tails) tail_jobs.push_back(DevTailJob{cigar_words, j, want_tails->w, want_tails->x_drop, want_tails->min_rows});
+        if (want_left_align) la_jobs.push_back(DevLeftAlignJob{r.ref_off, r.q_off, cigar_words, cigar_words, r.n, r.m, cap, j});      // (<= 2 NM + 1 words after it too)
         cigar_words += cap;
         path_steps += (u64)r.m + nm;
         return j;
@@ -294,20 +303,23 @@ struct Traceback {
         cigar_base = cigar_pool.size();
         if (jobs.empty()) return FLX_OK;
         int rc;
-        // the job tables (trace, MD, tails) up in one copy, packed in the lane's staging block
+        // the job tables (trace, MD, tails, left-align) up in one copy, packed in the lane's staging block
         auto const up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-        size_t const b_jobs = jobs.size() * sizeof(DevTraceJob), b_md = md_jobs.size() * sizeof(DevMdJob), b_tail = tail_jobs.size() * sizeof(DevTailJob);
-        size_t const o_md = up(b_jobs), o_tail = o_md + up(b_md), b_tables = o_tail + b_tail;
+        size_t const b_jobs = jobs.size() * sizeof(DevTraceJob), b_md = md_jobs.size() * sizeof(DevMdJob), b_tail = tail_jobs.size() * sizeof(DevTailJob),
+                     b_la = la_jobs.size() * sizeof(DevLeftAlignJob);
+        size_t const o_md = up(b_jobs), o_tail = o_md + up(b_md), o_la = o_tail + up(b_tail), b_tables = b_la ? o_la + b_la : o_tail + b_tail;
         if ((rc = lane->tjobs.ensure(b_tables + 16))) return rc;
         char* const h = (char*)lane->stage_begin(b_tables);
         if (!h) return FLX_ERR_NO_DEVICE;
         memcpy(h, jobs.data(), b_jobs);
         if (b_md) memcpy(h + o_md, md_jobs.data(), b_md);
         if (b_tail) memcpy(h + o_tail, tail_jobs.data(), b_tail);
+        if (b_la) memcpy(h + o_la, la_jobs.data(), b_la);
         FLX_HIP(hipMemcpyAsync(lane->tjobs.ptr, h, b_tables, hipMemcpyHostToDevice, lane->stream));
         const DevTraceJob* const d_jobs = lane->tjobs.as<DevTraceJob>();
         const DevMdJob* const d_md_jobs = (const DevMdJob*)((char*)lane->tjobs.ptr + o_md);
         const DevTailJob* const d_tail_jobs = (const DevTailJob*)((char*)lane->tjobs.ptr + o_tail);
+        const DevLeftAlignJob* const d_la_jobs = (const DevLeftAlignJob*)((char*)lane->tjobs.ptr + o_la);
         if ((rc = lane->tjob_out.ensure(jobs.size() * sizeof(DevTraceOut)))) return rc;
         if ((rc = lane->cigar.ensure(cigar_words * 4 + 16))) return rc;
         if (want_md) {
@@ -315,33 +327,49 @@ struct Traceback {
             if ((rc = lane->md.ensure(md_bytes + 16))) return rc;
         }
         if (want_tails && (rc = lane->tail_out.ensure(tail_jobs.size() * sizeof(DevTailOut)))) return rc;
+        if (want_left_align) {
+            if ((rc = lane->cigar_la.ensure(cigar_words * 4 + 16))) return rc;
+            if ((rc = lane->la_stat.ensure(la_jobs.size() * sizeof(DevLeftAlignStat)))) return rc;
+        }
+        // the words everything behind K5 reads: K5's, or the normalised ones
+        u32* const d_words = want_left_align ? lane->cigar_la.as<u32>() : lane->cigar.as<u32>();
         // The small result tables (16 bytes per path, MD lengths, tails) come back through the lane's mapped result block when it holds them
-        // all: K5 stores its DevTraceOuts there itself when nothing on the device reads them; md_build and cigar_tails read them, so with
-        // either they stay on the device and one publish_stage launch behind the stage hands all the tables over.
+        // all: K5 stores its DevTraceOuts there itself when nothing on the device reads them; md_build, cigar_tails and cigar_left_align read them, so with
+        // any of them they stay on the device and one publish_stage launch behind the stage hands all the tables over.
         outs.resize(jobs.size());
         md_outs.resize(md_jobs.size());
         tail_outs.resize(tail_jobs.size());
+        la_stats.resize(la_jobs.size());
         DevTraceOut* r_outs = (DevTraceOut*)lane->result_slot(outs.size() * sizeof(DevTraceOut));
         DevMdOut* r_md = want_md ? (DevMdOut*)lane->result_slot(md_outs.size() * sizeof(DevMdOut)) : nullptr;
         DevTailOut* r_tail = want_tails ? (DevTailOut*)lane->result_slot(tail_outs.size() * sizeof(DevTailOut)) : nullptr;
-        bool const mapped = r_outs && (!want_md || r_md) && (!want_tails || r_tail);
-        bool const direct = mapped && !want_md && !want_tails;
+        DevLeftAlignStat* r_la = want_left_align ? (DevLeftAlignStat*)lane->result_slot(la_stats.size() * sizeof(DevLeftAlignStat)) : nullptr;
+        bool const mapped = r_outs && (!want_md || r_md) && (!want_tails || r_tail) && (!want_left_align || r_la);
+        bool const direct = mapped && !want_md && !want_tails && !want_left_align;
         DevTraceOut* const d_outs = direct ? r_outs : lane->tjob_out.as<DevTraceOut>();
         rc = timed_launch(lane, "ed_traceback", path_steps * 18, path_steps, [&] {
             return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), d_jobs, (u32)jobs.size(), lane->cigar.as<u32>(), d_outs);
         });
         if (rc) return rc;
+        if (want_left_align) {
+            // (the words it reads and writes and the letters it compares are known once its results are back: they are added below)
+            rc = timed_launch(lane, "cigar_left_align", la_jobs.size() * (sizeof(DevLeftAlignJob) + 2 * sizeof(DevTraceOut) + sizeof(DevLeftAlignStat)), 0, [&] {
+                return DeviceApi::cigar_left_align(lane->stream, d_text, d_la_query, lane->cigar.as<u32>(), d_outs, d_la_jobs, (u32)la_jobs.size(), d_words,
+                                                   lane->la_stat.as<DevLeftAlignStat>());
+            });
+            if (rc) return rc;
+        }
         if (want_md) {
             // (its algorithmic bytes depend on what K5 finds: they are added below once the lengths are back)
             rc = timed_launch(lane, "md_build", 0, md_jobs.size(), [&] {
-                return DeviceApi::md_build(lane->stream, d_text, lane->cigar.as<u32>(), d_outs, d_md_jobs, (u32)md_jobs.size(), lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
+                return DeviceApi::md_build(lane->stream, d_text, d_words, d_outs, d_md_jobs, (u32)md_jobs.size(), lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
             });
             if (rc) return rc;
         }
         if (want_tails) {
             // (the CIGAR words it reads are known once K5's lengths are back: they are added below)
             rc = timed_launch(lane, "cigar_tails", tail_jobs.size() * (sizeof(DevTailJob) + sizeof(DevTraceOut) + sizeof(DevTailOut)), tail_jobs.size(), [&] {
-                return DeviceApi::cigar_tails(lane->stream, lane->cigar.as<u32>(), d_outs, d_tail_jobs, (u32)tail_jobs.size(), lane->tail_out.as<DevTailOut>());
+                return DeviceApi::cigar_tails(lane->stream, d_words, d_outs, d_tail_jobs, (u32)tail_jobs.size(), lane->tail_out.as<DevTailOut>());
             });
             if (rc) return rc;
         }
@@ -350,6 +378,7 @@ struct Traceback {
             pub.add(lane->tjob_out.ptr, r_outs, outs.size() * sizeof(DevTraceOut) / 4);
             if (want_md) pub.add(lane->md_out.ptr, r_md, md_outs.size() * sizeof(DevMdOut) / 4);
             if (want_tails) pub.add(lane->tail_out.ptr, r_tail, tail_outs.size() * sizeof(DevTailOut) / 4);
+            if (want_left_align) pub.add(lane->la_stat.ptr, r_la, la_stats.size() * sizeof(DevLeftAlignStat) / 4);
             int const e = DeviceApi::publish_stage(lane->stream, pub);
             if (e) { set_error(std::string("publish_stage: ") + hipGetErrorString((hipError_t)e)); return FLX_ERR_NO_DEVICE; }
         }
@@ -357,7 +386,7 @@ struct Traceback {
         cigar_pool.resize(cigar_base + cigar_words);
         if (prof) prof->mark("pool-resize");
         if (!mapped && (rc = d2h(lane, outs.data(), lane->tjob_out.ptr, outs.size() * sizeof(DevTraceOut)))) return rc;
-        if ((rc = d2h(lane, cigar_pool.data() + cigar_base, lane->cigar.ptr, cigar_words * 4))) return rc;
+        if ((rc = d2h(lane, cigar_pool.data() + cigar_base, d_words, cigar_words * 4))) return rc;
         if (want_md) {
             md_base = md_pool->size();
             md_pool->resize(md_base + md_bytes);
@@ -365,15 +394,23 @@ struct Traceback {
             if ((rc = d2h(lane, md_pool->data() + md_base, lane->md.ptr, md_bytes))) return rc;
         }
         if (want_tails && !mapped && (rc = d2h(lane, tail_outs.data(), lane->tail_out.ptr, tail_outs.size() * sizeof(DevTailOut)))) return rc;
+        if (want_left_align && !mapped && (rc = d2h(lane, la_stats.data(), lane->la_stat.ptr, la_stats.size() * sizeof(DevLeftAlignStat)))) return rc;
         if ((rc = lane->sync())) return rc;
         if (mapped) {
             memcpy(outs.data(), r_outs, outs.size() * sizeof(DevTraceOut));
+            if (want_left_align) memcpy(la_stats.data(), r_la, la_stats.size() * sizeof(DevLeftAlignStat));
             if (want_md) memcpy(md_outs.data(), r_md, md_outs.size() * sizeof(DevMdOut));
             if (want_tails) memcpy(tail_outs.data(), r_tail, tail_outs.size() * sizeof(DevTailOut));
         }
         if (prof) prof->mark("K5+d2h");
         for (auto const& t : outs)
-            if (t.cigar_len == 0xFFFFFFFFu) { set_error("ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+            if (t.cigar_len == 0xFFFFFFFFu) { set_error(want_left_align ? "ed_traceback / cigar_left_align: CIGAR slab overflow" : "ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+        if (want_left_align) {
+            // CIGAR words read and written + letters compared (both sides of every comparison); units: the gap words that moved or merged
+            u64 bytes = 0, moved = 0;
+            for (size_t j = 0; j < la_jobs.size(); ++j) { bytes += 4ull * la_stats[j].words_in + 4ull * outs[j].cigar_len + 2ull * la_stats[j].letters; moved += la_stats[j].moved; }
+            lane->ctx->account_more("cigar_left_align", bytes, moved);
+        }
         if (want_md) {
             // CIGAR words read + reference letters read (one per X / D column: at most NM) + MD bytes written
             u64 bytes = 0;
@@ -406,7 +443,7 @@ struct Traceback {
 
 // score, begin position and CIGAR (and MD string, when md_pool is given) for every (distinct) request
 int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
+                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer tprof("trace-jobs");
@@ -438,7 +475,7 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         tprof.mark("K4");
 
         // ---- traceback for the jobs that have an alignment within k
-        Traceback tb(md_pool != nullptr, tails, &tprof);
+        Traceback tb(md_pool != nullptr, tails, d_la_query, &tprof);
         hvec<u32> tjob_req;
         for (size_t c = 0; c < count; ++c) {
             if (outs[c].score == 0xFFFFFFFFu) continue;
@@ -462,9 +499,9 @@ int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequ
 
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
 int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails);
+        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query);
     });
 }
 
@@ -601,7 +638,7 @@ namespace {
 
 // the union form over distinct requests (n_requests: with their duplicates, for the debug line)
 int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& uniq, size_t n_requests,
-                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
+                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
     bool usable = !uniq.empty() && !getenv("FLX_NO_UNION");
     for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
     // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
@@ -634,7 +671,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
             members.push_back(id);
         }
     }
-    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails);      // nothing to share: the plain path
+    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query);      // nothing to share: the plain path
 
     ures.assign(uniq.size(), TraceResult{});
     hvec<AlignRequest> ureqs(unions.size());
@@ -709,7 +746,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         if (wouts_in_place) memcpy(wouts.data(), d_wouts, n_wins * sizeof(DevAlignOut));
 
         // ---- one traceback per distinct (union, end column); the members of a union share its trace job's CIGAR words and MD string
-        Traceback tb(md_pool != nullptr, tails);
+        Traceback tb(md_pool != nullptr, tails, d_la_query);
         hvec<u32> win_tjob(n_wins, 0xFFFFFFFFu);
         for (size_t w0 = 0; w0 < n_wins;) {                     // windows of one union are consecutive
             size_t w1 = w0;
@@ -742,7 +779,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
     }
     if (!fallback.empty()) {
         hvec<TraceResult> fres;
-        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails))) return rc;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails, d_la_query))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
     if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu traceback jobs %zu unions with several jobs %zu\n", n_requests, uniq.size(), unions.size(), fallback.size(), n_tjobs, n_unions_several_jobs);
@@ -752,9 +789,9 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
 }  // namespace
 
 int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails) {
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails);
+        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails, d_la_query);
     });
 }
 
@@ -801,6 +838,37 @@ int run_tail_jobs(Lane* lane, const u32* words, u64 n_words, hvec<DevTraceOut> c
     if (rc) return rc;
     if ((rc = d2h(lane, outs.data(), lane->tail_out.ptr, outs.size() * sizeof(DevTailOut)))) return rc;
     return lane->sync();
+}
+
+// One cigar_left_align launch over CIGAR words and DevTraceOuts made on the host: the kernel alone (the pipeline queues it behind K5).
+int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts,
+                        hvec<DevLeftAlignJob> const& jobs, u64 words_out, hvec<u32>& out_words) {
+    out_words.assign(words_out, 0u);
+    if (jobs.empty()) return FLX_OK;
+    int rc;
+    if ((rc = h2d(lane, lane->cigar, words, n_words * 4))) return rc;
+    if ((rc = h2d(lane, lane->tjob_out, touts.data(), touts.size() * sizeof(DevTraceOut)))) return rc;
+    if ((rc = h2d(lane, lane->la_jobs, jobs.data(), jobs.size() * sizeof(DevLeftAlignJob)))) return rc;
+    if ((rc = lane->cigar_la.ensure(words_out * 4 + 16))) return rc;
+    if ((rc = lane->la_stat.ensure(jobs.size() * sizeof(DevLeftAlignStat)))) return rc;
+    rc = timed_launch(lane, "cigar_left_align", jobs.size() * (sizeof(DevLeftAlignJob) + 2 * sizeof(DevTraceOut) + sizeof(DevLeftAlignStat)), 0, [&] {
+        return DeviceApi::cigar_left_align(lane->stream, d_text, d_query, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->la_jobs.as<DevLeftAlignJob>(),
+                                           (u32)jobs.size(), lane->cigar_la.as<u32>(), lane->la_stat.as<DevLeftAlignStat>());
+    });
+    if (rc) return rc;
+    hvec<DevLeftAlignStat> stats(jobs.size());
+    if ((rc = d2h(lane, touts.data(), lane->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
+    if ((rc = d2h(lane, out_words.data(), lane->cigar_la.ptr, words_out * 4))) return rc;
+    if ((rc = d2h(lane, stats.data(), lane->la_stat.ptr, stats.size() * sizeof(DevLeftAlignStat)))) return rc;
+    if ((rc = lane->sync())) return rc;
+    u64 bytes = 0, moved = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        if (touts[j].cigar_len == 0xFFFFFFFFu) { set_error("cigar_left_align: CIGAR slab overflow, or a path that leaves its window or its query"); return FLX_ERR_INTERNAL; }
+        bytes += 4ull * stats[j].words_in + 4ull * touts[j].cigar_len + 2ull * stats[j].letters;
+        moved += stats[j].moved;
+    }
+    lane->ctx->account_more("cigar_left_align", bytes, moved);
+    return FLX_OK;
 }
 
 int build_peq(Lane* ctx, const u8* d_seq, u64 len, DeviceBuffer& peq) {
@@ -880,13 +948,20 @@ extern "C" int flx_align_shapes(const flx_align_job* jobs, uint64_t n_jobs, flx_
 extern "C" int flx_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
                                uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                                uint32_t* cigar_pool, uint64_t* cigar_pool_words) {
-    return flx_align_batch_md(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, nullptr, nullptr, nullptr);
+    return flx_align_batch_gaps(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, nullptr, nullptr, nullptr, nullptr);
 }
-// out_md == NULL: no MD strings (flx_align_batch)
 extern "C" int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
                                   uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                                   uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes) {
-    std::string const fn = out_md ? "flx_align_batch_md" : "flx_align_batch";        // (flx_align_batch forwards here)
+    return flx_align_batch_gaps(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, out_md, md_pool, md_pool_bytes, nullptr);
+}
+// out_md == NULL: no MD strings (flx_align_batch); gaps NULL or zeroed: the gaps stay where K5 put them (flx_align_batch_md)
+extern "C" int flx_align_batch_gaps(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
+                                    uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
+                                    uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes,
+                                    const flx_gap_options* gaps) {
+    std::string const fn = gap_options_active(gaps) ? "flx_align_batch_gaps" : out_md ? "flx_align_batch_md" : "flx_align_batch";        // (both forward here)
+    if (!gap_options_valid(gaps)) return FLX_ERR_INVALID;
     if (out_md && !md_pool_bytes) { set_error(fn + ": null argument"); return FLX_ERR_INVALID; }
     uint64_t const md_pool_cap = md_pool_bytes ? *md_pool_bytes : 0;
     if (md_pool_bytes) *md_pool_bytes = 0;                                            // (out: bytes used, also on an early return)
@@ -950,7 +1025,7 @@ extern "C" int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_
     hvec<TraceResult> tres;
     hvec<u32> cig;
     hvec<u8> mdp;
-    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig, out_md ? &mdp : nullptr))) return rc;
+    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig, out_md ? &mdp : nullptr, nullptr, gap_options_active(gaps) ? L->seq.as<u8>() : nullptr))) return rc;
     uint64_t const cap = cigar_pool_words ? *cigar_pool_words : 0;
     if (cigar_pool_words) *cigar_pool_words = cig.size();
     if (any_trace && (!cigar_pool || cig.size() > cap)) { set_error("cigar pool too small"); return FLX_ERR_CAPACITY; }
@@ -1020,5 +1095,51 @@ extern "C" int flx_cigar_tails_batch(flx_ctx* ctx, const uint32_t* cigar_words, 
     hvec<DevTailOut> outs;
     if (int const rc = run_tail_jobs(lease.lane, cigar_words, n_words, touts, dj, outs)) return rc;
     for (uint64_t i = 0; i < n_jobs; ++i) memcpy(&out[i], &outs[i], sizeof(flx_tail_result));
+    return FLX_OK;
+}
+
+// ================================================================================================ C ABI: the left-align kernel alone
+extern "C" int flx_left_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                                    const uint32_t* cigar_words, uint64_t n_words, const flx_left_align_job* jobs, uint64_t n_jobs, uint32_t* out_words,
+                                    uint64_t* out_n_words, flx_cigar_ref* out) {
+    if (!ctx || !out_n_words || (n_jobs && (!jobs || !out)) || (n_words && !cigar_words) || (query_pool_len && !query_pool)) {
+        set_error("flx_left_align_batch: null argument"); return FLX_ERR_INVALID;
+    }
+    uint64_t const out_cap = *out_n_words;
+    *out_n_words = 0;
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    u64 const text_len = ref_pool ? ref_pool_len : ctx->hidx->n;
+    if (!left_align_jobs_valid(text_len, query_pool_len, cigar_words, n_words, jobs, n_jobs, "flx_left_align_batch")) return FLX_ERR_INVALID;      // (before any launch)
+    hvec<DevTraceOut> touts(n_jobs);
+    hvec<DevLeftAlignJob> dj(n_jobs);
+    u64 slab_words = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_left_align_job const& j = jobs[i];
+        u64 const cap = left_align_cap(cigar_words + j.cigar_offset, j.cigar_length);
+        touts[i] = DevTraceOut{j.begin, 0, j.cigar_length, 0};
+        dj[i] = DevLeftAlignJob{j.ref_offset, j.query_offset, j.cigar_offset, slab_words, j.ref_length, j.query_length, (u32)cap, (u32)i};
+        slab_words += cap;
+    }
+    FLX_HIP(hipSetDevice(ctx->device));
+    int rc;
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    Lane* L = lease.lane;
+    hvec<u32> slabs;
+    if (n_jobs) {
+        const u8* d_text = ctx->didx.text;
+        if (ref_pool && (rc = upload_padded(L, L->user_text, ref_pool, ref_pool_len, &d_text))) return rc;
+        if ((rc = h2d(L, L->seq, query_pool, query_pool_len, 192))) return rc;
+        if ((rc = run_left_align_jobs(L, d_text, L->seq.as<u8>(), cigar_words, n_words, touts, dj, slab_words, slabs))) return rc;
+    }
+    u64 used = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) used += touts[i].cigar_len;
+    *out_n_words = used;
+    if (used > out_cap || (used && !out_words)) { set_error("flx_left_align_batch: the output word pool is too small"); return FLX_ERR_CAPACITY; }
+    used = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) {                   // the slabs packed in job order
+        if (touts[i].cigar_len) memcpy(out_words + used, slabs.data() + dj[i].out_off + touts[i].cigar_start, 4ull * touts[i].cigar_len);
+        out[i] = flx_cigar_ref{used, touts[i].cigar_len, 0};
+        used += touts[i].cigar_len;
+    }
     return FLX_OK;
 }

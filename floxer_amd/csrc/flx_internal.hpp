@@ -187,6 +187,18 @@ struct DevTailJob {
 struct DevTailOut { u32 left_rows, left_cols, left_errors, left_words, right_rows, right_cols, right_errors, right_words; };   // = flx_tail_result
 static_assert(sizeof(DevTailOut) == 32 && sizeof(DevTailOut) == sizeof(flx_tail_result), "one 32-byte result per job");
 
+// ---- left-aligned gaps of traced paths (flx_leftalign.hip; the rule: flx_leftalign.hpp), one job per trace job: the kernel reads that
+// job's DevTraceOut and CIGAR words where K5 left them, writes the normalised words into a second slab and rewrites the DevTraceOut
+// (cigar_start 0, the new cigar_len, or 0xFFFFFFFF: the slab was too small, or the path leaves its window or its query)
+struct DevLeftAlignJob {
+    u64 ref_off, q_off;                            // the trace job's window in the text and its query in the query pool
+    u64 cigar_off, out_off;                        // the trace job's CIGAR slab and this job's slab in the second buffer (words)
+    u32 n, m;                                      // columns of the window, rows of the query: nothing is read beyond them
+    u32 out_cap;                                   // words of the second slab
+    u32 out_index;                                 // the trace job's DevTraceOut and this job's DevLeftAlignStat
+};
+struct DevLeftAlignStat { u32 words_in, letters, gaps, moved; };   // words read, letters compared (per sequence), gap words, gap words that moved or merged
+
 // ---- extension of a partial record's end (flx_extend.hip): one job per end, one wave per job
 struct DevExtendJob {
     u64 text_pos, q_pos;        // the first column's symbol in the device text, the first row's symbol in the device query pool
@@ -410,6 +422,9 @@ struct DeviceApi {
                         u8* d_md, DevMdOut* d_out);
     // flx_tails.hip: the tails of every job's path (flx_tails.hpp) from the CIGAR words and DevTraceOut that `traceback` left
     static int cigar_tails(void* stream, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevTailJob* d_jobs, u32 n_jobs, DevTailOut* d_out);
+    // flx_leftalign.hip: the words of every job normalised into d_cigar_out, the job's DevTraceOut rewritten to describe them
+    static int cigar_left_align(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, DevTraceOut* d_trace_out, const DevLeftAlignJob* d_jobs,
+                                u32 n_jobs, u32* d_cigar_out, DevLeftAlignStat* d_stats);
     // flx_extend.hip: lds_d = the largest min(d_max, row_limit) of the jobs (the launch's LDS: extend_lds_bytes(lds_d) <= 64 KiB)
     static size_t extend_lds_bytes(u32 d_max);
     static int extend(void* stream, const u8* d_text, const u8* d_query, const DevExtendJob* d_jobs, u32 n_jobs, u32 lds_d, DevExtendOut* d_out);

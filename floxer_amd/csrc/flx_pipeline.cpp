@@ -13,6 +13,7 @@
 #include "flx_pipeline.hpp"
 #include "flx_select.hpp"
 #include "flx_tails.hpp"
+#include "flx_leftalign.hpp"
 
 using namespace flx;
 
@@ -143,7 +144,9 @@ extern "C" int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* P, c
     return flx_align_reads_with_tags(ctx, P, read_pool, read_offsets, n_reads, O, nullptr, out);
 }
 // md and the partial alignments need the trace: refused together with without_cigar, before any work
-static bool run_options_valid(const flx_params* P, const flx_run_options* R, const flx_split_options* S) {
+static bool run_options_valid(const flx_params* P, const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G) {
+    if (!gap_options_valid(G)) return false;
+    if (gap_options_active(G) && P && P->without_cigar) { set_error("flx_gap_options.left_align needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (!split_options_valid(S)) return false;
     if (split_options_active(S)) {
         if (P && P->without_cigar) { set_error("flx_split_options.enable needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
@@ -169,11 +172,15 @@ extern "C" int flx_align_reads_opt(flx_ctx* ctx, const flx_params* P, const uint
 }
 extern "C" int flx_align_reads_split(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
                                      const flx_run_options* R, const flx_split_options* S, flx_run** out) {
-    if (!run_options_valid(P, R, S)) return FLX_ERR_INVALID;
+    return flx_align_reads_gaps(ctx, P, read_pool, read_offsets, n_reads, R, S, nullptr, out);
+}
+extern "C" int flx_align_reads_gaps(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                                    const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, flx_run** out) {
+    if (!run_options_valid(P, R, S, G)) return FLX_ERR_INVALID;
     flx_reads* rd = nullptr;
     int rc = flx_reads_upload(ctx, read_pool, read_offsets, n_reads, &rd);
     if (rc) return rc;
-    rc = flx_align_reads_resident_split(ctx, P, rd, R, S, out);
+    rc = flx_align_reads_resident_gaps(ctx, P, rd, R, S, G, out);
     flx_reads_free(rd);
     return rc;
 }
@@ -195,13 +202,18 @@ extern "C" int flx_align_reads_resident_opt(flx_ctx* ctx, const flx_params* P, c
 }
 extern "C" int flx_align_reads_resident_split(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R,
                                               const flx_split_options* S, flx_run** out) {
-    if (!run_options_valid(P, R, S)) return FLX_ERR_INVALID;
+    return flx_align_reads_resident_gaps(ctx, P, RD, R, S, nullptr, out);
+}
+extern "C" int flx_align_reads_resident_gaps(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R,
+                                             const flx_split_options* S, const flx_gap_options* G, flx_run** out) {
+    if (!run_options_valid(P, R, S, G)) return FLX_ERR_INVALID;
     RunOptions opt{};                            // (a NULL bundle, a NULL member and a zeroed struct are the same: that option is off)
     if (R && R->output) opt.output = *R->output;
     if (R && R->tags) opt.tags = *R->tags;
     if (R && R->partial) opt.partial = *R->partial;
     if (R && R->extend) opt.extend = *R->extend;
     if (S) opt.split = *S;
+    if (G) opt.gaps = *G;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }

@@ -121,12 +121,18 @@ u64 align_few_waves();          // FLX_ALIGN_FEW_WAVES overrides the threshold (
 int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, const char* kernel_name);
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates).
 // md_pool != null: the MD string of every traced path as well (flx_md.hip), its bytes in md_pool (shared like the CIGAR words);
-// tails != null: the tails of every traced path as well (flx_tails.hip), in TraceResult::tail
+// tails != null: the tails of every traced path as well (flx_tails.hip), in TraceResult::tail;
+// d_la_query != null: the device query pool's letters (q_off addresses them as it does the Peq planes), and every traced path's gaps are
+// left-aligned behind K5 (flx_leftalign.hip) before its MD string and tails are read off it
 int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr);
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
 int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr);
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr);
+// one cigar_left_align launch over words and DevTraceOuts made on the host (flx_left_align_batch): out_words receives the second buffer
+// (words_out words), touts the rewritten DevTraceOuts
+int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts,
+                        hvec<DevLeftAlignJob> const& jobs, u64 words_out, hvec<u32>& out_words);
 // one cigar_tails launch over words and DevTraceOuts made on the host (flx_cigar_tails_batch)
 int run_tail_jobs(Lane* lane, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevTailJob> const& jobs, hvec<DevTailOut>& outs);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
@@ -197,6 +203,7 @@ struct Slice {
     hvec<RootAlignment> root_res;
     hvec<u32> cig;                                                            // CIGAR pool of root_res
     bool want_md = false;                                                     // flx_tag_options.md: the traced paths' MD strings as well
+    bool want_left_align = false;                                             // flx_gap_options.left_align: every traced path's gaps left-aligned
     hvec<u8> md;                                                              // MD pool of root_res
     // split_tails, rescue_partials: the records of the reads they split / rescued, read by read in the order they are written in;
     // {q_from, q_to} read-forward
@@ -210,12 +217,12 @@ struct Slice {
     // traces windows of the slice's reads (root windows, partial records): CIGAR words into cig, MD strings into md when wanted
     // tails: the paths' tails as well (align_roots alone asks for them)
     int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres, const TailParams* tails = nullptr) {
-        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails);
+        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails, want_left_align ? RD->d_pool.as<u8>() : nullptr);
     }
 };
 
 // the options of a run by value (flx_run_options, validated): an option that is off is a zeroed member
-struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; };
+struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; flx_gap_options gaps; };
 
 // produces the slice's records (read_index relative to the whole batch)
 int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run);

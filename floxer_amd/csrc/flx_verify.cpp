@@ -1059,6 +1059,7 @@ int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_
     PhaseTimer prof;
     Slice S;
     S.want_md = R.tags.md;
+    S.want_left_align = R.gaps.left_align != 0;
     int rc;
     if ((rc = plan_reads(S, P, RD, first_read, end_read, run))) return rc;
     if ((rc = plan_seeds(S, P, RD))) return rc;

@@ -457,6 +457,62 @@ typedef struct flx_tail_result { uint32_t left_rows, left_cols, left_errors, lef
 int flx_cigar_tails(const uint32_t* cigar_words, uint64_t n_words, const flx_tail_job* jobs, uint64_t n_jobs, flx_tail_result* out);
 int flx_cigar_tails_batch(flx_ctx* ctx, const uint32_t* cigar_words, uint64_t n_words, const flx_tail_job* jobs, uint64_t n_jobs, flx_tail_result* out);
 
+/* Left-aligned indels: not floxer's. The traceback takes an up or left move as soon as one is valid, so inside a homopolymer or a tandem
+ * repeat a gap lands on the last copy: every CIGAR has its gaps right-aligned, floxer's (seqan3's) convention and the default here.
+ * Variant callers, VCF, minimap2 and bwa put a gap on the first copy. Off when the struct is zeroed (or NULL), and then nothing changes:
+ * no launch, no allocation, no byte of any output. With left_align = 1 (anything else but 0 is refused) every traced path of the run
+ * (root alignments, partial records, extended and split records) is normalised on the device directly behind the traceback (kernel
+ * cigar_left_align), before its MD string and its tails are computed, so CIGAR, MD and the cuts of flx_split_options agree:
+ *   - the words are processed left to right into an output list; = and X words are appended, a word of the last output word's op
+ *     merging with it. A gap word of kind K (I or D) and length L starts at position c of its own sequence (reference for D, query for
+ *     I). Repeat: no previous output word: stop. It is of kind K: remove it, add its length to L, move c left by it, repeat. It is X or
+ *     the other gap kind: stop. It is = of length E: Emax = E, or E - 1 when that = is the path's first word; s = the largest
+ *     s <= Emax with seq[c - i] == seq[c - i + L] for i = 1..s; s == 0: stop; else shorten the = by s (drop it at 0), c -= s, stop if
+ *     s < E, else repeat. Then append the gap and an = of the total shift, which merges with a following = word;
+ *   - position, the rows and columns consumed and NM do not change; every = column still pairs equal letters; the word count stays
+ *     <= 2 NM + 1 but can grow (5= 2D 1X becomes 2= 2D 3= 1X); the rule is idempotent.
+ * Limits: a gap does not move through X or through the other gap kind; a gap never becomes the path's first word (a gap that is the
+ * first word stays); letters are the index's ranks, so IUPAC codes collapse as they do in MD. params->without_cigar has no trace:
+ * refused together with left_align (FLX_ERR_INVALID) before any work. The rule: floxer_amd/csrc/flx_leftalign.hpp. The reserved fields
+ * must be 0. */
+typedef struct flx_gap_options { uint32_t left_align; uint32_t reserved[7]; } flx_gap_options;
+/* flx_align_reads_split / flx_align_reads_resident_split with the gap options (NULL or zeroed: exactly those calls, which forward here) */
+int flx_align_reads_gaps(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                         const flx_run_options* options, const flx_split_options* split, const flx_gap_options* gaps, flx_run** out);
+int flx_align_reads_resident_gaps(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_run_options* options,
+                                  const flx_split_options* split, const flx_gap_options* gaps, flx_run** out);
+/* flx_align_batch_md with the gap options: K4, K5, cigar_left_align, md_build on the WITH_CIGAR jobs. The three MD arguments may be NULL
+ * (no MD strings); gaps NULL or zeroed: exactly flx_align_batch_md / flx_align_batch. */
+int flx_align_batch_gaps(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                         const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out, uint32_t* cigar_pool, uint64_t* cigar_pool_words,
+                         flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes, const flx_gap_options* gaps);
+/* The rule alone on any CIGAR words: job i covers words [cigar_offset, cigar_offset + cigar_length) of the word pool, the reference
+ * window [ref_offset, ref_offset + ref_length) of ref_pool, whose column `begin` is the path's first, and the query [query_offset,
+ * query_offset + query_length) of query_pool. Letters are bytes compared for equality. out[i] receives where job i's words lie in
+ * out_words; *out_n_words: in = capacity of out_words in words, out = words used (the jobs' results packed in job order; twice the
+ * jobs' cigar_length in total always suffices; FLX_ERR_CAPACITY with the need stored when too small). A job outside its pools, an op
+ * other than = X I D, a zero-length word, op lengths that do not fit the window and the query (or reach 2^28), or a reserved field
+ * that is not 0 is refused (FLX_ERR_INVALID; flx_left_align_batch: before any launch). flx_left_align runs on the host and needs
+ * ref_pool; flx_left_align_batch runs the kernel, ref_pool == NULL there: the context's reference text (ref_offset is then a position
+ * in the padded concatenated text). Both give the same words. */
+typedef struct flx_left_align_job {
+    uint64_t cigar_offset;
+    uint32_t cigar_length;
+    uint32_t reserved;
+    uint64_t ref_offset;
+    uint32_t ref_length;
+    uint32_t begin;
+    uint64_t query_offset;
+    uint32_t query_length;
+    uint32_t reserved2;
+} flx_left_align_job;
+typedef struct flx_cigar_ref { uint64_t offset; uint32_t length; uint32_t reserved; } flx_cigar_ref;
+int flx_left_align(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len, const uint32_t* cigar_words,
+                   uint64_t n_words, const flx_left_align_job* jobs, uint64_t n_jobs, uint32_t* out_words, uint64_t* out_n_words, flx_cigar_ref* out);
+int flx_left_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                         const uint32_t* cigar_words, uint64_t n_words, const flx_left_align_job* jobs, uint64_t n_jobs, uint32_t* out_words,
+                         uint64_t* out_n_words, flx_cigar_ref* out);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
