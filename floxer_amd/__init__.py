@@ -218,6 +218,13 @@ class context:
         out["reads_split"] = int(pc.reserved[3])              # the reads mapped in full that split_options split at a chimeric tail
         return out
 
+    def search_counters(self):
+        """what the search kernel's work sharing did, over all search launches since the context was made (or path_counters(reset=True)):
+        launches, subtrees_queued, lane_handovers, wave_handovers, walks_abandoned"""
+        sc = capi.SearchCounters()
+        check(lib().flx_ctx_get_search_counters(self.h, C.byref(sc)))
+        return {n: int(getattr(sc, n)) for n, _ in capi.SearchCounters._fields_ if n != "reserved"}
+
     def kernel_stats(self):
         arr = (capi.KernelStat * 32)()
         n = C.c_uint32(32)

@@ -152,6 +152,10 @@ class PathCounters(C.Structure):
                                           "root_alignments_found", "records", "reads", "search_reruns")] + [("reserved", C.c_uint64 * 4)]
 
 
+class SearchCounters(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("launches", "subtrees_queued", "lane_handovers", "wave_handovers", "walks_abandoned")] + [("reserved", C.c_uint64 * 3)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("device_ms", C.c_double), ("algorithmic_bytes", C.c_uint64),
                 ("work_units", C.c_uint64)]
@@ -175,6 +179,7 @@ EXPORTED = [
     "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
     "flx_extend_batch", "flx_sam_set_sa", "flx_align_reads_split", "flx_align_reads_resident_split", "flx_cigar_tails", "flx_cigar_tails_batch",
     "flx_align_shapes", "flx_align_reads_gaps", "flx_align_reads_resident_gaps", "flx_align_batch_gaps", "flx_left_align", "flx_left_align_batch",
+    "flx_ctx_get_search_counters",
 ]
 
 _lib = None
@@ -324,6 +329,7 @@ def lib():
     L.flx_extend_batch.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(ExtendJob), C.c_uint64, C.POINTER(ExtendResult)]
     L.flx_ctx_get_path_counters.argtypes = [C.c_void_p, C.POINTER(PathCounters)]
     L.flx_ctx_reset_path_counters.argtypes = [C.c_void_p]
+    L.flx_ctx_get_search_counters.argtypes = [C.c_void_p, C.POINTER(SearchCounters)]
     L.flx_sim_genome.argtypes = [C.c_uint64, C.c_uint64, u8p]
     L.flx_sim_genome_repeats.argtypes = [C.c_uint64, C.c_uint64, u8p]
     L.flx_sim_reads.argtypes = [u8p, u64p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_uint64, u8p, C.c_uint64,

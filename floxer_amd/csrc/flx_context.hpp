@@ -117,6 +117,7 @@ struct flx_ctx {
     std::map<std::string, flx_kernel_stat> stats;
     std::vector<std::string> stat_order;
     flx_path_counters path{};        // guarded by mu
+    flx_search_counters search{};    // guarded by mu; reset with `path`
     flx_stats* read_stats = nullptr; // flx_ctx_set_stats: every batch adds its reads (flx_stats.cpp); not owned
 
     // lanes are handed out one holder at a time, so calls on one context may overlap (each waits for a free lane)

@@ -297,9 +297,17 @@ int search_seeds_device(Lane* ctx, const u8* d_seq_pool_or_null, const u8* h_seq
         if (getenv("FLX_SEARCH_DEBUG") && filtered) fprintf(stderr, "[fm_search filtered] subtrees queued %u (slots %u of %llu), filter words asked %u, children dropped %u, searches ended by the prefix lookup %u; text walk: lane-steps %u, wave-iterations %u in %u waves (longest %u)\n", counters[3], counters[16], (unsigned long long)item_cap, counters[10], counters[11], counters[12], counters[18], counters[19], counters[22], counters[21]);
         if (counters[1]) { set_error(counters[1] & 2u ? "fm_search: a subtree handed between waves was not taken" : "fm_search: DFS stack reservation exceeded"); return FLX_ERR_INTERNAL; }
         bool const items_fit = !item_cap || counters[16] <= item_cap;
-        if (items_fit && counters[0] <= hit_cap && (!device_select || sel_rows_total <= sel_cap)) break;      // (selected anchors <= rows)
-        if (attempt >= 3) { set_error("fm_search: hit buffer could not be sized"); return FLX_ERR_INTERNAL; }
-        { std::lock_guard<std::mutex> g(ctx->ctx->mu); ++ctx->ctx->path.search_reruns; }
+        bool const fits = items_fit && counters[0] <= hit_cap && (!device_select || sel_rows_total <= sel_cap);      // (selected anchors <= rows)
+        if (!fits && attempt >= 3) { set_error("fm_search: hit buffer could not be sized"); return FLX_ERR_INTERNAL; }
+        {
+            // what this launch's work sharing did (flx_search_counters), and the launch repeated when its buffers were outgrown
+            std::lock_guard<std::mutex> g(ctx->ctx->mu);
+            flx_search_counters& sc = ctx->ctx->search;
+            ++sc.launches;
+            if (filtered) { sc.subtrees_queued += counters[3]; sc.lane_handovers += counters[14]; sc.wave_handovers += counters[15]; sc.walks_abandoned += counters[20]; }
+            if (!fits) ++ctx->ctx->path.search_reruns;
+        }
+        if (fits) break;
         // (a wave reserves 64 slots at a time and leaves the rest of a range unused when a ballot's records do not fit into it: the slots
         // reserved are at most twice the records written plus one range per wave of both kernels, however the waves were scheduled)
         u64 const wave_ranges = (u64)(4096 + 8192 + 64) * 64;

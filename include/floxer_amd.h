@@ -544,6 +544,20 @@ typedef struct flx_path_counters {
 int flx_ctx_get_path_counters(flx_ctx* ctx, flx_path_counters* out);
 int flx_ctx_reset_path_counters(flx_ctx* ctx);
 
+/* What the work sharing of the search kernel did, summed over every search launch (repeated ones included) of the context since it was
+ * made or flx_ctx_reset_path_counters was called: the device's own counters of each launch, added up on the host when they come back
+ * with the launch's other results. Which lane or wave takes a subtree depends on scheduling: the last three differ from run to run,
+ * the results of the search never do. */
+typedef struct flx_search_counters {
+    uint64_t launches;           /* search launches */
+    uint64_t subtrees_queued;    /* one-row subtrees queued for the walk against the text */
+    uint64_t lane_handovers;     /* subtrees an idle lane took from a busy lane of its wave */
+    uint64_t wave_handovers;     /* subtrees a wave handed to a wave that had run out of work */
+    uint64_t walks_abandoned;    /* walks given up because their seed had passed the hard cap in another lane or wave */
+    uint64_t reserved[3];
+} flx_search_counters;
+int flx_ctx_get_search_counters(flx_ctx* ctx, flx_search_counters* out);
+
 /* ------------------------------------------------------------------------------------------------ statistics (--stats)
  * replaces statistics::search_and_alignment_statistics (include/statistics.hpp:24-172, src/lib/statistics.cpp): the reference's
  * count and eighteen histograms, same names, thresholds and renderings. input_hint: NULL / "real_nanopore" / "simulated"

@@ -23,6 +23,11 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(L, name), name
     assert b"floxer_amd" in capi.lib().flx_version()
+    # the search counters: a struct of their own (flx_path_counters is full and keeps its size), refused without a context
+    assert "flx_ctx_get_search_counters" in declared and C.sizeof(capi.SearchCounters) == 64 and C.sizeof(capi.PathCounters) == 128
+    assert [n for n, _ in capi.SearchCounters._fields_] == ["launches", "subtrees_queued", "lane_handovers", "wave_handovers", "walks_abandoned", "reserved"]
+    sc = capi.SearchCounters()
+    assert capi.lib().flx_ctx_get_search_counters(None, C.byref(sc)) != 0
 
 
 def test_one_hip_runtime_per_process_whichever_is_loaded_first():
