@@ -15,6 +15,7 @@ libfloxer_amd.so:
     aligner(..., extend=extend_options()), extend_batch()  not floxer's: the partial records' ends extended to the break (opt-in)
     aligner(..., split=split_options()), cigar_tails()  not floxer's: reads mapped in full that carry a chimeric tail are split (opt-in)
     aligner(..., gaps=gap_options()), left_align()  not floxer's: indels left-aligned on the device behind the traceback (opt-in)
+    aligner(..., realign=realign_options()), realign(), realign_batch(), align_batch_realign()  not floxer's: a traced path realigned under affine gap costs inside a band around it (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -361,6 +362,54 @@ def align_batch(ctx, query_pool, jobs, reference_pool=None, md=False, gaps=None)
     return out
 
 
+def _realign_room(options):
+    """(words, MD bytes) that the realigned path of an input with nm errors holds at most, as functions of nm: realign_cap and
+    realign_nm_bound of floxer_amd/csrc/flx_realign.hpp, the one place where Python sizes a buffer for a realigned path (a call that
+    needs more still says so with FLX_ERR_CAPACITY). options None or without enable: an edit path's 2 nm + 2 words and 8 nm + 6 bytes."""
+    if options is None or not options.enable:
+        return (lambda nm: 2 * nm + 2), (lambda nm: 8 * nm + 6)
+    sc = {k: int(getattr(options, k)) or v for k, v in REALIGN_DEFAULTS.items()}
+    c_max = max(sc["match"] + sc["mismatch"], sc["gap_open"] + sc["gap_extend"] + sc["match"])
+    c_min = min(sc["match"] + sc["mismatch"], sc["gap_open"] + sc["gap_extend"])
+    col_min = min(sc["match"] + sc["mismatch"], sc["gap_extend"])
+    return (lambda nm: max(2 * nm + 2, 2 * (nm * c_max // c_min) + 1)), (lambda nm: 8 * (nm * c_max // col_min) + 6)
+
+
+def align_batch_realign(ctx, query_pool, jobs, realign, reference_pool=None, md=False, gaps=None):
+    """flx_align_batch_realign: align_batch with every traced path realigned under affine gap costs behind the traceback
+    (realign = realign_options(...)), then left-aligned (gaps = gap_options(...)) and its MD string built (md=True) from the realigned
+    words. Returns a list of None | (num_errors, begin, cigar, md or None, score)."""
+    q = as_u8(query_pool)
+    arr = (capi.AlignJob * max(1, len(jobs)))()
+    cap_words = cap_md = 16
+    room_words, room_md = _realign_room(realign)
+    for i, (ro, rl, qo, ql, k, mode) in enumerate(jobs):
+        arr[i] = capi.AlignJob(ro, qo, rl, ql, k, mode)
+        cap_words += room_words(k)
+        cap_md += room_md(k)
+    res = (capi.AlignResult * max(1, len(jobs)))()
+    cig = np.zeros(cap_words, dtype=np.uint32)
+    words = C.c_uint64(cap_words)
+    if reference_pool is None:
+        rp, rl_ = None, 0
+    else:
+        ref = as_u8(reference_pool)
+        rp, rl_ = ptr(ref, u8p), len(ref)
+    refs = (capi.MdRef * max(1, len(jobs)))() if md else None
+    mdp = np.zeros(cap_md if md else 1, dtype=np.uint8)
+    md_bytes = C.c_uint64(cap_md)
+    scores = np.zeros(max(1, len(jobs)), dtype=np.int32)
+    check(lib().flx_align_batch_realign(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words), refs,
+                                        ptr(mdp, u8p) if md else None, C.byref(md_bytes) if md else None, C.byref(gaps) if gaps is not None else None,
+                                        C.byref(realign) if realign is not None else None, scores.ctypes.data_as(C.POINTER(C.c_int32))))
+    out = []
+    for i, r in enumerate(res[: len(jobs)]):
+        m = refs[i] if md else None
+        out.append((r.num_errors, r.begin, cigar_string(cig[r.cigar_offset: r.cigar_offset + r.cigar_length]),
+                    mdp[m.offset: m.offset + m.length].tobytes() if m is not None and m.length else None, int(scores[i])) if r.exists else None)
+    return out
+
+
 def align_shapes(jobs):
     """the launch shape align_batch would give every job of a call with these jobs (flx_align_shapes; no context, no GPU):
     [(words_per_lane, lanes_per_job, queue)], queue = the hand-over slots the job's ring occupies, 0 for a ring that never waits."""
@@ -406,7 +455,8 @@ class RunResult:
     int64 matrix {read_index, flag, ref_id, pos, nm, cigar_off, cigar_len}, made on first use. A run made with md=True also has
     `md_refs` ((n,2) uint64 {offset, length} into `md_bytes`) and `md`, a list of bytes / None per record, made on first use."""
 
-    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None):
+    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None, scores=None):
+        self.scores = scores            # int32 per record (flx_run_copy_scores) of a run made with realign=realign_options(...), else None
         self.raw = raw
         self.cigars = cigars
         self.skipped = skipped
@@ -643,6 +693,74 @@ def left_align_batch(ctx, query_pool, words, jobs, reference_pool=None):
     return _left_align_call(lib().flx_left_align_batch, (ctx.h,), reference_pool, query_pool, words, jobs)
 
 
+REALIGN_DEFAULTS = dict(match=2, mismatch=4, gap_open=4, gap_extend=2, band=16)
+
+
+def realign_options(enable=True, match=0, mismatch=0, gap_open=0, gap_extend=0, band=0):
+    """flx_realign_options (include/floxer_amd.h): not floxer's. A traced path is realigned under affine gap costs inside a band around
+    it (floxer_amd/csrc/flx_realign.hpp). 0 = the default of a field (REALIGN_DEFAULTS: the first piece of minimap2's map-ont scores,
+    conventions, fitted to nothing); each score <= 255, band <= 1024, max(a + b, o + e + a) <= 8 min(a + b, o + e)."""
+    o = capi.RealignOptions()
+    o.enable = int(bool(enable))
+    o.match, o.mismatch, o.gap_open, o.gap_extend, o.band = int(match), int(mismatch), int(gap_open), int(gap_extend), int(band)
+    return o
+
+
+def _realign_call(fn, head, reference_pool, query_pool, words, jobs, options):
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    n_words = len(w)
+    if n_words == 0:
+        w = np.zeros(1, np.uint32)
+    q = as_u8(query_pool)
+    n_q = len(q)
+    if n_q == 0:
+        q = np.zeros(1, np.uint8)
+    if reference_pool is None:
+        rp, rl_ = None, 0
+    else:
+        ref = as_u8(reference_pool)
+        rp, rl_ = ptr(ref, u8p), len(ref)
+    arr = (capi.RealignJob * max(1, len(jobs)))()
+    for i, (co, cl, ro, rl, begin, qo, ql) in enumerate(jobs):
+        arr[i] = capi.RealignJob(int(co), int(cl), 0, int(ro), int(rl), int(begin), int(qo), int(ql), 0)
+    res = (capi.RealignResult * max(1, len(jobs)))()
+    op = C.byref(options) if options is not None else None
+    # room for every job's bound, max(cigar_length, 2 floor(NM c_max / c_min) + 1) (the call is the request: `enable` is not looked at)
+    room_words, _ = _realign_room(options if options is not None else realign_options())
+    cap = 16
+    for co, cl, *_ in jobs:
+        part = w[int(co): int(co) + int(cl)] if int(co) + int(cl) <= n_words else w[:0]
+        cap += max(int(cl), room_words(int((part[(part & 15) != 7] >> 4).sum())))
+    n_out = C.c_uint64(cap)
+    out = np.zeros(cap, dtype=np.uint32)
+    rc = fn(*head, rp, rl_, ptr(q, u8p), n_q, ptr(w, u32p), n_words, arr, len(jobs), op, ptr(out, u32p), C.byref(n_out), res)
+    if rc == -3:                                                       # FLX_ERR_CAPACITY: the need is stored, once more with room for it
+        out = np.zeros(n_out.value, dtype=np.uint32)
+        rc = fn(*head, rp, rl_, ptr(q, u8p), n_q, ptr(w, u32p), n_words, arr, len(jobs), op, ptr(out, u32p), C.byref(n_out), res)
+    check(rc)
+    return [dict(words=out[r.offset: r.offset + r.length].copy(), num_errors=int(r.num_errors), score=int(r.score), diag_lo=int(r.diag_lo),
+                 diag_hi=int(r.diag_hi), kept=int(r.kept)) for r in res[: len(jobs)]]
+
+
+def realign(reference_pool, query_pool, words, jobs, options=None):
+    """flx_realign, the affine-gap realignment rule on the host (floxer_amd/csrc/flx_realign.hpp): words and jobs as left_align takes
+    them, options = realign_options(...) or None for the defaults. Returns one dict per job: words (uint32 array), num_errors, score,
+    diag_lo, diag_hi, kept."""
+    return _realign_call(lib().flx_realign, (), reference_pool, query_pool, words, jobs, options)
+
+
+def realign_batch(ctx, query_pool, words, jobs, options=None, reference_pool=None):
+    """flx_realign_batch: the same words and numbers from the kernel cigar_realign. reference_pool None = the context's reference text."""
+    return _realign_call(lib().flx_realign_batch, (ctx.h,), reference_pool, query_pool, words, jobs, options)
+
+
+def realign_counters(ctx):
+    """flx_ctx_get_realign_counters: (paths_realigned, paths_changed, paths_kept) since the last reset of the path counters"""
+    c = capi.RealignCounters()
+    check(lib().flx_ctx_get_realign_counters(ctx.h, C.byref(c)))
+    return int(c.paths_realigned), int(c.paths_changed), int(c.paths_kept)
+
+
 TAIL_FIELDS = ("left_rows", "left_cols", "left_errors", "left_words", "right_rows", "right_cols", "right_errors", "right_words")
 
 
@@ -715,7 +833,7 @@ def choose_partials(candidates, cigars=None, options=None):
     return out[: len(candidates)]
 
 
-def _collect_run(run, n, md=False):
+def _collect_run(run, n, md=False, scores=False):
     try:
         nr = lib().flx_run_num_records(run)
         nc = lib().flx_run_num_cigar_words(run)
@@ -732,21 +850,28 @@ def _collect_run(run, n, md=False):
             check(lib().flx_run_copy_md(run, refs.ctypes.data_as(C.POINTER(capi.MdRef)), ptr(md_bytes, u8p)))
             md_refs = np.stack([refs["off"][:nr], refs["len"][:nr].astype(np.uint64)], axis=1) if nr else np.zeros((0, 2), dtype=np.uint64)
             md_bytes = md_bytes[:nb]
+        sc = None
+        if scores:
+            sc = np.zeros(max(1, nr), dtype=np.int32)
+            check(lib().flx_run_copy_scores(run, sc.ctypes.data_as(C.POINTER(C.c_int32))))
+            sc = sc[:nr]
     finally:
         lib().flx_run_free(run)
-    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes)
+    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes, sc)
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None, gaps=None):
+    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None, gaps=None, realign=None):
         """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
         string (RunResult.md), built on the device; not together with without_cigar; partial: partial_options(...), None: a read
         without a full alignment is written as unmapped (floxer's output); extend: extend_options(...), None: a partial record ends at
         its PEX node's boundary (needs partial); split: split_options(...), None: a read mapped in full is one record whatever its
         ends look like (needs partial and output_options(max_alignments=1)); gaps: gap_options(...), None: gaps stay right-aligned
-        (floxer's output)"""
+        (floxer's output); realign: realign_options(...), None: every CIGAR stays an edit-distance path (floxer's output); with it
+        RunResult.scores holds the records' scores"""
         self.ctx, self.params, self.output, self.md, self.partial, self.extend, self.split = ctx, p, output, bool(md), partial, extend, split
         self.gaps = gaps
+        self.realign = realign
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
@@ -759,11 +884,12 @@ class aligner:
                 setattr(bundle, name, C.pointer(getattr(self, name)))
         split = C.byref(self.split) if self.split is not None else None
         gaps = C.byref(self.gaps) if self.gaps is not None else None
+        realign = C.byref(self.realign) if self.realign is not None else None
         if isinstance(reads, resident_reads):
             n = reads.n
-            check(lib().flx_align_reads_resident_gaps(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, gaps, C.byref(run)))
+            check(lib().flx_align_reads_resident_realign(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, gaps, realign, C.byref(run)))
         else:
             pool, offs, n = _pool_and_offsets(reads)
-            check(lib().flx_align_reads_gaps(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, gaps,
-                                             C.byref(run)))
-        return _collect_run(run, n, md=self.md)
+            check(lib().flx_align_reads_realign(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, gaps,
+                                                realign, C.byref(run)))
+        return _collect_run(run, n, md=self.md, scores=self.realign is not None and bool(self.realign.enable))

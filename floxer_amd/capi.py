@@ -117,6 +117,23 @@ class CigarRef(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RealignOptions(C.Structure):
+    _fields_ = [("enable", C.c_uint32), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32), ("gap_extend", C.c_uint32),
+                ("band", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+RealignJob = LeftAlignJob
+
+
+class RealignResult(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("num_errors", C.c_uint32), ("score", C.c_int32), ("diag_lo", C.c_int32),
+                ("diag_hi", C.c_int32), ("kept", C.c_uint32)]
+
+
+class RealignCounters(C.Structure):
+    _fields_ = [("paths_realigned", C.c_uint64), ("paths_changed", C.c_uint64), ("paths_kept", C.c_uint64), ("reserved", C.c_uint64 * 5)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -179,6 +196,8 @@ EXPORTED = [
     "flx_sam_write_tagged", "flx_align_reads_opt", "flx_align_reads_resident_opt", "flx_choose_partials", "flx_partial_mapq",
     "flx_extend_batch", "flx_sam_set_sa", "flx_align_reads_split", "flx_align_reads_resident_split", "flx_cigar_tails", "flx_cigar_tails_batch",
     "flx_align_shapes", "flx_align_reads_gaps", "flx_align_reads_resident_gaps", "flx_align_batch_gaps", "flx_left_align", "flx_left_align_batch",
+    "flx_realign", "flx_realign_batch", "flx_align_batch_realign", "flx_ctx_get_realign_counters", "flx_align_reads_realign",
+    "flx_align_reads_resident_realign", "flx_run_copy_scores", "flx_sam_write_scored",
     "flx_ctx_get_search_counters",
 ]
 
@@ -289,6 +308,14 @@ def lib():
     L.flx_left_align.argtypes = [u8p, C.c_uint64, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(LeftAlignJob), C.c_uint64, u32p, u64p,
                                  C.POINTER(CigarRef)]
     L.flx_left_align_batch.argtypes = [C.c_void_p] + L.flx_left_align.argtypes
+    L.flx_realign.argtypes = [u8p, C.c_uint64, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(RealignJob), C.c_uint64, C.POINTER(RealignOptions), u32p, u64p,
+                              C.POINTER(RealignResult)]
+    L.flx_realign_batch.argtypes = [C.c_void_p] + L.flx_realign.argtypes
+    L.flx_align_batch_realign.argtypes = L.flx_align_batch_gaps.argtypes + [C.POINTER(RealignOptions), C.POINTER(C.c_int32)]
+    L.flx_ctx_get_realign_counters.argtypes = [C.c_void_p, C.POINTER(RealignCounters)]
+    L.flx_align_reads_realign.argtypes = L.flx_align_reads_gaps.argtypes[:-1] + [C.POINTER(RealignOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_realign.argtypes = L.flx_align_reads_resident_gaps.argtypes[:-1] + [C.POINTER(RealignOptions), C.POINTER(C.c_void_p)]
+    L.flx_run_copy_scores.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]
@@ -300,6 +327,7 @@ def lib():
                                      C.POINTER(AlignResult), u32p, u64p, C.POINTER(MdRef), u8p, u64p]
     L.flx_sam_write_tagged.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), u8p, u64p, C.POINTER(C.c_char_p), C.POINTER(Record), C.c_uint64, u32p,
                                        C.POINTER(MdRef), u8p]
+    L.flx_sam_write_scored.argtypes = L.flx_sam_write_tagged.argtypes + [C.POINTER(C.c_int32)]
     L.flx_select_records.argtypes = [C.POINTER(Record), C.c_uint64, u32p, C.POINTER(OutputOptions), u8p]
     L.flx_assign_mapq.argtypes = [C.POINTER(Record), C.c_uint64, u32p, u64p, u8p]
     L.flx_run_num_records.restype = C.c_uint64

@@ -73,6 +73,8 @@ struct Options {
     bool split_tails = false;
     uint64_t split_tails_weight = 0, split_tails_xdrop = 0, split_tails_min_rows = 0;               // 0: the library's defaults
     bool left_align_indels = false;
+    bool realign_affine = false;
+    uint64_t realign_match = 0, realign_mismatch = 0, realign_gap_open = 0, realign_gap_extend = 0, realign_band = 0;   // 0: the library's defaults
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -109,6 +111,13 @@ const OptDef OPTS[] = {
     {0, "split-tails-min-rows", false, "not floxer's: the fewest query bases of a tail (default 100); needs --split-tails"},
     // nor this: every CIGAR's gaps moved to the first copy of a homopolymer or repeat instead of the last (flx_gap_options)
     {0, "left-align-indels", true, "opt-in, not floxer's: left-align the indels of every CIGAR (on the GPU behind the traceback; MD and split tails follow), as VCF, minimap2 and bwa do; not with -w"},
+    // nor these: every traced path realigned under affine gap costs inside a band around it, and its score written as AS:i (flx_realign_options)
+    {0, "realign-affine", true, "opt-in, not floxer's: realign every CIGAR under affine gap costs (on the GPU behind the traceback; NM, MD and everything that judges NM follow) and write AS:i; not with -w"},
+    {0, "realign-match", false, "not floxer's: the score of a match (default 2, at most 255); needs --realign-affine"},
+    {0, "realign-mismatch", false, "not floxer's: the cost of a mismatch (default 4, at most 255); needs --realign-affine"},
+    {0, "realign-gap-open", false, "not floxer's: the cost of opening a gap (default 4, at most 255); needs --realign-affine"},
+    {0, "realign-gap-extend", false, "not floxer's: the cost of every gap column (default 2, at most 255); needs --realign-affine"},
+    {0, "realign-band", false, "not floxer's: the diagonals added on either side of the path's own (default 16, at most 1024); needs --realign-affine"},
 };
 
 struct CliError { std::string msg; };
@@ -215,6 +224,12 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "sa-tag") o.sa_tag = true;
         else if (n == "split-tails") o.split_tails = true;
         else if (n == "left-align-indels") o.left_align_indels = true;
+        else if (n == "realign-affine") o.realign_affine = true;
+        else if (n == "realign-match") { o.realign_match = parse_u64(n, value); range_check(n, (double)o.realign_match, 1, 255); }
+        else if (n == "realign-mismatch") { o.realign_mismatch = parse_u64(n, value); range_check(n, (double)o.realign_mismatch, 1, 255); }
+        else if (n == "realign-gap-open") { o.realign_gap_open = parse_u64(n, value); range_check(n, (double)o.realign_gap_open, 1, 255); }
+        else if (n == "realign-gap-extend") { o.realign_gap_extend = parse_u64(n, value); range_check(n, (double)o.realign_gap_extend, 1, 255); }
+        else if (n == "realign-band") { o.realign_band = parse_u64(n, value); range_check(n, (double)o.realign_band, 1, 1024); }
         else if (n == "split-tails-weight") { o.split_tails_weight = parse_u64(n, value); range_check(n, (double)o.split_tails_weight, 1, 65535); }
         else if (n == "split-tails-xdrop") { o.split_tails_xdrop = parse_u64(n, value); range_check(n, (double)o.split_tails_xdrop, 1, 1073741824); }
         else if (n == "split-tails-min-rows") { o.split_tails_min_rows = parse_u64(n, value); range_check(n, (double)o.split_tails_min_rows, 1, 524287); }
@@ -252,6 +267,16 @@ Options parse_cli(int argc, char** argv) {
     if (!o.split_tails && (o.split_tails_weight || o.split_tails_xdrop || o.split_tails_min_rows))
         throw CliError{"The options --split-tails-weight, --split-tails-xdrop and --split-tails-min-rows need --split-tails."};
     if (o.left_align_indels && o.without_cigar) throw CliError{"The option --left-align-indels needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.realign_affine && o.without_cigar) throw CliError{"The option --realign-affine needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (!o.realign_affine && (o.realign_match || o.realign_mismatch || o.realign_gap_open || o.realign_gap_extend || o.realign_band))
+        throw CliError{"The options --realign-match, --realign-mismatch, --realign-gap-open, --realign-gap-extend and --realign-band need --realign-affine."};
+    if (o.realign_affine) {
+        // (the library's rule, stated here so that it is refused with the other options and before the index is read)
+        uint64_t const a = o.realign_match ? o.realign_match : 2, b = o.realign_mismatch ? o.realign_mismatch : 4, go = o.realign_gap_open ? o.realign_gap_open : 4,
+                       ge = o.realign_gap_extend ? o.realign_gap_extend : 2;
+        if (std::max(a + b, go + ge + a) > 8 * std::min(a + b, go + ge))
+            throw CliError{"The realign scores are too far apart: max(match + mismatch, gap-open + gap-extend + match) must not exceed 8 times min(match + mismatch, gap-open + gap-extend)."};
+    }
     return o;
 }
 
@@ -670,6 +695,14 @@ int main(int argc, char** argv) {
     flx_gap_options gap_opt;
     memset(&gap_opt, 0, sizeof(gap_opt));
     gap_opt.left_align = o.left_align_indels;
+    flx_realign_options realign_opt;
+    memset(&realign_opt, 0, sizeof(realign_opt));
+    realign_opt.enable = o.realign_affine;
+    realign_opt.match = (uint32_t)o.realign_match;
+    realign_opt.mismatch = (uint32_t)o.realign_mismatch;
+    realign_opt.gap_open = (uint32_t)o.realign_gap_open;
+    realign_opt.gap_extend = (uint32_t)o.realign_gap_extend;
+    realign_opt.band = (uint32_t)o.realign_band;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -683,7 +716,7 @@ int main(int argc, char** argv) {
     if (const char* env = getenv("FLX_BATCH_READS")) { size_t const v = strtoull(env, nullptr, 10); if (v) batch_reads = v; }
     // Batches are independent: up to three are in a context at a time (their chunks share its lanes), the next one is parsed
     // while they run, and results are written in input order.
-    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
+    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<int32_t> scores; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
     // FLX_CLI_PROFILE=1: seconds this run spent parsing (this thread), aligning (sum over the batches' tasks) and writing (the writer
     // thread) on stderr at the end: which of the three stages bounds the end-to-end rate
     std::atomic<uint64_t> us_parse{0}, us_align{0}, us_copy{0}, us_write{0}, us_records{0};
@@ -700,7 +733,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads_gaps(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &gap_opt, &run);
+        f.rc = flx_align_reads_realign(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &gap_opt, &realign_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));
@@ -712,6 +745,10 @@ int main(int argc, char** argv) {
             f.md_refs.resize(f.recs.size());
             f.md.resize(flx_run_num_md_bytes(run) + 1);
             flx_run_copy_md(run, f.md_refs.data(), f.md.data());
+        }
+        if (o.realign_affine) {
+            f.scores.resize(f.recs.size() + 1);
+            flx_run_copy_scores(run, f.scores.data());
         }
         flx_run_free(run);
         us_copy += now_us() - t1;
@@ -740,8 +777,8 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < f.skipped.size(); ++i)
             if (f.skipped[i]) log_line("warning", "skipping query: %s due to bad configuration regarding the number of errors.", batch.ids[i]);
         uint64_t const t0 = now_us();
-        if (flx_sam_write_tagged(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
-                                 o.md_tag ? f.md_refs.data() : nullptr, f.md.data()) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+        if (flx_sam_write_scored(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
+                                 o.md_tag ? f.md_refs.data() : nullptr, f.md.data(), o.realign_affine ? f.scores.data() : nullptr) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
         us_write += now_us() - t0;
         total_reads += batch.ids.size();
         total_records += f.recs.size();

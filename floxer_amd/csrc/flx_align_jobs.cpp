@@ -14,6 +14,7 @@
 #include "flx_pipeline.hpp"
 #include "flx_tails.hpp"
 #include "flx_leftalign.hpp"
+#include "flx_realign.hpp"
 
 namespace flx {
 
@@ -258,6 +259,8 @@ struct TracePlan {
     }
 };
 
+constexpr size_t REALIGN_LAUNCH_JOBS = 4096;      // jobs of one cigar_realign launch at most
+
 // K5 over the paths of one arena chunk, and their MD strings (flx_md.hip) when wanted: one MD job per trace job. The MD jobs go up with
 // the trace jobs, md_build is queued directly behind K5 (it reads K5's DevTraceOut and CIGAR words on the device: no host synchronisation
 // in between), and the bytes come back with the CIGAR words. A job's CIGAR slab holds 2 NM + 2 words and its MD slab md_slab_bytes(NM)
@@ -271,6 +274,8 @@ struct Traceback {
     const TailParams* const want_tails;
     const u8* const d_la_query;                                // null: gaps stay where K5 put them
     bool const want_left_align;
+    const RealignScores* const realign;                        // null: the paths stay edit-distance paths
+    const u8* const d_ra_query;                                // the device query pool's letters for cigar_realign
     PhaseTimer* const prof;
     hvec<DevTraceJob> jobs;
     hvec<DevTraceOut> outs;
@@ -280,21 +285,32 @@ struct Traceback {
     hvec<DevTailOut> tail_outs;
     hvec<DevLeftAlignJob> la_jobs;
     hvec<DevLeftAlignStat> la_stats;
+    hvec<DevRealignJob> ra_jobs;
+    hvec<DevRealignStat> ra_stats;
     u64 cigar_words = 0, path_steps = 0, md_bytes = 0;
     size_t cigar_base = 0, md_base = 0;                        // where this batch's slabs start in the host pools
-    explicit Traceback(bool md, const TailParams* tails, const u8* d_la_query_, PhaseTimer* prof_ = nullptr)
-        : want_md(md), want_tails(tails), d_la_query(d_la_query_), want_left_align(d_la_query_ != nullptr), prof(prof_) {}
+    explicit Traceback(bool md, const TailParams* tails, const u8* d_la_query_, PhaseTimer* prof_ = nullptr, const RealignScores* realign_ = nullptr,
+                       const u8* d_ra_query_ = nullptr)
+        : want_md(md), want_tails(tails), d_la_query(d_la_query_), want_left_align(d_la_query_ != nullptr), realign(d_ra_query_ ? realign_ : nullptr),
+          d_ra_query(d_ra_query_), prof(prof_) {}
     // the path that ends at end_col of the last row of r's DP, whose trace planes lie at trace_off; returns the trace job's index
     u32 add(AlignRequest const& r, u64 trace_off, AlignShape sh, u32 end_col, u32 nm) {
-        u32 const j = (u32)jobs.size(), cap = 2 * nm + 2;      // runs <= 2*NM + 1
+        // runs <= 2*NM + 1; a realigned path has at most realign_cap words (left-aligned too: gaps only merge there) and its NM stays
+        // below realign_nm_bound, which sizes its MD slab
+        u32 const j = (u32)jobs.size(), cap = realign ? (u32)std::max<u64>(2 * nm + 2, realign_cap(nm, 0, *realign)) : 2 * nm + 2;
+        u32 const nm_md = realign ? (u32)realign_nm_bound(nm, *realign) : nm;
         jobs.push_back(DevTraceJob{r.ref_off, r.q_off, trace_off, cigar_words, r.n, r.m, sh.lanes_per_job, sh.words_per_lane, end_col, cap, j, r.k});
         if (want_md) {
-            u64 const slab = md_slab_bytes(nm);
+            u64 const slab = md_slab_bytes(nm_md);
             md_jobs.push_back(DevMdJob{r.ref_off, cigar_words, md_bytes, r.n, (u32)slab, j, 0});
             md_bytes += slab;
         }
         if (want_tails) tail_jobs.push_back(DevTailJob{cigar_words, j, want_tails->w, want_tails->x_drop, want_tails->min_rows});
         if (want_left_align) la_jobs.push_back(DevLeftAlignJob{r.ref_off, r.q_off, cigar_words, cigar_words, r.n, r.m, cap, j});      // (<= 2 NM + 1 words after it too)
+        // (the diagonals of an edit path of NM errors span at most NM: the trace of a band of NM + 2 w + 1 cells always suffices)
+        if (realign)
+            ra_jobs.push_back(DevRealignJob{r.ref_off, r.q_off, cigar_words, cigar_words, 0, r.n, r.m, cap, j,
+                                            (u32)std::min<u64>(realign_trace_words(r.m, (u64)nm + 2u * (u64)realign->w + 1u), 0xFFFFFFFFull), 0});
         cigar_words += cap;
         path_steps += (u64)r.m + nm;
         return j;
@@ -331,8 +347,25 @@ struct Traceback {
             if ((rc = lane->cigar_la.ensure(cigar_words * 4 + 16))) return rc;
             if ((rc = lane->la_stat.ensure(la_jobs.size() * sizeof(DevLeftAlignStat)))) return rc;
         }
-        // the words everything behind K5 reads: K5's, or the normalised ones
-        u32* const d_words = want_left_align ? lane->cigar_la.as<u32>() : lane->cigar.as<u32>();
+        // cigar_realign's launches: at most REALIGN_LAUNCH_JOBS jobs each, their traces together inside the arena as it stands (K4's
+        // planes lie there until K5 has read them: it is not grown here)
+        hvec<size_t> ra_cuts{0};
+        if (realign) {
+            u64 const arena_words = lane->trace.cap / 4;
+            u64 used = 0;
+            for (size_t k = 0; k < ra_jobs.size(); ++k) {
+                if (ra_jobs[k].trace_cap > arena_words) ra_jobs[k].trace_cap = (u32)std::min<u64>(arena_words, 0xFFFFFFFFull);
+                if (k - ra_cuts.back() == REALIGN_LAUNCH_JOBS || used + ra_jobs[k].trace_cap > arena_words) { ra_cuts.push_back(k); used = 0; }
+                ra_jobs[k].trace_off = used;
+                used += ra_jobs[k].trace_cap;
+            }
+            ra_cuts.push_back(ra_jobs.size());
+            if ((rc = h2d(lane, lane->ra_jobs, ra_jobs.data(), ra_jobs.size() * sizeof(DevRealignJob)))) return rc;
+            if ((rc = lane->cigar_ra.ensure(cigar_words * 4 + 16))) return rc;
+        }
+        // the words everything behind K5 reads: K5's, the realigned or the normalised ones
+        u32* const d_ra_words = realign ? lane->cigar_ra.as<u32>() : lane->cigar.as<u32>();
+        u32* const d_words = want_left_align ? lane->cigar_la.as<u32>() : d_ra_words;
         // The small result tables (16 bytes per path, MD lengths, tails) come back through the lane's mapped result block when it holds them
         // all: K5 stores its DevTraceOuts there itself when nothing on the device reads them; md_build, cigar_tails and cigar_left_align read them, so with
         // any of them they stay on the device and one publish_stage launch behind the stage hands all the tables over.
@@ -340,21 +373,35 @@ struct Traceback {
         md_outs.resize(md_jobs.size());
         tail_outs.resize(tail_jobs.size());
         la_stats.resize(la_jobs.size());
+        ra_stats.resize(ra_jobs.size());
         DevTraceOut* r_outs = (DevTraceOut*)lane->result_slot(outs.size() * sizeof(DevTraceOut));
         DevMdOut* r_md = want_md ? (DevMdOut*)lane->result_slot(md_outs.size() * sizeof(DevMdOut)) : nullptr;
         DevTailOut* r_tail = want_tails ? (DevTailOut*)lane->result_slot(tail_outs.size() * sizeof(DevTailOut)) : nullptr;
         DevLeftAlignStat* r_la = want_left_align ? (DevLeftAlignStat*)lane->result_slot(la_stats.size() * sizeof(DevLeftAlignStat)) : nullptr;
+        DevRealignStat* r_ra = realign ? (DevRealignStat*)lane->result_slot(ra_stats.size() * sizeof(DevRealignStat)) : nullptr;
         bool const mapped = r_outs && (!want_md || r_md) && (!want_tails || r_tail) && (!want_left_align || r_la);
-        bool const direct = mapped && !want_md && !want_tails && !want_left_align;
+        // (nothing on the device reads cigar_realign's statistics: the kernel stores them in the block itself when it has room)
+        if (realign && !r_ra && (rc = lane->ra_stat.ensure(ra_jobs.size() * sizeof(DevRealignStat)))) return rc;
+        DevRealignStat* const d_ra_stats = r_ra ? r_ra : lane->ra_stat.as<DevRealignStat>();
+        bool const direct = mapped && !want_md && !want_tails && !want_left_align && !realign;
         DevTraceOut* const d_outs = direct ? r_outs : lane->tjob_out.as<DevTraceOut>();
         rc = timed_launch(lane, "ed_traceback", path_steps * 18, path_steps, [&] {
             return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), d_jobs, (u32)jobs.size(), lane->cigar.as<u32>(), d_outs);
         });
         if (rc) return rc;
+        for (size_t c = 0; realign && c + 1 < ra_cuts.size(); ++c) {
+            size_t const first = ra_cuts[c], count = ra_cuts[c + 1] - first;
+            // (the cells it computes are known once its results are back: they are added below)
+            rc = timed_launch(lane, "cigar_realign", count * (sizeof(DevRealignJob) + 2 * sizeof(DevTraceOut) + sizeof(DevRealignStat)), 0, [&] {
+                return DeviceApi::cigar_realign(lane->stream, d_text, d_ra_query, lane->cigar.as<u32>(), d_outs, lane->ra_jobs.as<DevRealignJob>() + first,
+                                                (u32)count, *realign, lane->trace.as<u32>(), d_ra_words, d_ra_stats);
+            });
+            if (rc) return rc;
+        }
         if (want_left_align) {
             // (the words it reads and writes and the letters it compares are known once its results are back: they are added below)
             rc = timed_launch(lane, "cigar_left_align", la_jobs.size() * (sizeof(DevLeftAlignJob) + 2 * sizeof(DevTraceOut) + sizeof(DevLeftAlignStat)), 0, [&] {
-                return DeviceApi::cigar_left_align(lane->stream, d_text, d_la_query, lane->cigar.as<u32>(), d_outs, d_la_jobs, (u32)la_jobs.size(), d_words,
+                return DeviceApi::cigar_left_align(lane->stream, d_text, d_la_query, d_ra_words, d_outs, d_la_jobs, (u32)la_jobs.size(), d_words,
                                                    lane->la_stat.as<DevLeftAlignStat>());
             });
             if (rc) return rc;
@@ -395,7 +442,9 @@ struct Traceback {
         }
         if (want_tails && !mapped && (rc = d2h(lane, tail_outs.data(), lane->tail_out.ptr, tail_outs.size() * sizeof(DevTailOut)))) return rc;
         if (want_left_align && !mapped && (rc = d2h(lane, la_stats.data(), lane->la_stat.ptr, la_stats.size() * sizeof(DevLeftAlignStat)))) return rc;
+        if (realign && !r_ra && (rc = d2h(lane, ra_stats.data(), lane->ra_stat.ptr, ra_stats.size() * sizeof(DevRealignStat)))) return rc;
         if ((rc = lane->sync())) return rc;
+        if (r_ra) memcpy(ra_stats.data(), r_ra, ra_stats.size() * sizeof(DevRealignStat));
         if (mapped) {
             memcpy(outs.data(), r_outs, outs.size() * sizeof(DevTraceOut));
             if (want_left_align) memcpy(la_stats.data(), r_la, la_stats.size() * sizeof(DevLeftAlignStat));
@@ -404,7 +453,20 @@ struct Traceback {
         }
         if (prof) prof->mark("K5+d2h");
         for (auto const& t : outs)
-            if (t.cigar_len == 0xFFFFFFFFu) { set_error(want_left_align ? "ed_traceback / cigar_left_align: CIGAR slab overflow" : "ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+            if (t.cigar_len == 0xFFFFFFFFu) { set_error(want_left_align || realign ? "ed_traceback / cigar_realign / cigar_left_align: CIGAR slab overflow" : "ed_traceback: CIGAR slab overflow"); return FLX_ERR_INTERNAL; }
+        if (realign) {
+            // the trace is written once and read along the path + the words written; units: DP cells
+            u64 bytes = 0, cells = 0, changed = 0, kept = 0;
+            for (size_t j = 0; j < ra_jobs.size(); ++j) {
+                bytes += ra_stats[j].cells / 2 + 4ull * outs[j].cigar_len;
+                cells += ra_stats[j].cells; changed += ra_stats[j].changed; kept += ra_stats[j].kept;
+            }
+            lane->ctx->account_more("cigar_realign", bytes, cells);
+            std::lock_guard<std::mutex> g(lane->ctx->mu);
+            lane->ctx->realign.paths_realigned += ra_jobs.size() - kept;
+            lane->ctx->realign.paths_changed += changed;
+            lane->ctx->realign.paths_kept += kept;
+        }
         if (want_left_align) {
             // CIGAR words read and written + letters compared (both sides of every comparison); units: the gap words that moved or merged
             u64 bytes = 0, moved = 0;
@@ -431,19 +493,21 @@ struct Traceback {
     TraceResult result(u32 j, u32 nm) const {
         TraceResult res;
         res.exists = true;
-        res.nm = nm;
+        res.nm = res.ed = nm;
         res.begin = outs[j].begin;
         res.cigar_off = cigar_base + jobs[j].cigar_off + outs[j].cigar_start;
         res.cigar_len = outs[j].cigar_len;
         if (want_md) { res.md_off = md_base + md_jobs[j].md_off; res.md_len = md_outs[j].len; }
         if (want_tails) res.tail = tail_outs[j];
+        if (realign) { res.nm = ra_stats[j].num_errors; res.score = ra_stats[j].score; }      // (a kept path: NM is K4's)
         return res;
     }
 };
 
 // score, begin position and CIGAR (and MD string, when md_pool is given) for every (distinct) request
 int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
+                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
+                          const RealignScores* realign, const u8* d_ra_query) {
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer tprof("trace-jobs");
@@ -475,7 +539,7 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         tprof.mark("K4");
 
         // ---- traceback for the jobs that have an alignment within k
-        Traceback tb(md_pool != nullptr, tails, d_la_query, &tprof);
+        Traceback tb(md_pool != nullptr, tails, d_la_query, &tprof, realign, d_ra_query);
         hvec<u32> tjob_req;
         for (size_t c = 0; c < count; ++c) {
             if (outs[c].score == 0xFFFFFFFFu) continue;
@@ -499,9 +563,10 @@ int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequ
 
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
 int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
+                   const RealignScores* realign, const u8* d_ra_query) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query);
+        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query);
     });
 }
 
@@ -638,7 +703,8 @@ namespace {
 
 // the union form over distinct requests (n_requests: with their duplicates, for the debug line)
 int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& uniq, size_t n_requests,
-                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
+                                hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
+                                const RealignScores* realign, const u8* d_ra_query) {
     bool usable = !uniq.empty() && !getenv("FLX_NO_UNION");
     for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
     // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
@@ -671,7 +737,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
             members.push_back(id);
         }
     }
-    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query);      // nothing to share: the plain path
+    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query);      // nothing to share: the plain path
 
     ures.assign(uniq.size(), TraceResult{});
     hvec<AlignRequest> ureqs(unions.size());
@@ -746,7 +812,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         if (wouts_in_place) memcpy(wouts.data(), d_wouts, n_wins * sizeof(DevAlignOut));
 
         // ---- one traceback per distinct (union, end column); the members of a union share its trace job's CIGAR words and MD string
-        Traceback tb(md_pool != nullptr, tails, d_la_query);
+        Traceback tb(md_pool != nullptr, tails, d_la_query, nullptr, realign, d_ra_query);
         hvec<u32> win_tjob(n_wins, 0xFFFFFFFFu);
         for (size_t w0 = 0; w0 < n_wins;) {                     // windows of one union are consecutive
             size_t w1 = w0;
@@ -779,7 +845,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
     }
     if (!fallback.empty()) {
         hvec<TraceResult> fres;
-        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails, d_la_query))) return rc;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
     if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu traceback jobs %zu unions with several jobs %zu\n", n_requests, uniq.size(), unions.size(), fallback.size(), n_tjobs, n_unions_several_jobs);
@@ -789,9 +855,10 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
 }  // namespace
 
 int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query) {
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
+                         const RealignScores* realign, const u8* d_ra_query) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails, d_la_query);
+        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query);
     });
 }
 
@@ -868,6 +935,64 @@ int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u
         moved += stats[j].moved;
     }
     lane->ctx->account_more("cigar_left_align", bytes, moved);
+    return FLX_OK;
+}
+
+// cigar_realign over CIGAR words and DevTraceOuts made on the host: the kernel alone. jobs[i].trace_cap holds the words of trace job i
+// needs (0: it does not fit the lane's arena and keeps its path); the jobs are cut into launches of at most REALIGN_LAUNCH_JOBS jobs
+// whose traces fit the arena together, and trace_off is set here.
+int run_realign_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts, hvec<DevRealignJob>& jobs,
+                     RealignScores const& scores, u64 words_out, hvec<u32>& out_words, hvec<DevRealignStat>& stats) {
+    out_words.assign(words_out, 0u);
+    stats.assign(jobs.size(), DevRealignStat{0, 0u, 0, 0, 0u, 0u, 0ull});
+    if (jobs.empty()) return FLX_OK;
+    int rc;
+    u64 const arena_words = std::max<u64>(lane->trace_budget_bytes / 4, 1);
+    hvec<size_t> cuts{0};
+    u64 used = 0, largest = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        if (jobs[j].trace_cap > arena_words) jobs[j].trace_cap = 0;
+        if (j - cuts.back() == REALIGN_LAUNCH_JOBS || used + jobs[j].trace_cap > arena_words) { cuts.push_back(j); used = 0; }
+        jobs[j].trace_off = used;
+        used += jobs[j].trace_cap;
+        largest = std::max(largest, used);
+    }
+    cuts.push_back(jobs.size());
+    if ((rc = h2d(lane, lane->cigar, words, n_words * 4))) return rc;
+    if ((rc = h2d(lane, lane->tjob_out, touts.data(), touts.size() * sizeof(DevTraceOut)))) return rc;
+    if ((rc = h2d(lane, lane->ra_jobs, jobs.data(), jobs.size() * sizeof(DevRealignJob)))) return rc;
+    if ((rc = lane->cigar_ra.ensure(words_out * 4 + 16))) return rc;
+    if ((rc = lane->ra_stat.ensure(jobs.size() * sizeof(DevRealignStat)))) return rc;
+    // (the arena is taken as the traceback stage takes it on first use: no reallocation when that stage runs later)
+    if ((rc = lane->trace.ensure(std::max<size_t>(largest * 4 + 64, lane->trace.ptr ? 0 : lane->trace_budget_bytes / 3 * 2)))) return rc;
+    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+        size_t const first = cuts[k], count = cuts[k + 1] - first;
+        // (the cells it computes are known once its results are back: they are added below)
+        rc = timed_launch(lane, "cigar_realign", count * (sizeof(DevRealignJob) + 2 * sizeof(DevTraceOut) + sizeof(DevRealignStat)), 0, [&] {
+            return DeviceApi::cigar_realign(lane->stream, d_text, d_query, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(),
+                                            lane->ra_jobs.as<DevRealignJob>() + first, (u32)count, scores, lane->trace.as<u32>(), lane->cigar_ra.as<u32>(),
+                                            lane->ra_stat.as<DevRealignStat>());
+        });
+        if (rc) return rc;
+    }
+    if ((rc = d2h(lane, touts.data(), lane->tjob_out.ptr, touts.size() * sizeof(DevTraceOut)))) return rc;
+    if ((rc = d2h(lane, out_words.data(), lane->cigar_ra.ptr, words_out * 4))) return rc;
+    if ((rc = d2h(lane, stats.data(), lane->ra_stat.ptr, stats.size() * sizeof(DevRealignStat)))) return rc;
+    if ((rc = lane->sync())) return rc;
+    // the trace is written once and read once along the path; work units: DP cells
+    u64 bytes = 0, cells = 0, changed = 0, kept = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        if (touts[j].cigar_len == 0xFFFFFFFFu) { set_error("cigar_realign: CIGAR slab overflow, or a path that leaves its window or its query"); return FLX_ERR_INTERNAL; }
+        bytes += stats[j].cells / 2 + 4ull * touts[j].cigar_len;
+        cells += stats[j].cells; changed += stats[j].changed; kept += stats[j].kept;
+    }
+    lane->ctx->account_more("cigar_realign", bytes, cells);
+    {
+        std::lock_guard<std::mutex> g(lane->ctx->mu);
+        lane->ctx->realign.paths_realigned += jobs.size() - kept;
+        lane->ctx->realign.paths_changed += changed;
+        lane->ctx->realign.paths_kept += kept;
+    }
     return FLX_OK;
 }
 
@@ -955,13 +1080,22 @@ extern "C" int flx_align_batch_md(flx_ctx* ctx, const uint8_t* ref_pool, uint64_
                                   uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes) {
     return flx_align_batch_gaps(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, out_md, md_pool, md_pool_bytes, nullptr);
 }
-// out_md == NULL: no MD strings (flx_align_batch); gaps NULL or zeroed: the gaps stay where K5 put them (flx_align_batch_md)
 extern "C" int flx_align_batch_gaps(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
                                     uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                                     uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes,
                                     const flx_gap_options* gaps) {
-    std::string const fn = gap_options_active(gaps) ? "flx_align_batch_gaps" : out_md ? "flx_align_batch_md" : "flx_align_batch";        // (both forward here)
-    if (!gap_options_valid(gaps)) return FLX_ERR_INVALID;
+    return flx_align_batch_realign(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, out_md, md_pool,
+                                   md_pool_bytes, gaps, nullptr, nullptr);
+}
+// out_md == NULL: no MD strings (flx_align_batch); gaps NULL or zeroed: the gaps stay where K5 put them (flx_align_batch_md); realign
+// NULL or zeroed: the paths stay edit-distance paths (flx_align_batch_gaps)
+extern "C" int flx_align_batch_realign(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
+                                       uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
+                                       uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes,
+                                       const flx_gap_options* gaps, const flx_realign_options* realign, int32_t* out_scores) {
+    std::string const fn = realign_options_active(realign) ? "flx_align_batch_realign" : gap_options_active(gaps) ? "flx_align_batch_gaps" : out_md ? "flx_align_batch_md" : "flx_align_batch";        // (all forward here)
+    if (!gap_options_valid(gaps) || !realign_options_valid(realign)) return FLX_ERR_INVALID;
+    RealignScores const ra_scores = realign_scores(realign);
     if (out_md && !md_pool_bytes) { set_error(fn + ": null argument"); return FLX_ERR_INVALID; }
     uint64_t const md_pool_cap = md_pool_bytes ? *md_pool_bytes : 0;
     if (md_pool_bytes) *md_pool_bytes = 0;                                            // (out: bytes used, also on an early return)
@@ -1012,6 +1146,7 @@ extern "C" int flx_align_batch_gaps(flx_ctx* ctx, const uint8_t* ref_pool, uint6
     hvec<u32> const &score_ids = B.ids[FLX_MODE_EXISTS], &rev_ids = B.ids[FLX_MODE_WITHOUT_CIGAR], &trace_ids = B.ids[FLX_MODE_WITH_CIGAR];
     for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_align_result{0, 0, 0, 0, 0, 0};
     if (out_md) for (uint64_t i = 0; i < n_jobs; ++i) out_md[i] = flx_md_ref{0, 0, 0};
+    if (out_scores) for (uint64_t i = 0; i < n_jobs; ++i) out_scores[i] = 0;
     hvec<DevAlignOut> outs;
     if ((rc = run_score_jobs(L, d_text, L->peq.as<u64>(), score_reqs, outs, "ed_align_exists"))) return rc;
     for (size_t i = 0; i < outs.size(); ++i)
@@ -1025,7 +1160,8 @@ extern "C" int flx_align_batch_gaps(flx_ctx* ctx, const uint8_t* ref_pool, uint6
     hvec<TraceResult> tres;
     hvec<u32> cig;
     hvec<u8> mdp;
-    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig, out_md ? &mdp : nullptr, nullptr, gap_options_active(gaps) ? L->seq.as<u8>() : nullptr))) return rc;
+    if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig, out_md ? &mdp : nullptr, nullptr, gap_options_active(gaps) ? L->seq.as<u8>() : nullptr,
+                             &ra_scores, realign_options_active(realign) ? L->seq.as<u8>() : nullptr))) return rc;
     uint64_t const cap = cigar_pool_words ? *cigar_pool_words : 0;
     if (cigar_pool_words) *cigar_pool_words = cig.size();
     if (any_trace && (!cigar_pool || cig.size() > cap)) { set_error("cigar pool too small"); return FLX_ERR_CAPACITY; }
@@ -1040,6 +1176,7 @@ extern "C" int flx_align_batch_gaps(flx_ctx* ctx, const uint8_t* ref_pool, uint6
             flx_align_result& r = out[trace_ids[i]];
             r.exists = 1; r.num_errors = tres[i].nm; r.begin = tres[i].begin; r.cigar_offset = tres[i].cigar_off; r.cigar_length = tres[i].cigar_len;
             if (out_md) out_md[trace_ids[i]] = flx_md_ref{tres[i].md_off, tres[i].md_len, 0};
+            if (out_scores) out_scores[trace_ids[i]] = tres[i].score;
         }
     return FLX_OK;
 }
@@ -1139,6 +1276,60 @@ extern "C" int flx_left_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint6
     for (uint64_t i = 0; i < n_jobs; ++i) {                   // the slabs packed in job order
         if (touts[i].cigar_len) memcpy(out_words + used, slabs.data() + dj[i].out_off + touts[i].cigar_start, 4ull * touts[i].cigar_len);
         out[i] = flx_cigar_ref{used, touts[i].cigar_len, 0};
+        used += touts[i].cigar_len;
+    }
+    return FLX_OK;
+}
+
+// ================================================================================================ C ABI: the realign kernel alone
+extern "C" int flx_realign_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                                 const uint32_t* cigar_words, uint64_t n_words, const flx_realign_job* jobs, uint64_t n_jobs,
+                                 const flx_realign_options* options, uint32_t* out_words, uint64_t* out_n_words, flx_realign_result* out) {
+    if (!realign_options_valid(options)) return FLX_ERR_INVALID;
+    if (!ctx || !out_n_words || (n_jobs && (!jobs || !out)) || (n_words && !cigar_words) || (query_pool_len && !query_pool)) {
+        set_error("flx_realign_batch: null argument"); return FLX_ERR_INVALID;
+    }
+    uint64_t const out_cap = *out_n_words;
+    *out_n_words = 0;
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    u64 const text_len = ref_pool ? ref_pool_len : ctx->hidx->n;
+    if (!left_align_jobs_valid(text_len, query_pool_len, cigar_words, n_words, jobs, n_jobs, "flx_realign_batch")) return FLX_ERR_INVALID;      // (before any launch)
+    RealignScores const scores = realign_scores(options);
+    hvec<DevTraceOut> touts(n_jobs);
+    hvec<DevRealignJob> dj(n_jobs);
+    u64 slab_words = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_realign_job const& j = jobs[i];
+        RealignShape const p = realign_shape(cigar_words + j.cigar_offset, j.cigar_length, scores);
+        u64 const cap = realign_cap(p.nm, j.cigar_length, scores);
+        u64 const need = realign_trace_words(p.m, (u64)((int64_t)p.d_max - p.d_min + 2 * (int64_t)scores.w + 1));
+        if (cap >= (1ull << 32)) { set_error("flx_realign_batch: a job's result could exceed 2^32 words"); return FLX_ERR_INVALID; }
+        touts[i] = DevTraceOut{j.begin, 0, j.cigar_length, 0};
+        // (a need beyond 32 bits is beyond every arena: 0 words, the path is kept)
+        dj[i] = DevRealignJob{j.ref_offset, j.query_offset, j.cigar_offset, slab_words, 0, j.ref_length, j.query_length, (u32)cap, (u32)i,
+                              need > 0xFFFFFFFFull ? 0u : (u32)need, 0};
+        slab_words += cap;
+    }
+    FLX_HIP(hipSetDevice(ctx->device));
+    int rc;
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    Lane* L = lease.lane;
+    hvec<u32> slabs;
+    hvec<DevRealignStat> stats;
+    if (n_jobs) {
+        const u8* d_text = ctx->didx.text;
+        if (ref_pool && (rc = upload_padded(L, L->user_text, ref_pool, ref_pool_len, &d_text))) return rc;
+        if ((rc = h2d(L, L->seq, query_pool, query_pool_len, 192))) return rc;
+        if ((rc = run_realign_jobs(L, d_text, L->seq.as<u8>(), cigar_words, n_words, touts, dj, scores, slab_words, slabs, stats))) return rc;
+    }
+    u64 used = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) used += touts[i].cigar_len;
+    *out_n_words = used;
+    if (used > out_cap || (used && !out_words)) { set_error("flx_realign_batch: the output word pool is too small"); return FLX_ERR_CAPACITY; }
+    used = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) {                   // the slabs packed in job order
+        if (touts[i].cigar_len) memcpy(out_words + used, slabs.data() + dj[i].out_off + touts[i].cigar_start, 4ull * touts[i].cigar_len);
+        out[i] = flx_realign_result{used, touts[i].cigar_len, stats[i].num_errors, stats[i].score, stats[i].diag_lo, stats[i].diag_hi, stats[i].kept};
         used += touts[i].cigar_len;
     }
     return FLX_OK;

@@ -307,6 +307,13 @@ int flx_ctx_reset_path_counters(flx_ctx* ctx) {
     std::lock_guard<std::mutex> g(ctx->mu);
     ctx->path = flx_path_counters{};
     ctx->search = flx_search_counters{};
+    ctx->realign = flx_realign_counters{};
+    return FLX_OK;
+}
+int flx_ctx_get_realign_counters(flx_ctx* ctx, flx_realign_counters* out) {
+    if (!ctx || !out) { set_error("null argument"); return FLX_ERR_INVALID; }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    *out = ctx->realign;
     return FLX_OK;
 }
 int flx_ctx_get_search_counters(flx_ctx* ctx, flx_search_counters* out) {

@@ -11,6 +11,7 @@
 #include "flx_select.hpp"
 #include "flx_tails.hpp"
 #include "flx_leftalign.hpp"
+#include "flx_realign.hpp"
 
 namespace flx {
 const char* last_error_cstr();
@@ -263,6 +264,32 @@ int flx_left_align(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t
     if (all.size() > out_cap || (!all.empty() && !out_words)) { set_error("flx_left_align: the output word pool is too small"); return FLX_ERR_CAPACITY; }
     if (!all.empty()) memcpy(out_words, all.data(), all.size() * 4);
     for (u64 i = 0; i < n_jobs; ++i) out[i] = refs[i];
+    return FLX_OK;
+}
+
+int flx_realign(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len, const uint32_t* cigar_words,
+                uint64_t n_words, const flx_realign_job* jobs, uint64_t n_jobs, const flx_realign_options* options, uint32_t* out_words,
+                uint64_t* out_n_words, flx_realign_result* out) {
+    if (!realign_options_valid(options)) return FLX_ERR_INVALID;
+    if (!out_n_words || (n_jobs && (!jobs || !out)) || (n_words && !cigar_words) || (ref_pool_len && !ref_pool) || (query_pool_len && !query_pool)) {
+        set_error("flx_realign: null argument"); return FLX_ERR_INVALID;
+    }
+    uint64_t const out_cap = *out_n_words;
+    *out_n_words = 0;
+    if (!left_align_jobs_valid(ref_pool_len, query_pool_len, cigar_words, n_words, jobs, n_jobs, "flx_realign")) return FLX_ERR_INVALID;
+    RealignScores const scores = realign_scores(options);
+    std::vector<uint32_t> all, one;
+    std::vector<flx_realign_result> res(n_jobs);
+    for (u64 i = 0; i < n_jobs; ++i) {
+        flx_realign_job const& j = jobs[i];
+        RealignOut const r = realign_path(cigar_words + j.cigar_offset, j.cigar_length, ref_pool + j.ref_offset, query_pool + j.query_offset, j.begin, scores, one);
+        res[i] = flx_realign_result{all.size(), (uint32_t)one.size(), r.num_errors, r.score, r.diag_lo, r.diag_hi, r.kept};
+        all.insert(all.end(), one.begin(), one.end());
+    }
+    *out_n_words = all.size();
+    if (all.size() > out_cap || (!all.empty() && !out_words)) { set_error("flx_realign: the output word pool is too small"); return FLX_ERR_CAPACITY; }
+    if (!all.empty()) memcpy(out_words, all.data(), all.size() * 4);
+    for (u64 i = 0; i < n_jobs; ++i) out[i] = res[i];
     return FLX_OK;
 }
 

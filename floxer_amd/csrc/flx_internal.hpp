@@ -199,6 +199,24 @@ struct DevLeftAlignJob {
 };
 struct DevLeftAlignStat { u32 words_in, letters, gaps, moved; };   // words read, letters compared (per sequence), gap words, gap words that moved or merged
 
+// ---- affine-gap realignment of traced paths (flx_realign.hip; the rule: flx_realign.hpp), one job per path: the kernel reads the job's
+// DevTraceOut and CIGAR words, runs the banded DP with its trace in the job's part of the trace arena, writes the new words right to
+// left into the job's slab of a second buffer and rewrites the DevTraceOut (begin stays; cigar_len 0xFFFFFFFF: the slab was too small,
+// or the path leaves its window or its query)
+struct DevRealignJob {
+    u64 ref_off, q_off;                            // the job's window in the text and its query in the query pool
+    u64 cigar_off, out_off;                        // the job's input words and its slab in the second buffer (words)
+    u64 trace_off;                                 // the job's part of the trace arena (32-bit words)
+    u32 n, m;                                      // columns of the window, rows of the query: nothing is read beyond them
+    u32 out_cap;                                   // words of the slab
+    u32 out_index;                                 // the job's DevTraceOut and DevRealignStat
+    u32 trace_cap;                                 // 32-bit words of its trace; a path that needs more keeps its words
+    u32 pad;
+};
+struct DevRealignStat { int32_t score; u32 num_errors; int32_t diag_lo, diag_hi; u32 kept, changed; u64 cells; };   // cells: band cells computed
+static_assert(sizeof(DevRealignJob) == 64 && sizeof(DevRealignStat) == 32, "device layouts");
+struct RealignScores;
+
 // ---- extension of a partial record's end (flx_extend.hip): one job per end, one wave per job
 struct DevExtendJob {
     u64 text_pos, q_pos;        // the first column's symbol in the device text, the first row's symbol in the device query pool
@@ -425,6 +443,9 @@ struct DeviceApi {
     // flx_leftalign.hip: the words of every job normalised into d_cigar_out, the job's DevTraceOut rewritten to describe them
     static int cigar_left_align(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, DevTraceOut* d_trace_out, const DevLeftAlignJob* d_jobs,
                                 u32 n_jobs, u32* d_cigar_out, DevLeftAlignStat* d_stats);
+    // flx_realign.hip: every job's path realigned into d_cigar_out, the job's DevTraceOut rewritten to describe the new words
+    static int cigar_realign(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, DevTraceOut* d_trace_out, const DevRealignJob* d_jobs,
+                             u32 n_jobs, RealignScores const& scores, u32* d_trace, u32* d_cigar_out, DevRealignStat* d_stats);
     // flx_extend.hip: lds_d = the largest min(d_max, row_limit) of the jobs (the launch's LDS: extend_lds_bytes(lds_d) <= 64 KiB)
     static size_t extend_lds_bytes(u32 d_max);
     static int extend(void* stream, const u8* d_text, const u8* d_query, const DevExtendJob* d_jobs, u32 n_jobs, u32 lds_d, DevExtendOut* d_out);

@@ -577,11 +577,11 @@ struct SpanCache { const uint32_t* of = nullptr; uint32_t len = 0; int64_t span 
 // one record as SAM text or as a BAM record, appended to `out`; false: the record cannot be represented (error set)
 // cigar_at (BAM): where in `out` the record's CIGAR array starts (SIZE_MAX: it has none of its own)
 // mdr (may be null): the record's MD string in md_bytes, written as MD:Z behind NM on a mapped record when its length is not 0; md_at (BAM):
-// where in `out` its bytes start (SIZE_MAX: none)
+// where in `out` its bytes start (SIZE_MAX: none); score (may be null): written as AS:i behind NM / MD on a mapped record
 bool format_record(flx_sam_writer const* w, flx_record const& r, const char* const* read_ids, const uint8_t* read_pool,
                    const uint64_t* read_offsets, const char* const* quals, const uint32_t* cigar_words, std::vector<uint8_t>& out, std::string& err,
                    SpanCache& span_cache, size_t* cigar_at = nullptr, const flx_md_ref* mdr = nullptr, const uint8_t* md_bytes = nullptr,
-                   size_t* md_at = nullptr, const std::string* sa = nullptr) {
+                   size_t* md_at = nullptr, const std::string* sa = nullptr, const int32_t* score = nullptr) {
     static const char ops[] = "MIDNSHP=X";
     const char* id = read_ids[r.read_index];
     if (md_at) *md_at = SIZE_MAX;
@@ -627,6 +627,7 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         else app(qual, slen);
         if (!unmapped) { app("\tNM:i:", 6); app_num(r.num_errors); }
         if (md) { app("\tMD:Z:", 6); app((const char*)md, mdr->length); }
+        if (score && !unmapped) { app("\tAS:i:", 6); app_num(*score); }
         if (sa && !sa->empty()) { app("\tSA:Z:", 6); app(sa->data(), sa->size()); }
         out.push_back('\n');
         return true;
@@ -694,6 +695,7 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         out.insert(out.end(), md, md + mdr->length);
         out.push_back(0);
     }
+    if (score && !unmapped) { out.push_back('A'); out.push_back('S'); out.push_back('i'); put32(*score); }
     if (sa && !sa->empty()) {
         out.push_back('S'); out.push_back('A'); out.push_back('Z');
         out.insert(out.end(), sa->begin(), sa->end());
@@ -772,6 +774,12 @@ extern "C" int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, con
 extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
                                     const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
                                     const flx_md_ref* md, const uint8_t* md_bytes) {
+    return flx_sam_write_scored(w, read_ids, read_pool, read_offsets, quals, records, n_records, cigar_words, md, md_bytes, nullptr);
+}
+
+extern "C" int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
+                                    const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
+                                    const flx_md_ref* md, const uint8_t* md_bytes, const int32_t* scores) {
     if (!w || (n_records && (!records || !read_ids || !read_pool || !read_offsets))) { set_error("flx_sam_write: null argument"); return FLX_ERR_INVALID; }
     if (w->failed) { set_error("write error on the alignment output"); return FLX_ERR_IO; }
     std::vector<std::string> sa;                               // (made once for the whole call: the parts below cut reads anywhere)
@@ -831,7 +839,7 @@ extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_i
             for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i) {
                 size_t cigar_at = SIZE_MAX, md_at = SIZE_MAX;
                 uint64_t const t_format = prof_ns();
-                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[i] : nullptr)) break;
+                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr)) break;
                 if (writer_profile()) g_ns_format += prof_ns() - t_format;
                 if (cigar_at != SIZE_MAX) {
                     cigar_at += base;
@@ -876,7 +884,7 @@ extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_i
         }
         SpanCache span_cache;
         for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i)
-            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes, nullptr, w->sa_tag ? &sa[i] : nullptr)) break;
+            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes, nullptr, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr)) break;
     });
     for (auto const& e : errs) if (!e.empty()) { set_error(e); return FLX_ERR_INVALID; }
     for (auto const& part : parts) {

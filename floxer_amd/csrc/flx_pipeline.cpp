@@ -14,6 +14,7 @@
 #include "flx_select.hpp"
 #include "flx_tails.hpp"
 #include "flx_leftalign.hpp"
+#include "flx_realign.hpp"
 
 using namespace flx;
 
@@ -144,8 +145,9 @@ extern "C" int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* P, c
     return flx_align_reads_with_tags(ctx, P, read_pool, read_offsets, n_reads, O, nullptr, out);
 }
 // md and the partial alignments need the trace: refused together with without_cigar, before any work
-static bool run_options_valid(const flx_params* P, const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G) {
-    if (!gap_options_valid(G)) return false;
+static bool run_options_valid(const flx_params* P, const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A) {
+    if (!gap_options_valid(G) || !realign_options_valid(A)) return false;
+    if (realign_options_active(A) && P && P->without_cigar) { set_error("flx_realign_options.enable needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (gap_options_active(G) && P && P->without_cigar) { set_error("flx_gap_options.left_align needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (!split_options_valid(S)) return false;
     if (split_options_active(S)) {
@@ -176,11 +178,16 @@ extern "C" int flx_align_reads_split(flx_ctx* ctx, const flx_params* P, const ui
 }
 extern "C" int flx_align_reads_gaps(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
                                     const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, flx_run** out) {
-    if (!run_options_valid(P, R, S, G)) return FLX_ERR_INVALID;
+    return flx_align_reads_realign(ctx, P, read_pool, read_offsets, n_reads, R, S, G, nullptr, out);
+}
+extern "C" int flx_align_reads_realign(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                                       const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A,
+                                       flx_run** out) {
+    if (!run_options_valid(P, R, S, G, A)) return FLX_ERR_INVALID;
     flx_reads* rd = nullptr;
     int rc = flx_reads_upload(ctx, read_pool, read_offsets, n_reads, &rd);
     if (rc) return rc;
-    rc = flx_align_reads_resident_gaps(ctx, P, rd, R, S, G, out);
+    rc = flx_align_reads_resident_realign(ctx, P, rd, R, S, G, A, out);
     flx_reads_free(rd);
     return rc;
 }
@@ -206,7 +213,11 @@ extern "C" int flx_align_reads_resident_split(flx_ctx* ctx, const flx_params* P,
 }
 extern "C" int flx_align_reads_resident_gaps(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R,
                                              const flx_split_options* S, const flx_gap_options* G, flx_run** out) {
-    if (!run_options_valid(P, R, S, G)) return FLX_ERR_INVALID;
+    return flx_align_reads_resident_realign(ctx, P, RD, R, S, G, nullptr, out);
+}
+extern "C" int flx_align_reads_resident_realign(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R,
+                                                const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A, flx_run** out) {
+    if (!run_options_valid(P, R, S, G, A)) return FLX_ERR_INVALID;
     RunOptions opt{};                            // (a NULL bundle, a NULL member and a zeroed struct are the same: that option is off)
     if (R && R->output) opt.output = *R->output;
     if (R && R->tags) opt.tags = *R->tags;
@@ -214,6 +225,7 @@ extern "C" int flx_align_reads_resident_gaps(flx_ctx* ctx, const flx_params* P, 
     if (R && R->extend) opt.extend = *R->extend;
     if (S) opt.split = *S;
     if (G) opt.gaps = *G;
+    if (realign_options_active(A)) opt.realign = *A;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
@@ -224,6 +236,8 @@ extern "C" int flx_align_reads_resident_gaps(flx_ctx* ctx, const flx_params* P, 
     auto run = std::make_unique<flx_run>();
     run->skipped.assign(n_reads, 0);
     run->has_md = opt.tags.md;
+    run->has_scores = opt.realign.enable != 0;
+    run->realign = opt.realign;
     if (n_reads == 0) { *out = run.release(); return FLX_OK; }       // an empty batch is an empty run
     // reads are independent units (parallelization.cpp:77-87): the batch is cut into contiguous chunks and every lane (a host
     // thread with its own stream and workspaces) takes the next chunk when it is done with its last one.
@@ -360,6 +374,33 @@ extern "C" int flx_run_copy_md(const flx_run* run, flx_md_ref* refs, uint8_t* md
         if (md_bytes && !part.md.empty()) memcpy(md_bytes + mb, part.md.data(), part.md.size());
         rb += part.records.size();
         mb += part.md.size();
+    };
+    emit(*run);
+    for (auto const& p : run->parts) emit(p);
+    return FLX_OK;
+}
+// a record's score is read off its written words: the realigned path's H[m][n] is the score of its own words, and left-alignment, clips
+// and the extension of a partial record leave words whose score is again their own
+extern "C" int flx_run_copy_scores(const flx_run* run, int32_t* scores) {
+    if (!run) { set_error("null run"); return FLX_ERR_INVALID; }
+    if (!run->has_scores) { set_error("flx_run_copy_scores: the run was made without flx_realign_options.enable"); return FLX_ERR_INVALID; }
+    if (!scores) return FLX_OK;
+    RealignScores const s = realign_scores(&run->realign);
+    uint64_t rb = 0;
+    auto emit = [&](flx_run const& part) {
+        for (size_t r = 0; r < part.records.size(); ++r) {
+            flx_record const& rec = part.records[r];
+            int64_t score = 0;
+            if (!(rec.flag & 4u))
+                for (uint32_t t = 0; t < rec.cigar_length; ++t) {
+                    uint32_t const w = part.cigars[rec.cigar_offset + t], op = w & 15u, len = w >> 4;
+                    if (op == 7u) score += (int64_t)s.a * len;
+                    else if (op == 8u) score -= (int64_t)s.b * len;
+                    else if (op == 1u || op == 2u) score -= s.o + (int64_t)s.e * len;
+                }
+            scores[rb + r] = (int32_t)std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, score));
+        }
+        rb += part.records.size();
     };
     emit(*run);
     for (auto const& p : run->parts) emit(p);

@@ -23,6 +23,8 @@ struct flx_run {
     bool has_md = false;               // made with flx_tag_options.md: md_refs is parallel to records, offsets relative to this object's `md`
     flx::hvec<flx_md_ref> md_refs;
     flx::hvec<flx::u8> md;
+    bool has_scores = false;           // made with flx_realign_options.enable: `realign` holds the options the records' scores are taken under
+    flx_realign_options realign{};
     flx::hvec<flx_run> parts;          // a batch result is the in-order list of its slices (no concatenation on the host)
 };
 
@@ -109,7 +111,11 @@ constexpr int SEARCH_NEEDS_HOST_SEEDS = 1;
 
 // ---- flx_align_jobs.cpp
 struct AlignRequest { u64 ref_off, q_off; u32 n, m, k; };
-struct TraceResult { bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; };
+struct TraceResult {
+    bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{};
+    int32_t score = 0;          // a realigned path (flx_realign.hip): its score; nm is then its num_errors and
+    u32 ed = 0;                 // ed the edit distance K4 found (nm without the option)
+};
 // the values of the tail rule (flx_tails.hpp) for the traces that want it, defaults resolved
 struct TailParams { u32 w, x_drop, min_rows; };
 // host milliseconds of the host-rounds form, summed over a chunk's rounds (FLX_HOST_PROFILE); owned by the chunk
@@ -124,15 +130,23 @@ int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignReq
 // tails != null: the tails of every traced path as well (flx_tails.hip), in TraceResult::tail;
 // d_la_query != null: the device query pool's letters (q_off addresses them as it does the Peq planes), and every traced path's gaps are
 // left-aligned behind K5 (flx_leftalign.hip) before its MD string and tails are read off it
+// d_ra_query != null: the same letters, and every traced path is realigned under *realign behind K5 (flx_realign.hip) before all of that
+struct RealignScores;
 int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr);
+                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr,
+                   const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
 int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr);
+                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr,
+                         const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr);
 // one cigar_left_align launch over words and DevTraceOuts made on the host (flx_left_align_batch): out_words receives the second buffer
 // (words_out words), touts the rewritten DevTraceOuts
 int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts,
                         hvec<DevLeftAlignJob> const& jobs, u64 words_out, hvec<u32>& out_words);
+// cigar_realign over words and DevTraceOuts made on the host (flx_realign_batch), cut into launches that fit the lane's trace arena:
+// jobs[i].trace_cap = the trace words job i needs on entry; out_words receives the second buffer, touts the rewritten DevTraceOuts
+int run_realign_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts, hvec<DevRealignJob>& jobs,
+                     RealignScores const& scores, u64 words_out, hvec<u32>& out_words, hvec<DevRealignStat>& stats);
 // one cigar_tails launch over words and DevTraceOuts made on the host (flx_cigar_tails_batch)
 int run_tail_jobs(Lane* lane, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevTailJob> const& jobs, hvec<DevTailOut>& outs);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
@@ -166,7 +180,8 @@ struct AnchorState {
 };
 
 struct Span { u64 offset, length, extra; };
-struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; };
+// (ed: the edit distance verification found, what the statistics count; nm differs from it on a realigned path only)
+struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; u32 ed = 0; };
 
 // a record rescue_partials (flx_partial.hpp: a soft-clipped part of a read without a mapped record) or split_tails (flx_tails.hpp: the
 // kept part and the tails of a read mapped in full) leaves for write_records
@@ -204,6 +219,7 @@ struct Slice {
     hvec<u32> cig;                                                            // CIGAR pool of root_res
     bool want_md = false;                                                     // flx_tag_options.md: the traced paths' MD strings as well
     bool want_left_align = false;                                             // flx_gap_options.left_align: every traced path's gaps left-aligned
+    const RealignScores* realign = nullptr;                                   // flx_realign_options.enable: every traced path realigned under these scores
     hvec<u8> md;                                                              // MD pool of root_res
     // split_tails, rescue_partials: the records of the reads they split / rescued, read by read in the order they are written in;
     // {q_from, q_to} read-forward
@@ -217,12 +233,13 @@ struct Slice {
     // traces windows of the slice's reads (root windows, partial records): CIGAR words into cig, MD strings into md when wanted
     // tails: the paths' tails as well (align_roots alone asks for them)
     int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres, const TailParams* tails = nullptr) {
-        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails, want_left_align ? RD->d_pool.as<u8>() : nullptr);
+        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails, want_left_align ? RD->d_pool.as<u8>() : nullptr,
+                                    realign, realign ? RD->d_pool.as<u8>() : nullptr);
     }
 };
 
 // the options of a run by value (flx_run_options, validated): an option that is off is a zeroed member
-struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; flx_gap_options gaps; };
+struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; flx_gap_options gaps; flx_realign_options realign; };
 
 // produces the slice's records (read_index relative to the whole batch)
 int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run);

@@ -16,6 +16,7 @@
 #include "flx_mapq.hpp"
 #include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
+#include "flx_realign.hpp"
 #include "flx_select.hpp"
 #include "flx_tails.hpp"
 
@@ -567,7 +568,7 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, 
         hvec<DevAlignOut> outs;
         if ((rc = run_score_jobs(lane, ctx->text_rev.as<u8>() + TEXT_PAD, RD->d_peq_rev.as<u64>(), rev, outs, "ed_align_exists"))) return rc;
         for (size_t i = 0; i < outs.size(); ++i)
-            if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
+            if (outs[i].score != 0xFFFFFFFFu) { root_res[i].exists = true; root_res[i].nm = root_res[i].ed = outs[i].score; root_res[i].start = root_spans[i].offset + (root_reqs[i].n - outs[i].end_col); }
     } else {
         hvec<TraceResult> tres;
         // (flx_split_options: the tails of every root path come back with its CIGAR words; no other trace of the slice asks for them)
@@ -575,7 +576,7 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, 
         if ((rc = S.trace_windows(lane, RD, root_reqs, tres, R.split.enable ? &tails : nullptr))) return rc;
         for (size_t i = 0; i < tres.size(); ++i)
             if (tres[i].exists)
-                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len, tres[i].tail};
+                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len, tres[i].tail, tres[i].ed};
     }
     return FLX_OK;
 }
@@ -1027,7 +1028,7 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
         }
         if (st_local) {                                                                                  // parallelization.cpp:262-268
             u64 n_al = 0;
-            for (u32 i : roots_of_read[r]) if (root_res[i].exists) { ++n_al; st_local->at(Stats::EDIT_DISTANCE).add(root_res[i].nm); }
+            for (u32 i : roots_of_read[r]) if (root_res[i].exists) { ++n_al; st_local->at(Stats::EDIT_DISTANCE).add(root_res[i].ed); }      // (what verification found: a realigned NM is not one)
             st_local->at(Stats::ALIGNMENTS_PER_QUERY).add(n_al);
         }
     }
@@ -1060,6 +1061,8 @@ int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_
     Slice S;
     S.want_md = R.tags.md;
     S.want_left_align = R.gaps.left_align != 0;
+    RealignScores const realign = realign_scores(&R.realign);
+    if (R.realign.enable) S.realign = &realign;
     int rc;
     if ((rc = plan_reads(S, P, RD, first_read, end_read, run))) return rc;
     if ((rc = plan_seeds(S, P, RD))) return rc;

@@ -513,6 +513,91 @@ int flx_left_align_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_poo
                          const uint32_t* cigar_words, uint64_t n_words, const flx_left_align_job* jobs, uint64_t n_jobs, uint32_t* out_words,
                          uint64_t* out_n_words, flx_cigar_ref* out);
 
+/* Affine-gap realignment of a traced path: not floxer's. Every CIGAR here is an edit-distance path whose traceback takes the first valid
+ * move among up, left and diagonal, so an indel of several bases often comes out scattered (1D 2= 1D 1= 1D) where a scored aligner
+ * writes 3D and an X or two; left-alignment moves a gap but merges none through an X or the other gap kind. The rule (kernel
+ * cigar_realign on the device, floxer_amd/csrc/flx_realign.hpp on the host) runs a global DP with affine gap costs over exactly the rows
+ * and columns the path consumes, inside a band around the path, and takes its optimum:
+ *   - match a, mismatch b, gap open o, gap extend e, all positive; a gap of length L costs o + e L. Letters are the index's ranks: equal
+ *     rank = match, no special case for ranks 0 and 5;
+ *   - band: d = j - i over the cells the input path visits, (0,0) included; lo = min d - band, hi = max d + band; nothing outside it;
+ *   - H[0][0] = 0, E[i][j] = max(H[i][j-1] - o - e, E[i][j-1] - e) (a D column), F[i][j] = max(H[i-1][j] - o - e, F[i-1][j] - e) (an I
+ *     row), H[i][j] = max(H[i-1][j-1] + (a or -b), E[i][j], F[i][j]), 32-bit signed;
+ *   - traceback from the last cell in state H, ties as everywhere here up > left > diagonal: H == F: to state F; else H == E: to state
+ *     E; else = or X. State F emits one I, steps up and stays while F[i][j] == F[i-1][j] - e; state E is its mirror image with D.
+ * Position and the rows and columns consumed never change. score = H[m][n] is at least the input path's score; num_errors = the X, I and
+ * D lengths of the new words and can exceed the edit distance; every = pairs equal letters, every X unequal ones; with
+ * c_max = max(a + b, o + e + a) and c_min = min(a + b, o + e) the result has at most 2 floor(NM c_max / c_min) + 1 words, NM being the
+ * input's X + I + D lengths. The rule is not idempotent: the band follows the input path. Limits: one gap-cost piece; nothing beyond
+ * the path's own columns (the ends stay where verification put them).
+ * 0 in a score field or in band is its default: match 2, mismatch 4, gap_open 4, gap_extend 2, band 16, the first piece of minimap2's
+ * map-ont scores: conventions, fitted to nothing. Bounds: each score <= 255, band <= 1024, c_max <= 8 c_min; enable is 0 or 1 and the
+ * reserved fields are 0; anything else is refused (FLX_ERR_INVALID) before any work. */
+typedef struct flx_realign_options {
+    uint32_t enable;       /* 0 off, 1 on, anything else refused */
+    uint32_t match;        /* 0: 2 */
+    uint32_t mismatch;     /* 0: 4 */
+    uint32_t gap_open;     /* 0: 4 */
+    uint32_t gap_extend;   /* 0: 2 */
+    uint32_t band;         /* 0: 16 */
+    uint32_t reserved[2];  /* must be 0 */
+} flx_realign_options;
+/* The rule alone on any CIGAR words: the jobs are flx_left_align's (same fields, same checks: a job outside its pools, an op other than
+ * = X I D, a zero-length word, op lengths that do not fit the window and the query, a reserved field that is not 0: FLX_ERR_INVALID,
+ * flx_realign_batch: before any launch). options: the scores and the band (NULL: the defaults; `enable` is judged and otherwise not
+ * looked at: the call is the request). out[i]: where job i's words lie in out_words (packed in job order), and its numbers;
+ * *out_n_words: in = capacity of out_words in words, out = words used (FLX_ERR_CAPACITY with the need stored when too small;
+ * max(cigar_length, 2 floor(NM c_max / c_min) + 1) per job always suffices). kept = 1: the path keeps its input words, with score 0 and
+ * num_errors = its NM: a path so long that (rows + columns + 2) max(a, b, o + e) reaches 2^29, and in flx_realign_batch also one whose
+ * trace (about rows * (hi - lo + 1) / 2 bytes) is larger than the context's trace arena. flx_realign runs on the host and needs
+ * ref_pool; flx_realign_batch runs the kernel, at most 4096 jobs and one trace arena per launch; ref_pool == NULL there: the context's
+ * reference text. Both give the same words and numbers. */
+typedef flx_left_align_job flx_realign_job;
+typedef struct flx_realign_result {
+    uint64_t offset;
+    uint32_t length;
+    uint32_t num_errors;
+    int32_t score;
+    int32_t diag_lo;
+    int32_t diag_hi;
+    uint32_t kept;
+} flx_realign_result;
+int flx_realign(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len, const uint32_t* cigar_words,
+                uint64_t n_words, const flx_realign_job* jobs, uint64_t n_jobs, const flx_realign_options* options, uint32_t* out_words,
+                uint64_t* out_n_words, flx_realign_result* out);
+int flx_realign_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                      const uint32_t* cigar_words, uint64_t n_words, const flx_realign_job* jobs, uint64_t n_jobs,
+                      const flx_realign_options* options, uint32_t* out_words, uint64_t* out_n_words, flx_realign_result* out);
+/* flx_align_batch_gaps with the realign options: K4, K5, cigar_realign, cigar_left_align, md_build on the WITH_CIGAR jobs, in that order,
+ * so left-alignment and MD read the realigned words. out[i].num_errors is then the realigned path's num_errors, begin stays, and
+ * out_scores[i] (may be NULL) receives its score (0 for jobs without a path, and for kept paths, which flx_realign_counters counts). realign NULL or with enable 0: exactly
+ * flx_align_batch_gaps, which forwards here. The launches are cut as flx_realign_batch cuts them. */
+int flx_align_batch_realign(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                            const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out, uint32_t* cigar_pool, uint64_t* cigar_pool_words,
+                            flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes, const flx_gap_options* gaps,
+                            const flx_realign_options* realign, int32_t* out_scores);
+/* flx_align_reads_gaps / flx_align_reads_resident_gaps with the realign options: every traced path of the run (root, partial, extended
+ * and split records) goes through cigar_realign behind K5, in front of cigar_left_align, md_build and cigar_tails, which read the
+ * realigned words. A record's num_errors is then its realigned path's, and that number is what the primary choice, the output options
+ * (-N, -D, MAPQ), the partial choice and the budgets of the split and extend retraces see; positions, rows, columns and the record order never
+ * change, and the statistics (flx_ctx_set_stats) keep counting the edit distance verification found. Refused together with
+ * params->without_cigar. realign NULL or with enable 0: exactly the _gaps calls, which forward here: no launch, no allocation, no byte
+ * of any output changes. */
+int flx_align_reads_realign(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                            const flx_run_options* options, const flx_split_options* split, const flx_gap_options* gaps,
+                            const flx_realign_options* realign, flx_run** out);
+int flx_align_reads_resident_realign(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_run_options* options,
+                                     const flx_split_options* split, const flx_gap_options* gaps, const flx_realign_options* realign,
+                                     flx_run** out);
+/* One score per record of a run made with flx_realign_options.enable, in flx_run_copy's order: the score of the record's written path
+ * under the run's scores (a per = column, -b per X column, -(o + e L) per I or D word of length L; clips count nothing), which for a
+ * root record is H[m][n] of its realignment; 0 for unmapped records. FLX_ERR_INVALID on a run made without the option. */
+int flx_run_copy_scores(const flx_run* run, int32_t* scores);
+/* what cigar_realign did on this context (runs, flx_realign_batch, flx_align_batch_realign) since the last flx_ctx_reset_path_counters: paths through the kernel, paths whose words
+ * changed, paths kept */
+typedef struct flx_realign_counters { uint64_t paths_realigned; uint64_t paths_changed; uint64_t paths_kept; uint64_t reserved[5]; } flx_realign_counters;
+int flx_ctx_get_realign_counters(flx_ctx* ctx, flx_realign_counters* out);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -585,6 +670,11 @@ int flx_sam_write(flx_sam_writer* w, const char* const* read_ids, const uint8_t*
 int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
                          const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
                          const flx_md_ref* md, const uint8_t* md_bytes);
+/* flx_sam_write_tagged with an AS:i tag behind NM / MD on every mapped record (scores[i], as flx_run_copy_scores gives them; ASi in BAM).
+ * scores == NULL: exactly flx_sam_write_tagged. */
+int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
+                         const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
+                         const flx_md_ref* md, const uint8_t* md_bytes, const int32_t* scores);
 int flx_sam_close(flx_sam_writer* w);
 /* record formatting and BGZF block compression of flx_sam_write on n_threads host threads (default 1; output bytes do not depend on it) */
 int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads);
