@@ -16,6 +16,7 @@ libfloxer_amd.so:
     aligner(..., split=split_options()), cigar_tails()  not floxer's: reads mapped in full that carry a chimeric tail are split (opt-in)
     aligner(..., gaps=gap_options()), left_align()  not floxer's: indels left-aligned on the device behind the traceback (opt-in)
     aligner(..., realign=realign_options()), realign(), realign_batch(), align_batch_realign()  not floxer's: a traced path realigned under affine gap costs inside a band around it (opt-in)
+    aligner(..., cs=cs_options()), cs_string(), cs_batch(), align_batch_cs()  not floxer's: minimap2's cs difference string, short or long form, built on the device behind the MD strings (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -227,8 +228,8 @@ class context:
         return {n: int(getattr(sc, n)) for n, _ in capi.SearchCounters._fields_ if n != "reserved"}
 
     def kernel_stats(self):
-        arr = (capi.KernelStat * 32)()
-        n = C.c_uint32(32)
+        arr = (capi.KernelStat * 64)()
+        n = C.c_uint32(64)
         check(lib().flx_ctx_get_kernel_stats(self.h, arr, C.byref(n)))
         return {a.name.decode(): dict(launches=a.launches, device_ms=a.device_ms, algorithmic_bytes=a.algorithmic_bytes,
                                       work_units=a.work_units) for a in arr[: n.value]}
@@ -410,6 +411,50 @@ def align_batch_realign(ctx, query_pool, jobs, realign, reference_pool=None, md=
     return out
 
 
+def align_batch_cs(ctx, query_pool, jobs, cs, reference_pool=None, md=False, gaps=None, realign=None):
+    """flx_align_batch_cs: align_batch_realign with the cs string of every traced path (cs = cs_options(...)), read off the final words
+    (realigned, then left-aligned) behind the MD strings. Returns a list of None | (num_errors, begin, cigar, md or None, score, cs or
+    None), the strings as bytes; cs None or cs_options with form 0: no strings (flx_align_batch_realign's results)."""
+    q = as_u8(query_pool)
+    arr = (capi.AlignJob * max(1, len(jobs)))()
+    cap_words = cap_md = cap_cs = 16
+    room_words, room_md = _realign_room(realign)
+    form = int(cs.form) if cs is not None else 0
+    for i, (ro, rl, qo, ql, k, mode) in enumerate(jobs):
+        arr[i] = capi.AlignJob(ro, qo, rl, ql, k, mode)
+        cap_words += room_words(k)
+        cap_md += room_md(k)
+        nm = (room_md(k) - 6) // 8                 # the NM that sizes the MD slab sizes the cs slab (cs_slab_bytes, flx_internal.hpp)
+        cap_cs += ql + 3 * nm + 1 if form == 2 else 10 * nm + 7
+    res = (capi.AlignResult * max(1, len(jobs)))()
+    cig = np.zeros(cap_words, dtype=np.uint32)
+    words = C.c_uint64(cap_words)
+    if reference_pool is None:
+        rp, rl_ = None, 0
+    else:
+        ref = as_u8(reference_pool)
+        rp, rl_ = ptr(ref, u8p), len(ref)
+    refs = (capi.MdRef * max(1, len(jobs)))() if md else None
+    mdp = np.zeros(cap_md if md else 1, dtype=np.uint8)
+    md_bytes = C.c_uint64(cap_md)
+    scores = np.zeros(max(1, len(jobs)), dtype=np.int32)
+    cs_refs = (capi.MdRef * max(1, len(jobs)))()
+    csp = np.zeros(cap_cs, dtype=np.uint8)
+    cs_bytes = C.c_uint64(cap_cs)
+    check(lib().flx_align_batch_cs(ctx.h, rp, rl_, ptr(q, u8p), len(q), arr, len(jobs), res, ptr(cig, u32p), C.byref(words), refs,
+                                   ptr(mdp, u8p) if md else None, C.byref(md_bytes) if md else None, C.byref(gaps) if gaps is not None else None,
+                                   C.byref(realign) if realign is not None else None, scores.ctypes.data_as(C.POINTER(C.c_int32)),
+                                   C.byref(cs) if cs is not None else None, cs_refs, ptr(csp, u8p), C.byref(cs_bytes)))
+    out = []
+    for i, r in enumerate(res[: len(jobs)]):
+        m = refs[i] if md else None
+        c = cs_refs[i] if form else None
+        out.append((r.num_errors, r.begin, cigar_string(cig[r.cigar_offset: r.cigar_offset + r.cigar_length]),
+                    mdp[m.offset: m.offset + m.length].tobytes() if m is not None and m.length else None, int(scores[i]),
+                    csp[c.offset: c.offset + c.length].tobytes() if c is not None and c.length else None) if r.exists else None)
+    return out
+
+
 def align_shapes(jobs):
     """the launch shape align_batch would give every job of a call with these jobs (flx_align_shapes; no context, no GPU):
     [(words_per_lane, lanes_per_job, queue)], queue = the hand-over slots the job's ring occupies, 0 for a ring that never waits."""
@@ -453,9 +498,13 @@ def params(error_probability=None, query_errors=None, seed_errors=2, max_anchors
 class RunResult:
     """records of one flx_align_reads* call. `raw` is the flx_record array as the C ABI returns it; `rows` is the same as an (n,7)
     int64 matrix {read_index, flag, ref_id, pos, nm, cigar_off, cigar_len}, made on first use. A run made with md=True also has
-    `md_refs` ((n,2) uint64 {offset, length} into `md_bytes`) and `md`, a list of bytes / None per record, made on first use."""
+    `md_refs` ((n,2) uint64 {offset, length} into `md_bytes`) and `md`, a list of bytes / None per record, made on first use; a run
+    made with cs=cs_options(...) has `cs_refs`, `cs_bytes` and `cs` in the same way."""
 
-    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None, scores=None):
+    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None, scores=None, cs_refs=None, cs_bytes=None):
+        self.cs_refs = cs_refs
+        self.cs_bytes = cs_bytes
+        self._cs = None
         self.scores = scores            # int32 per record (flx_run_copy_scores) of a run made with realign=realign_options(...), else None
         self.raw = raw
         self.cigars = cigars
@@ -474,6 +523,16 @@ class RunResult:
             buf = self.md_bytes.tobytes()
             self._md = [buf[int(o): int(o) + int(n)] if n else None for o, n in self.md_refs]
         return self._md
+
+    @property
+    def cs(self):
+        """the records' cs strings (bytes; None for a record without one); None for a run made without cs=cs_options(...)"""
+        if self.cs_refs is None:
+            return None
+        if self._cs is None:
+            buf = self.cs_bytes.tobytes()
+            self._cs = [buf[int(o): int(o) + int(n)] if n else None for o, n in self.cs_refs]
+        return self._cs
 
     @property
     def n_records(self):
@@ -754,6 +813,55 @@ def realign_batch(ctx, query_pool, words, jobs, options=None, reference_pool=Non
     return _realign_call(lib().flx_realign_batch, (ctx.h,), reference_pool, query_pool, words, jobs, options)
 
 
+def cs_options(long=False):
+    """flx_cs_options (include/floxer_amd.h): not floxer's. Every mapped record gets minimap2's cs difference string, built on the device
+    behind the MD strings (floxer_amd/csrc/flx_cs.hpp): the short form, or with long=True the long form, which holds the matched letters
+    as well. Not together with without_cigar."""
+    o = capi.CsOptions()
+    o.form = 2 if long else 1
+    return o
+
+
+def _cs_call(fn, head, reference_pool, query_pool, words, jobs, long):
+    q = as_u8(query_pool)
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
+    if reference_pool is None:
+        rp, rl_ = None, 0
+    else:
+        ref = as_u8(reference_pool)
+        rp, rl_ = ptr(ref, u8p), len(ref)
+    arr = (capi.CsJob * max(1, len(jobs)))()
+    cap = 16
+    for i, (co, cl, ro, rl, begin, qo, ql) in enumerate(jobs):
+        arr[i] = capi.CsJob(int(co), int(cl), 0, int(ro), int(rl), int(begin), int(qo), int(ql), 0)
+        # (the short form of a word is never longer than its long form: 1 + len, 3 len for X)
+        cap += sum((3 if int(x) & 15 == 8 else 1) * (int(x) >> 4) + 1 for x in w[int(co): int(co) + int(cl)]) if 0 <= int(co) <= len(w) else 0
+    refs = (capi.MdRef * max(1, len(jobs)))()
+    options = cs_options(long=long)
+    while True:
+        out = np.zeros(cap, dtype=np.uint8)
+        n = C.c_uint64(cap)
+        rc = fn(*head, rp, rl_, ptr(q, u8p), len(q), ptr(w, u32p), len(w), arr, len(jobs), C.byref(options), ptr(out, u8p), C.byref(n), refs)
+        if rc == -3 and n.value > cap:
+            cap = n.value
+            continue
+        check(rc)
+        break
+    return [out[r.offset: r.offset + r.length].tobytes() for r in refs[: len(jobs)]]
+
+
+def cs_string(reference_pool, query_pool, words, jobs, long=False):
+    """flx_cs, the cs rule on the host (floxer_amd/csrc/flx_cs.hpp): words = BAM CIGAR words (ops = X I D), jobs = [(cigar_offset,
+    cigar_length, ref_offset, ref_length, begin, query_offset, query_length)] as left_align takes them, query_offset the path's first
+    query row. Returns one bytes object per job."""
+    return _cs_call(lib().flx_cs, (), reference_pool, query_pool, words, jobs, long)
+
+
+def cs_batch(ctx, query_pool, words, jobs, long=False, reference_pool=None):
+    """flx_cs_batch: the same bytes from the kernel cs_build. reference_pool None = the context's reference text."""
+    return _cs_call(lib().flx_cs_batch, (ctx.h,), reference_pool, query_pool, words, jobs, long)
+
+
 def realign_counters(ctx):
     """flx_ctx_get_realign_counters: (paths_realigned, paths_changed, paths_kept) since the last reset of the path counters"""
     c = capi.RealignCounters()
@@ -833,7 +941,7 @@ def choose_partials(candidates, cigars=None, options=None):
     return out[: len(candidates)]
 
 
-def _collect_run(run, n, md=False, scores=False):
+def _collect_run(run, n, md=False, scores=False, cs=False):
     try:
         nr = lib().flx_run_num_records(run)
         nc = lib().flx_run_num_cigar_words(run)
@@ -855,23 +963,33 @@ def _collect_run(run, n, md=False, scores=False):
             sc = np.zeros(max(1, nr), dtype=np.int32)
             check(lib().flx_run_copy_scores(run, sc.ctypes.data_as(C.POINTER(C.c_int32))))
             sc = sc[:nr]
+        cs_refs = cs_bytes = None
+        if cs:
+            nb = lib().flx_run_num_cs_bytes(run)
+            refs = np.zeros(max(1, nr), dtype=_MD_DTYPE)
+            cs_bytes = np.zeros(max(1, nb), dtype=np.uint8)
+            check(lib().flx_run_copy_cs(run, refs.ctypes.data_as(C.POINTER(capi.MdRef)), ptr(cs_bytes, u8p)))
+            cs_refs = np.stack([refs["off"][:nr], refs["len"][:nr].astype(np.uint64)], axis=1) if nr else np.zeros((0, 2), dtype=np.uint64)
+            cs_bytes = cs_bytes[:nb]
     finally:
         lib().flx_run_free(run)
-    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes, sc)
+    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes, sc, cs_refs, cs_bytes)
 
 
 class aligner:
-    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None, gaps=None, realign=None):
+    def __init__(self, ctx, p, output=None, md=False, partial=None, extend=None, split=None, gaps=None, realign=None, cs=None):
         """output: output_options(...), None: every alignment is written (floxer's output); md: every mapped record gets its MD
         string (RunResult.md), built on the device; not together with without_cigar; partial: partial_options(...), None: a read
         without a full alignment is written as unmapped (floxer's output); extend: extend_options(...), None: a partial record ends at
         its PEX node's boundary (needs partial); split: split_options(...), None: a read mapped in full is one record whatever its
         ends look like (needs partial and output_options(max_alignments=1)); gaps: gap_options(...), None: gaps stay right-aligned
         (floxer's output); realign: realign_options(...), None: every CIGAR stays an edit-distance path (floxer's output); with it
-        RunResult.scores holds the records' scores"""
+        RunResult.scores holds the records' scores; cs: cs_options(...), None: no cs strings (floxer's output); with it RunResult.cs
+        holds the records' cs strings"""
         self.ctx, self.params, self.output, self.md, self.partial, self.extend, self.split = ctx, p, output, bool(md), partial, extend, split
         self.gaps = gaps
         self.realign = realign
+        self.cs = cs
 
     def align_reads(self, reads):
         """reads: list of rank arrays, (pool, offsets), or resident_reads. Returns RunResult with records in --threads 1 order."""
@@ -885,11 +1003,21 @@ class aligner:
         split = C.byref(self.split) if self.split is not None else None
         gaps = C.byref(self.gaps) if self.gaps is not None else None
         realign = C.byref(self.realign) if self.realign is not None else None
-        if isinstance(reads, resident_reads):
+        want_cs = self.cs is not None and bool(self.cs.form)
+        if self.cs is not None:
+            cs = C.byref(self.cs)
+            if isinstance(reads, resident_reads):
+                n = reads.n
+                check(lib().flx_align_reads_resident_cs(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, gaps, realign, cs, C.byref(run)))
+            else:
+                pool, offs, n = _pool_and_offsets(reads)
+                check(lib().flx_align_reads_cs(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, gaps,
+                                               realign, cs, C.byref(run)))
+        elif isinstance(reads, resident_reads):
             n = reads.n
             check(lib().flx_align_reads_resident_realign(self.ctx.h, C.byref(self.params), reads.h, C.byref(bundle), split, gaps, realign, C.byref(run)))
         else:
             pool, offs, n = _pool_and_offsets(reads)
             check(lib().flx_align_reads_realign(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, gaps,
                                                 realign, C.byref(run)))
-        return _collect_run(run, n, md=self.md, scores=self.realign is not None and bool(self.realign.enable))
+        return _collect_run(run, n, md=self.md, scores=self.realign is not None and bool(self.realign.enable), cs=want_cs)

@@ -134,6 +134,13 @@ class RealignCounters(C.Structure):
     _fields_ = [("paths_realigned", C.c_uint64), ("paths_changed", C.c_uint64), ("paths_kept", C.c_uint64), ("reserved", C.c_uint64 * 5)]
 
 
+class CsOptions(C.Structure):
+    _fields_ = [("form", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+CsJob = LeftAlignJob
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -199,6 +206,8 @@ EXPORTED = [
     "flx_realign", "flx_realign_batch", "flx_align_batch_realign", "flx_ctx_get_realign_counters", "flx_align_reads_realign",
     "flx_align_reads_resident_realign", "flx_run_copy_scores", "flx_sam_write_scored",
     "flx_ctx_get_search_counters",
+    "flx_align_reads_cs", "flx_align_reads_resident_cs", "flx_run_num_cs_bytes", "flx_run_copy_cs", "flx_align_batch_cs", "flx_cs", "flx_cs_batch",
+    "flx_sam_write_cs",
 ]
 
 _lib = None
@@ -316,6 +325,15 @@ def lib():
     L.flx_align_reads_realign.argtypes = L.flx_align_reads_gaps.argtypes[:-1] + [C.POINTER(RealignOptions), C.POINTER(C.c_void_p)]
     L.flx_align_reads_resident_realign.argtypes = L.flx_align_reads_resident_gaps.argtypes[:-1] + [C.POINTER(RealignOptions), C.POINTER(C.c_void_p)]
     L.flx_run_copy_scores.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.flx_align_reads_cs.argtypes = L.flx_align_reads_realign.argtypes[:-1] + [C.POINTER(CsOptions), C.POINTER(C.c_void_p)]
+    L.flx_align_reads_resident_cs.argtypes = L.flx_align_reads_resident_realign.argtypes[:-1] + [C.POINTER(CsOptions), C.POINTER(C.c_void_p)]
+    L.flx_run_num_cs_bytes.restype = C.c_uint64
+    L.flx_run_num_cs_bytes.argtypes = [C.c_void_p]
+    L.flx_run_copy_cs.argtypes = [C.c_void_p, C.POINTER(MdRef), u8p]
+    L.flx_align_batch_cs.argtypes = L.flx_align_batch_realign.argtypes + [C.POINTER(CsOptions), C.POINTER(MdRef), u8p, u64p]
+    L.flx_cs.argtypes = [u8p, C.c_uint64, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(CsJob), C.c_uint64, C.POINTER(CsOptions), u8p, u64p,
+                         C.POINTER(MdRef)]
+    L.flx_cs_batch.argtypes = [C.c_void_p] + L.flx_cs.argtypes
     L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]
@@ -328,6 +346,7 @@ def lib():
     L.flx_sam_write_tagged.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), u8p, u64p, C.POINTER(C.c_char_p), C.POINTER(Record), C.c_uint64, u32p,
                                        C.POINTER(MdRef), u8p]
     L.flx_sam_write_scored.argtypes = L.flx_sam_write_tagged.argtypes + [C.POINTER(C.c_int32)]
+    L.flx_sam_write_cs.argtypes = L.flx_sam_write_scored.argtypes + [C.POINTER(MdRef), u8p]
     L.flx_select_records.argtypes = [C.POINTER(Record), C.c_uint64, u32p, C.POINTER(OutputOptions), u8p]
     L.flx_assign_mapq.argtypes = [C.POINTER(Record), C.c_uint64, u32p, u64p, u8p]
     L.flx_run_num_records.restype = C.c_uint64

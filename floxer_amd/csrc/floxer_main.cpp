@@ -66,6 +66,7 @@ struct Options {
     uint64_t max_alignments = 0;                  // 0: no cap
     bool mapping_quality = false;
     bool md_tag = false;
+    bool cs_tag = false, cs_tag_long = false;
     bool partial_alignments = false;
     uint64_t partial_min_span = 0, partial_max = 0;   // 0: the library's defaults
     bool partial_extend = false, sa_tag = false;
@@ -94,6 +95,9 @@ const OptDef OPTS[] = {
     {'Q', "mapping-quality", true, "not floxer's: MAPQ from the read's distinct loci within its error budget instead of 255 (0..60; computed before -D / -N drop records)"},
     // nor this one: an MD:Z tag on every mapped record (flx_tag_options.md), built on the GPU next to the CIGARs
     {0, "md-tag", true, "not floxer's: MD:Z tag (reference bases at mismatches and deletions) on every mapped record; not with -w"},
+    // nor these: minimap2's cs:Z difference string on every mapped record (flx_cs_options), built on the GPU behind the MD strings
+    {0, "cs-tag", true, "not floxer's: cs:Z tag, short form (both sequences' letters at mismatches, insertions and deletions) on every mapped record; not with -w or --cs-tag-long"},
+    {0, "cs-tag-long", true, "not floxer's: cs:Z tag, long form (the matched letters as well) on every mapped record; not with -w or --cs-tag"},
     // nor these: soft-clipped partial alignments, primary + supplementary, for reads that would be unmapped (flx_partial_options, flx_partial.hpp)
     {0, "partial-alignments", true, "not floxer's: a read without a full alignment gets its largest verified parts as soft-clipped records (primary, then flag 2048); not with -w"},
     {0, "partial-min-span", false, "not floxer's: the fewest query bases of a partial alignment (default 1000)"},
@@ -214,6 +218,8 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "drop-duplicate-alignments") o.drop_duplicate_alignments = true;
         else if (n == "mapping-quality") o.mapping_quality = true;
         else if (n == "md-tag") o.md_tag = true;
+        else if (n == "cs-tag") o.cs_tag = true;
+        else if (n == "cs-tag-long") o.cs_tag_long = true;
         else if (n == "partial-alignments") o.partial_alignments = true;
         else if (n == "partial-min-span") { o.partial_min_span = parse_u64(n, value); range_check(n, (double)o.partial_min_span, 1, 100000); }
         else if (n == "partial-max") { o.partial_max = parse_u64(n, value); range_check(n, (double)o.partial_max, 1, 65535); }
@@ -255,6 +261,8 @@ Options parse_cli(int argc, char** argv) {
         throw CliError{"The hard maximum number of anchors (" + std::to_string(o.max_anchors_hard) + ") should not be smaller than the soft maximum number of anchors (" + std::to_string(o.max_anchors_soft) + ")."};
     if (o.seed_sampling_step_size == 0) throw CliError{"Validation failed for option --seed-sampling-step-size: must be at least 1."};
     if (o.md_tag && o.without_cigar) throw CliError{"The option --md-tag needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.cs_tag && o.cs_tag_long) throw CliError{"The options --cs-tag and --cs-tag-long select one form of the same tag and cannot be combined."};
+    if ((o.cs_tag || o.cs_tag_long) && o.without_cigar) throw CliError{"The options --cs-tag and --cs-tag-long need the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     if (o.partial_alignments && o.without_cigar) throw CliError{"The option --partial-alignments needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
     if (!o.partial_alignments && (o.partial_min_span || o.partial_max)) throw CliError{"The options --partial-min-span and --partial-max need --partial-alignments."};
     if (o.partial_extend && !o.partial_alignments) throw CliError{"The option --partial-extend needs --partial-alignments."};
@@ -703,6 +711,9 @@ int main(int argc, char** argv) {
     realign_opt.gap_open = (uint32_t)o.realign_gap_open;
     realign_opt.gap_extend = (uint32_t)o.realign_gap_extend;
     realign_opt.band = (uint32_t)o.realign_band;
+    flx_cs_options cs_opt;
+    memset(&cs_opt, 0, sizeof(cs_opt));
+    cs_opt.form = o.cs_tag_long ? 2u : o.cs_tag ? 1u : 0u;
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
@@ -716,7 +727,7 @@ int main(int argc, char** argv) {
     if (const char* env = getenv("FLX_BATCH_READS")) { size_t const v = strtoull(env, nullptr, 10); if (v) batch_reads = v; }
     // Batches are independent: up to three are in a context at a time (their chunks share its lanes), the next one is parsed
     // while they run, and results are written in input order.
-    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<int32_t> scores; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
+    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<int32_t> scores; std::vector<flx_md_ref> cs_refs; std::vector<uint8_t> cs; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
     // FLX_CLI_PROFILE=1: seconds this run spent parsing (this thread), aligning (sum over the batches' tasks) and writing (the writer
     // thread) on stderr at the end: which of the three stages bounds the end-to-end rate
     std::atomic<uint64_t> us_parse{0}, us_align{0}, us_copy{0}, us_write{0}, us_records{0};
@@ -733,7 +744,7 @@ int main(int argc, char** argv) {
             if (!ok) { f.rc = FLX_ERR_INVALID; f.err = perr; f.reader_error = true; f.batch = std::move(b); return f; }
         }
         uint64_t const t0 = now_us();
-        f.rc = flx_align_reads_realign(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &gap_opt, &realign_opt, &run);
+        f.rc = flx_align_reads_cs(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &gap_opt, &realign_opt, &cs_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
         f.recs.resize(flx_run_num_records(run));
@@ -749,6 +760,11 @@ int main(int argc, char** argv) {
         if (o.realign_affine) {
             f.scores.resize(f.recs.size() + 1);
             flx_run_copy_scores(run, f.scores.data());
+        }
+        if (cs_opt.form) {
+            f.cs_refs.resize(f.recs.size());
+            f.cs.resize(flx_run_num_cs_bytes(run) + 1);
+            flx_run_copy_cs(run, f.cs_refs.data(), f.cs.data());
         }
         flx_run_free(run);
         us_copy += now_us() - t1;
@@ -777,8 +793,9 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < f.skipped.size(); ++i)
             if (f.skipped[i]) log_line("warning", "skipping query: %s due to bad configuration regarding the number of errors.", batch.ids[i]);
         uint64_t const t0 = now_us();
-        if (flx_sam_write_scored(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
-                                 o.md_tag ? f.md_refs.data() : nullptr, f.md.data(), o.realign_affine ? f.scores.data() : nullptr) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+        if (flx_sam_write_cs(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
+                             o.md_tag ? f.md_refs.data() : nullptr, f.md.data(), o.realign_affine ? f.scores.data() : nullptr,
+                             cs_opt.form ? f.cs_refs.data() : nullptr, f.cs.data()) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
         us_write += now_us() - t0;
         total_reads += batch.ids.size();
         total_records += f.recs.size();

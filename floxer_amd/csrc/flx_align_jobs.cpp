@@ -15,6 +15,7 @@
 #include "flx_tails.hpp"
 #include "flx_leftalign.hpp"
 #include "flx_realign.hpp"
+#include "flx_cs.hpp"
 
 namespace flx {
 
@@ -268,7 +269,9 @@ constexpr size_t REALIGN_LAUNCH_JOBS = 4096;      // jobs of one cigar_realign l
 // (flx_tails.hip) when wanted: one tail job per trace job as well, cigar_tails queued behind K5 (behind md_build if both are on), its
 // 32-byte results back with the CIGAR words. Left-aligned gaps (flx_leftalign.hip) when wanted: one job per trace job again,
 // cigar_left_align queued between K5 and md_build; it writes the normalised words into a second slab buffer of the same layout and
-// rewrites K5's DevTraceOuts, and everything behind it (md_build, cigar_tails, the copy back) takes that buffer instead of K5's.
+// rewrites K5's DevTraceOuts, and everything behind it (md_build, cigar_tails, the copy back) takes that buffer instead of K5's. The cs
+// strings (flx_cs.hip) when wanted: one job per trace job once more, cs_build queued behind md_build's place on the same words and
+// DevTraceOuts, a slab of cs_slab_bytes per job under the NM that sizes the MD slab, its bytes back with the CIGAR words.
 struct Traceback {
     bool const want_md;
     const TailParams* const want_tails;
@@ -276,6 +279,7 @@ struct Traceback {
     bool const want_left_align;
     const RealignScores* const realign;                        // null: the paths stay edit-distance paths
     const u8* const d_ra_query;                                // the device query pool's letters for cigar_realign
+    const CsWant* const cs;                                    // null: no cs strings
     PhaseTimer* const prof;
     hvec<DevTraceJob> jobs;
     hvec<DevTraceOut> outs;
@@ -287,12 +291,14 @@ struct Traceback {
     hvec<DevLeftAlignStat> la_stats;
     hvec<DevRealignJob> ra_jobs;
     hvec<DevRealignStat> ra_stats;
-    u64 cigar_words = 0, path_steps = 0, md_bytes = 0;
-    size_t cigar_base = 0, md_base = 0;                        // where this batch's slabs start in the host pools
+    hvec<DevCsJob> cs_jobs;
+    hvec<DevCsOut> cs_outs;
+    u64 cigar_words = 0, path_steps = 0, md_bytes = 0, cs_bytes = 0;
+    size_t cigar_base = 0, md_base = 0, cs_base = 0;           // where this batch's slabs start in the host pools
     explicit Traceback(bool md, const TailParams* tails, const u8* d_la_query_, PhaseTimer* prof_ = nullptr, const RealignScores* realign_ = nullptr,
-                       const u8* d_ra_query_ = nullptr)
+                       const u8* d_ra_query_ = nullptr, const CsWant* cs_ = nullptr)
         : want_md(md), want_tails(tails), d_la_query(d_la_query_), want_left_align(d_la_query_ != nullptr), realign(d_ra_query_ ? realign_ : nullptr),
-          d_ra_query(d_ra_query_), prof(prof_) {}
+          d_ra_query(d_ra_query_), cs(cs_), prof(prof_) {}
     // the path that ends at end_col of the last row of r's DP, whose trace planes lie at trace_off; returns the trace job's index
     u32 add(AlignRequest const& r, u64 trace_off, AlignShape sh, u32 end_col, u32 nm) {
         // runs <= 2*NM + 1; a realigned path has at most realign_cap words (left-aligned too: gaps only merge there) and its NM stays
@@ -311,6 +317,11 @@ struct Traceback {
         if (realign)
             ra_jobs.push_back(DevRealignJob{r.ref_off, r.q_off, cigar_words, cigar_words, 0, r.n, r.m, cap, j,
                                             (u32)std::min<u64>(realign_trace_words(r.m, (u64)nm + 2u * (u64)realign->w + 1u), 0xFFFFFFFFull), 0});
+        if (cs) {
+            u64 const slab = cs_slab_bytes(nm_md, r.m, cs->form);
+            cs_jobs.push_back(DevCsJob{r.ref_off, r.q_off, cigar_words, cs_bytes, r.n, r.m, (u32)slab, j});
+            cs_bytes += slab;
+        }
         cigar_words += cap;
         path_steps += (u64)r.m + nm;
         return j;
@@ -322,8 +333,9 @@ struct Traceback {
         // the job tables (trace, MD, tails, left-align) up in one copy, packed in the lane's staging block
         auto const up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
         size_t const b_jobs = jobs.size() * sizeof(DevTraceJob), b_md = md_jobs.size() * sizeof(DevMdJob), b_tail = tail_jobs.size() * sizeof(DevTailJob),
-                     b_la = la_jobs.size() * sizeof(DevLeftAlignJob);
-        size_t const o_md = up(b_jobs), o_tail = o_md + up(b_md), o_la = o_tail + up(b_tail), b_tables = b_la ? o_la + b_la : o_tail + b_tail;
+                     b_la = la_jobs.size() * sizeof(DevLeftAlignJob), b_cs = cs_jobs.size() * sizeof(DevCsJob);
+        size_t const o_md = up(b_jobs), o_tail = o_md + up(b_md), o_la = o_tail + up(b_tail), o_cs = o_la + up(b_la),
+                     b_tables = b_cs ? o_cs + b_cs : b_la ? o_la + b_la : o_tail + b_tail;
         if ((rc = lane->tjobs.ensure(b_tables + 16))) return rc;
         char* const h = (char*)lane->stage_begin(b_tables);
         if (!h) return FLX_ERR_NO_DEVICE;
@@ -331,11 +343,13 @@ struct Traceback {
         if (b_md) memcpy(h + o_md, md_jobs.data(), b_md);
         if (b_tail) memcpy(h + o_tail, tail_jobs.data(), b_tail);
         if (b_la) memcpy(h + o_la, la_jobs.data(), b_la);
+        if (b_cs) memcpy(h + o_cs, cs_jobs.data(), b_cs);
         FLX_HIP(hipMemcpyAsync(lane->tjobs.ptr, h, b_tables, hipMemcpyHostToDevice, lane->stream));
         const DevTraceJob* const d_jobs = lane->tjobs.as<DevTraceJob>();
         const DevMdJob* const d_md_jobs = (const DevMdJob*)((char*)lane->tjobs.ptr + o_md);
         const DevTailJob* const d_tail_jobs = (const DevTailJob*)((char*)lane->tjobs.ptr + o_tail);
         const DevLeftAlignJob* const d_la_jobs = (const DevLeftAlignJob*)((char*)lane->tjobs.ptr + o_la);
+        const DevCsJob* const d_cs_jobs = (const DevCsJob*)((char*)lane->tjobs.ptr + o_cs);
         if ((rc = lane->tjob_out.ensure(jobs.size() * sizeof(DevTraceOut)))) return rc;
         if ((rc = lane->cigar.ensure(cigar_words * 4 + 16))) return rc;
         if (want_md) {
@@ -343,6 +357,7 @@ struct Traceback {
             if ((rc = lane->md.ensure(md_bytes + 16))) return rc;
         }
         if (want_tails && (rc = lane->tail_out.ensure(tail_jobs.size() * sizeof(DevTailOut)))) return rc;
+        if (cs && (rc = lane->cs.ensure(cs_bytes + 16))) return rc;
         if (want_left_align) {
             if ((rc = lane->cigar_la.ensure(cigar_words * 4 + 16))) return rc;
             if ((rc = lane->la_stat.ensure(la_jobs.size() * sizeof(DevLeftAlignStat)))) return rc;
@@ -374,6 +389,7 @@ struct Traceback {
         tail_outs.resize(tail_jobs.size());
         la_stats.resize(la_jobs.size());
         ra_stats.resize(ra_jobs.size());
+        cs_outs.resize(cs_jobs.size());
         DevTraceOut* r_outs = (DevTraceOut*)lane->result_slot(outs.size() * sizeof(DevTraceOut));
         DevMdOut* r_md = want_md ? (DevMdOut*)lane->result_slot(md_outs.size() * sizeof(DevMdOut)) : nullptr;
         DevTailOut* r_tail = want_tails ? (DevTailOut*)lane->result_slot(tail_outs.size() * sizeof(DevTailOut)) : nullptr;
@@ -383,7 +399,11 @@ struct Traceback {
         // (nothing on the device reads cigar_realign's statistics: the kernel stores them in the block itself when it has room)
         if (realign && !r_ra && (rc = lane->ra_stat.ensure(ra_jobs.size() * sizeof(DevRealignStat)))) return rc;
         DevRealignStat* const d_ra_stats = r_ra ? r_ra : lane->ra_stat.as<DevRealignStat>();
-        bool const direct = mapped && !want_md && !want_tails && !want_left_align && !realign;
+        // (nor cs_build's lengths)
+        DevCsOut* const r_cs = cs ? (DevCsOut*)lane->result_slot(cs_outs.size() * sizeof(DevCsOut)) : nullptr;
+        if (cs && !r_cs && (rc = lane->cs_out.ensure(cs_jobs.size() * sizeof(DevCsOut)))) return rc;
+        DevCsOut* const d_cs_outs = r_cs ? r_cs : lane->cs_out.as<DevCsOut>();
+        bool const direct = mapped && !want_md && !want_tails && !want_left_align && !realign && !cs;
         DevTraceOut* const d_outs = direct ? r_outs : lane->tjob_out.as<DevTraceOut>();
         rc = timed_launch(lane, "ed_traceback", path_steps * 18, path_steps, [&] {
             return DeviceApi::traceback(lane->stream, d_text, d_peq, lane->trace.as<u64>(), d_jobs, (u32)jobs.size(), lane->cigar.as<u32>(), d_outs);
@@ -410,6 +430,13 @@ struct Traceback {
             // (its algorithmic bytes depend on what K5 finds: they are added below once the lengths are back)
             rc = timed_launch(lane, "md_build", 0, md_jobs.size(), [&] {
                 return DeviceApi::md_build(lane->stream, d_text, d_words, d_outs, d_md_jobs, (u32)md_jobs.size(), lane->md.as<u8>(), lane->md_out.as<DevMdOut>());
+            });
+            if (rc) return rc;
+        }
+        if (cs) {
+            // (what it reads and writes is known once the lengths are back: added below)
+            rc = timed_launch(lane, "cs_build", 0, 0, [&] {
+                return DeviceApi::cs_build(lane->stream, d_text, cs->d_query, d_words, d_outs, d_cs_jobs, (u32)cs_jobs.size(), cs->form, lane->cs.as<u8>(), d_cs_outs);
             });
             if (rc) return rc;
         }
@@ -440,11 +467,18 @@ struct Traceback {
             if (!mapped && (rc = d2h(lane, md_outs.data(), lane->md_out.ptr, md_outs.size() * sizeof(DevMdOut)))) return rc;
             if ((rc = d2h(lane, md_pool->data() + md_base, lane->md.ptr, md_bytes))) return rc;
         }
+        if (cs) {
+            cs_base = cs->pool->size();
+            cs->pool->resize(cs_base + cs_bytes);
+            if (!r_cs && (rc = d2h(lane, cs_outs.data(), lane->cs_out.ptr, cs_outs.size() * sizeof(DevCsOut)))) return rc;
+            if ((rc = d2h(lane, cs->pool->data() + cs_base, lane->cs.ptr, cs_bytes))) return rc;
+        }
         if (want_tails && !mapped && (rc = d2h(lane, tail_outs.data(), lane->tail_out.ptr, tail_outs.size() * sizeof(DevTailOut)))) return rc;
         if (want_left_align && !mapped && (rc = d2h(lane, la_stats.data(), lane->la_stat.ptr, la_stats.size() * sizeof(DevLeftAlignStat)))) return rc;
         if (realign && !r_ra && (rc = d2h(lane, ra_stats.data(), lane->ra_stat.ptr, ra_stats.size() * sizeof(DevRealignStat)))) return rc;
         if ((rc = lane->sync())) return rc;
         if (r_ra) memcpy(ra_stats.data(), r_ra, ra_stats.size() * sizeof(DevRealignStat));
+        if (r_cs) memcpy(cs_outs.data(), r_cs, cs_outs.size() * sizeof(DevCsOut));
         if (mapped) {
             memcpy(outs.data(), r_outs, outs.size() * sizeof(DevTraceOut));
             if (want_left_align) memcpy(la_stats.data(), r_la, la_stats.size() * sizeof(DevLeftAlignStat));
@@ -482,6 +516,16 @@ struct Traceback {
             }
             lane->ctx->account_more("md_build", bytes, 0);
         }
+        if (cs) {
+            // CIGAR words read + the string written + a letter read per letter written (at most the string again); units: output bytes
+            u64 bytes = 0, written = 0;
+            for (size_t j = 0; j < cs_jobs.size(); ++j) {
+                if (cs_outs[j].len == 0xFFFFFFFFu) { set_error("cs_build: cs slab overflow, or a path that leaves its window or its query"); return FLX_ERR_INTERNAL; }
+                bytes += 4ull * outs[j].cigar_len + 2ull * cs_outs[j].len;
+                written += cs_outs[j].len;
+            }
+            lane->ctx->account_more("cs_build", bytes, written);
+        }
         if (want_tails) {
             u64 bytes = 0;
             for (auto const& t : outs) bytes += 4ull * t.cigar_len;
@@ -498,6 +542,7 @@ struct Traceback {
         res.cigar_off = cigar_base + jobs[j].cigar_off + outs[j].cigar_start;
         res.cigar_len = outs[j].cigar_len;
         if (want_md) { res.md_off = md_base + md_jobs[j].md_off; res.md_len = md_outs[j].len; }
+        if (cs) { res.cs_off = cs_base + cs_jobs[j].cs_off; res.cs_len = cs_outs[j].len; }
         if (want_tails) res.tail = tail_outs[j];
         if (realign) { res.nm = ra_stats[j].num_errors; res.score = ra_stats[j].score; }      // (a kept path: NM is K4's)
         return res;
@@ -507,7 +552,7 @@ struct Traceback {
 // score, begin position and CIGAR (and MD string, when md_pool is given) for every (distinct) request
 int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                           hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
-                          const RealignScores* realign, const u8* d_ra_query) {
+                          const RealignScores* realign, const u8* d_ra_query, const CsWant* cs) {
     results.assign(reqs.size(), TraceResult{});
     if (reqs.empty()) return FLX_OK;
     PhaseTimer tprof("trace-jobs");
@@ -539,7 +584,7 @@ int run_trace_jobs_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<Al
         tprof.mark("K4");
 
         // ---- traceback for the jobs that have an alignment within k
-        Traceback tb(md_pool != nullptr, tails, d_la_query, &tprof, realign, d_ra_query);
+        Traceback tb(md_pool != nullptr, tails, d_la_query, &tprof, realign, d_ra_query, cs);
         hvec<u32> tjob_req;
         for (size_t c = 0; c < count; ++c) {
             if (outs[c].score == 0xFFFFFFFFu) continue;
@@ -564,9 +609,9 @@ int run_score_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequ
 // score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
 int run_trace_jobs(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                    hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
-                   const RealignScores* realign, const u8* d_ra_query) {
+                   const RealignScores* realign, const u8* d_ra_query, const CsWant* cs) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query);
+        return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query, cs);
     });
 }
 
@@ -704,7 +749,7 @@ namespace {
 // the union form over distinct requests (n_requests: with their duplicates, for the debug line)
 int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& uniq, size_t n_requests,
                                 hvec<TraceResult>& ures, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
-                                const RealignScores* realign, const u8* d_ra_query) {
+                                const RealignScores* realign, const u8* d_ra_query, const CsWant* cs) {
     bool usable = !uniq.empty() && !getenv("FLX_NO_UNION");
     for (auto const& r : uniq) usable = usable && r.k < 0xFFFFu;
     // ---- unions: same query rows, starts within UNION_MAX_SHIFT of the first member
@@ -737,7 +782,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
             members.push_back(id);
         }
     }
-    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query);      // nothing to share: the plain path
+    if (!usable || unions.size() == uniq.size()) return run_trace_jobs_unique(ctx, d_text, d_peq, uniq, ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query, cs);      // nothing to share: the plain path
 
     ures.assign(uniq.size(), TraceResult{});
     hvec<AlignRequest> ureqs(unions.size());
@@ -812,7 +857,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
         if (wouts_in_place) memcpy(wouts.data(), d_wouts, n_wins * sizeof(DevAlignOut));
 
         // ---- one traceback per distinct (union, end column); the members of a union share its trace job's CIGAR words and MD string
-        Traceback tb(md_pool != nullptr, tails, d_la_query, nullptr, realign, d_ra_query);
+        Traceback tb(md_pool != nullptr, tails, d_la_query, nullptr, realign, d_ra_query, cs);
         hvec<u32> win_tjob(n_wins, 0xFFFFFFFFu);
         for (size_t w0 = 0; w0 < n_wins;) {                     // windows of one union are consecutive
             size_t w1 = w0;
@@ -845,7 +890,7 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
     }
     if (!fallback.empty()) {
         hvec<TraceResult> fres;
-        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query))) return rc;
+        if ((rc = run_trace_jobs_unique(ctx, d_text, d_peq, fallback, fres, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query, cs))) return rc;
         for (size_t i = 0; i < fallback.size(); ++i) ures[fallback_of[i]] = fres[i];
     }
     if (getenv("FLX_ALIGN_DEBUG")) fprintf(stderr, "[root unions] requests %zu distinct %zu unions %zu aligned on their own %zu traceback jobs %zu unions with several jobs %zu\n", n_requests, uniq.size(), unions.size(), fallback.size(), n_tjobs, n_unions_several_jobs);
@@ -856,9 +901,9 @@ int run_trace_jobs_union_unique(Lane* ctx, const u8* d_text, const u64* d_peq, h
 
 int run_trace_jobs_union(Lane* ctx, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool, const TailParams* tails, const u8* d_la_query,
-                         const RealignScores* realign, const u8* d_ra_query) {
+                         const RealignScores* realign, const u8* d_ra_query, const CsWant* cs) {
     return run_deduplicated(reqs, results, [&](hvec<AlignRequest> const& uniq, hvec<TraceResult>& ures) {
-        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query);
+        return run_trace_jobs_union_unique(ctx, d_text, d_peq, uniq, reqs.size(), ures, cigar_pool, md_pool, tails, d_la_query, realign, d_ra_query, cs);
     });
 }
 
@@ -935,6 +980,38 @@ int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u
         moved += stats[j].moved;
     }
     lane->ctx->account_more("cigar_left_align", bytes, moved);
+    return FLX_OK;
+}
+
+// One cs_build launch over CIGAR words and DevTraceOuts made on the host: the kernel alone (the pipeline queues it behind md_build).
+int run_cs_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevCsJob> const& jobs,
+                u32 form, u64 slab_bytes, hvec<u8>& slabs, hvec<u32>& lens) {
+    slabs.assign(slab_bytes, (u8)0);
+    lens.assign(jobs.size(), 0u);
+    if (jobs.empty()) return FLX_OK;
+    int rc;
+    if ((rc = h2d(lane, lane->cigar, words, n_words * 4))) return rc;
+    if ((rc = h2d(lane, lane->tjob_out, touts.data(), touts.size() * sizeof(DevTraceOut)))) return rc;
+    if ((rc = h2d(lane, lane->cs_jobs, jobs.data(), jobs.size() * sizeof(DevCsJob)))) return rc;
+    if ((rc = lane->cs.ensure(slab_bytes + 16))) return rc;
+    if ((rc = lane->cs_out.ensure(jobs.size() * sizeof(DevCsOut)))) return rc;
+    rc = timed_launch(lane, "cs_build", 0, 0, [&] {
+        return DeviceApi::cs_build(lane->stream, d_text, d_query, lane->cigar.as<u32>(), lane->tjob_out.as<DevTraceOut>(), lane->cs_jobs.as<DevCsJob>(),
+                                   (u32)jobs.size(), form, lane->cs.as<u8>(), lane->cs_out.as<DevCsOut>());
+    });
+    if (rc) return rc;
+    hvec<DevCsOut> outs(jobs.size());
+    if ((rc = d2h(lane, outs.data(), lane->cs_out.ptr, outs.size() * sizeof(DevCsOut)))) return rc;
+    if (slab_bytes && (rc = d2h(lane, slabs.data(), lane->cs.ptr, slab_bytes))) return rc;
+    if ((rc = lane->sync())) return rc;
+    u64 bytes = 0, written = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        if (outs[j].len == 0xFFFFFFFFu) { set_error("cs_build: cs slab overflow, or a path that leaves its window or its query"); return FLX_ERR_INTERNAL; }
+        lens[j] = outs[j].len;
+        bytes += 4ull * touts[j].cigar_len + 2ull * outs[j].len;
+        written += outs[j].len;
+    }
+    lane->ctx->account_more("cs_build", bytes, written);
     return FLX_OK;
 }
 
@@ -1093,9 +1170,23 @@ extern "C" int flx_align_batch_realign(flx_ctx* ctx, const uint8_t* ref_pool, ui
                                        uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
                                        uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes,
                                        const flx_gap_options* gaps, const flx_realign_options* realign, int32_t* out_scores) {
-    std::string const fn = realign_options_active(realign) ? "flx_align_batch_realign" : gap_options_active(gaps) ? "flx_align_batch_gaps" : out_md ? "flx_align_batch_md" : "flx_align_batch";        // (all forward here)
+    return flx_align_batch_cs(ctx, ref_pool, ref_pool_len, query_pool, query_pool_len, jobs, n_jobs, out, cigar_pool, cigar_pool_words, out_md, md_pool, md_pool_bytes,
+                              gaps, realign, out_scores, nullptr, nullptr, nullptr, nullptr);
+}
+// cs NULL or zeroed: no cs strings (flx_align_batch_realign)
+extern "C" int flx_align_batch_cs(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool,
+                                  uint64_t query_pool_len, const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out,
+                                  uint32_t* cigar_pool, uint64_t* cigar_pool_words, flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes,
+                                  const flx_gap_options* gaps, const flx_realign_options* realign, int32_t* out_scores, const flx_cs_options* cs,
+                                  flx_md_ref* out_cs, uint8_t* cs_pool, uint64_t* cs_pool_bytes) {
+    if (!cs_options_valid(cs)) return FLX_ERR_INVALID;                                 // (before the context is looked at)
+    uint32_t const cs_form = cs_options_form(cs);
+    std::string const fn = cs_form ? "flx_align_batch_cs" : realign_options_active(realign) ? "flx_align_batch_realign" : gap_options_active(gaps) ? "flx_align_batch_gaps" : out_md ? "flx_align_batch_md" : "flx_align_batch";        // (all forward here)
     if (!gap_options_valid(gaps) || !realign_options_valid(realign)) return FLX_ERR_INVALID;
     RealignScores const ra_scores = realign_scores(realign);
+    if (cs_form && (!out_cs || !cs_pool_bytes)) { set_error(fn + ": null argument"); return FLX_ERR_INVALID; }
+    uint64_t const cs_pool_cap = cs_pool_bytes ? *cs_pool_bytes : 0;
+    if (cs_pool_bytes) *cs_pool_bytes = 0;                                            // (out: bytes used, also on an early return)
     if (out_md && !md_pool_bytes) { set_error(fn + ": null argument"); return FLX_ERR_INVALID; }
     uint64_t const md_pool_cap = md_pool_bytes ? *md_pool_bytes : 0;
     if (md_pool_bytes) *md_pool_bytes = 0;                                            // (out: bytes used, also on an early return)
@@ -1147,6 +1238,7 @@ extern "C" int flx_align_batch_realign(flx_ctx* ctx, const uint8_t* ref_pool, ui
     for (uint64_t i = 0; i < n_jobs; ++i) out[i] = flx_align_result{0, 0, 0, 0, 0, 0};
     if (out_md) for (uint64_t i = 0; i < n_jobs; ++i) out_md[i] = flx_md_ref{0, 0, 0};
     if (out_scores) for (uint64_t i = 0; i < n_jobs; ++i) out_scores[i] = 0;
+    if (cs_form) for (uint64_t i = 0; i < n_jobs; ++i) out_cs[i] = flx_md_ref{0, 0, 0};
     hvec<DevAlignOut> outs;
     if ((rc = run_score_jobs(L, d_text, L->peq.as<u64>(), score_reqs, outs, "ed_align_exists"))) return rc;
     for (size_t i = 0; i < outs.size(); ++i)
@@ -1159,9 +1251,10 @@ extern "C" int flx_align_batch_realign(flx_ctx* ctx, const uint8_t* ref_pool, ui
         }
     hvec<TraceResult> tres;
     hvec<u32> cig;
-    hvec<u8> mdp;
+    hvec<u8> mdp, csp;
+    CsWant const want_cs{cs_form, L->seq.as<u8>(), &csp};
     if ((rc = run_trace_jobs(L, d_text, L->peq.as<u64>(), trace_reqs, tres, cig, out_md ? &mdp : nullptr, nullptr, gap_options_active(gaps) ? L->seq.as<u8>() : nullptr,
-                             &ra_scores, realign_options_active(realign) ? L->seq.as<u8>() : nullptr))) return rc;
+                             &ra_scores, realign_options_active(realign) ? L->seq.as<u8>() : nullptr, cs_form ? &want_cs : nullptr))) return rc;
     uint64_t const cap = cigar_pool_words ? *cigar_pool_words : 0;
     if (cigar_pool_words) *cigar_pool_words = cig.size();
     if (any_trace && (!cigar_pool || cig.size() > cap)) { set_error("cigar pool too small"); return FLX_ERR_CAPACITY; }
@@ -1171,12 +1264,18 @@ extern "C" int flx_align_batch_realign(flx_ctx* ctx, const uint8_t* ref_pool, ui
         if (!mdp.empty() && (!md_pool || mdp.size() > md_pool_cap)) { set_error("md pool too small"); return FLX_ERR_CAPACITY; }
         if (!mdp.empty()) memcpy(md_pool, mdp.data(), mdp.size());
     }
+    if (cs_form) {
+        *cs_pool_bytes = csp.size();
+        if (!csp.empty() && (!cs_pool || csp.size() > cs_pool_cap)) { set_error("cs pool too small"); return FLX_ERR_CAPACITY; }
+        if (!csp.empty()) memcpy(cs_pool, csp.data(), csp.size());
+    }
     for (size_t i = 0; i < tres.size(); ++i)
         if (tres[i].exists) {
             flx_align_result& r = out[trace_ids[i]];
             r.exists = 1; r.num_errors = tres[i].nm; r.begin = tres[i].begin; r.cigar_offset = tres[i].cigar_off; r.cigar_length = tres[i].cigar_len;
             if (out_md) out_md[trace_ids[i]] = flx_md_ref{tres[i].md_off, tres[i].md_len, 0};
             if (out_scores) out_scores[trace_ids[i]] = tres[i].score;
+            if (cs_form) out_cs[trace_ids[i]] = flx_md_ref{tres[i].cs_off, tres[i].cs_len, 0};
         }
     return FLX_OK;
 }
@@ -1331,6 +1430,56 @@ extern "C" int flx_realign_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t
         if (touts[i].cigar_len) memcpy(out_words + used, slabs.data() + dj[i].out_off + touts[i].cigar_start, 4ull * touts[i].cigar_len);
         out[i] = flx_realign_result{used, touts[i].cigar_len, stats[i].num_errors, stats[i].score, stats[i].diag_lo, stats[i].diag_hi, stats[i].kept};
         used += touts[i].cigar_len;
+    }
+    return FLX_OK;
+}
+
+// ================================================================================================ C ABI: the cs kernel alone
+extern "C" int flx_cs_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                            const uint32_t* cigar_words, uint64_t n_words, const flx_cs_job* jobs, uint64_t n_jobs, const flx_cs_options* options,
+                            uint8_t* out_bytes, uint64_t* out_n_bytes, flx_md_ref* out) {
+    if (!cs_options_valid(options)) return FLX_ERR_INVALID;
+    if (cs_options_form(options) == 0) { set_error("flx_cs_batch: form must be 1 (short) or 2 (long)"); return FLX_ERR_INVALID; }
+    if (!ctx || !out_n_bytes || (n_jobs && (!jobs || !out)) || (n_words && !cigar_words) || (query_pool_len && !query_pool)) {
+        set_error("flx_cs_batch: null argument"); return FLX_ERR_INVALID;
+    }
+    uint64_t const out_cap = *out_n_bytes;
+    *out_n_bytes = 0;
+    if (n_jobs >= (1ull << 31)) { set_error("too many jobs in one call"); return FLX_ERR_INVALID; }
+    u64 const text_len = ref_pool ? ref_pool_len : ctx->hidx->n;
+    if (!left_align_jobs_valid(text_len, query_pool_len, cigar_words, n_words, jobs, n_jobs, "flx_cs_batch")) return FLX_ERR_INVALID;      // (before any launch)
+    u32 const form = cs_options_form(options);
+    hvec<DevTraceOut> touts(n_jobs);
+    hvec<DevCsJob> dj(n_jobs);
+    u64 slab_bytes = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) {
+        flx_cs_job const& j = jobs[i];
+        u64 const need = cs_path_bytes(cigar_words + j.cigar_offset, j.cigar_length, form);      // (below 2^30: rows and columns are below 2^28)
+        touts[i] = DevTraceOut{j.begin, 0, j.cigar_length, 0};
+        dj[i] = DevCsJob{j.ref_offset, j.query_offset, j.cigar_offset, slab_bytes, j.ref_length, j.query_length, (u32)need, (u32)i};
+        slab_bytes += need;
+    }
+    FLX_HIP(hipSetDevice(ctx->device));
+    int rc;
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    Lane* L = lease.lane;
+    hvec<u8> slabs;
+    hvec<u32> lens;
+    if (n_jobs) {
+        const u8* d_text = ctx->didx.text;
+        if (ref_pool && (rc = upload_padded(L, L->user_text, ref_pool, ref_pool_len, &d_text))) return rc;
+        if ((rc = h2d(L, L->seq, query_pool, query_pool_len, 192))) return rc;
+        if ((rc = run_cs_jobs(L, d_text, L->seq.as<u8>(), cigar_words, n_words, touts, dj, form, slab_bytes, slabs, lens))) return rc;
+    }
+    u64 used = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) used += lens[i];
+    *out_n_bytes = used;
+    if (used > out_cap || (used && !out_bytes)) { set_error("flx_cs_batch: the output byte pool is too small"); return FLX_ERR_CAPACITY; }
+    used = 0;
+    for (uint64_t i = 0; i < n_jobs; ++i) {                   // the strings packed in job order
+        if (lens[i]) memcpy(out_bytes + used, slabs.data() + dj[i].cs_off, lens[i]);
+        out[i] = flx_md_ref{used, lens[i], 0};
+        used += lens[i];
     }
     return FLX_OK;
 }

@@ -12,6 +12,7 @@
 #include "flx_tails.hpp"
 #include "flx_leftalign.hpp"
 #include "flx_realign.hpp"
+#include "flx_cs.hpp"
 
 namespace flx {
 const char* last_error_cstr();
@@ -290,6 +291,32 @@ int flx_realign(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* q
     if (all.size() > out_cap || (!all.empty() && !out_words)) { set_error("flx_realign: the output word pool is too small"); return FLX_ERR_CAPACITY; }
     if (!all.empty()) memcpy(out_words, all.data(), all.size() * 4);
     for (u64 i = 0; i < n_jobs; ++i) out[i] = res[i];
+    return FLX_OK;
+}
+
+int flx_cs(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len, const uint32_t* cigar_words,
+           uint64_t n_words, const flx_cs_job* jobs, uint64_t n_jobs, const flx_cs_options* options, uint8_t* out_bytes, uint64_t* out_n_bytes,
+           flx_md_ref* out) {
+    if (!cs_options_valid(options)) return FLX_ERR_INVALID;
+    if (cs_options_form(options) == 0) { set_error("flx_cs: form must be 1 (short) or 2 (long)"); return FLX_ERR_INVALID; }
+    if (!out_n_bytes || (n_jobs && (!jobs || !out)) || (n_words && !cigar_words) || (ref_pool_len && !ref_pool) || (query_pool_len && !query_pool)) {
+        set_error("flx_cs: null argument"); return FLX_ERR_INVALID;
+    }
+    uint64_t const out_cap = *out_n_bytes;
+    *out_n_bytes = 0;
+    if (!left_align_jobs_valid(ref_pool_len, query_pool_len, cigar_words, n_words, jobs, n_jobs, "flx_cs")) return FLX_ERR_INVALID;
+    std::vector<uint8_t> all;
+    std::vector<flx_md_ref> refs(n_jobs);
+    for (u64 i = 0; i < n_jobs; ++i) {
+        flx_cs_job const& j = jobs[i];
+        size_t const at = all.size();
+        cs_path(cigar_words + j.cigar_offset, j.cigar_length, ref_pool + j.ref_offset, query_pool + j.query_offset, j.begin, cs_options_form(options), all);
+        refs[i] = flx_md_ref{at, (uint32_t)(all.size() - at), 0};
+    }
+    *out_n_bytes = all.size();
+    if (all.size() > out_cap || (!all.empty() && !out_bytes)) { set_error("flx_cs: the output byte pool is too small"); return FLX_ERR_CAPACITY; }
+    if (!all.empty()) memcpy(out_bytes, all.data(), all.size());
+    for (u64 i = 0; i < n_jobs; ++i) out[i] = refs[i];
     return FLX_OK;
 }
 

@@ -177,6 +177,27 @@ struct DevMdOut { u32 len; u32 pad; };             // len 0xFFFFFFFF: the slab w
 // of a run of '=' columns, which is at most the number of query rows: <= 102 400 (align_supported_max_query), six digits. 8 nm + 6 in all.
 constexpr u64 md_slab_bytes(u64 nm) { return 8 * nm + 6; }
 
+// ---- cs strings of traced paths (flx_cs.hip; the rule: flx_cs.hpp), one job per trace job: the kernel reads that job's DevTraceOut and
+// CIGAR words where K5 (or cigar_realign / cigar_left_align) left them, the window in the text and the oriented query in the query pool
+struct DevCsJob {
+    u64 ref_off, q_off;                            // the trace job's window in the text and its query in the query pool
+    u64 cigar_off, cs_off;                         // the trace job's CIGAR slab (words), this job's cs slab (bytes)
+    u32 n, m;                                      // columns of the window, rows of the query: nothing is read beyond them
+    u32 cs_cap;                                    // bytes of the cs slab
+    u32 out_index;                                 // the trace job's DevTraceOut and this job's DevCsOut
+};
+struct DevCsOut { u32 len; u32 pad; };             // len 0xFFFFFFFF: the slab was too small, or the path leaves its window or its query
+static_assert(sizeof(DevCsJob) == 48, "device layout");
+// Bytes that hold the cs string of any path of m query rows whose X, I and D lengths sum to nm. K5 merges runs as it writes, and
+// cigar_realign and cigar_left_align promise the same: no two neighbouring words share an op, so the x X columns, i inserted and d
+// deleted letters (x + i + d = nm) lie in at most nm words other than '=' and there are at most nm + 1 '=' words.
+//   both forms:  an X column is 3 bytes; a gap word of length L is 1 + L <= 2 L bytes: 3 x + 2 i + 2 d <= 3 nm
+//   short form:  an '=' word is ':' and the digits of its length, which is at most the query rows <= 102 400 (align_supported_max_query),
+//                six digits: 7 (nm + 1) + 3 nm = 10 nm + 7; reached by one '=' word of 100 000 columns and more (nm = 0)
+//   long form:   the '=' words hold one '=' each and m - x - i letters: (m - x - i) + (nm + 1) + 3 x + 2 i + 2 d = m + nm + 1 + 2 x + i
+//                + 2 d <= m + 3 nm + 1; reached by = X = X ... = with single X columns
+constexpr u64 cs_slab_bytes(u64 nm, u64 m, u32 form) { return form == 2u ? m + 3 * nm + 1 : 10 * nm + 7; }
+
 // ---- chimeric tails of traced paths (flx_tails.hip; the rule: flx_tails.hpp), one job per trace job: the kernel reads that job's
 // DevTraceOut and CIGAR words where K5 left them on the device
 struct DevTailJob {
@@ -438,6 +459,9 @@ struct DeviceApi {
     // flx_md.hip: the MD string of every job from the CIGAR words and DevTraceOut that `traceback` left at d_cigar / d_trace_out
     static int md_build(void* stream, const u8* d_text, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevMdJob* d_jobs, u32 n_jobs,
                         u8* d_md, DevMdOut* d_out);
+    // flx_cs.hip: the cs string (form 1 short, 2 long) of every job from the same words and DevTraceOuts, the text and the query pool
+    static int cs_build(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevCsJob* d_jobs,
+                        u32 n_jobs, u32 form, u8* d_cs, DevCsOut* d_out);
     // flx_tails.hip: the tails of every job's path (flx_tails.hpp) from the CIGAR words and DevTraceOut that `traceback` left
     static int cigar_tails(void* stream, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevTailJob* d_jobs, u32 n_jobs, DevTailOut* d_out);
     // flx_leftalign.hip: the words of every job normalised into d_cigar_out, the job's DevTraceOut rewritten to describe them

@@ -577,11 +577,14 @@ struct SpanCache { const uint32_t* of = nullptr; uint32_t len = 0; int64_t span 
 // one record as SAM text or as a BAM record, appended to `out`; false: the record cannot be represented (error set)
 // cigar_at (BAM): where in `out` the record's CIGAR array starts (SIZE_MAX: it has none of its own)
 // mdr (may be null): the record's MD string in md_bytes, written as MD:Z behind NM on a mapped record when its length is not 0; md_at (BAM):
-// where in `out` its bytes start (SIZE_MAX: none); score (may be null): written as AS:i behind NM / MD on a mapped record
+// where in `out` its bytes start (SIZE_MAX: none); score (may be null): written as AS:i behind NM / MD on a mapped record; csr (may be
+// null): the record's cs string in cs_bytes, written as cs:Z behind NM / MD / AS and in front of SA on a mapped record when its length is
+// not 0; cs_at (BAM): where in `out` its bytes start (SIZE_MAX: none)
 bool format_record(flx_sam_writer const* w, flx_record const& r, const char* const* read_ids, const uint8_t* read_pool,
                    const uint64_t* read_offsets, const char* const* quals, const uint32_t* cigar_words, std::vector<uint8_t>& out, std::string& err,
                    SpanCache& span_cache, size_t* cigar_at = nullptr, const flx_md_ref* mdr = nullptr, const uint8_t* md_bytes = nullptr,
-                   size_t* md_at = nullptr, const std::string* sa = nullptr, const int32_t* score = nullptr) {
+                   size_t* md_at = nullptr, const std::string* sa = nullptr, const int32_t* score = nullptr, const flx_md_ref* csr = nullptr,
+                   const uint8_t* cs_bytes = nullptr, size_t* cs_at = nullptr) {
     static const char ops[] = "MIDNSHP=X";
     const char* id = read_ids[r.read_index];
     if (md_at) *md_at = SIZE_MAX;
@@ -592,6 +595,15 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         // (a tab or a line end would break the SAM line, a zero byte the BAM tag)
         for (uint32_t b = 0; b < mdr->length; ++b)
             if (!((md[b] >= '0' && md[b] <= '9') || (md[b] >= 'A' && md[b] <= 'Z') || md[b] == '^')) { err = std::string("MD string with a byte outside [0-9A-Z^] in a record of read ") + id; return false; }
+    }
+    if (cs_at) *cs_at = SIZE_MAX;
+    const uint8_t* cs = nullptr;
+    if (csr && csr->length && !(r.flag & 4u)) {
+        if (!cs_bytes) { err = "cs references without cs bytes"; return false; }
+        cs = cs_bytes + csr->offset;
+        static const struct Table { bool ok[256]; Table() { for (int c = 0; c < 256; ++c) ok[c] = (c >= '0' && c <= '9') || (c != 0 && strchr(":*+=-acgtnACGTN", c) != nullptr); } } table;
+        for (uint32_t b = 0; b < csr->length; ++b)
+            if (!table.ok[cs[b]]) { err = std::string("cs string with a byte outside [0-9:*+=acgtnACGTN-] in a record of read ") + id; return false; }
     }
     if (w->mapq_from_records && r.reserved > 254u) { err = std::string("mapping quality above 254 in the record of read ") + id; return false; }
     uint32_t const mapq = w->mapq_from_records ? r.reserved : 255u;
@@ -628,6 +640,7 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         if (!unmapped) { app("\tNM:i:", 6); app_num(r.num_errors); }
         if (md) { app("\tMD:Z:", 6); app((const char*)md, mdr->length); }
         if (score && !unmapped) { app("\tAS:i:", 6); app_num(*score); }
+        if (cs) { app("\tcs:Z:", 6); app((const char*)cs, csr->length); }
         if (sa && !sa->empty()) { app("\tSA:Z:", 6); app(sa->data(), sa->size()); }
         out.push_back('\n');
         return true;
@@ -696,6 +709,12 @@ bool format_record(flx_sam_writer const* w, flx_record const& r, const char* con
         out.push_back(0);
     }
     if (score && !unmapped) { out.push_back('A'); out.push_back('S'); out.push_back('i'); put32(*score); }
+    if (cs) {
+        out.push_back('c'); out.push_back('s'); out.push_back('Z');
+        if (cs_at) *cs_at = out.size();
+        out.insert(out.end(), cs, cs + csr->length);
+        out.push_back(0);
+    }
     if (sa && !sa->empty()) {
         out.push_back('S'); out.push_back('A'); out.push_back('Z');
         out.insert(out.end(), sa->begin(), sa->end());
@@ -780,6 +799,12 @@ extern "C" int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_i
 extern "C" int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
                                     const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
                                     const flx_md_ref* md, const uint8_t* md_bytes, const int32_t* scores) {
+    return flx_sam_write_cs(w, read_ids, read_pool, read_offsets, quals, records, n_records, cigar_words, md, md_bytes, scores, nullptr, nullptr);
+}
+
+extern "C" int flx_sam_write_cs(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
+                                const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
+                                const flx_md_ref* md, const uint8_t* md_bytes, const int32_t* scores, const flx_md_ref* cs_refs, const uint8_t* cs_bytes) {
     if (!w || (n_records && (!records || !read_ids || !read_pool || !read_offsets))) { set_error("flx_sam_write: null argument"); return FLX_ERR_INVALID; }
     if (w->failed) { set_error("write error on the alignment output"); return FLX_ERR_IO; }
     std::vector<std::string> sa;                               // (made once for the whole call: the parts below cut reads anywhere)
@@ -835,11 +860,12 @@ extern "C" int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_i
             };
             size_t prev_cigar_at = SIZE_MAX;                   // stream position of the previous record's CIGAR array
             size_t prev_md_at = SIZE_MAX;                      // and of its MD string
+            size_t prev_cs_at = SIZE_MAX;                      // and of its cs string
             SpanCache span_cache;
             for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i) {
-                size_t cigar_at = SIZE_MAX, md_at = SIZE_MAX;
+                size_t cigar_at = SIZE_MAX, md_at = SIZE_MAX, cs_at = SIZE_MAX;
                 uint64_t const t_format = prof_ns();
-                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr)) break;
+                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr, cs_refs ? cs_refs + i : nullptr, cs_bytes, &cs_at)) break;
                 if (writer_profile()) g_ns_format += prof_ns() - t_format;
                 if (cigar_at != SIZE_MAX) {
                     cigar_at += base;
@@ -854,6 +880,13 @@ extern "C" int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_i
                     hints.push_back(StreamHint{md_at, (size_t)md[i].length, same ? md_at - prev_md_at : 0});
                 }
                 prev_md_at = md_at;
+                // and the cs string, behind the MD string
+                if (cs_at != SIZE_MAX) {
+                    cs_at += base;
+                    bool const same = prev_cs_at != SIZE_MAX && i > r0 && cs_refs[i].offset == cs_refs[i - 1].offset && cs_refs[i].length == cs_refs[i - 1].length;
+                    hints.push_back(StreamHint{cs_at, (size_t)cs_refs[i].length, same ? cs_at - prev_cs_at : 0});
+                }
+                prev_cs_at = cs_at;
                 deflate_full_blocks(false);
             }
             if (errs[p].empty()) deflate_full_blocks(true);
@@ -884,7 +917,7 @@ extern "C" int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_i
         }
         SpanCache span_cache;
         for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i)
-            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes, nullptr, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr)) break;
+            if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, parts[p], errs[p], span_cache, nullptr, md ? md + i : nullptr, md_bytes, nullptr, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr, cs_refs ? cs_refs + i : nullptr, cs_bytes)) break;
     });
     for (auto const& e : errs) if (!e.empty()) { set_error(e); return FLX_ERR_INVALID; }
     for (auto const& part : parts) {

@@ -81,7 +81,7 @@ constexpr Workspace WORKSPACES[] = {
     FLX_WS(rows_out), FLX_WS(jobs), FLX_WS(job_out), FLX_WS(trace), FLX_WS(tjobs), FLX_WS(tjob_out), FLX_WS(cigar), FLX_WS(md), FLX_WS(md_jobs), FLX_WS(md_out), FLX_WS(user_text), FLX_WS(user_text_rev),
     FLX_WS(lastrow), FLX_WS(row_windows), FLX_WS(row_out), FLX_WS(seed_cnt), FLX_WS(hit_off), FLX_WS(grouped), FLX_WS(sel_stat), FLX_WS(sel_n), FLX_WS(sel_off),
     FLX_WS(sel_out), FLX_WS(sel_tmp), FLX_WS(sel_rows), FLX_WS(sel_row_off), FLX_WS(sel_sparse), FLX_WS(sel_lists), FLX_WS(vr), FLX_WS(qpack), FLX_WS(items),
-    FLX_WS(seed_gen), FLX_WS(mailboxes), FLX_WS(ext_jobs), FLX_WS(ext_out), FLX_WS(tail_jobs), FLX_WS(tail_out), FLX_WS(cigar_la), FLX_WS(la_jobs), FLX_WS(la_stat), FLX_WS(cigar_ra), FLX_WS(ra_jobs), FLX_WS(ra_stat)};
+    FLX_WS(seed_gen), FLX_WS(mailboxes), FLX_WS(ext_jobs), FLX_WS(ext_out), FLX_WS(tail_jobs), FLX_WS(tail_out), FLX_WS(cigar_la), FLX_WS(la_jobs), FLX_WS(la_stat), FLX_WS(cigar_ra), FLX_WS(ra_jobs), FLX_WS(ra_stat), FLX_WS(cs), FLX_WS(cs_jobs), FLX_WS(cs_out)};
 #undef FLX_WS
 }  // namespace
 std::vector<DeviceBuffer*> Lane::workspaces() {

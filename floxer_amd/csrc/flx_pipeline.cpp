@@ -15,6 +15,7 @@
 #include "flx_tails.hpp"
 #include "flx_leftalign.hpp"
 #include "flx_realign.hpp"
+#include "flx_cs.hpp"
 
 using namespace flx;
 
@@ -145,8 +146,10 @@ extern "C" int flx_align_reads_with_options(flx_ctx* ctx, const flx_params* P, c
     return flx_align_reads_with_tags(ctx, P, read_pool, read_offsets, n_reads, O, nullptr, out);
 }
 // md and the partial alignments need the trace: refused together with without_cigar, before any work
-static bool run_options_valid(const flx_params* P, const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A) {
-    if (!gap_options_valid(G) || !realign_options_valid(A)) return false;
+static bool run_options_valid(const flx_params* P, const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A,
+                              const flx_cs_options* C) {
+    if (!cs_options_valid(C) || !gap_options_valid(G) || !realign_options_valid(A)) return false;
+    if (cs_options_form(C) && P && P->without_cigar) { set_error("flx_cs_options.form needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (realign_options_active(A) && P && P->without_cigar) { set_error("flx_realign_options.enable needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (gap_options_active(G) && P && P->without_cigar) { set_error("flx_gap_options.left_align needs the CIGAR's trace: it cannot be combined with without_cigar"); return false; }
     if (!split_options_valid(S)) return false;
@@ -183,11 +186,16 @@ extern "C" int flx_align_reads_gaps(flx_ctx* ctx, const flx_params* P, const uin
 extern "C" int flx_align_reads_realign(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
                                        const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A,
                                        flx_run** out) {
-    if (!run_options_valid(P, R, S, G, A)) return FLX_ERR_INVALID;
+    return flx_align_reads_cs(ctx, P, read_pool, read_offsets, n_reads, R, S, G, A, nullptr, out);
+}
+extern "C" int flx_align_reads_cs(flx_ctx* ctx, const flx_params* P, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                                  const flx_run_options* R, const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A,
+                                  const flx_cs_options* C, flx_run** out) {
+    if (!run_options_valid(P, R, S, G, A, C)) return FLX_ERR_INVALID;
     flx_reads* rd = nullptr;
     int rc = flx_reads_upload(ctx, read_pool, read_offsets, n_reads, &rd);
     if (rc) return rc;
-    rc = flx_align_reads_resident_realign(ctx, P, rd, R, S, G, A, out);
+    rc = flx_align_reads_resident_cs(ctx, P, rd, R, S, G, A, C, out);
     flx_reads_free(rd);
     return rc;
 }
@@ -217,7 +225,11 @@ extern "C" int flx_align_reads_resident_gaps(flx_ctx* ctx, const flx_params* P, 
 }
 extern "C" int flx_align_reads_resident_realign(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R,
                                                 const flx_split_options* S, const flx_gap_options* G, const flx_realign_options* A, flx_run** out) {
-    if (!run_options_valid(P, R, S, G, A)) return FLX_ERR_INVALID;
+    return flx_align_reads_resident_cs(ctx, P, RD, R, S, G, A, nullptr, out);
+}
+extern "C" int flx_align_reads_resident_cs(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_run_options* R, const flx_split_options* S,
+                                           const flx_gap_options* G, const flx_realign_options* A, const flx_cs_options* C, flx_run** out) {
+    if (!run_options_valid(P, R, S, G, A, C)) return FLX_ERR_INVALID;
     RunOptions opt{};                            // (a NULL bundle, a NULL member and a zeroed struct are the same: that option is off)
     if (R && R->output) opt.output = *R->output;
     if (R && R->tags) opt.tags = *R->tags;
@@ -226,6 +238,7 @@ extern "C" int flx_align_reads_resident_realign(flx_ctx* ctx, const flx_params* 
     if (S) opt.split = *S;
     if (G) opt.gaps = *G;
     if (realign_options_active(A)) opt.realign = *A;
+    if (C) opt.cs = *C;
     if (!ctx || !P || !out || !RD || RD->ctx != ctx) { set_error("flx_align_reads_resident: null argument or reads of another context"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
@@ -238,6 +251,7 @@ extern "C" int flx_align_reads_resident_realign(flx_ctx* ctx, const flx_params* 
     run->has_md = opt.tags.md;
     run->has_scores = opt.realign.enable != 0;
     run->realign = opt.realign;
+    run->has_cs = opt.cs.form != 0;
     if (n_reads == 0) { *out = run.release(); return FLX_OK; }       // an empty batch is an empty run
     // reads are independent units (parallelization.cpp:77-87): the batch is cut into contiguous chunks and every lane (a host
     // thread with its own stream and workspaces) takes the next chunk when it is done with its last one.
@@ -374,6 +388,27 @@ extern "C" int flx_run_copy_md(const flx_run* run, flx_md_ref* refs, uint8_t* md
         if (md_bytes && !part.md.empty()) memcpy(md_bytes + mb, part.md.data(), part.md.size());
         rb += part.records.size();
         mb += part.md.size();
+    };
+    emit(*run);
+    for (auto const& p : run->parts) emit(p);
+    return FLX_OK;
+}
+extern "C" uint64_t flx_run_num_cs_bytes(const flx_run* run) {
+    if (!run) return 0;
+    uint64_t n = run->cs.size();
+    for (auto const& p : run->parts) n += p.cs.size();
+    return n;
+}
+// the parts' cs offsets are rebased onto the concatenation of their pools, as flx_run_copy_md rebases the MD offsets
+extern "C" int flx_run_copy_cs(const flx_run* run, flx_md_ref* refs, uint8_t* bytes) {
+    if (!run) { set_error("null run"); return FLX_ERR_INVALID; }
+    if (!run->has_cs) { set_error("flx_run_copy_cs: the run was made without flx_cs_options.form"); return FLX_ERR_INVALID; }
+    uint64_t rb = 0, cb = 0;
+    auto emit = [&](flx_run const& part) {
+        if (refs) for (size_t r = 0; r < part.cs_refs.size(); ++r) { refs[rb + r] = part.cs_refs[r]; if (part.cs_refs[r].length) refs[rb + r].offset += cb; }
+        if (bytes && !part.cs.empty()) memcpy(bytes + cb, part.cs.data(), part.cs.size());
+        rb += part.records.size();
+        cb += part.cs.size();
     };
     emit(*run);
     for (auto const& p : run->parts) emit(p);

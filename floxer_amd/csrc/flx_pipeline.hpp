@@ -25,6 +25,9 @@ struct flx_run {
     flx::hvec<flx::u8> md;
     bool has_scores = false;           // made with flx_realign_options.enable: `realign` holds the options the records' scores are taken under
     flx_realign_options realign{};
+    bool has_cs = false;               // made with flx_cs_options.form != 0: cs_refs is parallel to records, offsets relative to this object's `cs`
+    flx::hvec<flx_md_ref> cs_refs;
+    flx::hvec<flx::u8> cs;
     flx::hvec<flx_run> parts;          // a batch result is the in-order list of its slices (no concatenation on the host)
 };
 
@@ -115,7 +118,11 @@ struct TraceResult {
     bool exists = false; u32 nm = 0; u32 begin = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{};
     int32_t score = 0;          // a realigned path (flx_realign.hip): its score; nm is then its num_errors and
     u32 ed = 0;                 // ed the edit distance K4 found (nm without the option)
+    u64 cs_off = 0; u32 cs_len = 0;      // its cs string (flx_cs.hip) in the caller's cs pool, when wanted
 };
+// the cs strings of the traced paths (flx_cs.hip) for the traces that want them: form 1 (short) or 2 (long), the device query pool's
+// letters (q_off addresses them as it does the Peq planes) and the host pool the bytes land in (shared by duplicates like the CIGAR words)
+struct CsWant { u32 form; const u8* d_query; hvec<u8>* pool; };
 // the values of the tail rule (flx_tails.hpp) for the traces that want it, defaults resolved
 struct TailParams { u32 w, x_drop, min_rows; };
 // host milliseconds of the host-rounds form, summed over a chunk's rounds (FLX_HOST_PROFILE); owned by the chunk
@@ -131,14 +138,19 @@ int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignReq
 // d_la_query != null: the device query pool's letters (q_off addresses them as it does the Peq planes), and every traced path's gaps are
 // left-aligned behind K5 (flx_leftalign.hip) before its MD string and tails are read off it
 // d_ra_query != null: the same letters, and every traced path is realigned under *realign behind K5 (flx_realign.hip) before all of that
+// cs != null: the cs string of every traced path as well (flx_cs.hip), read off the final words behind md_build
 struct RealignScores;
 int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                    hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr,
-                   const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr);
+                   const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr, const CsWant* cs = nullptr);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
 int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
                          hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr,
-                         const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr);
+                         const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr, const CsWant* cs = nullptr);
+// one cs_build launch over words and DevTraceOuts made on the host (flx_cs_batch): slabs receives the jobs' slabs (slab_bytes bytes),
+// lens the length of every job's string
+int run_cs_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevCsJob> const& jobs,
+                u32 form, u64 slab_bytes, hvec<u8>& slabs, hvec<u32>& lens);
 // one cigar_left_align launch over words and DevTraceOuts made on the host (flx_left_align_batch): out_words receives the second buffer
 // (words_out words), touts the rewritten DevTraceOuts
 int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts,
@@ -181,7 +193,7 @@ struct AnchorState {
 
 struct Span { u64 offset, length, extra; };
 // (ed: the edit distance verification found, what the statistics count; nm differs from it on a realigned path only)
-struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; u32 ed = 0; };
+struct RootAlignment { bool exists = false; u64 start = 0; u32 nm = 0; u64 cigar_off = 0; u32 cigar_len = 0; u64 md_off = 0; u32 md_len = 0; DevTailOut tail{}; u32 ed = 0; u64 cs_off = 0; u32 cs_len = 0; };
 
 // a record rescue_partials (flx_partial.hpp: a soft-clipped part of a read without a mapped record) or split_tails (flx_tails.hpp: the
 // kept part and the tails of a read mapped in full) leaves for write_records
@@ -190,6 +202,7 @@ struct PartialRecord {
     u32 o_from, o_to;           // the traced rows in the oriented sequence (the node, before extend_partials moves them)
     u64 core_off; u32 core_len; // the traced words without the clips
     bool split = false;         // a record of a split read: written instead of the read's root records
+    u64 cs_off = 0; u32 cs_len = 0;      // the cs string of the traced words (flx_cs_options)
 };
 
 struct Slice {
@@ -221,6 +234,8 @@ struct Slice {
     bool want_left_align = false;                                             // flx_gap_options.left_align: every traced path's gaps left-aligned
     const RealignScores* realign = nullptr;                                   // flx_realign_options.enable: every traced path realigned under these scores
     hvec<u8> md;                                                              // MD pool of root_res
+    u32 cs_form = 0;                                                          // flx_cs_options.form: the traced paths' cs strings as well
+    hvec<u8> cs;                                                              // cs pool of root_res
     // split_tails, rescue_partials: the records of the reads they split / rescued, read by read in the order they are written in;
     // {q_from, q_to} read-forward
     hvec<PartialRecord> partials;
@@ -233,13 +248,14 @@ struct Slice {
     // traces windows of the slice's reads (root windows, partial records): CIGAR words into cig, MD strings into md when wanted
     // tails: the paths' tails as well (align_roots alone asks for them)
     int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres, const TailParams* tails = nullptr) {
+        CsWant const want_cs{cs_form, RD->d_pool.as<u8>(), &cs};
         return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails, want_left_align ? RD->d_pool.as<u8>() : nullptr,
-                                    realign, realign ? RD->d_pool.as<u8>() : nullptr);
+                                    realign, realign ? RD->d_pool.as<u8>() : nullptr, cs_form ? &want_cs : nullptr);
     }
 };
 
 // the options of a run by value (flx_run_options, validated): an option that is off is a zeroed member
-struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; flx_gap_options gaps; flx_realign_options realign; };
+struct RunOptions { flx_output_options output; flx_tag_options tags; flx_partial_options partial; flx_extend_options extend; flx_split_options split; flx_gap_options gaps; flx_realign_options realign; flx_cs_options cs; };
 
 // produces the slice's records (read_index relative to the whole batch)
 int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_reads* RD, u64 first_read, u64 end_read, flx_run* run);

@@ -576,7 +576,7 @@ int align_roots(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, 
         if ((rc = S.trace_windows(lane, RD, root_reqs, tres, R.split.enable ? &tails : nullptr))) return rc;
         for (size_t i = 0; i < tres.size(); ++i)
             if (tres[i].exists)
-                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len, tres[i].tail, tres[i].ed};
+                root_res[i] = RootAlignment{true, root_spans[i].offset + tres[i].begin, tres[i].nm, tres[i].cigar_off, tres[i].cigar_len, tres[i].md_off, tres[i].md_len, tres[i].tail, tres[i].ed, tres[i].cs_off, tres[i].cs_len};
     }
     return FLX_OK;
 }
@@ -692,6 +692,7 @@ int split_tails(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, 
         PartialRecord kept{sp.read, pa.orientation ? 16u : 0u, pa.ref_id, pr.start + t.left_cols + kt.begin, kt.nm, clipped.first, clipped.second, kt.md_off, kt.md_len,
                            q_from, q_to, 0, o_from, o_to, kt.cigar_off, kt.cigar_len};
         kept.split = true;
+        kept.cs_off = kt.cs_off; kept.cs_len = kt.cs_len;
         S.partials.push_back(kept);
         // the supplementaries: choose_partials over the tail candidates
         pc.clear();
@@ -717,6 +718,7 @@ int split_tails(Slice& S, Lane* lane, const flx_params* P, RunOptions const& R, 
             PartialRecord sup{sp.read, 2048u | (cands[c].orientation ? 16u : 0u), cands[c].ref_id, pc[j].start, ct.nm, cl.first, cl.second, ct.md_off, ct.md_len,
                               pc[j].q_from, pc[j].q_to, quality[j], nd.from, nd.to, ct.cigar_off, ct.cigar_len};
             sup.split = true;
+            sup.cs_off = ct.cs_off; sup.cs_len = ct.cs_len;
             S.partials.push_back(sup);
         }
     }
@@ -797,6 +799,8 @@ int rescue_partials(Slice& S, Lane* lane, const flx_params* P, RunOptions const&
             auto const clipped = append_clipped(S.cig, nd.from, tres[c].cigar_off, tres[c].cigar_len, len - 1 - nd.to);
             S.partials.push_back(PartialRecord{(u32)r, (u32)flags[j], cands[c].ref_id, pc[j].start, tres[c].nm, clipped.first, clipped.second, tres[c].md_off,
                                                tres[c].md_len, pc[j].q_from, pc[j].q_to, quality[j], nd.from, nd.to, tres[c].cigar_off, tres[c].cigar_len});
+            S.partials.back().cs_off = tres[c].cs_off;
+            S.partials.back().cs_len = tres[c].cs_len;
         }
     }
     // (split_tails has left its records in front of these: read by read again, a read's records in the order they were made in)
@@ -887,6 +891,8 @@ int extend_partials(Slice& S, Lane* lane, RunOptions const& R, const flx_reads* 
         p.core_len = tres[j].cigar_len;
         p.md_off = tres[j].md_off;
         p.md_len = tres[j].md_len;
+        p.cs_off = tres[j].cs_off;
+        p.cs_len = tres[j].cs_len;
         std::tie(p.cigar_off, p.cigar_len) = append_clipped(S.cig, p.o_from, p.core_off, p.core_len, len - 1 - p.o_to);
     }
     return FLX_OK;
@@ -943,6 +949,9 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
     // MD (flx_tag_options.md): one {offset, length} per record, parallel to run->records; the selection moves it with the records it keeps
     bool const md = S.want_md;
     run->has_md = md;
+    // cs (flx_cs_options.form): the same, parallel to run->records
+    bool const cs = S.cs_form != 0;
+    run->has_cs = cs;
     size_t next_partial = 0;
     u64 n_partial_records = 0, n_rescued = 0, n_split = 0;
     for (size_t r = 0; r < reads.size(); ++r) {
@@ -962,6 +971,7 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
                 run->records.push_back(flx_record{reads[r].read_index, flag, (int32_t)ref, saturate_i32(root_res[i].start), root_res[i].nm,
                                                   root_res[i].cigar_off, root_res[i].cigar_len, 0});
                 if (md) run->md_refs.push_back(flx_md_ref{root_res[i].md_off, root_res[i].md_len, 0});
+                if (cs) run->cs_refs.push_back(flx_md_ref{root_res[i].cs_off, root_res[i].cs_len, 0});
                 if (mapq) {
                     if (mq_keys.empty()) mq_scratch.spans.clear();
                     u64 const span = root_res[i].cigar_len ? cigar_reference_span_cached(cig.data() + root_res[i].cigar_off, root_res[i].cigar_len, mq_scratch)
@@ -983,6 +993,7 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
             n_dropped += run->records.size() - rec0;
             run->records.resize(rec0);
             if (md) run->md_refs.resize(rec0);
+            if (cs) run->cs_refs.resize(rec0);
         }
         if (rescued) {                                           // (a read without a mapped record, or a split one)
             for (; next_partial < S.partials.size() && S.partials[next_partial].read == r; ++next_partial) {
@@ -990,12 +1001,14 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
                 run->records.push_back(flx_record{reads[r].read_index, p.flag, (int32_t)p.ref_id, saturate_i32(p.start), p.nm, p.cigar_off, p.cigar_len,
                                                   split && !(p.flag & 2048u) ? split_mapq : p.mapq});
                 if (md) run->md_refs.push_back(flx_md_ref{p.md_off, p.md_len, 0});
+                if (cs) run->cs_refs.push_back(flx_md_ref{p.cs_off, p.cs_len, 0});
                 ++n_partial_records;
             }
             if (split) ++n_split; else ++n_rescued;
         } else if (!primary_written) {
             run->records.push_back(flx_record{reads[r].read_index, 4u, -1, 0, 0, 0, 0, 0});
             if (md) run->md_refs.push_back(flx_md_ref{0, 0, 0});
+            if (cs) run->cs_refs.push_back(flx_md_ref{0, 0, 0});
         }
         if (mapq && !mq_keys.empty()) {
             mq_q.resize(mq_keys.size());
@@ -1020,11 +1033,13 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
             for (size_t j = 0; j < n; ++j)
                 if (sel_keep[j]) {
                     if (md) run->md_refs[w] = run->md_refs[rec0 + j];
+                    if (cs) run->cs_refs[w] = run->cs_refs[rec0 + j];
                     run->records[w++] = run->records[rec0 + j];
                 }
             n_dropped += run->records.size() - w;
             run->records.resize(w);
             if (md) run->md_refs.resize(w);
+            if (cs) run->cs_refs.resize(w);
         }
         if (st_local) {                                                                                  // parallelization.cpp:262-268
             u64 n_al = 0;
@@ -1040,6 +1055,7 @@ void write_records(Slice& S, flx_ctx* ctx, RunOptions const& R, u64 n_slice_read
     if (select) compact_cigars(run, cig);
     run->cigars = std::move(cig);
     if (md) run->md = std::move(S.md);              // (not compacted under -D / -N: the dropped records' bytes stay, unreferenced)
+    if (cs) run->cs = std::move(S.cs);              // (nor this pool)
     {
         u64 found = 0;
         for (auto const& rr : root_res) found += rr.exists;
@@ -1060,6 +1076,7 @@ int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_
     PhaseTimer prof;
     Slice S;
     S.want_md = R.tags.md;
+    S.cs_form = R.cs.form;
     S.want_left_align = R.gaps.left_align != 0;
     RealignScores const realign = realign_scores(&R.realign);
     if (R.realign.enable) S.realign = &realign;

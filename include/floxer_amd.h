@@ -598,6 +598,64 @@ int flx_run_copy_scores(const flx_run* run, int32_t* scores);
 typedef struct flx_realign_counters { uint64_t paths_realigned; uint64_t paths_changed; uint64_t paths_kept; uint64_t reserved[5]; } flx_realign_counters;
 int flx_ctx_get_realign_counters(flx_ctx* ctx, flx_realign_counters* out);
 
+/* The cs tag, minimap2's difference string, short and long form: not floxer's. MD names the reference letters under an X or a D and says
+ * nothing of the read's letters at an X or an I; cs holds both sides in one string, and its long form the matched letters too, so a
+ * record's read part and reference part can be rebuilt from the tag alone. Off when the struct is zeroed (or NULL), and then nothing
+ * changes: no launch, no allocation, no byte of any output. form = 1 (short) or 2 (long), anything else but 0 refused: every traced path
+ * of the run gets its string on the device (kernel cs_build, queued behind md_build's place: K4, K5, cigar_realign, cigar_left_align,
+ * md_build, cs_build, then cigar_tails in runs), read off the final words (realigned, then left-aligned), the window in the text and the
+ * record's oriented sequence in the query pool (for a flag-16 record the reverse-complemented read, as SEQ is written):
+ *   - the walk starts at the path's first reference column and first traced query row and goes left to right; every word emits on its
+ *     own, nothing merges across words (which is where cs differs from MD);
+ *   - = of length L: short form ':' and L in decimal, long form '=' and the L reference letters in upper case (they equal the query's by
+ *     construction); X of length L: per column '*', the reference letter, the query letter, lower case (3 L bytes, both forms); I of
+ *     length L: '+' and the L query letters, lower case; D of length L: '-' and the L reference letters, lower case;
+ *   - letters are the index's ranks: 1..4 give acgt / ACGT, anything else (0 and 5 included) n / N, the limit MD has: IUPAC codes and
+ *     lower-case FASTA letters are not recoverable. Nothing is compared again: an X over equal ranks is emitted as it stands. There is
+ *     no '~' (no introns). minimap2's own example has this shape: :6-ata:10+gtc:4*at:3;
+ *   - soft clips emit nothing: for partial, extended and split records the string covers the traced core only, like MD, and the query
+ *     starts at the core's first row. Records that share a CIGAR share their cs bytes; an unmapped record has none (length 0).
+ * A path of m query rows and NM errors needs at most 10 NM + 7 bytes (short) or m + 3 NM + 1 (long): floxer_amd/csrc/flx_internal.hpp.
+ * The output options (-D, -N, MAPQ) and SA:Z do not interact with it; MD and cs may both be on. params->without_cigar has no trace:
+ * refused together with form != 0 (FLX_ERR_INVALID), as are a form above 2 and a reserved field that is not 0, before any work and
+ * before the context is looked at. The rule: floxer_amd/csrc/flx_cs.hpp. */
+typedef struct flx_cs_options { uint32_t form; uint32_t reserved[7]; } flx_cs_options;
+/* flx_align_reads_realign / flx_align_reads_resident_realign with the cs options (NULL or zeroed: exactly those calls, which forward here) */
+int flx_align_reads_cs(flx_ctx* ctx, const flx_params* params, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                       const flx_run_options* options, const flx_split_options* split, const flx_gap_options* gaps,
+                       const flx_realign_options* realign, const flx_cs_options* cs, flx_run** out);
+int flx_align_reads_resident_cs(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_run_options* options,
+                                const flx_split_options* split, const flx_gap_options* gaps, const flx_realign_options* realign,
+                                const flx_cs_options* cs, flx_run** out);
+/* The cs strings of a run made with flx_cs_options.form != 0, the contract of flx_run_num_md_bytes / flx_run_copy_md: refs[i] is record
+ * i's {offset, length} into the bytes (length 0: the record has none), in flx_run_copy's order; either pointer may be NULL. -D / -N
+ * select records together with their cs; the pool is not compacted. FLX_ERR_INVALID on a run made without the option. */
+uint64_t flx_run_num_cs_bytes(const flx_run* run);
+int flx_run_copy_cs(const flx_run* run, flx_md_ref* refs, uint8_t* bytes);
+/* flx_align_batch_realign with the cs options: K4, K5, cigar_realign, cigar_left_align, md_build, cs_build on the WITH_CIGAR jobs.
+ * out_cs[i]: where job i's string lies in cs_pool (length 0: a job without a path, or of another mode); *cs_pool_bytes: in = capacity,
+ * out = bytes used (the jobs' slabs as the device filled them, gaps included; FLX_ERR_CAPACITY with the need stored when too small).
+ * cs NULL or zeroed: exactly flx_align_batch_realign, which forwards here, and the three cs arguments are not looked at. */
+int flx_align_batch_cs(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                       const flx_align_job* jobs, uint64_t n_jobs, flx_align_result* out, uint32_t* cigar_pool, uint64_t* cigar_pool_words,
+                       flx_md_ref* out_md, uint8_t* md_pool, uint64_t* md_pool_bytes, const flx_gap_options* gaps,
+                       const flx_realign_options* realign, int32_t* out_scores, const flx_cs_options* cs, flx_md_ref* out_cs,
+                       uint8_t* cs_pool, uint64_t* cs_pool_bytes);
+/* The rule alone on any CIGAR words: the jobs are flx_left_align's (same fields, same checks: a job outside its pools, an op other than
+ * = X I D, a zero-length word, op lengths that do not fit the window and the query, a reserved field that is not 0: FLX_ERR_INVALID,
+ * flx_cs_batch: before any launch); query_offset is the path's first query row. options: the form, which must be 1 or 2 here (the call
+ * is the request). out[i]: where job i's string lies in out_bytes (packed in job order); *out_n_bytes: in = capacity of out_bytes, out =
+ * bytes used (FLX_ERR_CAPACITY with the need stored when too small). flx_cs runs on the host and needs ref_pool; flx_cs_batch runs the
+ * kernel, ref_pool == NULL there: the context's reference text (ref_offset is then a position in the padded concatenated text; this
+ * needs no host text, so a context on an index image works). Both give the same bytes. */
+typedef flx_left_align_job flx_cs_job;
+int flx_cs(const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len, const uint32_t* cigar_words,
+           uint64_t n_words, const flx_cs_job* jobs, uint64_t n_jobs, const flx_cs_options* options, uint8_t* out_bytes, uint64_t* out_n_bytes,
+           flx_md_ref* out);
+int flx_cs_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, const uint8_t* query_pool, uint64_t query_pool_len,
+                 const uint32_t* cigar_words, uint64_t n_words, const flx_cs_job* jobs, uint64_t n_jobs, const flx_cs_options* options,
+                 uint8_t* out_bytes, uint64_t* out_n_bytes, flx_md_ref* out);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -675,6 +733,13 @@ int flx_sam_write_tagged(flx_sam_writer* w, const char* const* read_ids, const u
 int flx_sam_write_scored(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
                          const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
                          const flx_md_ref* md, const uint8_t* md_bytes, const int32_t* scores);
+/* flx_sam_write_scored with a cs:Z tag behind NM / MD / AS and in front of SA on every mapped record i with cs_refs[i].length > 0 (its
+ * bytes: cs_bytes + cs_refs[i].offset; csZ...\0 in BAM, where a string that repeats the previous record's is announced to the deflate
+ * encoder as MD's is). Bytes outside [0-9:*+=acgtnACGTN-] are refused with FLX_ERR_INVALID. cs_refs == NULL: exactly
+ * flx_sam_write_scored. */
+int flx_sam_write_cs(flx_sam_writer* w, const char* const* read_ids, const uint8_t* read_pool, const uint64_t* read_offsets,
+                     const char* const* quals, const flx_record* records, uint64_t n_records, const uint32_t* cigar_words,
+                     const flx_md_ref* md, const uint8_t* md_bytes, const int32_t* scores, const flx_md_ref* cs_refs, const uint8_t* cs_bytes);
 int flx_sam_close(flx_sam_writer* w);
 /* record formatting and BGZF block compression of flx_sam_write on n_threads host threads (default 1; output bytes do not depend on it) */
 int flx_sam_set_threads(flx_sam_writer* w, uint32_t n_threads);
