@@ -17,6 +17,7 @@ libfloxer_amd.so:
     aligner(..., gaps=gap_options()), left_align()  not floxer's: indels left-aligned on the device behind the traceback (opt-in)
     aligner(..., realign=realign_options()), realign(), realign_batch(), align_batch_realign()  not floxer's: a traced path realigned under affine gap costs inside a band around it (opt-in)
     aligner(..., cs=cs_options()), cs_string(), cs_batch(), align_batch_cs()  not floxer's: minimap2's cs difference string, short or long form, built on the device behind the MD strings (opt-in)
+    coverage(ctx, coverage_options()), coverage_host()  not floxer's: depth of coverage accumulated on the device from the records of runs: equal-depth runs, per-window sums (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -501,7 +502,8 @@ class RunResult:
     `md_refs` ((n,2) uint64 {offset, length} into `md_bytes`) and `md`, a list of bytes / None per record, made on first use; a run
     made with cs=cs_options(...) has `cs_refs`, `cs_bytes` and `cs` in the same way."""
 
-    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None, scores=None, cs_refs=None, cs_bytes=None):
+    def __init__(self, raw, cigars, skipped, md_refs=None, md_bytes=None, scores=None, cs_refs=None, cs_bytes=None, has_mapq=None):
+        self.has_mapq = has_mapq        # the run was made with output_options(mapq=True): `mapq` holds mapping qualities (None: unknown, a result not made by an aligner)
         self.cs_refs = cs_refs
         self.cs_bytes = cs_bytes
         self._cs = None
@@ -941,7 +943,7 @@ def choose_partials(candidates, cigars=None, options=None):
     return out[: len(candidates)]
 
 
-def _collect_run(run, n, md=False, scores=False, cs=False):
+def _collect_run(run, n, md=False, scores=False, cs=False, has_mapq=None):
     try:
         nr = lib().flx_run_num_records(run)
         nc = lib().flx_run_num_cigar_words(run)
@@ -973,7 +975,7 @@ def _collect_run(run, n, md=False, scores=False, cs=False):
             cs_bytes = cs_bytes[:nb]
     finally:
         lib().flx_run_free(run)
-    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes, sc, cs_refs, cs_bytes)
+    return RunResult(raw, cig[:nc], skipped[:n], md_refs, md_bytes, sc, cs_refs, cs_bytes, has_mapq)
 
 
 class aligner:
@@ -1020,4 +1022,111 @@ class aligner:
             pool, offs, n = _pool_and_offsets(reads)
             check(lib().flx_align_reads_realign(self.ctx.h, C.byref(self.params), ptr(pool, u8p), ptr(offs, u64p), n, C.byref(bundle), split, gaps,
                                                 realign, C.byref(run)))
-        return _collect_run(run, n, md=self.md, scores=self.realign is not None and bool(self.realign.enable), cs=want_cs)
+        return _collect_run(run, n, md=self.md, scores=self.realign is not None and bool(self.realign.enable), cs=want_cs,
+                            has_mapq=self.output is not None and bool(self.output.mapq))
+
+
+def coverage_options(count_deletions=False, count_secondary=False, min_mapq=0, report_zero=False):
+    """flx_coverage_options: count_deletions: D columns add depth (samtools depth -J); count_secondary: flag-256 records count;
+    min_mapq: a record counts only with at least this mapping quality (needs runs made with output_options(mapq=True));
+    report_zero: runs() lists the stretches of depth 0 too"""
+    o = capi.CoverageOptions()
+    o.count_deletions = 1 if count_deletions else 0
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq = int(min_mapq)
+    o.report_zero = 1 if report_zero else 0
+    return o
+
+
+RUN_DTYPE = np.dtype([("ref", "<i4"), ("depth", "<u4"), ("start", "<u8"), ("end", "<u8")])
+WINDOW_DTYPE = np.dtype([("ref", "<i4"), ("max_depth", "<u4"), ("start", "<u8"), ("end", "<u8"), ("depth_sum", "<u8"), ("covered", "<u8")])
+
+
+def _records_and_words(records, cigar_words):
+    rec = np.ascontiguousarray(np.asarray(records, dtype=_REC_DTYPE))
+    words = np.ascontiguousarray(np.asarray(cigar_words, dtype=np.uint32))
+    return rec, words
+
+
+def coverage_geometry():
+    """(elements per scan tile, tile sums per second-level block) of the finish scan: a test hook"""
+    g = np.zeros(2, dtype=np.uint32)
+    check(lib().flx_coverage_geometry(ptr(g, u32p)))
+    return int(g[0]), int(g[1])
+
+
+class coverage:
+    """Depth of coverage over the sequences of a context's index (ctx) or over `lengths` on `device`: add the records of runs, absorb
+    the objects of other devices, finish once, then read runs(), windows(w) and depth(ref, a, b). Not floxer's. Adds may come from
+    several threads at once."""
+
+    def __init__(self, ctx=None, options=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_coverage_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if lengths is None:
+                raise FloxerError("coverage needs a context or a list of reference lengths")
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+            check(lib().flx_coverage_create_for_lengths(int(device), ptr(lens, u64p), len(lens), opt, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_coverage_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed.
+        With min_mapq a run made without output_options(mapq=True) is refused, as flx_coverage_add_run refuses it: its records hold no
+        mapping quality. add_records cannot know and takes the records' `res` as it stands."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("coverage.add: min_mapq needs a run made with output_options(mapq=True)")
+            return self.add_records(run.raw, run.cigars)
+        check(lib().flx_coverage_add_run(self.h, run))
+
+    def add_records(self, records, cigar_words):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to"""
+        rec, words = _records_and_words(records, cigar_words)
+        check(lib().flx_coverage_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words)))
+
+    def absorb(self, other):
+        check(lib().flx_coverage_absorb(self.h, other.h))
+
+    def finish(self):
+        check(lib().flx_coverage_finish(self.h))
+
+    def runs(self):
+        n = lib().flx_coverage_num_runs(self.h)
+        out = np.zeros(max(1, n), dtype=RUN_DTYPE)
+        check(lib().flx_coverage_copy_runs(self.h, out.ctypes.data_as(C.POINTER(capi.DepthRun)), n))
+        return out[:n]
+
+    def windows(self, w=0):
+        n = lib().flx_coverage_num_windows(self.h, int(w))
+        out = np.zeros(max(1, n), dtype=WINDOW_DTYPE)
+        check(lib().flx_coverage_copy_windows(self.h, int(w), out.ctypes.data_as(C.POINTER(capi.DepthWindow)), n))
+        return out[:n]
+
+    def depth(self, ref, a, b):
+        out = np.zeros(max(1, int(b) - int(a)), dtype=np.uint32)
+        check(lib().flx_coverage_copy_depth(self.h, int(ref), int(a), int(b), ptr(out, u32p)))
+        return out[: max(0, int(b) - int(a))]
+
+
+def coverage_host(lengths, records, cigar_words, options=None):
+    """the rule alone on the host (flx_coverage_host): the depth of every position of the concatenated sequences, uint32"""
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+    rec, words = _records_and_words(records, cigar_words)
+    depth = np.zeros(max(1, int(lens.sum())), dtype=np.uint32)
+    check(lib().flx_coverage_host(ptr(lens, u64p), len(lens), C.byref(options) if options is not None else None,
+                                  rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(depth, u32p)))
+    return depth[: int(lens.sum())]

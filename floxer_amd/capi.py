@@ -141,6 +141,20 @@ class CsOptions(C.Structure):
 CsJob = LeftAlignJob
 
 
+class CoverageOptions(C.Structure):
+    _fields_ = [("count_deletions", C.c_uint32), ("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("report_zero", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class DepthRun(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("depth", C.c_uint32), ("start", C.c_uint64), ("end", C.c_uint64)]
+
+
+class DepthWindow(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("max_depth", C.c_uint32), ("start", C.c_uint64), ("end", C.c_uint64), ("depth_sum", C.c_uint64),
+                ("covered", C.c_uint64)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -208,6 +222,9 @@ EXPORTED = [
     "flx_ctx_get_search_counters",
     "flx_align_reads_cs", "flx_align_reads_resident_cs", "flx_run_num_cs_bytes", "flx_run_copy_cs", "flx_align_batch_cs", "flx_cs", "flx_cs_batch",
     "flx_sam_write_cs",
+    "flx_coverage_create", "flx_coverage_create_for_lengths", "flx_coverage_free", "flx_coverage_add_run", "flx_coverage_add_records",
+    "flx_coverage_absorb", "flx_coverage_finish", "flx_coverage_num_runs", "flx_coverage_copy_runs", "flx_coverage_num_windows",
+    "flx_coverage_copy_windows", "flx_coverage_copy_depth", "flx_coverage_geometry", "flx_coverage_host",
 ]
 
 _lib = None
@@ -334,6 +351,23 @@ def lib():
     L.flx_cs.argtypes = [u8p, C.c_uint64, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(CsJob), C.c_uint64, C.POINTER(CsOptions), u8p, u64p,
                          C.POINTER(MdRef)]
     L.flx_cs_batch.argtypes = [C.c_void_p] + L.flx_cs.argtypes
+    L.flx_coverage_create.argtypes = [C.c_void_p, C.POINTER(CoverageOptions), C.POINTER(C.c_void_p)]
+    L.flx_coverage_create_for_lengths.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(CoverageOptions), C.POINTER(C.c_void_p)]
+    L.flx_coverage_free.restype = None
+    L.flx_coverage_free.argtypes = [C.c_void_p]
+    L.flx_coverage_add_run.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_coverage_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64]
+    L.flx_coverage_absorb.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_coverage_finish.argtypes = [C.c_void_p]
+    L.flx_coverage_num_runs.restype = C.c_uint64
+    L.flx_coverage_num_runs.argtypes = [C.c_void_p]
+    L.flx_coverage_copy_runs.argtypes = [C.c_void_p, C.POINTER(DepthRun), C.c_uint64]
+    L.flx_coverage_num_windows.restype = C.c_uint64
+    L.flx_coverage_num_windows.argtypes = [C.c_void_p, C.c_uint64]
+    L.flx_coverage_copy_windows.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DepthWindow), C.c_uint64]
+    L.flx_coverage_copy_depth.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
+    L.flx_coverage_geometry.argtypes = [u32p]
+    L.flx_coverage_host.argtypes = [u64p, C.c_uint32, C.POINTER(CoverageOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u32p]
     L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]

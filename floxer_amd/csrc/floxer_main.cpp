@@ -76,6 +76,10 @@ struct Options {
     bool left_align_indels = false;
     bool realign_affine = false;
     uint64_t realign_match = 0, realign_mismatch = 0, realign_gap_open = 0, realign_gap_extend = 0, realign_band = 0;   // 0: the library's defaults
+    std::string coverage, coverage_summary, coverage_windows;      // output files of the depth track; empty: not written
+    uint64_t coverage_window = 0, coverage_min_mapq = 0;
+    bool coverage_deletions = false, coverage_secondary = false, coverage_zero = false;
+    bool wants_coverage() const { return !coverage.empty() || !coverage_summary.empty() || !coverage_windows.empty(); }
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -122,6 +126,15 @@ const OptDef OPTS[] = {
     {0, "realign-gap-open", false, "not floxer's: the cost of opening a gap (default 4, at most 255); needs --realign-affine"},
     {0, "realign-gap-extend", false, "not floxer's: the cost of every gap column (default 2, at most 255); needs --realign-affine"},
     {0, "realign-band", false, "not floxer's: the diagonals added on either side of the path's own (default 16, at most 1024); needs --realign-affine"},
+    // nor these: depth of coverage, accumulated on the GPU from every batch's records (flx_coverage, flx_coverage.hpp)
+    {0, "coverage", false, "not floxer's: depth of coverage as a bedGraph file (name, start, end, depth; 0-based, half-open; <file.bedgraph>); not with -w"},
+    {0, "coverage-summary", false, "not floxer's: one line per reference sequence (name, length, covered, depth_sum, max_depth; <file.tsv>); not with -w"},
+    {0, "coverage-windows", false, "not floxer's: depth per window (name, start, end, depth_sum, covered, max_depth; <file.tsv>); needs --coverage-window, not with -w"},
+    {0, "coverage-window", false, "not floxer's: the window size of --coverage-windows (at least 1)"},
+    {0, "coverage-deletions", true, "not floxer's: deleted reference bases count as covered (samtools depth -J); needs one of the coverage outputs"},
+    {0, "coverage-secondary", true, "not floxer's: secondary records (flag 256) count too; needs one of the coverage outputs"},
+    {0, "coverage-zero", true, "not floxer's: --coverage lists the stretches of depth 0 as well; needs one of the coverage outputs"},
+    {0, "coverage-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and one of the coverage outputs"},
 };
 
 struct CliError { std::string msg; };
@@ -239,6 +252,14 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "split-tails-weight") { o.split_tails_weight = parse_u64(n, value); range_check(n, (double)o.split_tails_weight, 1, 65535); }
         else if (n == "split-tails-xdrop") { o.split_tails_xdrop = parse_u64(n, value); range_check(n, (double)o.split_tails_xdrop, 1, 1073741824); }
         else if (n == "split-tails-min-rows") { o.split_tails_min_rows = parse_u64(n, value); range_check(n, (double)o.split_tails_min_rows, 1, 524287); }
+        else if (n == "coverage") o.coverage = value;
+        else if (n == "coverage-summary") o.coverage_summary = value;
+        else if (n == "coverage-windows") o.coverage_windows = value;
+        else if (n == "coverage-window") { o.coverage_window = parse_u64(n, value); if (o.coverage_window < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
+        else if (n == "coverage-deletions") o.coverage_deletions = true;
+        else if (n == "coverage-secondary") o.coverage_secondary = true;
+        else if (n == "coverage-zero") o.coverage_zero = true;
+        else if (n == "coverage-min-mapq") { o.coverage_min_mapq = parse_u64(n, value); range_check(n, (double)o.coverage_min_mapq, 1, 254); }
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -285,6 +306,14 @@ Options parse_cli(int argc, char** argv) {
         if (std::max(a + b, go + ge + a) > 8 * std::min(a + b, go + ge))
             throw CliError{"The realign scores are too far apart: max(match + mismatch, gap-open + gap-extend + match) must not exceed 8 times min(match + mismatch, gap-open + gap-extend)."};
     }
+    if (o.wants_coverage() && o.without_cigar) throw CliError{"The options --coverage, --coverage-summary and --coverage-windows need the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (!o.wants_coverage() && (o.coverage_deletions || o.coverage_secondary || o.coverage_zero || o.coverage_min_mapq || o.coverage_window))
+        throw CliError{"The options --coverage-deletions, --coverage-secondary, --coverage-zero, --coverage-min-mapq and --coverage-window need one of --coverage, --coverage-summary and --coverage-windows."};
+    if (o.coverage_min_mapq && !o.mapping_quality) throw CliError{"The option --coverage-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
+    if (o.coverage_windows.empty() != (o.coverage_window == 0)) throw CliError{"The options --coverage-windows and --coverage-window need each other."};
+    if (!o.coverage.empty() && !has_ext(o.coverage, {"bedgraph"}, false)) throw CliError{"Validation failed for option --coverage: Expected one of the following valid extensions: [bedgraph]."};
+    if (!o.coverage_summary.empty() && !has_ext(o.coverage_summary, {"tsv"}, false)) throw CliError{"Validation failed for option --coverage-summary: Expected one of the following valid extensions: [tsv]."};
+    if (!o.coverage_windows.empty() && !has_ext(o.coverage_windows, {"tsv"}, false)) throw CliError{"Validation failed for option --coverage-windows: Expected one of the following valid extensions: [tsv]."};
     return o;
 }
 
@@ -578,6 +607,53 @@ std::vector<int> parse_devices(std::string spec, int n_available, std::string& e
     return out;
 }
 
+// the depth track's files: every device's accumulator summed into the first, finished there, and its runs and windows written as text
+bool write_coverage(Options const& o, std::vector<flx_coverage*> const& covs, std::vector<std::string> const& names) {
+    for (size_t i = 1; i < covs.size(); ++i)
+        if (flx_coverage_absorb(covs[0], covs[i]) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    flx_coverage* const cov = covs[0];
+    if (flx_coverage_finish(cov) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    auto open_out = [](std::string const& path) {
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) log_line("error", "cannot open output file: %s", path.c_str());
+        return f;
+    };
+    auto windows_of = [&](uint64_t w, std::vector<flx_depth_window>& out) {
+        out.resize(flx_coverage_num_windows(cov, w));
+        if (flx_coverage_copy_windows(cov, w, out.data(), out.size()) == FLX_OK) return true;
+        log_line("error", "%s", flx_last_error());
+        return false;
+    };
+    bool ok = true;
+    if (!o.coverage.empty()) {
+        std::vector<flx_depth_run> runs(flx_coverage_num_runs(cov));
+        if (flx_coverage_copy_runs(cov, runs.data(), runs.size()) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+        FILE* f = open_out(o.coverage);
+        if (!f) return false;
+        for (auto const& r : runs) fprintf(f, "%s\t%llu\t%llu\t%u\n", names[(size_t)r.reference_id].c_str(), (unsigned long long)r.start, (unsigned long long)r.end, r.depth);
+        ok = fclose(f) == 0 && ok;
+    }
+    if (!o.coverage_summary.empty()) {
+        std::vector<flx_depth_window> win;
+        if (!windows_of(0, win)) return false;
+        FILE* f = open_out(o.coverage_summary);
+        if (!f) return false;
+        for (auto const& w : win) fprintf(f, "%s\t%llu\t%llu\t%llu\t%u\n", names[(size_t)w.reference_id].c_str(), (unsigned long long)w.end, (unsigned long long)w.covered, (unsigned long long)w.depth_sum, w.max_depth);
+        ok = fclose(f) == 0 && ok;
+    }
+    if (!o.coverage_windows.empty()) {
+        std::vector<flx_depth_window> win;
+        if (!windows_of(o.coverage_window, win)) return false;
+        FILE* f = open_out(o.coverage_windows);
+        if (!f) return false;
+        for (auto const& w : win)
+            fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu\t%u\n", names[(size_t)w.reference_id].c_str(), (unsigned long long)w.start, (unsigned long long)w.end, (unsigned long long)w.depth_sum, (unsigned long long)w.covered, w.max_depth);
+        ok = fclose(f) == 0 && ok;
+    }
+    if (!ok) log_line("error", "write error on a coverage output");
+    return ok;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -644,6 +720,20 @@ int main(int argc, char** argv) {
         ctxs.push_back(c);
     }
     log_line("info", "running on %zu HIP device context%s", ctxs.size(), ctxs.size() == 1 ? "" : "s");
+    // the depth track: one accumulator per device, fed by every batch that device aligns and summed into the first after the last batch
+    flx_coverage_options cov_opt;
+    memset(&cov_opt, 0, sizeof(cov_opt));
+    cov_opt.count_deletions = o.coverage_deletions;
+    cov_opt.count_secondary = o.coverage_secondary;
+    cov_opt.min_mapq = (uint32_t)o.coverage_min_mapq;
+    cov_opt.report_zero = o.coverage_zero;
+    std::vector<flx_coverage*> covs;
+    if (o.wants_coverage())
+        for (flx_ctx* c : ctxs) {
+            flx_coverage* cov = nullptr;
+            if (flx_coverage_create(c, &cov_opt, &cov) != FLX_OK) { log_line("error", "cannot set up the coverage accumulator: %s", flx_last_error()); return -1; }
+            covs.push_back(cov);
+        }
 
     std::vector<const char*> ref_id_ptrs;
     for (auto const& s : ref.ids) ref_id_ptrs.push_back(s.c_str());
@@ -747,6 +837,11 @@ int main(int argc, char** argv) {
         f.rc = flx_align_reads_cs(ctx, &p, b->pool.data(), b->offsets.data(), b->ids.size(), &run_opt, &split_opt, &gap_opt, &realign_opt, &cs_opt, &run);
         us_align += now_us() - t0;
         if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
+        if (!covs.empty()) {
+            size_t const at = std::find(ctxs.begin(), ctxs.end(), ctx) - ctxs.begin();
+            f.rc = flx_coverage_add_run(covs[at], run);
+            if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
+        }
         f.recs.resize(flx_run_num_records(run));
         f.cig.resize(flx_run_num_cigar_words(run) + 1);
         f.skipped.resize(b->ids.size());
@@ -852,6 +947,8 @@ int main(int argc, char** argv) {
     if (flx_sam_close(out) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
     // (the alignment phase ends with the output file: floxer.cpp:154-179 stops its watch there; giving 40 GB of HBM back is not part of it)
     double const secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_align).count();
+    if (!covs.empty() && !failed.load() && !timed_out && !write_coverage(o, covs, ref.ids)) failed.store(true);
+    for (flx_coverage* c : covs) flx_coverage_free(c);
     for (flx_ctx* c : ctxs) flx_ctx_destroy(c);
     flx_index_free(index);
     if (failed.load() || timed_out) return -1;

@@ -252,6 +252,7 @@ extern "C" int flx_align_reads_resident_cs(flx_ctx* ctx, const flx_params* P, co
     run->has_scores = opt.realign.enable != 0;
     run->realign = opt.realign;
     run->has_cs = opt.cs.form != 0;
+    run->has_mapq = opt.output.mapq != 0;
     if (n_reads == 0) { *out = run.release(); return FLX_OK; }       // an empty batch is an empty run
     // reads are independent units (parallelization.cpp:77-87): the batch is cut into contiguous chunks and every lane (a host
     // thread with its own stream and workspaces) takes the next chunk when it is done with its last one.

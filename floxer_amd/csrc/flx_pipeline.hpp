@@ -28,6 +28,7 @@ struct flx_run {
     bool has_cs = false;               // made with flx_cs_options.form != 0: cs_refs is parallel to records, offsets relative to this object's `cs`
     flx::hvec<flx_md_ref> cs_refs;
     flx::hvec<flx::u8> cs;
+    bool has_mapq = false;             // made with flx_output_options.mapq: the records' `reserved` holds their mapping quality
     flx::hvec<flx_run> parts;          // a batch result is the in-order list of its slices (no concatenation on the host)
 };
 

@@ -656,6 +656,55 @@ int flx_cs_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_pool_len, c
                  const uint32_t* cigar_words, uint64_t n_words, const flx_cs_job* jobs, uint64_t n_jobs, const flx_cs_options* options,
                  uint8_t* out_bytes, uint64_t* out_n_bytes, flx_md_ref* out);
 
+/* ------------------------------------------------------------------------------------------------ depth of coverage
+ * Not floxer's, which writes records and leaves their pile-up to a coordinate sort and a second tool. A coverage object belongs to a list
+ * of reference lengths and holds one u32 of depth per reference position in HBM, indexed by position in the unpadded concatenation of the
+ * sequences in reference-id order (4 bytes per symbol + 4). A sequence of 2^31 symbols or more cannot be addressed by
+ * flx_record.position and is refused at creation. The rule (floxer_amd/csrc/flx_coverage.hpp), samtools depth's default filters plus -Q / -J:
+ *   - a record with flag & 4 never counts; one with flag & 256 only with count_secondary; supplementary records (2048) always count;
+ *     with min_mapq > 0 a record counts only if flx_record.reserved >= min_mapq;
+ *   - a counted record is walked from `position` over its CIGAR words: every = and X column adds 1 at its reference position, I and S
+ *     add nothing, D columns advance the position and add 1 only with count_deletions;
+ *   - refused (FLX_ERR_INVALID, on the host before any launch; the accumulator stays as it was): a counted record without CIGAR words
+ *     (a run made with without_cigar), an op other than = X I D S, a zero-length word, a reference_id outside the list, a span that ends
+ *     behind its sequence, words outside the pool.
+ * flx_coverage_create takes the lengths from the context's index (a meta-imported one included) and allocates and clears the accumulator
+ * on the context's device; flx_coverage_create_for_lengths is the same without an index (a test hook, and for callers that kept
+ * records). A failed allocation returns FLX_ERR_NO_DEVICE and leaves nothing behind. options NULL: all zero; reserved fields must be 0.
+ * flx_coverage_add_run adds the written records of a run (it needs min_mapq == 0 or a run made with flx_output_options.mapq),
+ * flx_coverage_add_records any record array with its CIGAR word pool; both may be called from several host threads at once.
+ * flx_coverage_absorb: into += from, `from` is left cleared; same lengths and options, both before finish; the two may live on different
+ * devices. flx_coverage_finish turns the differences into depths in place and is final: a later add, absorb or finish is
+ * FLX_ERR_INVALID, and the copy calls work only behind it:
+ *   - runs: maximal stretches of equal depth inside one sequence, 0-based and half-open, in position order; a run never crosses a
+ *     sequence boundary; runs of depth 0 only with report_zero. flx_coverage_copy_runs: FLX_ERR_CAPACITY when capacity is too small;
+ *   - windows of size W (0: one per sequence): for every sequence and every [kW, min((k+1)W, len)) the sum of the depths, the positions
+ *     with depth > 0 and the largest depth; flx_coverage_num_windows counts them;
+ *   - flx_coverage_copy_depth (a test hook): the depths of [from, to) of one sequence.
+ * Everything is integer: nothing depends on the order of adds, the number of calls, host threads or devices.
+ * flx_coverage_geometry (a test hook): out[0] = elements per scan tile, out[1] = tile sums one second-level block scans.
+ * flx_coverage_host: the rule alone on the host, no device: depth (sum of ref_lens entries) is added to; the same refusals, and depth
+ * is untouched when it refuses. */
+typedef struct flx_coverage flx_coverage;
+typedef struct flx_coverage_options { uint32_t count_deletions, count_secondary, min_mapq, report_zero; uint32_t reserved[4]; } flx_coverage_options;
+typedef struct flx_depth_run    { int32_t reference_id; uint32_t depth; uint64_t start, end; } flx_depth_run;
+typedef struct flx_depth_window { int32_t reference_id; uint32_t max_depth; uint64_t start, end, depth_sum, covered; } flx_depth_window;
+int  flx_coverage_create(flx_ctx* ctx, const flx_coverage_options* o, flx_coverage** out);
+int  flx_coverage_create_for_lengths(int hip_device, const uint64_t* ref_lens, uint32_t n_refs, const flx_coverage_options* o, flx_coverage** out);
+void flx_coverage_free(flx_coverage* c);
+int  flx_coverage_add_run(flx_coverage* c, const flx_run* run);
+int  flx_coverage_add_records(flx_coverage* c, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words);
+int  flx_coverage_absorb(flx_coverage* into, flx_coverage* from);
+int  flx_coverage_finish(flx_coverage* c);
+uint64_t flx_coverage_num_runs(const flx_coverage* c);
+int  flx_coverage_copy_runs(const flx_coverage* c, flx_depth_run* out, uint64_t capacity);
+uint64_t flx_coverage_num_windows(const flx_coverage* c, uint64_t window);
+int  flx_coverage_copy_windows(flx_coverage* c, uint64_t window, flx_depth_window* out, uint64_t capacity);
+int  flx_coverage_copy_depth(const flx_coverage* c, uint32_t reference_id, uint64_t from, uint64_t to, uint32_t* out);
+int  flx_coverage_geometry(uint32_t out[2]);
+int  flx_coverage_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_coverage_options* o, const flx_record* records, uint64_t n,
+                       const uint32_t* cigar_words, uint64_t n_words, uint32_t* depth /* sum of ref_lens entries, added to */);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
