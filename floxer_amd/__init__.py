@@ -662,6 +662,25 @@ class resident_reads:
     __del__ = close
 
 
+_CLIMB_DTYPE = np.dtype([("read", np.uint32), ("orientation", np.uint32), ("leaf", np.uint32), ("ref", np.uint32), ("pos", np.uint64)])
+
+
+def climb_anchors(ctx, p, reads, anchors, host_rounds=False):
+    """the verification rounds alone (flx_climb_anchors, a test hook): anchors = rows (read, orientation, leaf, reference_id,
+    position) in (read, orientation) order on a resident_reads batch. Returns (status, node, requests): status[i] 0 dead / 1 at the
+    root, node[i] the inner node anchor i failed at or the root's index, requests the call's inner tests requested."""
+    arr = np.zeros(len(anchors), dtype=_CLIMB_DTYPE)
+    for i, f in enumerate(("read", "orientation", "leaf", "ref", "pos")):
+        arr[f] = [a[i] for a in anchors]
+    n = len(arr)
+    status, node = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32)
+    opt = capi.ClimbOptions(int(host_rounds))
+    requests = C.c_uint64(0)
+    check(lib().flx_climb_anchors(ctx.h, C.byref(p), reads.h, arr.ctypes.data_as(C.c_void_p), n, C.byref(opt), ptr(status, u8p), ptr(node, u32p),
+                                  C.byref(requests)))
+    return status[:n], node[:n], int(requests.value)
+
+
 _MD_DTYPE = np.dtype([("off", np.uint64), ("len", np.uint32), ("res", np.uint32)])
 
 

@@ -13,6 +13,7 @@
 #include <tuple>
 #include <vector>
 
+#include "flx_fm_core.hpp"
 #include "flx_mapq.hpp"
 #include "flx_partial.hpp"
 #include "flx_pipeline.hpp"
@@ -1116,3 +1117,92 @@ int align_slice(Lane* lane, const flx_params* P, RunOptions const& R, const flx_
 }
 
 }  // namespace flx
+
+// ---- the climb alone (flx_climb_anchors, include/floxer_amd.h): a test hook. plan_reads, the caller's anchors in place of
+//      anchors_to_reads, start_climb and one of the two drivers, as align_slice calls them; nothing of a run's path is changed for it.
+namespace {
+// the Peq planes and the 2-bit form of the batch's pool, as the first flx_align_reads_resident call on the batch builds them
+int climb_read_planes(flx_ctx* ctx, const flx_reads* RD) {
+    using namespace flx;
+    std::lock_guard<std::mutex> g(RD->peq_mu);
+    if (RD->peq_built || !RD->n_reads) return FLX_OK;
+    LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+    take_spare_read_buffer(ctx, 2, RD->d_peq);
+    take_spare_read_buffer(ctx, 1, RD->d_pack);
+    int const rc = build_peq(lease.lane, RD->d_pool.as<u8>(), RD->pool.size(), RD->d_peq);
+    if (rc) return rc;
+    if (ctx->didx.filter) {
+        int const rc2 = RD->d_pack.ensure(pack_words_for(RD->pool.size()) * 4 + 64);
+        if (rc2) return rc2;
+        int const e = DeviceApi::pack_pool(lease.lane->stream, RD->d_pool.as<u8>(), RD->pool.size(), RD->d_pack.as<u32>());
+        if (e) { set_error(std::string("pack_pool: ") + hipGetErrorString((hipError_t)e)); return FLX_ERR_NO_DEVICE; }
+    }
+    if (!RD->peq_event) FLX_HIP(hipEventCreateWithFlags(&RD->peq_event, hipEventDisableTiming));
+    FLX_HIP(hipEventRecord(RD->peq_event, lease.lane->stream));
+    RD->peq_built = true;
+    return FLX_OK;
+}
+}  // namespace
+
+extern "C" int flx_climb_anchors(flx_ctx* ctx, const flx_params* P, const flx_reads* RD, const flx_climb_anchor* anchors, uint64_t n_anchors,
+                                 const flx_climb_options* O, uint8_t* out_status, uint32_t* out_node, uint64_t* out_requests) {
+    using namespace flx;
+    if (!ctx || !P || !RD || RD->ctx != ctx || (n_anchors && (!anchors || !out_status || !out_node))) {
+        set_error("flx_climb_anchors: null argument or reads of another context"); return FLX_ERR_INVALID;
+    }
+    if (O && (O->driver > 1 || O->reserved[0] || O->reserved[1] || O->reserved[2])) { set_error("flx_climb_anchors: unknown driver, or reserved options set"); return FLX_ERR_INVALID; }
+    if (P->query_error_probability < 0 && P->query_num_errors < P->pex_seed_num_errors) { set_error("query errors must be >= seed errors (floxer_cli.cpp:180)"); return FLX_ERR_INVALID; }
+    if (P->pex_seed_num_errors > 3) { set_error("invalid parameters"); return FLX_ERR_INVALID; }
+    if (n_anchors >= (1ull << 31)) { set_error("flx_climb_anchors: too many anchors"); return FLX_ERR_INVALID; }
+    if (out_requests) *out_requests = 0;
+    FLX_HIP(hipSetDevice(ctx->device));
+    HostIndex const& H = *ctx->hidx;
+    Slice S;
+    flx_run run;
+    run.skipped.assign(RD->n_reads, 0);
+    int rc;
+    if ((rc = plan_reads(S, P, RD, 0, RD->n_reads, &run))) return rc;
+    hvec<u32> kept_of(RD->n_reads, 0xFFFFFFFFu);
+    for (size_t r = 0; r < S.reads.size(); ++r) kept_of[S.reads[r].read_index] = (u32)r;
+    S.A.reserve(n_anchors);
+    u64 prev_query = 0;
+    for (u64 i = 0; i < n_anchors; ++i) {
+        flx_climb_anchor const& in = anchors[i];
+        if (in.read >= RD->n_reads || in.orientation > 1 || kept_of[in.read] == 0xFFFFFFFFu) { set_error("flx_climb_anchors: an anchor of no read, of a read the input rules skip, or of no orientation"); return FLX_ERR_INVALID; }
+        u64 const query = 2ull * kept_of[in.read] + in.orientation;
+        if (query < prev_query) { set_error("flx_climb_anchors: anchors out of (read, orientation) order"); return FLX_ERR_INVALID; }
+        prev_query = query;
+        PexTree const& tree = S.reads[kept_of[in.read]].tree_ref();
+        if (in.leaf >= tree.leaves.size()) { set_error("flx_climb_anchors: a leaf outside the read's tree"); return FLX_ERR_INVALID; }
+        if (in.reference_id >= H.seq_len.size()) { set_error("flx_climb_anchors: a reference outside the index"); return FLX_ERR_INVALID; }
+        flx_pex_node const& leaf = tree.leaves[in.leaf];
+        u64 const rows = leaf.to - leaf.from + 1;
+        if (in.position >= H.seq_len[in.reference_id] || in.position + rows > H.seq_len[in.reference_id] + leaf.num_errors) {
+            set_error("flx_climb_anchors: a position whose leaf does not lie inside the reference sequence"); return FLX_ERR_INVALID;
+        }
+        AnchorState a{};
+        a.read = kept_of[in.read]; a.orientation = (u8)in.orientation; a.leaf = in.leaf; a.ref_id = in.reference_id; a.pos = in.position;
+        a.node = FLX_NULL_ID;
+        S.A.push_back(a);
+    }
+    if (n_anchors == 0) return FLX_OK;
+    if ((rc = climb_read_planes(ctx, RD))) return rc;
+    {
+        LaneLease lease(ctx, ctx->external_stream ? 0 : -1);
+        Lane* const lane = lease.lane;
+        FLX_HIP(hipStreamWaitEvent(lane->stream, RD->peq_event, 0));
+        u32 const n_climbing = start_climb(S, P);
+        ExistsTimes times;
+        if (O && O->driver == 1) rc = climb_on_host(S, lane, RD, times);
+        else rc = n_climbing ? climb_on_device(S, lane, RD) : FLX_OK;
+        if (rc) return rc;
+    }
+    for (u64 i = 0; i < n_anchors; ++i) {
+        AnchorState const& a = S.A[i];
+        if (a.alive && !a.at_root) { set_error("flx_climb_anchors: an anchor neither failed nor reached the root"); return FLX_ERR_INTERNAL; }
+        out_status[i] = a.alive ? 1 : 0;
+        out_node[i] = a.node;
+    }
+    if (out_requests) *out_requests = S.n_inner_requested;
+    return FLX_OK;
+}

@@ -750,6 +750,23 @@ typedef struct flx_search_counters {
 } flx_search_counters;
 int flx_ctx_get_search_counters(flx_ctx* ctx, flx_search_counters* out);
 
+/* The climb alone (a test hook for the kernels of the verification rounds, like flx_search_groups for K1): the reads' PEX trees as
+ * flx_align_reads_resident plans them, the caller's anchors instead of a search's, then the rounds; no search, no interval pass, no
+ * trace. anchors[i].read is the read's index in the batch; the anchors must come in (read, orientation) order, as a search leaves them.
+ * out_status[i]: 0 = dead, 1 = at the root; out_node[i]: the inner node the anchor failed at, or the root's index (0xFFFFFFFF when the
+ * anchor never had an inner node: direct_full_verification, or a tree of one node). Anchors enter alive and below the root; the states
+ * a run never hands to the rounds (already dead, already at the root with a node to test) cannot be given. Refused with FLX_ERR_INVALID
+ * before any launch: anchors out of order, a read that the input rules skip, a leaf outside the read's tree, a reference outside the
+ * index, a position whose leaf (less its errors) does not lie inside the reference sequence.
+ * options (NULL: all zero): driver 0 = the device rounds, 1 = the host rounds (per call; FLX_HOST_ROUNDS is not read).
+ * out_requests (may be NULL): the call's flx_path_counters.inner_tests_requested - the device rounds count an anchor that is tested
+ * alone again in its next round, the host rounds count every request once, so the difference of the two drivers on one input is the
+ * number of anchors the device sent on alone. The context's counters are not touched. */
+typedef struct flx_climb_anchor { uint32_t read, orientation, leaf, reference_id; uint64_t position; } flx_climb_anchor;
+typedef struct flx_climb_options { uint32_t driver, reserved[3]; } flx_climb_options;
+int flx_climb_anchors(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_climb_anchor* anchors, uint64_t n_anchors,
+                      const flx_climb_options* options, uint8_t* out_status, uint32_t* out_node, uint64_t* out_requests);
+
 /* ------------------------------------------------------------------------------------------------ statistics (--stats)
  * replaces statistics::search_and_alignment_statistics (include/statistics.hpp:24-172, src/lib/statistics.cpp): the reference's
  * count and eighteen histograms, same names, thresholds and renderings. input_hint: NULL / "real_nanopore" / "simulated"
