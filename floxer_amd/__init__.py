@@ -18,6 +18,7 @@ libfloxer_amd.so:
     aligner(..., realign=realign_options()), realign(), realign_batch(), align_batch_realign()  not floxer's: a traced path realigned under affine gap costs inside a band around it (opt-in)
     aligner(..., cs=cs_options()), cs_string(), cs_batch(), align_batch_cs()  not floxer's: minimap2's cs difference string, short or long form, built on the device behind the MD strings (opt-in)
     coverage(ctx, coverage_options()), coverage_host()  not floxer's: depth of coverage accumulated on the device from the records of runs: equal-depth runs, per-window sums (opt-in)
+    pileup(ctx, pileup_options()), pileup_host(), pileup_sites_host()  not floxer's: per-position allele counts (depth, mismatch letters, deletions, insertions) accumulated on the device from the records of runs, and the table of candidate variant sites (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -1149,3 +1150,119 @@ def coverage_host(lengths, records, cigar_words, options=None):
     check(lib().flx_coverage_host(ptr(lens, u64p), len(lens), C.byref(options) if options is not None else None,
                                   rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(depth, u32p)))
     return depth[: int(lens.sum())]
+
+
+def pileup_options(count_secondary=False, min_mapq=0, min_depth=0, min_count=0, min_permille=0):
+    """flx_pileup_options: count_secondary: flag-256 records count; min_mapq: a record counts only with at least this mapping quality
+    (needs runs made with output_options(mapq=True)); a position is a site when DEPTH + DEL >= min_depth, its largest plane among A, C,
+    G, T, DEL, INS >= min_count and that plane * 1000 >= min_permille * (DEPTH + DEL); 0 takes the defaults 4, 2 and 200, conventions of
+    this project that are fitted to nothing"""
+    o = capi.PileupOptions()
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq = int(min_mapq)
+    o.min_depth, o.min_count, o.min_permille = int(min_depth), int(min_count), int(min_permille)
+    return o
+
+
+SITE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<u4"), ("depth", "<u4"), ("del", "<u4"), ("ins", "<u4"), ("alt", "<u4", (4,)), ("res", "<u4")])
+PILEUP_PLANES = ("DEPTH", "DEL", "A", "C", "G", "T", "INS")
+
+
+class pileup:
+    """Allele pileup over the sequences of a context's index (ctx) or over `lengths` on `device`: per position the depth, the read letter
+    of every mismatch column, the deletions and the insertions of the records added; absorb the objects of other devices, finish once,
+    then read sites() and counts(ref, a, b). Not floxer's, and no variant caller: exact counts. Adds may come from several threads."""
+
+    def __init__(self, ctx=None, options=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_pileup_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if lengths is None:
+                raise FloxerError("pileup needs a context or a list of reference lengths")
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+            check(lib().flx_pileup_create_for_lengths(int(device), ptr(lens, u64p), len(lens), opt, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_pileup_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run, reads):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed;
+        reads: the batch the run was made from: a list of rank arrays, (pool, offsets), or a resident_reads batch (with a raw handle only:
+        its letters are read in HBM). With min_mapq a run made without output_options(mapq=True) is refused."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("pileup.add: min_mapq needs a run made with output_options(mapq=True)")
+            if isinstance(reads, resident_reads):
+                raise FloxerError("pileup.add: a RunResult needs the reads in host memory; a resident batch goes with a raw run handle")
+            return self.add_records(run.raw, run.cigars, reads)
+        if isinstance(reads, resident_reads):
+            check(lib().flx_pileup_add_run_resident(self.h, run, reads.h))
+        else:
+            pool, offs, n = _pool_and_offsets(reads)
+            check(lib().flx_pileup_add_run(self.h, run, ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def add_records(self, records, cigar_words, reads):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        reads: a list of rank arrays or (pool, offsets), indexed by the records' `read`"""
+        rec, words = _records_and_words(records, cigar_words)
+        pool, offs, n = _pool_and_offsets(reads)
+        check(lib().flx_pileup_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words),
+                                           ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def absorb(self, other):
+        check(lib().flx_pileup_absorb(self.h, other.h))
+
+    def finish(self):
+        check(lib().flx_pileup_finish(self.h))
+
+    def sites(self):
+        n = lib().flx_pileup_num_sites(self.h)
+        out = np.zeros(max(1, n), dtype=SITE_DTYPE)
+        check(lib().flx_pileup_copy_sites(self.h, out.ctypes.data_as(C.POINTER(capi.PileupSite)), n))
+        return out[:n]
+
+    def counts(self, ref, a, b):
+        """the seven planes of [a, b) of sequence ref: a (7, b - a) uint32 array in the order of PILEUP_PLANES"""
+        w = max(0, int(b) - int(a))
+        out = np.zeros(7 * max(1, w), dtype=np.uint32)
+        check(lib().flx_pileup_copy_counts(self.h, int(ref), int(a), int(b), ptr(out, u32p)))
+        return out[: 7 * w].reshape(7, w)
+
+
+def pileup_host(lengths, records, cigar_words, reads, options=None, counts=None):
+    """the rule alone on the host (flx_pileup_host): a (7, total) uint32 array over the concatenated sequences in the order of
+    PILEUP_PLANES; counts: such an array that is added to"""
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+    rec, words = _records_and_words(records, cigar_words)
+    pool, offs, n = _pool_and_offsets(reads)
+    total = int(lens.sum())
+    out = np.zeros((7, max(1, total)), dtype=np.uint32) if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    check(lib().flx_pileup_host(ptr(lens, u64p), len(lens), C.byref(options) if options is not None else None,
+                                rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(pool, u8p), ptr(offs, u64p), n,
+                                ptr(out, u32p)))
+    return out[:, :total] if counts is None else out
+
+
+def pileup_sites_host(lengths, counts, options=None):
+    """the site rule alone on the host (flx_pileup_sites_host) over a (7, total) count array: a structured array of SITE_DTYPE"""
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    opt = C.byref(options) if options is not None else None
+    n = C.c_uint64(0)
+    rc = lib().flx_pileup_sites_host(ptr(lens, u64p), len(lens), opt, ptr(cnt, u32p), None, C.byref(n))
+    if rc not in (0, -3):                                               # (FLX_ERR_CAPACITY: n holds the need)
+        check(rc)
+    out = np.zeros(max(1, n.value), dtype=SITE_DTYPE)
+    check(lib().flx_pileup_sites_host(ptr(lens, u64p), len(lens), opt, ptr(cnt, u32p), out.ctypes.data_as(C.POINTER(capi.PileupSite)), C.byref(n)))
+    return out[: n.value]

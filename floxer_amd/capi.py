@@ -155,6 +155,16 @@ class DepthWindow(C.Structure):
                 ("covered", C.c_uint64)]
 
 
+class PileupOptions(C.Structure):
+    _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("min_depth", C.c_uint32), ("min_count", C.c_uint32),
+                ("min_permille", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class PileupSite(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("depth", C.c_uint32), ("del_", C.c_uint32), ("ins", C.c_uint32),
+                ("alt", C.c_uint32 * 4), ("reserved", C.c_uint32)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -233,6 +243,9 @@ EXPORTED = [
     "flx_coverage_create", "flx_coverage_create_for_lengths", "flx_coverage_free", "flx_coverage_add_run", "flx_coverage_add_records",
     "flx_coverage_absorb", "flx_coverage_finish", "flx_coverage_num_runs", "flx_coverage_copy_runs", "flx_coverage_num_windows",
     "flx_coverage_copy_windows", "flx_coverage_copy_depth", "flx_coverage_geometry", "flx_coverage_host",
+    "flx_pileup_create", "flx_pileup_create_for_lengths", "flx_pileup_free", "flx_pileup_add_records", "flx_pileup_add_run",
+    "flx_pileup_add_run_resident", "flx_pileup_absorb", "flx_pileup_finish", "flx_pileup_num_sites", "flx_pileup_copy_sites",
+    "flx_pileup_copy_counts", "flx_pileup_host", "flx_pileup_sites_host",
 ]
 
 _lib = None
@@ -376,6 +389,21 @@ def lib():
     L.flx_coverage_copy_depth.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
     L.flx_coverage_geometry.argtypes = [u32p]
     L.flx_coverage_host.argtypes = [u64p, C.c_uint32, C.POINTER(CoverageOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u32p]
+    L.flx_pileup_create.argtypes = [C.c_void_p, C.POINTER(PileupOptions), C.POINTER(C.c_void_p)]
+    L.flx_pileup_create_for_lengths.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(PileupOptions), C.POINTER(C.c_void_p)]
+    L.flx_pileup_free.restype = None
+    L.flx_pileup_free.argtypes = [C.c_void_p]
+    L.flx_pileup_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64]
+    L.flx_pileup_add_run.argtypes = [C.c_void_p, C.c_void_p, u8p, u64p, C.c_uint64]
+    L.flx_pileup_add_run_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flx_pileup_absorb.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_pileup_finish.argtypes = [C.c_void_p]
+    L.flx_pileup_num_sites.restype = C.c_uint64
+    L.flx_pileup_num_sites.argtypes = [C.c_void_p]
+    L.flx_pileup_copy_sites.argtypes = [C.c_void_p, C.POINTER(PileupSite), C.c_uint64]
+    L.flx_pileup_copy_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
+    L.flx_pileup_host.argtypes = [u64p, C.c_uint32, C.POINTER(PileupOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64, u32p]
+    L.flx_pileup_sites_host.argtypes = [u64p, C.c_uint32, C.POINTER(PileupOptions), u32p, C.POINTER(PileupSite), u64p]
     L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]

@@ -80,6 +80,9 @@ struct Options {
     uint64_t coverage_window = 0, coverage_min_mapq = 0;
     bool coverage_deletions = false, coverage_secondary = false, coverage_zero = false;
     bool wants_coverage() const { return !coverage.empty() || !coverage_summary.empty() || !coverage_windows.empty(); }
+    std::string pileup;                                           // output file of the variant-site table; empty: not written
+    uint64_t pileup_min_depth = 0, pileup_min_count = 0, pileup_min_permille = 0, pileup_min_mapq = 0;      // 0: the library's defaults
+    bool pileup_secondary = false;
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -135,6 +138,13 @@ const OptDef OPTS[] = {
     {0, "coverage-secondary", true, "not floxer's: secondary records (flag 256) count too; needs one of the coverage outputs"},
     {0, "coverage-zero", true, "not floxer's: --coverage lists the stretches of depth 0 as well; needs one of the coverage outputs"},
     {0, "coverage-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and one of the coverage outputs"},
+    // nor these: per-position allele counts and the table of candidate variant sites, accumulated on the GPU (flx_pileup, flx_pileup.hpp)
+    {0, "pileup", false, "not floxer's: candidate variant sites, one line each (name, position, reference letter, depth, A, C, G, T, del, ins; the position is 1-based, as mpileup and VCF have it; <file.tsv>); exact counts, no variant calls; not with -w"},
+    {0, "pileup-min-depth", false, "not floxer's: a site needs at least this many records over it, deletions included (default 4, a convention fitted to nothing); needs --pileup"},
+    {0, "pileup-min-count", false, "not floxer's: a site needs at least this many records for its largest of A, C, G, T, del, ins (default 2, a convention fitted to nothing); needs --pileup"},
+    {0, "pileup-min-fraction", false, "not floxer's: and that count must be at least this fraction of the records over it, in (0, 1] (default 0.2, a convention fitted to nothing); needs --pileup"},
+    {0, "pileup-secondary", true, "not floxer's: secondary records (flag 256) count too; needs --pileup"},
+    {0, "pileup-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and --pileup"},
 };
 
 struct CliError { std::string msg; };
@@ -260,6 +270,16 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "coverage-secondary") o.coverage_secondary = true;
         else if (n == "coverage-zero") o.coverage_zero = true;
         else if (n == "coverage-min-mapq") { o.coverage_min_mapq = parse_u64(n, value); range_check(n, (double)o.coverage_min_mapq, 1, 254); }
+        else if (n == "pileup") o.pileup = value;
+        else if (n == "pileup-min-depth") { o.pileup_min_depth = parse_u64(n, value); range_check(n, (double)o.pileup_min_depth, 1, 4294967295.0); }
+        else if (n == "pileup-min-count") { o.pileup_min_count = parse_u64(n, value); range_check(n, (double)o.pileup_min_count, 1, 4294967295.0); }
+        else if (n == "pileup-min-fraction") {
+            double const f = parse_double(n, value);
+            if (!(f > 0.0 && f <= 1.0)) throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not in (0, 1]."};
+            o.pileup_min_permille = std::max<uint64_t>(1, flx_floating_point_error_aware_ceil(f * 1000.0));
+        }
+        else if (n == "pileup-secondary") o.pileup_secondary = true;
+        else if (n == "pileup-min-mapq") { o.pileup_min_mapq = parse_u64(n, value); range_check(n, (double)o.pileup_min_mapq, 1, 254); }
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
             if (value != "real_nanopore" && value != "simulated") throw CliError{"Validation failed for option --" + n + ": Value " + value + " is not one of [real_nanopore,simulated]."};
@@ -314,6 +334,11 @@ Options parse_cli(int argc, char** argv) {
     if (!o.coverage.empty() && !has_ext(o.coverage, {"bedgraph"}, false)) throw CliError{"Validation failed for option --coverage: Expected one of the following valid extensions: [bedgraph]."};
     if (!o.coverage_summary.empty() && !has_ext(o.coverage_summary, {"tsv"}, false)) throw CliError{"Validation failed for option --coverage-summary: Expected one of the following valid extensions: [tsv]."};
     if (!o.coverage_windows.empty() && !has_ext(o.coverage_windows, {"tsv"}, false)) throw CliError{"Validation failed for option --coverage-windows: Expected one of the following valid extensions: [tsv]."};
+    if (!o.pileup.empty() && o.without_cigar) throw CliError{"The option --pileup needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.pileup.empty() && (o.pileup_min_depth || o.pileup_min_count || o.pileup_min_permille || o.pileup_secondary || o.pileup_min_mapq))
+        throw CliError{"The options --pileup-min-depth, --pileup-min-count, --pileup-min-fraction, --pileup-secondary and --pileup-min-mapq need --pileup."};
+    if (o.pileup_min_mapq && !o.mapping_quality) throw CliError{"The option --pileup-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
+    if (!o.pileup.empty() && !has_ext(o.pileup, {"tsv"}, false)) throw CliError{"Validation failed for option --pileup: Expected one of the following valid extensions: [tsv]."};
     return o;
 }
 
@@ -654,6 +679,28 @@ bool write_coverage(Options const& o, std::vector<flx_coverage*> const& covs, st
     return ok;
 }
 
+// the variant-site table: every device's accumulator summed into the first, finished there, and its sites written as text with the
+// reference letter from the sequences read here (ranks 1..4 are ACGT, anything else N) and the position 1-based
+bool write_pileup(Options const& o, std::vector<flx_pileup*> const& piles, Reference const& ref) {
+    for (size_t i = 1; i < piles.size(); ++i)
+        if (flx_pileup_absorb(piles[0], piles[i]) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    flx_pileup* const pile = piles[0];
+    if (flx_pileup_finish(pile) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    std::vector<flx_pileup_site> sites(flx_pileup_num_sites(pile));
+    if (flx_pileup_copy_sites(pile, sites.data(), sites.size()) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    std::vector<uint64_t> starts(ref.lens.size() + 1, 0);
+    for (size_t r = 0; r < ref.lens.size(); ++r) starts[r + 1] = starts[r] + ref.lens[r];
+    FILE* f = fopen(o.pileup.c_str(), "w");
+    if (!f) { log_line("error", "cannot open output file: %s", o.pileup.c_str()); return false; }
+    for (auto const& s : sites) {
+        uint8_t const rank = ref.pool[starts[(size_t)s.reference_id] + s.position];
+        fprintf(f, "%s\t%llu\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", ref.ids[(size_t)s.reference_id].c_str(), (unsigned long long)s.position + 1,
+                rank >= 1 && rank <= 4 ? "ACGT"[rank - 1] : 'N', s.depth, s.alt[0], s.alt[1], s.alt[2], s.alt[3], s.del, s.ins);
+    }
+    if (fclose(f) != 0) { log_line("error", "write error on the pileup output"); return false; }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -733,6 +780,21 @@ int main(int argc, char** argv) {
             flx_coverage* cov = nullptr;
             if (flx_coverage_create(c, &cov_opt, &cov) != FLX_OK) { log_line("error", "cannot set up the coverage accumulator: %s", flx_last_error()); return -1; }
             covs.push_back(cov);
+        }
+    // the allele pileup: one accumulator per device too, fed with every batch's run and its own host reads
+    flx_pileup_options pile_opt;
+    memset(&pile_opt, 0, sizeof(pile_opt));
+    pile_opt.count_secondary = o.pileup_secondary;
+    pile_opt.min_mapq = (uint32_t)o.pileup_min_mapq;
+    pile_opt.min_depth = (uint32_t)o.pileup_min_depth;
+    pile_opt.min_count = (uint32_t)o.pileup_min_count;
+    pile_opt.min_permille = (uint32_t)o.pileup_min_permille;
+    std::vector<flx_pileup*> piles;
+    if (!o.pileup.empty())
+        for (flx_ctx* c : ctxs) {
+            flx_pileup* pile = nullptr;
+            if (flx_pileup_create(c, &pile_opt, &pile) != FLX_OK) { log_line("error", "cannot set up the pileup accumulator: %s", flx_last_error()); return -1; }
+            piles.push_back(pile);
         }
 
     std::vector<const char*> ref_id_ptrs;
@@ -842,6 +904,11 @@ int main(int argc, char** argv) {
             f.rc = flx_coverage_add_run(covs[at], run);
             if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
         }
+        if (!piles.empty()) {
+            size_t const at = std::find(ctxs.begin(), ctxs.end(), ctx) - ctxs.begin();
+            f.rc = flx_pileup_add_run(piles[at], run, b->pool.data(), b->offsets.data(), b->ids.size());
+            if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
+        }
         f.recs.resize(flx_run_num_records(run));
         f.cig.resize(flx_run_num_cigar_words(run) + 1);
         f.skipped.resize(b->ids.size());
@@ -949,6 +1016,8 @@ int main(int argc, char** argv) {
     double const secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_align).count();
     if (!covs.empty() && !failed.load() && !timed_out && !write_coverage(o, covs, ref.ids)) failed.store(true);
     for (flx_coverage* c : covs) flx_coverage_free(c);
+    if (!piles.empty() && !failed.load() && !timed_out && !write_pileup(o, piles, ref)) failed.store(true);
+    for (flx_pileup* c : piles) flx_pileup_free(c);
     for (flx_ctx* c : ctxs) flx_ctx_destroy(c);
     flx_index_free(index);
     if (failed.load() || timed_out) return -1;

@@ -705,6 +705,71 @@ int  flx_coverage_geometry(uint32_t out[2]);
 int  flx_coverage_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_coverage_options* o, const flx_record* records, uint64_t n,
                        const uint32_t* cigar_words, uint64_t n_words, uint32_t* depth /* sum of ref_lens entries, added to */);
 
+/* ------------------------------------------------------------------------------------------------ allele pileup and variant sites
+ * Not floxer's, and coverage's successor: where does the sample differ from the reference, and how many reads say so? A pileup object
+ * belongs to a list of reference lengths (the limits of the coverage object: coverage_lengths_valid) and holds seven u32 counts per
+ * reference position in HBM, indexed by position in the unpadded concatenation of the sequences in reference-id order, as planes in this
+ * fixed order: DEPTH = 0, DEL = 1, A = 2, C = 3, G = 4, T = 5, INS = 6. That is 7 x 4 bytes per reference symbol plus the tile arrays:
+ * about 87 GB at GRCh38 size, next to 43 GB of index. Nobody has run it at that size. It is no variant caller: no genotype, no quality
+ * model, no base qualities; it is the exact integer counts a caller starts from. The rule (floxer_amd/csrc/flx_pileup.hpp):
+ *   - which records count: exactly coverage's filter. flag & 4 never; flag & 256 only with count_secondary; 2048 always; with
+ *     min_mapq > 0 only if flx_record.reserved >= min_mapq;
+ *   - the walk starts at `position` with query row 0 of the record's oriented sequence: the read as given for flag bit 16 clear, its
+ *     reverse complement for bit 16 set, as SEQ is written. Over the CIGAR words, left to right:
+ *       =  of length L: DEPTH + 1 on its L columns; both cursors advance;
+ *       X  of length L: DEPTH + 1 on its L columns, and for each column the oriented read's rank r at that row decides: r in 1..4 adds 1
+ *          to plane A + r - 1 at that position, r = 0 or 5 (N) counts in DEPTH only. Nothing is compared with the reference, whose text is
+ *          never read: an X over equal ranks is counted under the read's letter as it stands, as cs does;
+ *       D  of length L: DEL + 1 on its L columns; the reference cursor advances;
+ *       I  of length L: INS + 1 at one anchor position, the reference position of the record's preceding reference-consuming column (a
+ *          column of =, X or D), or the record's first reference-consuming column when none precedes this word; the query cursor
+ *          advances; one insertion is one event whatever its length;
+ *       S: the query cursor advances, nothing is counted;
+ *   - refused (FLX_ERR_INVALID, on the host before any launch; the accumulator stays as it was): all that the coverage calls refuse (a
+ *     counted record without CIGAR words, an op other than = X I D S, a zero-length word, a reference_id outside the list, a negative
+ *     position, a span that ends behind its sequence, words outside the pool), a read_index outside the reads given, a record whose
+ *     query-consuming lengths (= X I S) do not sum to exactly its read's length, a record with no reference-consuming column;
+ *   - sites, computed after the DEPTH and DEL differences have been summed: cov = DEPTH + DEL (64-bit), best = max(A, C, G, T, DEL, INS);
+ *     position p is a site iff cov >= min_depth, best >= min_count and best * 1000 >= min_permille * cov in 64-bit integers. 0 takes the
+ *     defaults min_depth 4, min_count 2, min_permille 200: conventions of this project, fitted to nothing. min_permille above 1000 is
+ *     refused. Sites come in position order: reference id ascending, then position ascending.
+ * The contracts mirror coverage's one for one. options NULL: all zero; reserved fields must be 0. A failed allocation returns
+ * FLX_ERR_NO_DEVICE and leaves nothing behind. Reads are given as flx_align_reads takes them: one rank pool, read i =
+ * pool[offsets[i], offsets[i+1]), and flx_record.read_index names one of them. Adds may come from several host threads at once; only the
+ * reads that counted records refer to go up, once per orientation used. flx_pileup_add_run walks a run and its parts and judges
+ * everything before adding anything; it needs min_mapq == 0 or a run made with flx_output_options.mapq, and refuses a run made with
+ * without_cigar. flx_pileup_add_run_resident reads the letters straight from the batch's device pool (the forward sequence and its
+ * reverse complement behind it) when the batch lives on the object's device; otherwise the batch's host copy goes through the staged
+ * path. flx_pileup_absorb: into += from, `from` is left cleared; equal lengths and options, both unfinished; the two may live on
+ * different devices. flx_pileup_finish is final: a later add, absorb or finish is FLX_ERR_INVALID, and the copy calls work only behind it.
+ * flx_pileup_copy_sites: FLX_ERR_CAPACITY when capacity is below flx_pileup_num_sites. flx_pileup_copy_counts (a test hook): the seven
+ * planes of [from, to) of one sequence. Everything is integer: nothing depends on the order of adds, host threads or devices.
+ * flx_pileup_host: the rule alone on the host, no device: counts (7 * sum of ref_lens entries, plane-major) is added to; the same
+ * refusals, and counts is untouched when it refuses. flx_pileup_sites_host: the site rule over such counts; *n_sites holds the capacity
+ * of `out` on entry and the number of sites on return (FLX_ERR_CAPACITY when that is more; `out` may be NULL with capacity 0).
+ * FLX_PILEUP_PROFILE (environment): every add prints its records, words, uploaded bytes, pileup_add's device time and its wall time to
+ * stderr. */
+typedef struct flx_pileup flx_pileup;
+typedef struct flx_pileup_options { uint32_t count_secondary, min_mapq, min_depth, min_count, min_permille; uint32_t reserved[3]; } flx_pileup_options;
+typedef struct flx_pileup_site { int32_t reference_id; uint32_t position; uint32_t depth, del, ins; uint32_t alt[4]; uint32_t reserved; } flx_pileup_site;   /* position 0-based; alt: A, C, G, T */
+int  flx_pileup_create(flx_ctx* ctx, const flx_pileup_options* o, flx_pileup** out);
+int  flx_pileup_create_for_lengths(int hip_device, const uint64_t* ref_lens, uint32_t n_refs, const flx_pileup_options* o, flx_pileup** out);
+void flx_pileup_free(flx_pileup* p);
+int  flx_pileup_add_records(flx_pileup* p, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                            const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_pileup_add_run(flx_pileup* p, const flx_run* run, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_pileup_add_run_resident(flx_pileup* p, const flx_run* run, const flx_reads* reads);
+int  flx_pileup_absorb(flx_pileup* into, flx_pileup* from);
+int  flx_pileup_finish(flx_pileup* p);
+uint64_t flx_pileup_num_sites(const flx_pileup* p);
+int  flx_pileup_copy_sites(const flx_pileup* p, flx_pileup_site* out, uint64_t capacity);
+int  flx_pileup_copy_counts(const flx_pileup* p, uint32_t reference_id, uint64_t from, uint64_t to, uint32_t* out /* 7 * (to - from), plane-major */);
+int  flx_pileup_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_pileup_options* o, const flx_record* records, uint64_t n,
+                     const uint32_t* cigar_words, uint64_t n_words, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads,
+                     uint32_t* counts /* 7 * total, plane-major, added to */);
+int  flx_pileup_sites_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_pileup_options* o, const uint32_t* counts,
+                           flx_pileup_site* out, uint64_t* n_sites /* in: capacity, out: needed */);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
