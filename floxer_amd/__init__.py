@@ -19,6 +19,7 @@ libfloxer_amd.so:
     aligner(..., cs=cs_options()), cs_string(), cs_batch(), align_batch_cs()  not floxer's: minimap2's cs difference string, short or long form, built on the device behind the MD strings (opt-in)
     coverage(ctx, coverage_options()), coverage_host()  not floxer's: depth of coverage accumulated on the device from the records of runs: equal-depth runs, per-window sums (opt-in)
     pileup(ctx, pileup_options()), pileup_host(), pileup_sites_host()  not floxer's: per-position allele counts (depth, mismatch letters, deletions, insertions) accumulated on the device from the records of runs, and the table of candidate variant sites (opt-in)
+    record_sorter(n_refs), sort_host(), sort_geometry()  not floxer's: the coordinate order of records (reference, position, strand, then the caller's ordinal), sorted on the device by a radix sort over 128-bit keys (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
 """
@@ -1266,3 +1267,87 @@ def pileup_sites_host(lengths, counts, options=None):
     out = np.zeros(max(1, n.value), dtype=SITE_DTYPE)
     check(lib().flx_pileup_sites_host(ptr(lens, u64p), len(lens), opt, ptr(cnt, u32p), out.ctypes.data_as(C.POINTER(capi.PileupSite)), C.byref(n)))
     return out[: n.value]
+
+
+# ------------------------------------------------------------------------------------------------ coordinate order of records
+SORT_ENTRY_DTYPE = np.dtype([("ordinal", "<u8"), ("ref", "<i4"), ("pos", "<i4"), ("end", "<u4"), ("flag", "<u4")])
+
+
+def sort_options(initial_capacity=0, tile_keys=0):
+    """flx_sort_options, both test hooks (0: the default): initial_capacity: the records the key table holds before it first grows;
+    tile_keys: the keys one block orders per pass, a multiple of the block's threads"""
+    o = capi.SortOptions()
+    o.initial_capacity = int(initial_capacity)
+    o.tile_keys = int(tile_keys)
+    return o
+
+
+def sort_geometry():
+    """(default keys per tile, bits per digit, default initial capacity, entries per tile of the digit table's scan): a test hook"""
+    g = np.zeros(4, dtype=np.uint32)
+    check(lib().flx_sort_geometry(ptr(g, u32p)))
+    return tuple(int(x) for x in g)
+
+
+class record_sorter:
+    """The coordinate order of the records of runs: add records (record i of an add has ordinal first_ordinal + i), finish once, then
+    read entries(a, b). Not floxer's. device=-1 opens no device and orders on the host (for machines without a GPU). Adds may come from
+    several threads at once."""
+
+    def __init__(self, n_refs, device=0, options=None):
+        self.h = C.c_void_p()
+        check(lib().flx_sort_create(int(device), int(n_refs), C.byref(options) if options is not None else None, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_sort_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(lib().flx_sort_num_records(self.h))
+
+    def add_records(self, records, cigar_words, first_ordinal, want_order=True):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to.
+        Returns the add's own records in key order, as indices into `records` (None with want_order=False)."""
+        rec, words = _records_and_words(records, cigar_words)
+        order = np.zeros(max(1, len(rec)), dtype=np.uint32) if want_order else None
+        check(lib().flx_sort_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), int(first_ordinal),
+                                         ptr(order, u32p) if want_order else None))
+        return order[: len(rec)] if want_order else None
+
+    def add(self, run, first_ordinal, want_order=True):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed"""
+        if isinstance(run, RunResult):
+            return self.add_records(run.raw, run.cigars, first_ordinal, want_order)
+        n = int(lib().flx_run_num_records(run))
+        order = np.zeros(max(1, n), dtype=np.uint32) if want_order else None
+        check(lib().flx_sort_add_run(self.h, run, int(first_ordinal), ptr(order, u32p) if want_order else None))
+        return order[:n] if want_order else None
+
+    def finish(self):
+        check(lib().flx_sort_finish(self.h))
+
+    def entries(self, a=0, b=None):
+        """the sorted entries [a, b) behind finish: a structured array of SORT_ENTRY_DTYPE (an unplaced record's ref is -1)"""
+        b = len(self) if b is None else int(b)
+        out = np.zeros(max(1, b - int(a)), dtype=SORT_ENTRY_DTYPE)
+        check(lib().flx_sort_copy(self.h, int(a), b, out.ctypes.data_as(C.POINTER(capi.SortEntry))))
+        return out[: max(0, b - int(a))]
+
+
+def sort_host(n_refs, records, cigar_words, ordinals):
+    """the rule alone on the host (flx_sort_host): record i has ordinal ordinals[i]; the entries in key order"""
+    rec, words = _records_and_words(records, cigar_words)
+    ords = np.ascontiguousarray(np.asarray(ordinals, dtype=np.uint64))
+    if len(ords) != len(rec):
+        raise FloxerError("sort_host: one ordinal per record")
+    out = np.zeros(max(1, len(rec)), dtype=SORT_ENTRY_DTYPE)
+    check(lib().flx_sort_host(int(n_refs), rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(ords, u64p),
+                              out.ctypes.data_as(C.POINTER(capi.SortEntry))))
+    return out[: len(rec)]

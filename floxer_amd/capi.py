@@ -165,6 +165,14 @@ class PileupSite(C.Structure):
                 ("alt", C.c_uint32 * 4), ("reserved", C.c_uint32)]
 
 
+class SortOptions(C.Structure):
+    _fields_ = [("initial_capacity", C.c_uint64), ("tile_keys", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class SortEntry(C.Structure):
+    _fields_ = [("ordinal", C.c_uint64), ("reference_id", C.c_int32), ("position", C.c_int32), ("end", C.c_uint32), ("flag", C.c_uint32)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -246,6 +254,8 @@ EXPORTED = [
     "flx_pileup_create", "flx_pileup_create_for_lengths", "flx_pileup_free", "flx_pileup_add_records", "flx_pileup_add_run",
     "flx_pileup_add_run_resident", "flx_pileup_absorb", "flx_pileup_finish", "flx_pileup_num_sites", "flx_pileup_copy_sites",
     "flx_pileup_copy_counts", "flx_pileup_host", "flx_pileup_sites_host",
+    "flx_sort_create", "flx_sort_free", "flx_sort_add_records", "flx_sort_add_run", "flx_sort_finish", "flx_sort_num_records", "flx_sort_copy",
+    "flx_sort_geometry", "flx_sort_host", "flx_sam_open_sorted",
 ]
 
 _lib = None
@@ -389,6 +399,17 @@ def lib():
     L.flx_coverage_copy_depth.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
     L.flx_coverage_geometry.argtypes = [u32p]
     L.flx_coverage_host.argtypes = [u64p, C.c_uint32, C.POINTER(CoverageOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u32p]
+    L.flx_sort_create.argtypes = [C.c_int, C.c_uint32, C.POINTER(SortOptions), C.POINTER(C.c_void_p)]
+    L.flx_sort_free.restype = None
+    L.flx_sort_free.argtypes = [C.c_void_p]
+    L.flx_sort_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, C.c_uint64, u32p]
+    L.flx_sort_add_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u32p]
+    L.flx_sort_finish.argtypes = [C.c_void_p]
+    L.flx_sort_num_records.restype = C.c_uint64
+    L.flx_sort_num_records.argtypes = [C.c_void_p]
+    L.flx_sort_copy.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SortEntry)]
+    L.flx_sort_geometry.argtypes = [u32p]
+    L.flx_sort_host.argtypes = [C.c_uint32, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.POINTER(SortEntry)]
     L.flx_pileup_create.argtypes = [C.c_void_p, C.POINTER(PileupOptions), C.POINTER(C.c_void_p)]
     L.flx_pileup_create_for_lengths.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(PileupOptions), C.POINTER(C.c_void_p)]
     L.flx_pileup_free.restype = None
@@ -431,6 +452,7 @@ def lib():
     L.flx_sam_open.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.flx_sam_write.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), u8p, u64p, C.POINTER(C.c_char_p), C.POINTER(Record), C.c_uint64, u32p]
     L.flx_sam_close.argtypes = [C.c_void_p]
+    L.flx_sam_open_sorted.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.flx_stats_create.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
     L.flx_stats_free.argtypes = [C.c_void_p]
     L.flx_stats_merge.argtypes = [C.c_void_p, C.c_void_p]

@@ -83,6 +83,8 @@ struct Options {
     std::string pileup;                                           // output file of the variant-site table; empty: not written
     uint64_t pileup_min_depth = 0, pileup_min_count = 0, pileup_min_permille = 0, pileup_min_mapq = 0;      // 0: the library's defaults
     bool pileup_secondary = false;
+    bool sort_by_coordinate = false, bam_index = false;           // a coordinate-sorted BAM (flx_sam_open_sorted) and its BAI index
+    std::string sort_tmp;                                         // the spill file's directory; empty: the output's
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -145,6 +147,10 @@ const OptDef OPTS[] = {
     {0, "pileup-min-fraction", false, "not floxer's: and that count must be at least this fraction of the records over it, in (0, 1] (default 0.2, a convention fitted to nothing); needs --pileup"},
     {0, "pileup-secondary", true, "not floxer's: secondary records (flag 256) count too; needs --pileup"},
     {0, "pileup-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and --pileup"},
+    // nor these: the output in coordinate order, its keys sorted on the GPU (flx_sort, flx_sort.hpp), and its BAI index
+    {0, "sort-by-coordinate", true, "not floxer's: write the records in coordinate order (reference, position, strand; unmapped last) with @HD SO:coordinate; needs a .bam output"},
+    {0, "bam-index", true, "not floxer's: write the BAI index <output>.bai as well; needs --sort-by-coordinate"},
+    {0, "sort-tmp", false, "not floxer's: the directory of the sort's spill file (default: the output's directory); needs --sort-by-coordinate"},
 };
 
 struct CliError { std::string msg; };
@@ -279,6 +285,9 @@ Options parse_cli(int argc, char** argv) {
             o.pileup_min_permille = std::max<uint64_t>(1, flx_floating_point_error_aware_ceil(f * 1000.0));
         }
         else if (n == "pileup-secondary") o.pileup_secondary = true;
+        else if (n == "sort-by-coordinate") o.sort_by_coordinate = true;
+        else if (n == "bam-index") o.bam_index = true;
+        else if (n == "sort-tmp") { o.sort_tmp = value; if (value.empty()) throw CliError{"Validation failed for option --" + n + ": the directory's name is empty."}; }
         else if (n == "pileup-min-mapq") { o.pileup_min_mapq = parse_u64(n, value); range_check(n, (double)o.pileup_min_mapq, 1, 254); }
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
@@ -339,6 +348,8 @@ Options parse_cli(int argc, char** argv) {
         throw CliError{"The options --pileup-min-depth, --pileup-min-count, --pileup-min-fraction, --pileup-secondary and --pileup-min-mapq need --pileup."};
     if (o.pileup_min_mapq && !o.mapping_quality) throw CliError{"The option --pileup-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
     if (!o.pileup.empty() && !has_ext(o.pileup, {"tsv"}, false)) throw CliError{"Validation failed for option --pileup: Expected one of the following valid extensions: [tsv]."};
+    if (!o.sort_by_coordinate && (o.bam_index || !o.sort_tmp.empty())) throw CliError{"The options --bam-index and --sort-tmp need --sort-by-coordinate."};
+    if (o.sort_by_coordinate && !has_ext(o.output, {"bam"}, false)) throw CliError{"The option --sort-by-coordinate writes BAM and needs an -o/--output that ends in .bam."};
     return o;
 }
 
@@ -800,7 +811,13 @@ int main(int argc, char** argv) {
     std::vector<const char*> ref_id_ptrs;
     for (auto const& s : ref.ids) ref_id_ptrs.push_back(s.c_str());
     flx_sam_writer* out = nullptr;
-    if (flx_sam_open(o.output.c_str(), ref_id_ptrs.data(), ref.lens.data(), (uint32_t)ref.ids.size(), &out) != FLX_OK) { log_line("error", "%s", flx_last_error()); return -1; }
+    if (o.sort_by_coordinate) {
+        // the keys are sorted on the first device; the spill file is <dir>/<output's name>.sort.<pid>.tmp
+        size_t const slash = o.output.find_last_of('/');
+        std::string const dir = !o.sort_tmp.empty() ? o.sort_tmp : slash == std::string::npos ? std::string(".") : slash == 0 ? std::string("/") : o.output.substr(0, slash);
+        std::string const spill = dir + "/" + (slash == std::string::npos ? o.output : o.output.substr(slash + 1)) + ".sort." + std::to_string((long long)getpid()) + ".tmp";
+        if (flx_sam_open_sorted(o.output.c_str(), spill.c_str(), devices[0], o.bam_index ? 1 : 0, ref_id_ptrs.data(), ref.lens.data(), (uint32_t)ref.ids.size(), &out) != FLX_OK) { log_line("error", "%s", flx_last_error()); return -1; }
+    } else if (flx_sam_open(o.output.c_str(), ref_id_ptrs.data(), ref.lens.data(), (uint32_t)ref.ids.size(), &out) != FLX_OK) { log_line("error", "%s", flx_last_error()); return -1; }
 
     flx_params p;
     flx_params_default(&p);
@@ -1011,7 +1028,9 @@ int main(int argc, char** argv) {
     { std::lock_guard<std::mutex> g(q_mu); no_more = true; }
     q_cv.notify_all();
     writer.join();
+    auto const t_close = std::chrono::steady_clock::now();
     if (flx_sam_close(out) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+    else if (o.sort_by_coordinate) log_line("info", "sorting the keys, merging the spilled batches%s took %.3f seconds", o.bam_index ? " and writing the index" : "", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_close).count());
     // (the alignment phase ends with the output file: floxer.cpp:154-179 stops its watch there; giving 40 GB of HBM back is not part of it)
     double const secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_align).count();
     if (!covs.empty() && !failed.load() && !timed_out && !write_coverage(o, covs, ref.ids)) failed.store(true);

@@ -18,9 +18,14 @@
 #include <thread>
 #include <vector>
 
+#include <unistd.h>
+
 #include "flx_internal.hpp"
+#include "flx_sort.hpp"
 
 using namespace flx;
+
+const SortCalls* flx::g_sort_calls = nullptr;
 
 struct flx_sam_writer {
     FILE* f = nullptr;
@@ -32,6 +37,18 @@ struct flx_sam_writer {
     bool mapq_from_records = false;  // MAPQ column: flx_record.reserved instead of 255 (flx_sam_set_mapq)
     bool sa_tag = false;             // SA:Z on the records of reads that have a supplementary record (flx_sam_set_sa)
     bool failed = false;
+    // sorted mode (flx_sam_open_sorted): every flx_sam_write* call is spilled as a run of BGZF members in key order, flx_sam_close merges
+    // the runs in the order the device sort gives, writes the header, the records and, when asked, the BAI index
+    bool sorted = false, write_index = false;
+    flx_sort* sorter = nullptr;
+    FILE* spill = nullptr;
+    std::string path, spill_path;
+    uint64_t n_calls = 0;
+    struct Run { uint64_t offset, length; };
+    std::vector<Run> runs;           // run k: the bytes of call k in the spill file
+    uint64_t spill_bytes = 0;
+    bool track_blocks = false;       // the merge: the compressed size of every block written, in order
+    std::vector<uint32_t> block_sizes;
 };
 
 namespace {
@@ -39,6 +56,8 @@ namespace {
 // FLX_WRITER_PROFILE=1: seconds the writer's threads spent formatting records, deflating and on checksums (summed over the threads), on
 // stderr when the file is closed
 std::atomic<uint64_t> g_ns_format{0}, g_ns_deflate{0}, g_ns_crc{0};
+// and, for a sorted writer's close, the wall time of the merge's stages: inflating the runs, deflating and writing the merged stream
+std::atomic<uint64_t> g_ns_merge_inflate{0}, g_ns_merge_flush{0};
 bool writer_profile() { static bool const v = getenv("FLX_WRITER_PROFILE") != nullptr; return v; }
 inline uint64_t prof_ns() { return writer_profile() ? (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0; }
 
@@ -502,6 +521,7 @@ bool bgzf_flush(flx_sam_writer* w, bool all) {
     });
     bool ok = true;
     for (size_t b = 0; b < n_blocks && ok; ++b) ok = sizes[b] != 0 && fwrite(out.get() + b * BGZF_MAX_OUT, 1, sizes[b], w->f) == sizes[b];
+    if (w->track_blocks) for (size_t b = 0; b < n_blocks; ++b) w->block_sizes.push_back((uint32_t)sizes[b]);
     size_t const used = all ? w->pending.size() : n_full * BGZF_BLOCK;
     w->pending.erase(w->pending.begin(), w->pending.begin() + (long)used);
     return ok;
@@ -516,19 +536,27 @@ bool emit(flx_sam_writer* w, const void* data, size_t len) {
 
 template <class T> void put(std::vector<uint8_t>& v, T x) { const uint8_t* p = (const uint8_t*)&x; v.insert(v.end(), p, p + sizeof(T)); }
 
-int reg2bin(int64_t beg, int64_t end) {
-    --end;
-    if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-    return 0;
-}
+// (reg2bin: flx_sort.hpp, shared with the index builder)
 
 std::string header_text(flx_sam_writer const* w) {
-    std::string h = "@HD\tVN:1.6\n";
+    std::string h = w->sorted ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\n";
     for (size_t i = 0; i < w->ref_ids.size(); ++i) h += "@SQ\tSN:" + w->ref_ids[i] + "\tLN:" + std::to_string(w->ref_lens[i]) + "\n";
+    return h;
+}
+
+std::vector<uint8_t> bam_header(flx_sam_writer const* w) {
+    std::string const text = header_text(w);
+    std::vector<uint8_t> h;
+    h.insert(h.end(), {'B', 'A', 'M', 1});
+    put<int32_t>(h, (int32_t)text.size());
+    h.insert(h.end(), text.begin(), text.end());
+    put<int32_t>(h, (int32_t)w->ref_ids.size());
+    for (size_t i = 0; i < w->ref_ids.size(); ++i) {
+        put<int32_t>(h, (int32_t)w->ref_ids[i].size() + 1);
+        h.insert(h.end(), w->ref_ids[i].begin(), w->ref_ids[i].end());
+        h.push_back(0);
+        put<int32_t>(h, (int32_t)w->ref_lens[i]);
+    }
     return h;
 }
 
@@ -551,17 +579,7 @@ extern "C" int flx_sam_open(const char* path, const char* const* ref_ids, const 
     bool ok;
     if (!bam) ok = emit(w, text.data(), text.size());
     else {
-        std::vector<uint8_t> h;
-        h.insert(h.end(), {'B', 'A', 'M', 1});
-        put<int32_t>(h, (int32_t)text.size());
-        h.insert(h.end(), text.begin(), text.end());
-        put<int32_t>(h, (int32_t)n_refs);
-        for (uint32_t i = 0; i < n_refs; ++i) {
-            put<int32_t>(h, (int32_t)w->ref_ids[i].size() + 1);
-            h.insert(h.end(), w->ref_ids[i].begin(), w->ref_ids[i].end());
-            h.push_back(0);
-            put<int32_t>(h, (int32_t)w->ref_lens[i]);
-        }
+        std::vector<uint8_t> const h = bam_header(w);
         ok = emit(w, h.data(), h.size());
     }
     if (!ok) { fclose(f); delete w; set_error("write error"); return FLX_ERR_IO; }
@@ -809,6 +827,21 @@ extern "C" int flx_sam_write_cs(flx_sam_writer* w, const char* const* read_ids, 
     if (w->failed) { set_error("write error on the alignment output"); return FLX_ERR_IO; }
     std::vector<std::string> sa;                               // (made once for the whole call: the parts below cut reads anywhere)
     if (w->sa_tag) build_sa_strings(w, records, n_records, cigar_words, sa);
+    // sorted mode: the call's records are added to the sort as run k with ordinals k << 32 | i, and formatted in the key order the add
+    // returns; `at` names the record behind place i of that order (the identity otherwise). The SA strings above were made in
+    // written order and are indexed through it like everything else.
+    std::vector<uint32_t> order;
+    if (w->sorted) {
+        if (n_records >= (1ull << 32)) { set_error("flx_sam_write: 2^32 records or more in one call of a sorted writer"); return FLX_ERR_INVALID; }
+        if (w->n_calls >= (1ull << 31)) { set_error("flx_sam_write: 2^31 calls of a sorted writer"); return FLX_ERR_INVALID; }
+        order.resize(n_records);
+        uint64_t n_words = 0;                                  // the pool's extent, as far as these records say
+        for (uint64_t i = 0; i < n_records; ++i) if (records[i].cigar_length) n_words = std::max<uint64_t>(n_words, records[i].cigar_offset + records[i].cigar_length);
+        int const rc = g_sort_calls->add_records(w->sorter, records, n_records, cigar_words, cigar_words ? n_words : 0, w->n_calls << 32, order.data());
+        if (rc) return rc;
+    }
+    auto const at = [&](uint64_t i) -> uint64_t { return w->sorted ? order[i] : i; };
+    FILE* const dst = w->sorted ? w->spill : w->f;
     if (w->bam) {
         // BAM: a worker formats a fixed number of records at a time into a small buffer and deflates every 64 KB of it into BGZF blocks as
         // it goes (the last block of a part is short: BGZF blocks need not be full), so the uncompressed records - 280 KB per read at default
@@ -865,36 +898,46 @@ extern "C" int flx_sam_write_cs(flx_sam_writer* w, const char* const* read_ids, 
             for (uint64_t i = r0; i < r1 && errs[p].empty(); ++i) {
                 size_t cigar_at = SIZE_MAX, md_at = SIZE_MAX, cs_at = SIZE_MAX;
                 uint64_t const t_format = prof_ns();
-                if (!format_record(w, records[i], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + i : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[i] : nullptr, scores ? scores + i : nullptr, cs_refs ? cs_refs + i : nullptr, cs_bytes, &cs_at)) break;
+                uint64_t const j = at(i), jp = i > r0 ? at(i - 1) : j;       // this record and the one written before it
+                if (!format_record(w, records[j], read_ids, read_pool, read_offsets, quals, cigar_words, raw, errs[p], span_cache, &cigar_at, md ? md + j : nullptr, md_bytes, &md_at, w->sa_tag ? &sa[j] : nullptr, scores ? scores + j : nullptr, cs_refs ? cs_refs + j : nullptr, cs_bytes, &cs_at)) break;
                 if (writer_profile()) g_ns_format += prof_ns() - t_format;
                 if (cigar_at != SIZE_MAX) {
                     cigar_at += base;
-                    bool const same = prev_cigar_at != SIZE_MAX && i > r0 && records[i].cigar_offset == records[i - 1].cigar_offset && records[i].cigar_length == records[i - 1].cigar_length;
-                    hints.push_back(StreamHint{cigar_at, 4 * (size_t)records[i].cigar_length, same ? cigar_at - prev_cigar_at : 0});
+                    bool const same = prev_cigar_at != SIZE_MAX && i > r0 && records[j].cigar_offset == records[jp].cigar_offset && records[j].cigar_length == records[jp].cigar_length;
+                    hints.push_back(StreamHint{cigar_at, 4 * (size_t)records[j].cigar_length, same ? cigar_at - prev_cigar_at : 0});
                 }
                 prev_cigar_at = cigar_at;
                 // the MD string repeats exactly when the CIGAR array does (records of one traced path): announced the same way, behind it
                 if (md_at != SIZE_MAX) {
                     md_at += base;
-                    bool const same = prev_md_at != SIZE_MAX && i > r0 && md[i].offset == md[i - 1].offset && md[i].length == md[i - 1].length;
-                    hints.push_back(StreamHint{md_at, (size_t)md[i].length, same ? md_at - prev_md_at : 0});
+                    bool const same = prev_md_at != SIZE_MAX && i > r0 && md[j].offset == md[jp].offset && md[j].length == md[jp].length;
+                    hints.push_back(StreamHint{md_at, (size_t)md[j].length, same ? md_at - prev_md_at : 0});
                 }
                 prev_md_at = md_at;
                 // and the cs string, behind the MD string
                 if (cs_at != SIZE_MAX) {
                     cs_at += base;
-                    bool const same = prev_cs_at != SIZE_MAX && i > r0 && cs_refs[i].offset == cs_refs[i - 1].offset && cs_refs[i].length == cs_refs[i - 1].length;
-                    hints.push_back(StreamHint{cs_at, (size_t)cs_refs[i].length, same ? cs_at - prev_cs_at : 0});
+                    bool const same = prev_cs_at != SIZE_MAX && i > r0 && cs_refs[j].offset == cs_refs[jp].offset && cs_refs[j].length == cs_refs[jp].length;
+                    hints.push_back(StreamHint{cs_at, (size_t)cs_refs[j].length, same ? cs_at - prev_cs_at : 0});
                 }
                 prev_cs_at = cs_at;
                 deflate_full_blocks(false);
             }
             if (errs[p].empty()) deflate_full_blocks(true);
         });
-        for (auto const& e : errs) if (!e.empty()) { set_error(e); return FLX_ERR_INVALID; }
-        for (auto const& part : parts)
-            if (!part.empty() && fwrite(part.data(), 1, part.size(), w->f) != part.size()) { w->failed = true; break; }
-        if (w->failed) { set_error("write error on the alignment output"); return FLX_ERR_IO; }
+        for (auto const& e : errs) if (!e.empty()) { if (w->sorted) w->failed = true; set_error(e); return FLX_ERR_INVALID; }      // (a sorted writer: the sort holds records that have no run)
+        uint64_t written = 0;
+        for (auto const& part : parts) {
+            if (!part.empty() && fwrite(part.data(), 1, part.size(), dst) != part.size()) { w->failed = true; break; }
+            written += part.size();
+        }
+        if (w->failed) { set_error(w->sorted ? "write error on the sort's spill file" : "write error on the alignment output"); return FLX_ERR_IO; }
+        if (w->sorted) {
+            w->runs.resize((size_t)w->n_calls + 1, flx_sam_writer::Run{w->spill_bytes, 0});
+            w->runs[(size_t)w->n_calls] = flx_sam_writer::Run{w->spill_bytes, written};
+            w->spill_bytes += written;
+            ++w->n_calls;
+        }
         return FLX_OK;
     }
     // SAM: records are formatted in parallel (contiguous ranges, one buffer each), then written in order
@@ -929,8 +972,236 @@ extern "C" int flx_sam_write_cs(flx_sam_writer* w, const char* const* read_ids, 
     return FLX_OK;
 }
 
+namespace {
+
+// One spilled run read back: its BGZF members inflated in sequence, record by record (a record's length is its own block_size).
+struct RunReader {
+    int fd = -1;
+    uint64_t at = 0, end = 0;                                  // the bytes of the run not yet read from the spill file
+    z_stream zs;
+    bool ready = false;
+    std::vector<uint8_t> in, buf;                              // compressed input; inflated bytes, buf[head, buf.size()) not yet taken
+    size_t head = 0;
+    ~RunReader() { if (ready) inflateEnd(&zs); }
+    bool open(int fd_, uint64_t offset, uint64_t length) {
+        fd = fd_; at = offset; end = offset + length;
+        memset(&zs, 0, sizeof(zs));
+        if (inflateInit2(&zs, 31) != Z_OK) return false;
+        ready = true;
+        in.resize(1u << 16);
+        return true;
+    }
+    // at least `need` bytes behind head, or false (the run ends early or does not inflate)
+    bool fill(size_t need) {
+        while (buf.size() - head < need) {
+            if (head && head == buf.size()) { buf.clear(); head = 0; }
+            else if (head >= (1u << 20)) { buf.erase(buf.begin(), buf.begin() + (long)head); head = 0; }
+            if (zs.avail_in == 0) {
+                if (at >= end) return false;
+                ssize_t const got = pread(fd, in.data(), (size_t)std::min<uint64_t>(in.size(), end - at), (off_t)at);
+                if (got <= 0) return false;
+                at += (uint64_t)got;
+                zs.next_in = in.data();
+                zs.avail_in = (uInt)got;
+            }
+            size_t const before = buf.size();
+            buf.resize(before + (1u << 17));
+            zs.next_out = buf.data() + before;
+            zs.avail_out = 1u << 17;
+            int const rc = inflate(&zs, Z_NO_FLUSH);
+            buf.resize(before + ((1u << 17) - zs.avail_out));
+            if (rc == Z_STREAM_END) { if (inflateReset(&zs) != Z_OK) return false; }      // the next member of the run
+            else if (rc != Z_OK && rc != Z_BUF_ERROR) return false;
+        }
+        return true;
+    }
+    // the next record, block_size included, appended to out
+    bool next(std::vector<uint8_t>& out) {
+        if (!fill(4)) return false;
+        int32_t size;
+        memcpy(&size, buf.data() + head, 4);
+        if (size < 32 || !fill(4 + (size_t)size)) return false;
+        out.insert(out.end(), buf.begin() + (long)head, buf.begin() + (long)(head + 4 + (size_t)size));
+        head += 4 + (size_t)size;
+        return true;
+    }
+};
+
+// The BAI index (SAMv1 5.2) of one reference, fed with its records in file order.
+struct BaiReference {
+    struct Chunk { uint64_t beg, end; };
+    std::vector<std::pair<uint32_t, std::vector<Chunk>>> bins;      // in order of first use; sorted by bin when written
+    std::vector<size_t> bin_slot = std::vector<size_t>(37450, SIZE_MAX);
+    std::vector<uint64_t> linear;                              // 0: no record yet
+    std::vector<char> linear_set;
+    uint32_t last_bin = 0xFFFFFFFFu;
+    uint64_t first = 0, last = 0, n_mapped = 0;
+    void add(uint32_t pos, uint32_t end, uint64_t vbeg, uint64_t vend) {
+        uint32_t const bin = reg2bin(pos, end);
+        // records consecutive in the file with the same reference and bin extend one chunk; anything else starts a new one
+        if (bin == last_bin) bins[bin_slot[bin]].second.back().end = vend;
+        else {
+            if (bin_slot[bin] == SIZE_MAX) { bin_slot[bin] = bins.size(); bins.emplace_back(bin, std::vector<Chunk>()); }
+            bins[bin_slot[bin]].second.push_back(Chunk{vbeg, vend});
+            last_bin = bin;
+        }
+        size_t const w0 = pos >> 14, w1 = (end - 1) >> 14;
+        if (linear.size() <= w1) { linear.resize(w1 + 1, 0); linear_set.resize(w1 + 1, 0); }
+        for (size_t x = w0; x <= w1; ++x) if (!linear_set[x]) { linear[x] = vbeg; linear_set[x] = 1; }      // (file order: the first to touch a window has the smallest offset)
+        if (n_mapped == 0) first = vbeg;
+        last = vend;
+        ++n_mapped;
+    }
+    void write(std::vector<uint8_t>& out) {
+        std::sort(bins.begin(), bins.end(), [](auto const& a, auto const& b) { return a.first < b.first; });
+        put<int32_t>(out, (int32_t)(bins.size() + (n_mapped ? 1 : 0)));
+        for (auto const& b : bins) {
+            put<uint32_t>(out, b.first);
+            put<int32_t>(out, (int32_t)b.second.size());
+            for (auto const& c : b.second) { put<uint64_t>(out, c.beg); put<uint64_t>(out, c.end); }
+        }
+        if (n_mapped) {                                        // the pseudo-bin: the reference's extent in the file and its record counts
+            put<uint32_t>(out, 37450u);
+            put<int32_t>(out, 2);
+            put<uint64_t>(out, first); put<uint64_t>(out, last);
+            put<uint64_t>(out, n_mapped); put<uint64_t>(out, 0);      // (a record with flag 4 is unplaced under the sort's key: none is counted here)
+        }
+        put<int32_t>(out, (int32_t)linear.size());
+        uint64_t before = 0;
+        for (size_t x = 0; x < linear.size(); ++x) { if (linear_set[x]) before = linear[x]; put<uint64_t>(out, before); }      // an empty window takes its predecessor's value
+    }
+};
+
+// sorted mode's close: header, the runs merged in the sort's order, EOF block, index. false: error set.
+bool merge_sorted(flx_sam_writer* w) {
+    if (fflush(w->spill) != 0) { set_error("write error on the sort's spill file"); return false; }
+    if (g_sort_calls->finish(w->sorter) != FLX_OK) return false;
+    uint64_t const n = g_sort_calls->num_records(w->sorter);
+    std::vector<RunReader> readers(w->runs.size());
+    for (size_t k = 0; k < w->runs.size(); ++k)
+        if (w->runs[k].length && !readers[k].open(fileno(w->spill), w->runs[k].offset, w->runs[k].length)) { set_error("cannot read the sort's spill file"); return false; }
+    w->track_blocks = true;
+    std::vector<uint8_t> const header = bam_header(w);
+    w->pending.assign(header.begin(), header.end());
+    uint64_t flushed = 0;                                      // bytes of the stream that have left w->pending
+    std::vector<uint64_t> ustart;                              // per record, with an index: where it starts in the uncompressed stream
+    if (w->write_index) ustart.reserve(n);
+    std::vector<flx_sort_entry> entries;
+    constexpr uint64_t STRETCH = 1u << 20;
+    constexpr size_t FLUSH_AT = 16u << 20;
+    for (uint64_t e0 = 0; e0 < n; e0 += STRETCH) {
+        uint64_t const e1 = std::min(n, e0 + STRETCH);
+        entries.resize(e1 - e0);
+        if (g_sort_calls->copy(w->sorter, e0, e1, entries.data()) != FLX_OK) return false;
+        for (auto const& e : entries) {
+            uint64_t const run = e.ordinal >> 32;
+            if (w->write_index) ustart.push_back(flushed + w->pending.size());
+            uint64_t const t_inflate = prof_ns();
+            if (run >= readers.size() || !readers[run].ready || !readers[run].next(w->pending)) { set_error("the sort's spill file ends early or does not inflate"); return false; }
+            if (writer_profile()) g_ns_merge_inflate += prof_ns() - t_inflate;
+            if (w->pending.size() >= FLUSH_AT) {
+                size_t const full = w->pending.size() / BGZF_BLOCK * BGZF_BLOCK;
+                uint64_t const t_flush = prof_ns();
+                if (!bgzf_flush(w, false)) { set_error("write error on the alignment output"); return false; }
+                if (writer_profile()) g_ns_merge_flush += prof_ns() - t_flush;
+                flushed += full;
+            }
+        }
+    }
+    uint64_t const total = flushed + w->pending.size();
+    uint64_t const t_flush = prof_ns();
+    if (!bgzf_flush(w, true)) { set_error("write error on the alignment output"); return false; }
+    if (writer_profile()) {
+        g_ns_merge_flush += prof_ns() - t_flush;
+        fprintf(stderr, "[flx writer profile] sorted close: %llu records, %zu runs, spill %.1f MB, merged stream %.1f MB; inflating the runs %.2f s, deflating and writing the output %.2f s (wall)\n",
+                (unsigned long long)n, w->runs.size(), w->spill_bytes / 1e6, total / 1e6, g_ns_merge_inflate.load() / 1e9, g_ns_merge_flush.load() / 1e9);
+    }
+    uint8_t eof_block[BGZF_MAX_OUT];
+    size_t const n_eof = bgzf_compress_block(nullptr, 0, eof_block);   // BGZF EOF marker block
+    if (n_eof == 0 || fwrite(eof_block, 1, n_eof, w->f) != n_eof) { set_error("write error on the alignment output"); return false; }
+    if (!w->write_index) return true;
+    // ---- the index. The stream was cut into blocks of BGZF_BLOCK bytes: block b starts at file offset coffset[b]; a byte at the end of
+    // the last block is the first of the EOF block
+    std::vector<uint64_t> coffset(w->block_sizes.size() + 1, 0);
+    for (size_t b = 0; b < w->block_sizes.size(); ++b) coffset[b + 1] = coffset[b] + w->block_sizes[b];
+    auto const voffset = [&](uint64_t u) { return coffset[(size_t)(u / BGZF_BLOCK)] << 16 | (u % BGZF_BLOCK); };
+    auto const voffset_behind = [&](uint64_t u) { return u == total ? coffset.back() << 16 : voffset(u); };
+    std::vector<uint8_t> bai{'B', 'A', 'I', 1};
+    put<int32_t>(bai, (int32_t)w->ref_ids.size());
+    std::string const bai_path = w->path + ".bai";
+    FILE* const fi = fopen(bai_path.c_str(), "wb");
+    if (!fi) { set_error("cannot open the index file: " + bai_path); return false; }
+    bool ok = true;
+    auto const drain = [&] { if (!bai.empty()) { ok = fwrite(bai.data(), 1, bai.size(), fi) == bai.size() && ok; bai.clear(); } };
+    uint64_t n_no_coor = 0;
+    size_t ref = 0;                                            // the reference being collected
+    auto cur = std::make_unique<BaiReference>();
+    for (uint64_t e0 = 0; e0 < n && ok; e0 += STRETCH) {
+        uint64_t const e1 = std::min(n, e0 + STRETCH);
+        entries.resize(e1 - e0);
+        if (g_sort_calls->copy(w->sorter, e0, e1, entries.data()) != FLX_OK) { fclose(fi); return false; }
+        for (uint64_t i = e0; i < e1; ++i) {
+            flx_sort_entry const& e = entries[i - e0];
+            if (e.reference_id < 0) { ++n_no_coor; continue; }
+            while (ref < (size_t)e.reference_id) { cur->write(bai); drain(); cur = std::make_unique<BaiReference>(); ++ref; }
+            cur->add((uint32_t)e.position, e.end, voffset(ustart[i]), voffset_behind(i + 1 < n ? ustart[i + 1] : total));
+        }
+    }
+    for (; ref < w->ref_ids.size(); ++ref) { cur->write(bai); drain(); cur = std::make_unique<BaiReference>(); }
+    put<uint64_t>(bai, n_no_coor);
+    drain();
+    ok = fclose(fi) == 0 && ok;
+    if (!ok) set_error("write error on the index file: " + bai_path);
+    return ok;
+}
+
+}  // namespace
+
+extern "C" int flx_sam_open_sorted(const char* path, const char* spill_path, int hip_device, int write_index, const char* const* ref_ids,
+                                   const uint64_t* ref_lens, uint32_t n_refs, flx_sam_writer** out) {
+    if (!path || !spill_path || !out || (n_refs && (!ref_ids || !ref_lens))) { set_error("flx_sam_open_sorted: null argument"); return FLX_ERR_INVALID; }
+    std::string const p(path);
+    if (p.size() < 4 || p.compare(p.size() - 4, 4, ".bam") != 0) { set_error("flx_sam_open_sorted: a coordinate-sorted output must end in .bam"); return FLX_ERR_INVALID; }
+    if (write_index)
+        for (uint32_t i = 0; i < n_refs; ++i)
+            if (ref_lens[i] > (1ull << 29)) { set_error(std::string("flx_sam_open_sorted: a BAI index cannot address sequence ") + ref_ids[i] + " (" + std::to_string(ref_lens[i]) + " symbols, more than 2^29)"); return FLX_ERR_INVALID; }
+    auto w = std::make_unique<flx_sam_writer>();
+    w->bam = true;
+    w->sorted = true;
+    w->write_index = write_index != 0;
+    w->path = p;
+    w->spill_path = spill_path;
+    for (uint32_t i = 0; i < n_refs; ++i) { w->ref_ids.emplace_back(ref_ids[i]); w->ref_lens.push_back(ref_lens[i]); }
+    if (!g_sort_calls) { set_error("flx_sam_open_sorted: this build holds no sort object (flx_sort_api.cpp)"); return FLX_ERR_UNSUPPORTED; }
+    int const rc = g_sort_calls->create(hip_device, n_refs, nullptr, &w->sorter);
+    if (rc) return rc;
+    w->spill = fopen(spill_path, "w+b");
+    if (!w->spill) { g_sort_calls->free(w->sorter); set_error(std::string("cannot create the sort's spill file: ") + spill_path); return FLX_ERR_IO; }
+    w->f = fopen(path, "wb");
+    if (!w->f) {
+        fclose(w->spill);
+        remove(spill_path);
+        g_sort_calls->free(w->sorter);
+        set_error(std::string("cannot open output file: ") + path);
+        return FLX_ERR_IO;
+    }
+    *out = w.release();
+    return FLX_OK;
+}
+
 extern "C" int flx_sam_close(flx_sam_writer* w) {
     if (!w) return FLX_OK;
+    if (w->sorted) {
+        bool ok = !w->failed, merge_failed = false;                // (a failed merge has set its own error)
+        if (ok && !(ok = merge_sorted(w))) merge_failed = true;
+        ok = (fclose(w->f) == 0) && ok;
+        fclose(w->spill);
+        remove(w->spill_path.c_str());                         // on failure as well
+        g_sort_calls->free(w->sorter);
+        delete w;
+        if (!ok) { if (!merge_failed) set_error("write error while closing the alignment output"); return FLX_ERR_IO; }
+        return FLX_OK;
+    }
     if (writer_profile() && w->bam)
         fprintf(stderr, "[flx writer profile] summed over the I/O threads: formatting %.2f s, deflate %.2f s, checksums %.2f s\n", g_ns_format.load() / 1e9, g_ns_deflate.load() / 1e9, g_ns_crc.load() / 1e9);
     bool ok = !w->failed;

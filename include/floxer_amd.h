@@ -770,6 +770,50 @@ int  flx_pileup_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_pileup
 int  flx_pileup_sites_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_pileup_options* o, const uint32_t* counts,
                            flx_pileup_site* out, uint64_t* n_sites /* in: capacity, out: needed */);
 
+/* ------------------------------------------------------------------------------------------------ coordinate order of records
+ * Not floxer's. A sort object holds one 16-byte key and {end, flag} per record added, in HBM, and orders them on the device with a
+ * least-significant-digit radix sort (8-bit digits, floxer_amd/csrc/flx_sort.hip). The rule (floxer_amd/csrc/flx_sort.hpp): a key is
+ * two u64 compared ascending as (hi, lo),
+ *     hi = ref << 32 | (u32)position     ref = 0xFFFFFFFF for a record with flag & 4 or reference_id < 0 (unplaced), else reference_id
+ *     lo = ((flag >> 4) & 1) << 63 | ordinal
+ * which is samtools sort's order (reference, position, forward strand before reverse, unplaced records last) with ties broken by the
+ * ordinal: record i of an add has ordinal first_ordinal + i. The order is total and does not depend on the order of adds, host
+ * threads, batch size or devices. A record's end is position + max(1, span) for a mapped record, span the summed lengths of its = X D
+ * words (0 for a record without words, as in a without_cigar run), and position + 1 for an unplaced one: the convention of the BAM bin.
+ *   - refused (FLX_ERR_INVALID, on the host before any launch; the object stays as it was): a mapped record with reference_id >= n_refs
+ *     or position < 0, an op other than = X I D S, a zero-length word, words outside the pool, an end above 2^31 - 1, an ordinal of 2^63
+ *     or more, a first_ordinal that an earlier add of this object was given (a full duplicate check is not made);
+ *   - out_order (may be NULL) receives the add's own records in key order, as indices into `records` (flx_sort_add_run: into the run's
+ *     records as flx_run_copy lists them), sorted on the device with the same kernels;
+ *   - adds may come from several host threads at once. The key table grows by reallocation and a device-to-device copy; a failed
+ *     allocation is FLX_ERR_NO_DEVICE and leaves the object as it was. At most 2^32 - 1 records per object: FLX_ERR_CAPACITY beyond;
+ *   - flx_sort_finish sorts everything added and is final: a later add or finish is FLX_ERR_INVALID. Behind it flx_sort_copy gives
+ *     the sorted entries [from, to); an unplaced record's entry has reference_id -1;
+ *   - hip_device = -1: no device is opened, and every add and the finish run flx_sort_host's code on the host. That is for tests on
+ *     a machine without a GPU and for callers that want the order without a device; the CLI never uses it;
+ *   - flx_sort_options, NULL or all zero for the defaults, the reserved fields 0; both members are test hooks: initial_capacity is the records the
+ *     table holds before it first grows, tile_keys the keys one block orders per pass, a multiple of the block's threads;
+ *   - flx_sort_geometry (a test hook): out[0] = default keys per tile, out[1] = bits per digit, out[2] = default initial capacity,
+ *     out[3] = entries per tile of the digit table's scan. The table has 256 entries per tile of keys and is scanned in two levels at
+ *     most: past out[3]^2 / 256 tiles the tiles grow instead;
+ *   - flx_sort_host: the rule alone on the host, no device: record i has ordinal ordinals[i]; out_sorted receives n entries.
+ * FLX_SORT_PROFILE (environment): every add and the finish print their records, uploaded bytes, passes run, device time and wall
+ * time to stderr. */
+typedef struct flx_sort flx_sort;
+typedef struct flx_sort_options { uint64_t initial_capacity; uint32_t tile_keys; uint32_t reserved[5]; } flx_sort_options;
+typedef struct flx_sort_entry { uint64_t ordinal; int32_t reference_id; int32_t position; uint32_t end; uint32_t flag; } flx_sort_entry;
+int  flx_sort_create(int hip_device, uint32_t n_refs, const flx_sort_options* o, flx_sort** out);
+void flx_sort_free(flx_sort* s);
+int  flx_sort_add_records(flx_sort* s, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                          uint64_t first_ordinal, uint32_t* out_order /* n entries; may be NULL */);
+int  flx_sort_add_run(flx_sort* s, const flx_run* run, uint64_t first_ordinal, uint32_t* out_order /* flx_run_num_records entries; may be NULL */);
+int  flx_sort_finish(flx_sort* s);
+uint64_t flx_sort_num_records(const flx_sort* s);
+int  flx_sort_copy(const flx_sort* s, uint64_t from, uint64_t to, flx_sort_entry* out);
+int  flx_sort_geometry(uint32_t out[4]);
+int  flx_sort_host(uint32_t n_refs, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                   const uint64_t* ordinals, flx_sort_entry* out_sorted);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
@@ -883,6 +927,22 @@ int flx_sam_set_mapq(flx_sam_writer* w, int from_records);
  * I, D) and mapQ what the writer puts into that record's MAPQ column. A read's records must be contiguous within one flx_sam_write
  * call, as in every flx_run. Default off: then no byte changes. */
 int flx_sam_set_sa(flx_sam_writer* w, int on);
+/* A coordinate-sorted BAM (not floxer's), optionally with its BAI index <path>.bai (SAMv1 5.2). The writer owns a sort object
+ * (flx_sort_create) on hip_device; -1 orders on the host, for tests and callers without a device. The setters and all four
+ * flx_sam_write* calls work as on any writer. Call k of flx_sam_write* (from 0) adds its records to the sort with first_ordinal
+ * k << 32, formats and deflates them in the key order that add returns, and appends the BGZF members to the spill file as run k: fewer
+ * than 2^32 records per call. flx_sam_close writes the header with @HD VN:1.6 SO:coordinate, finishes the sort, streams its entries,
+ * takes for every entry the next record of run ordinal >> 32 (every run is inflated in sequence), deflates the merged stream into
+ * the output, writes the EOF block and the index, and removes the spill file, on failure as well. Records with equal reference,
+ * position and strand keep the order they were written in. The output's bytes do not depend on flx_sam_set_threads.
+ * The index: records consecutive in the file with the same reference and bin extend one chunk, anything else starts a new one (no
+ * further merging); a chunk ends at the virtual offset of the first byte behind its last record (the next block's start when that
+ * is a block's end); the linear index has ((max end - 1) >> 14) + 1 windows, an empty one repeats its predecessor (0 in front of
+ * the first); bin 37450 holds the reference's first and last offset and its record counts; n_no_coor counts the unplaced records.
+ * Refused up front: a path that does not end in .bam (FLX_ERR_INVALID), a spill file or an output that cannot be created (FLX_ERR_IO),
+ * write_index with a sequence longer than 2^29 (FLX_ERR_INVALID; the message names it). */
+int flx_sam_open_sorted(const char* path /* .bam only */, const char* spill_path, int hip_device, int write_index,
+                        const char* const* ref_ids, const uint64_t* ref_lens, uint32_t n_refs, flx_sam_writer** out);
 
 /* ------------------------------------------------------------------------------------------------ synthetic inputs
  * The reference's simulator (src/main/simulated_dataset.cpp:30-49, 81-223), multi-threaded and with a portable generator:
