@@ -1351,3 +1351,121 @@ def sort_host(n_refs, records, cigar_words, ordinals):
     check(lib().flx_sort_host(int(n_refs), rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(ords, u64p),
                               out.ctypes.data_as(C.POINTER(capi.SortEntry))))
     return out[: len(rec)]
+
+
+# ------------------------------------------------------------------------------------------------ PAF output
+PAF_SUMMARY_DTYPE = np.dtype([(n, "<u4") for n in ("query_start", "query_end", "ref_end", "matches", "mismatches", "ins_bases", "del_bases", "gap_opens")])
+
+
+def _read_offsets(read_lengths):
+    lens = np.asarray(read_lengths, dtype=np.uint64)
+    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
+    if len(lens):
+        offs[1:] = np.cumsum(lens)
+    return offs
+
+
+def _paf_call(fn, head, records, cigar_words, read_lengths, ref_lens, out):
+    rec, words = _records_and_words(records, cigar_words)
+    offs = _read_offsets(read_lengths)
+    lens = np.ascontiguousarray(np.asarray(ref_lens, dtype=np.uint64))
+    if out is None:
+        out = np.zeros(max(1, len(rec)), dtype=PAF_SUMMARY_DTYPE)
+    elif out.dtype != PAF_SUMMARY_DTYPE or not out.flags["C_CONTIGUOUS"] or len(out) < len(rec):
+        raise FloxerError("paf: out must be a contiguous PAF_SUMMARY_DTYPE array with one entry per record")
+    check(fn(*head, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p) if len(words) else None, len(words), ptr(offs, u64p), len(offs) - 1,
+             ptr(lens, u64p) if len(lens) else None, len(lens), out.ctypes.data_as(C.POINTER(capi.PafSummary))))
+    return out[: len(rec)]
+
+
+class paf:
+    """Per-record PAF summaries (query interval, reference end, matching columns, block length, gap opens), reduced on `device` from the
+    records' CIGAR words. Not floxer's. device=-1 opens no device and applies the host rule (for machines without a GPU). Calls may
+    come from several threads; they are serialised inside the object."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        check(lib().flx_paf_create(int(device), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_paf_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def summarize(self, records, cigar_words, read_lengths, ref_lens, out=None):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        read_lengths: one entry per read of the batch, indexed by the records' `read`; ref_lens: the reference sequences' lengths.
+        Returns a structured array of PAF_SUMMARY_DTYPE, one entry per record (all zeros for an unmapped record); out: such an array
+        to fill. A refused call (FloxerError) leaves `out` as it was."""
+        return _paf_call(lib().flx_paf_summarize, (self.h,), records, cigar_words, read_lengths, ref_lens, out)
+
+
+def paf_summarize_host(records, cigar_words, read_lengths, ref_lens, out=None):
+    """the rule alone on the host (flx_paf_summarize_host); arguments and result as paf.summarize"""
+    return _paf_call(lib().flx_paf_summarize_host, (), records, cigar_words, read_lengths, ref_lens, out)
+
+
+def paf_options(write_cigar=False, write_unmapped=False, mapq_from_records=False, skip_secondary=False):
+    """flx_paf_options: write_cigar: a cg:Z tag with the record's own words (= and X kept, S included); write_unmapped: a line for
+    every unmapped record (minimap2's --paf-no-hit form); mapq_from_records: column 12 from the records instead of 255;
+    skip_secondary: records with flag 256 produce no line"""
+    o = capi.PafOptions()
+    o.write_cigar, o.write_unmapped = int(bool(write_cigar)), int(bool(write_unmapped))
+    o.mapq_from_records, o.skip_secondary = int(bool(mapq_from_records)), int(bool(skip_secondary))
+    return o
+
+
+class paf_writer:
+    """A PAF file (flx_paf_open): write(...) appends one line per mapped record in call order. Host only."""
+
+    def __init__(self, path, ref_ids, ref_lens, options=None):
+        self.h = C.c_void_p()
+        ids = [r.encode() if isinstance(r, str) else bytes(r) for r in ref_ids]
+        arr = (C.c_char_p * max(1, len(ids)))(*ids)
+        lens = np.ascontiguousarray(np.asarray(ref_lens, dtype=np.uint64))
+        if len(lens) != len(ids):
+            raise FloxerError("paf_writer: one length per reference id")
+        check(lib().flx_paf_open(str(path).encode(), arr, ptr(lens, u64p) if len(lens) else None, len(ids), C.byref(options) if options is not None else None,
+                                 C.byref(self.h)))
+
+    def write(self, read_ids, read_lengths, records, cigar_words, summaries, scores=None, cs_refs=None, cs_bytes=None):
+        """read_ids / read_lengths: one entry per read of the batch; summaries: paf.summarize's result for `records`; scores: int32 per
+        record (RunResult.scores) for AS:i; cs_refs / cs_bytes: RunResult.cs_refs and RunResult.cs_bytes for cs:Z"""
+        rec, words = _records_and_words(records, cigar_words)
+        ids = [r.encode() if isinstance(r, str) else bytes(r) for r in read_ids]
+        arr = (C.c_char_p * max(1, len(ids)))(*ids)
+        offs = _read_offsets(read_lengths)
+        summ = np.ascontiguousarray(summaries, dtype=PAF_SUMMARY_DTYPE)
+        if len(summ) != len(rec):
+            raise FloxerError("paf_writer.write: one summary per record")
+        sc = np.ascontiguousarray(scores, dtype=np.int32) if scores is not None else None
+        refs = cs = None
+        if cs_refs is not None:
+            refs = np.zeros(max(1, len(rec)), dtype=_MD_DTYPE)
+            r2 = np.asarray(cs_refs)
+            if len(r2):
+                if r2.dtype.names:
+                    refs[: len(rec)] = r2
+                else:
+                    refs["off"][: len(rec)], refs["len"][: len(rec)] = r2[:, 0], r2[:, 1]
+            cs = as_u8(cs_bytes) if cs_bytes is not None and len(cs_bytes) else np.zeros(1, np.uint8)
+        check(lib().flx_paf_write(self.h, arr, ptr(offs, u64p), rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p) if len(words) else None,
+                                  summ.ctypes.data_as(C.POINTER(capi.PafSummary)), sc.ctypes.data_as(C.POINTER(C.c_int32)) if sc is not None else None,
+                                  refs.ctypes.data_as(C.POINTER(capi.MdRef)) if refs is not None else None, ptr(cs, u8p) if cs is not None else None))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            check(lib().flx_paf_close(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -173,6 +173,15 @@ class SortEntry(C.Structure):
     _fields_ = [("ordinal", C.c_uint64), ("reference_id", C.c_int32), ("position", C.c_int32), ("end", C.c_uint32), ("flag", C.c_uint32)]
 
 
+class PafSummary(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("query_start", "query_end", "ref_end", "matches", "mismatches", "ins_bases", "del_bases", "gap_opens")]
+
+
+class PafOptions(C.Structure):
+    _fields_ = [("write_cigar", C.c_uint32), ("write_unmapped", C.c_uint32), ("mapq_from_records", C.c_uint32), ("skip_secondary", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("cigar_offset", C.c_uint64), ("cigar_length", C.c_uint32), ("error_weight", C.c_uint32), ("x_drop", C.c_uint32),
                 ("min_tail_rows", C.c_uint32)]
@@ -256,6 +265,7 @@ EXPORTED = [
     "flx_pileup_copy_counts", "flx_pileup_host", "flx_pileup_sites_host",
     "flx_sort_create", "flx_sort_free", "flx_sort_add_records", "flx_sort_add_run", "flx_sort_finish", "flx_sort_num_records", "flx_sort_copy",
     "flx_sort_geometry", "flx_sort_host", "flx_sam_open_sorted",
+    "flx_paf_create", "flx_paf_free", "flx_paf_summarize", "flx_paf_summarize_host", "flx_paf_open", "flx_paf_write", "flx_paf_close",
 ]
 
 _lib = None
@@ -425,6 +435,15 @@ def lib():
     L.flx_pileup_copy_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
     L.flx_pileup_host.argtypes = [u64p, C.c_uint32, C.POINTER(PileupOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64, u32p]
     L.flx_pileup_sites_host.argtypes = [u64p, C.c_uint32, C.POINTER(PileupOptions), u32p, C.POINTER(PileupSite), u64p]
+    L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.flx_paf_free.restype = None
+    L.flx_paf_free.argtypes = [C.c_void_p]
+    L.flx_paf_summarize.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_uint32, C.POINTER(PafSummary)]
+    L.flx_paf_summarize_host.argtypes = [C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64, u64p, C.c_uint32, C.POINTER(PafSummary)]
+    L.flx_paf_open.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), u64p, C.c_uint32, C.POINTER(PafOptions), C.POINTER(C.c_void_p)]
+    L.flx_paf_write.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), u64p, C.POINTER(Record), C.c_uint64, u32p, C.POINTER(PafSummary), C.POINTER(C.c_int32),
+                                C.POINTER(MdRef), u8p]
+    L.flx_paf_close.argtypes = [C.c_void_p]
     L.flx_cigar_tails.argtypes = [u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_cigar_tails_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.POINTER(TailJob), C.c_uint64, C.POINTER(TailResult)]
     L.flx_choose_partials.argtypes = [C.POINTER(PartialCandidate), C.c_uint64, u32p, C.POINTER(PartialOptions), C.POINTER(C.c_int32)]

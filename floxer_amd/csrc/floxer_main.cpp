@@ -85,6 +85,8 @@ struct Options {
     bool pileup_secondary = false;
     bool sort_by_coordinate = false, bam_index = false;           // a coordinate-sorted BAM (flx_sam_open_sorted) and its BAI index
     std::string sort_tmp;                                         // the spill file's directory; empty: the output's
+    std::string paf;                                              // the PAF output; empty: not written
+    bool paf_cigar = false, paf_unmapped = false, paf_skip_secondary = false;
 };
 
 struct OptDef { char short_id; const char* long_id; bool flag; const char* note = nullptr; };   // short_id 0: long spelling only; note: printed by --help
@@ -151,6 +153,11 @@ const OptDef OPTS[] = {
     {0, "sort-by-coordinate", true, "not floxer's: write the records in coordinate order (reference, position, strand; unmapped last) with @HD SO:coordinate; needs a .bam output"},
     {0, "bam-index", true, "not floxer's: write the BAI index <output>.bai as well; needs --sort-by-coordinate"},
     {0, "sort-tmp", false, "not floxer's: the directory of the sort's spill file (default: the output's directory); needs --sort-by-coordinate"},
+    // nor these: the mappings as PAF lines, their per-record numbers reduced on the GPU from the CIGARs (flx_paf, flx_paf.hpp)
+    {0, "paf", false, "not floxer's: one PAF line per mapped record (tp, NM, de and, with --realign-affine, -Q, --cs-tag or --cs-tag-long, AS, the MAPQ column and cs; <file.paf>); with it -o/--output may be left out; not with -w"},
+    {0, "paf-cigar", true, "not floxer's: a cg:Z tag with the record's CIGAR (= and X kept, as minimap2 --eqx writes it); needs --paf"},
+    {0, "paf-unmapped", true, "not floxer's: a line for every unmapped read as well (minimap2's --paf-no-hit form); needs --paf"},
+    {0, "paf-skip-secondary", true, "not floxer's: secondary records (flag 256) produce no PAF line; needs --paf"},
 };
 
 struct CliError { std::string msg; };
@@ -288,6 +295,10 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "sort-by-coordinate") o.sort_by_coordinate = true;
         else if (n == "bam-index") o.bam_index = true;
         else if (n == "sort-tmp") { o.sort_tmp = value; if (value.empty()) throw CliError{"Validation failed for option --" + n + ": the directory's name is empty."}; }
+        else if (n == "paf") o.paf = value;
+        else if (n == "paf-cigar") o.paf_cigar = true;
+        else if (n == "paf-unmapped") o.paf_unmapped = true;
+        else if (n == "paf-skip-secondary") o.paf_skip_secondary = true;
         else if (n == "pileup-min-mapq") { o.pileup_min_mapq = parse_u64(n, value); range_check(n, (double)o.pileup_min_mapq, 1, 254); }
         else if (n == "max-alignments") { o.max_alignments = parse_u64(n, value); if (o.max_alignments < 1) throw CliError{"Validation failed for option --" + n + ": must be at least 1."}; }
         else if (n == "stats-input-hint") {
@@ -297,12 +308,12 @@ Options parse_cli(int argc, char** argv) {
     }
     if (!seen_ref) throw CliError{"Option -r/--reference is required but not set."};
     if (!seen_q) throw CliError{"Option -q/--queries is required but not set."};
-    if (!seen_out) throw CliError{"Option -o/--output is required but not set."};
+    if (!seen_out && o.paf.empty()) throw CliError{"Option -o/--output is required but not set."};      // (a PAF output alone is an output)
     if (!has_ext(o.reference, {"fa", "fasta", "fna", "ffn", "fas", "faa", "mpfa", "frn"}, true)) throw CliError{"Validation failed for option -r/--reference: Expected one of the following valid extensions: [fa,fasta,fna,ffn,fas,faa,mpfa,frn](.gz)."};
     if (!file_readable(o.reference)) throw CliError{"Validation failed for option -r/--reference: The file " + o.reference + " does not exist!"};
     if (!has_ext(o.queries, {"fq", "fastq"}, true)) throw CliError{"Validation failed for option -q/--queries: Expected one of the following valid extensions: [fq,fastq](.gz)."};
     if (!file_readable(o.queries)) throw CliError{"Validation failed for option -q/--queries: The file " + o.queries + " does not exist!"};
-    if (!has_ext(o.output, {"bam", "sam"}, false)) throw CliError{"Validation failed for option -o/--output: Expected one of the following valid extensions: [bam,sam]."};
+    if (seen_out && !has_ext(o.output, {"bam", "sam"}, false)) throw CliError{"Validation failed for option -o/--output: Expected one of the following valid extensions: [bam,sam]."};
     // cross validation, floxer_cli.cpp:173-204
     if (!o.has_query_errors && !o.has_error_probability) throw CliError{"Either a fixed number of errors in the query or an error probability must be given."};
     if (!o.has_error_probability && o.query_errors < o.seed_errors)
@@ -350,6 +361,9 @@ Options parse_cli(int argc, char** argv) {
     if (!o.pileup.empty() && !has_ext(o.pileup, {"tsv"}, false)) throw CliError{"Validation failed for option --pileup: Expected one of the following valid extensions: [tsv]."};
     if (!o.sort_by_coordinate && (o.bam_index || !o.sort_tmp.empty())) throw CliError{"The options --bam-index and --sort-tmp need --sort-by-coordinate."};
     if (o.sort_by_coordinate && !has_ext(o.output, {"bam"}, false)) throw CliError{"The option --sort-by-coordinate writes BAM and needs an -o/--output that ends in .bam."};
+    if (!o.paf.empty() && o.without_cigar) throw CliError{"The option --paf needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.paf.empty() && (o.paf_cigar || o.paf_unmapped || o.paf_skip_secondary)) throw CliError{"The options --paf-cigar, --paf-unmapped and --paf-skip-secondary need --paf."};
+    if (!o.paf.empty() && !has_ext(o.paf, {"paf"}, false)) throw CliError{"Validation failed for option --paf: Expected one of the following valid extensions: [paf]."};
     return o;
 }
 
@@ -810,8 +824,26 @@ int main(int argc, char** argv) {
 
     std::vector<const char*> ref_id_ptrs;
     for (auto const& s : ref.ids) ref_id_ptrs.push_back(s.c_str());
-    flx_sam_writer* out = nullptr;
-    if (o.sort_by_coordinate) {
+    // the PAF output: one summariser per device context, fed with every batch's copied records, and one writer
+    std::vector<flx_paf*> pafs;
+    flx_paf_writer* paf_out = nullptr;
+    if (!o.paf.empty()) {
+        for (int d : devices) {
+            flx_paf* s = nullptr;
+            if (flx_paf_create(d, &s) != FLX_OK) { log_line("error", "cannot set up the PAF summariser: %s", flx_last_error()); return -1; }
+            pafs.push_back(s);
+        }
+        flx_paf_options paf_opt;
+        memset(&paf_opt, 0, sizeof(paf_opt));
+        paf_opt.write_cigar = o.paf_cigar;
+        paf_opt.write_unmapped = o.paf_unmapped;
+        paf_opt.mapq_from_records = o.mapping_quality;
+        paf_opt.skip_secondary = o.paf_skip_secondary;
+        if (flx_paf_open(o.paf.c_str(), ref_id_ptrs.data(), ref.lens.data(), (uint32_t)ref.ids.size(), &paf_opt, &paf_out) != FLX_OK) { log_line("error", "%s", flx_last_error()); return -1; }
+    }
+    flx_sam_writer* out = nullptr;                                 // stays null when --paf is the only output
+    if (o.output.empty()) out = nullptr;
+    else if (o.sort_by_coordinate) {
         // the keys are sorted on the first device; the spill file is <dir>/<output's name>.sort.<pid>.tmp
         size_t const slash = o.output.find_last_of('/');
         std::string const dir = !o.sort_tmp.empty() ? o.sort_tmp : slash == std::string::npos ? std::string(".") : slash == 0 ? std::string("/") : o.output.substr(0, slash);
@@ -841,8 +873,10 @@ int main(int argc, char** argv) {
     out_opt.drop_duplicates = o.drop_duplicate_alignments;
     out_opt.max_alignments_per_read = o.max_alignments;
     out_opt.mapq = o.mapping_quality;            // (the options go with every batch, whichever device context aligns it)
-    flx_sam_set_mapq(out, o.mapping_quality);
-    flx_sam_set_sa(out, o.sa_tag);
+    if (out) {
+        flx_sam_set_mapq(out, o.mapping_quality);
+        flx_sam_set_sa(out, o.sa_tag);
+    }
     flx_tag_options tag_opt;
     memset(&tag_opt, 0, sizeof(tag_opt));
     tag_opt.md = o.md_tag;
@@ -886,20 +920,20 @@ int main(int argc, char** argv) {
 
     struct stat qst;
     stat(o.queries.c_str(), &qst);
-    log_line("info", "aligning queries from a %lld bytes large file against %zu references on the GPU and writing output file to %s", (long long)qst.st_size, ref.ids.size(), o.output.c_str());
+    log_line("info", "aligning queries from a %lld bytes large file against %zu references on the GPU and writing output file to %s", (long long)qst.st_size, ref.ids.size(), out ? o.output.c_str() : o.paf.c_str());
     auto const t_align = std::chrono::steady_clock::now();
     unsigned const n_io = io_threads(o.threads);
     FastqReader qin(o.queries.c_str(), n_io);
     if (!qin.is_open()) { log_line("error", "cannot open %s", o.queries.c_str()); return -1; }
-    flx_sam_set_threads(out, n_io);
+    if (out) flx_sam_set_threads(out, n_io);
     size_t batch_reads = 16384;      // 1024 reads per lane and chunk (see flx_align_reads_resident)
     if (const char* env = getenv("FLX_BATCH_READS")) { size_t const v = strtoull(env, nullptr, 10); if (v) batch_reads = v; }
     // Batches are independent: up to three are in a context at a time (their chunks share its lanes), the next one is parsed
     // while they run, and results are written in input order.
-    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<int32_t> scores; std::vector<flx_md_ref> cs_refs; std::vector<uint8_t> cs; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
+    struct Finished { std::unique_ptr<ReadBatch> batch; std::vector<flx_record> recs; std::vector<uint32_t> cig; std::vector<flx_md_ref> md_refs; std::vector<uint8_t> md; std::vector<int32_t> scores; std::vector<flx_md_ref> cs_refs; std::vector<uint8_t> cs; std::vector<flx_paf_summary> paf; std::vector<uint8_t> skipped; int rc = FLX_OK; std::string err; bool reader_error = false; };
     // FLX_CLI_PROFILE=1: seconds this run spent parsing (this thread), aligning (sum over the batches' tasks) and writing (the writer
     // thread) on stderr at the end: which of the three stages bounds the end-to-end rate
-    std::atomic<uint64_t> us_parse{0}, us_align{0}, us_copy{0}, us_write{0}, us_records{0};
+    std::atomic<uint64_t> us_parse{0}, us_align{0}, us_copy{0}, us_write{0}, us_records{0}, us_paf{0}, us_paf_write{0};
     auto const now_us = [] { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     auto align_batch = [&](std::unique_ptr<ReadBatch> b, flx_ctx* ctx) {
         Finished f;
@@ -947,6 +981,15 @@ int main(int argc, char** argv) {
         }
         flx_run_free(run);
         us_copy += now_us() - t1;
+        if (!pafs.empty()) {
+            uint64_t const t2 = now_us();
+            size_t const at = std::find(ctxs.begin(), ctxs.end(), ctx) - ctxs.begin();
+            f.paf.resize(f.recs.size() + 1);
+            f.rc = flx_paf_summarize(pafs[at], f.recs.data(), f.recs.size(), f.cig.data(), f.cig.size() - 1, b->offsets.data(), b->ids.size(), ref.lens.data(),
+                                     (uint32_t)ref.ids.size(), f.paf.data());
+            us_paf += now_us() - t2;
+            if (f.rc != FLX_OK) { f.err = flx_last_error(); f.batch = std::move(b); return f; }
+        }
         f.batch = std::move(b);
         return f;
     };
@@ -972,10 +1015,16 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < f.skipped.size(); ++i)
             if (f.skipped[i]) log_line("warning", "skipping query: %s due to bad configuration regarding the number of errors.", batch.ids[i]);
         uint64_t const t0 = now_us();
-        if (flx_sam_write_cs(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
+        if (out && flx_sam_write_cs(out, batch.ids.data(), batch.pool.data(), batch.offsets.data(), batch.quals.data(), f.recs.data(), f.recs.size(), f.cig.data(),
                              o.md_tag ? f.md_refs.data() : nullptr, f.md.data(), o.realign_affine ? f.scores.data() : nullptr,
                              cs_opt.form ? f.cs_refs.data() : nullptr, f.cs.data()) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
         us_write += now_us() - t0;
+        if (paf_out && !failed.load()) {
+            uint64_t const t1 = now_us();
+            if (flx_paf_write(paf_out, batch.ids.data(), batch.offsets.data(), f.recs.data(), f.recs.size(), f.cig.data(), f.paf.data(),
+                              o.realign_affine ? f.scores.data() : nullptr, cs_opt.form ? f.cs_refs.data() : nullptr, f.cs.data()) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+            us_paf_write += now_us() - t1;
+        }
         total_reads += batch.ids.size();
         total_records += f.recs.size();
         log_line("debug", "finished a batch: %llu queries, %llu records so far", (unsigned long long)total_reads, (unsigned long long)total_records);
@@ -1029,7 +1078,9 @@ int main(int argc, char** argv) {
     q_cv.notify_all();
     writer.join();
     auto const t_close = std::chrono::steady_clock::now();
-    if (flx_sam_close(out) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+    if (paf_out && flx_paf_close(paf_out) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
+    for (flx_paf* s : pafs) flx_paf_free(s);
+    if (out && flx_sam_close(out) != FLX_OK) { log_line("error", "%s", flx_last_error()); failed.store(true); }
     else if (o.sort_by_coordinate) log_line("info", "sorting the keys, merging the spilled batches%s took %.3f seconds", o.bam_index ? " and writing the index" : "", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_close).count());
     // (the alignment phase ends with the output file: floxer.cpp:154-179 stops its watch there; giving 40 GB of HBM back is not part of it)
     double const secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_align).count();
@@ -1045,6 +1096,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "[flx cli profile] reader thread: reading %.2f s, line ends %.2f s; records (ids, rank encoding: in the batches' own tasks) %.2f s\n", qin.s_read, qin.s_scan, us_records.load() / 1e6);
         fprintf(stderr, "[flx cli profile] wall %.2f s: parsing %.2f s (reader thread), aligning %.2f s summed over %llu batches (up to %zu in flight), copying results %.2f s, writing %.2f s (writer thread, %u I/O threads)\n",
                 secs, us_parse.load() / 1e6, us_align.load() / 1e6, (unsigned long long)n_batches, max_in_flight, us_copy.load() / 1e6, us_write.load() / 1e6, n_io);
+        if (!o.paf.empty()) fprintf(stderr, "[flx cli profile] PAF: summaries %.2f s summed over the batches' tasks, writing %.2f s (writer thread)\n", us_paf.load() / 1e6, us_paf_write.load() / 1e6);
     }
     if (stats) {                                                                       // floxer.cpp:182-192
         uint64_t len = 0;

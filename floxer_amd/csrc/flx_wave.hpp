@@ -29,5 +29,12 @@ __device__ __forceinline__ i64 wave_inclusive_scan(i64 v) {
     }
     return v;
 }
+// The sum of v over the 64 lanes of a wave, in every lane: six __shfl_xor steps over 64-bit values, no LDS; every lane of the wave must
+// call it.
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+#pragma unroll
+    for (u32 d = 1; d < 64u; d <<= 1) v += (u64)__shfl_xor((unsigned long long)v, (int)d);
+    return v;
+}
 
 }  // namespace flx

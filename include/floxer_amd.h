@@ -814,6 +814,59 @@ int  flx_sort_geometry(uint32_t out[4]);
 int  flx_sort_host(uint32_t n_refs, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
                    const uint64_t* ordinals, flx_sort_entry* out_sorted);
 
+/* ------------------------------------------------------------------------------------------------ PAF output
+ * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
+ * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
+ * I 1, D 2, S 4:
+ *     lead / trail = the summed S words in front of the first / behind the last non-S word;
+ *     matches, mismatches, ins_bases, del_bases = the summed lengths of the = X I D words;
+ *     gap_opens = the I and D words that are the record's first word or whose predecessor has another op;
+ *     ref_end = position + matches + mismatches + del_bases;
+ *     query_start, query_end on the read as given: lead and read_len - trail, with flag & 16 trail and read_len - lead.
+ *   - a record with flag & 4 or reference_id < 0 gets all zeros; secondary and supplementary records are summarised like any other;
+ *   - refused (FLX_ERR_INVALID, on the host before any launch; `out` stays as it was): a mapped record without words (a without_cigar
+ *     run), an op other than = X I D S, a zero-length word, a reference_id outside the list, a negative position, a span that ends
+ *     behind its sequence, words outside the pool, an S word with non-S words on both sides, a read_index outside the reads,
+ *     lead + matches + mismatches + ins_bases + trail != the read's length, no reference-consuming column, a sum of 2^31 or more;
+ *   - flx_paf_summarize judges on the host, uploads one 24-byte job per record and the stretch of the word pool the records use, runs
+ *     paf_summarise (floxer_amd/csrc/flx_paf.hip: one wave per record, 64 words per pass) and downloads 32 bytes per record. n == 0:
+ *     FLX_OK without a launch. A record the kernel still finds in breach of the rule has 0xFFFFFFFF in every field and the call returns
+ *     FLX_ERR_INTERNAL. The object owns its stream and its grow-only device buffers; a failed growth is FLX_ERR_NO_DEVICE and leaves
+ *     the object as it was. Calls on one object may come from several host threads: the records are judged outside the object's lock,
+ *     upload, launch and download are serialised inside it. hip_device = -1: no device is opened and the call applies the host rule;
+ *   - flx_paf_summarize_host: the rule alone on the host, no device.
+ * FLX_PAF_PROFILE (environment): every flx_paf_summarize prints its records, words, uploaded bytes, the kernel's device time and the
+ * call's wall time to stderr.
+ *
+ * The writer is host-only and writes one line per mapped record in call order, the fields separated by tabs:
+ *     qname qlen query_start query_end strand tname tlen position ref_end matches block mapq, block = matches + mismatches + ins_bases +
+ *     del_bases, mapq 255 or, with mapq_from_records, flx_record.reserved (above 254: FLX_ERR_INVALID, as flx_sam_set_mapq has it),
+ *     then tp:A:S for flag & 256 and tp:A:P otherwise (supplementary records are P, as in minimap2), NM:i: with num_errors, AS:i: when
+ *     scores are given, de:f: the gap-compressed divergence (mismatches + gap_opens) / (matches + mismatches + gap_opens) rounded half
+ *     up to four decimals in integers, cg:Z: with write_cigar (the record's own words as <len><op>, = and X kept, S included: minimap2's
+ *     --eqx form), cs:Z: when cs_refs is given and the record's length there is above 0.
+ * skip_secondary leaves out records with flag & 256; write_unmapped writes `qname qlen 0 0 * * 0 0 0 0 0 0` (minimap2's --paf-no-hit
+ * form, no tags) for a record with flag & 4 or reference_id < 0, which otherwise produces no line. A call is formatted in full before
+ * any byte of it is written: a refused call (a summary whose fields are all 0xFFFFFFFF, a summary without columns, a mapped record
+ * outside the references, a cs byte outside [0-9:*+=acgtnACGTN-]) writes nothing. options NULL: all zero; the switches are 0 or 1 and
+ * the reserved fields 0. */
+typedef struct flx_paf flx_paf;
+typedef struct flx_paf_summary { uint32_t query_start, query_end, ref_end, matches /* = */, mismatches /* X */, ins_bases, del_bases, gap_opens; } flx_paf_summary;
+typedef struct flx_paf_options { uint32_t write_cigar, write_unmapped, mapq_from_records, skip_secondary; uint32_t reserved[4]; } flx_paf_options;
+typedef struct flx_paf_writer flx_paf_writer;
+int  flx_paf_create(int hip_device, flx_paf** out);
+void flx_paf_free(flx_paf* p);
+int  flx_paf_summarize(flx_paf* p, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                       const uint64_t* read_offsets, uint64_t n_reads, const uint64_t* ref_lens, uint32_t n_refs, flx_paf_summary* out);
+int  flx_paf_summarize_host(const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                            const uint64_t* read_offsets, uint64_t n_reads, const uint64_t* ref_lens, uint32_t n_refs, flx_paf_summary* out);
+int  flx_paf_open(const char* path, const char* const* ref_ids, const uint64_t* ref_lens, uint32_t n_refs, const flx_paf_options* o,
+                  flx_paf_writer** out);
+int  flx_paf_write(flx_paf_writer* w, const char* const* read_ids, const uint64_t* read_offsets, const flx_record* records, uint64_t n,
+                   const uint32_t* cigar_words, const flx_paf_summary* summaries, const int32_t* scores /* may be NULL */,
+                   const flx_md_ref* cs_refs /* may be NULL */, const uint8_t* cs_bytes);
+int  flx_paf_close(flx_paf_writer* w);
+
 uint64_t flx_run_num_records(const flx_run* run);
 uint64_t flx_run_num_cigar_words(const flx_run* run);
 int flx_run_copy(const flx_run* run, flx_record* records, uint32_t* cigar_words, uint8_t* skipped);
