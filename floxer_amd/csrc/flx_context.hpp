@@ -23,6 +23,16 @@ namespace flx {
         }                                                                                               \
     } while (0)
 
+// the one check of a launch: rc is the hipError_t that a launch function returned
+#define FLX_LAUNCH(name, rc)                                                                            \
+    do {                                                                                                \
+        int const e__ = (rc);                                                                           \
+        if (e__ != 0) {                                                                                 \
+            set_error(std::string(name) + ": launch failed: " + hipGetErrorString((hipError_t)e__));    \
+            return FLX_ERR_NO_DEVICE;                                                                   \
+        }                                                                                               \
+    } while (0)
+
 struct DeviceBuffer {
     void* ptr = nullptr;
     size_t cap = 0;
@@ -167,15 +177,14 @@ struct ResultScope {
 template <class F>
 int timed_launch(Lane* lane, const char* name, u64 bytes, u64 units, F&& launch) {
     if (!lane->ctx->timing) {
-        int const rc = launch();
-        if (rc != 0) { set_error(std::string(name) + ": launch failed: " + hipGetErrorString((hipError_t)rc)); return FLX_ERR_NO_DEVICE; }
+        FLX_LAUNCH(name, launch());
         return FLX_OK;
     }
     hipEvent_t const a = lane->get_event(), b = lane->get_event();
     FLX_HIP(hipEventRecord(a, lane->stream));
     int const rc = launch();
     FLX_HIP(hipEventRecord(b, lane->stream));
-    if (rc != 0) { set_error(std::string(name) + ": launch failed: " + hipGetErrorString((hipError_t)rc)); return FLX_ERR_NO_DEVICE; }
+    FLX_LAUNCH(name, rc);
     lane->pending.push_back(PendingTiming{name, a, b, bytes, units});
     return FLX_OK;
 }

@@ -4,23 +4,21 @@
 //                     wave-uniform carry between passes, gives every word its first position; a counted word adds +1 there and -1 behind
 //                     its last column (device-scope integer atomicAdd). Neighbouring counted words of a pass (= then X) share a
 //                     boundary whose +1 and -1 cancel: neither is issued.
-//   coverage_scan_*   the inclusive prefix sum that turns the differences into depths, in place: sums per tile, a scan of the tile sums
-//                     (the same launches again while there are more sums than one tile), the apply pass. No block waits for another
-//                     block: no look-back, no flags, no spins.
+//   (the scan)        the inclusive prefix sum that turns the differences into depths, in place: flx_scan.hip.
 //   coverage_heads    a position is a run head when it is the first of a sequence or its depth differs from its predecessor's. Mode 0
-//                     counts the heads per tile (all of them, and those that are reported), the counts are scanned with the scan above,
+//                     counts the heads per tile (all of them, and those that are reported), the counts are scanned with the same scan,
 //                     mode 1 writes the positions of all heads, mode 2 writes the reported runs: a run ends where the next head starts.
 //   coverage_windows  one segmented reduction for every window size: a lane folds a strip of 16 positions, flushing when a window ends
 //                     inside the strip, the wave folds its lanes by window with a segmented scan, the last lane of a window adds the
 //                     wave's part to the window (64-bit atomicAdd, atomicMax).
-//   coverage_sum      into += from, for flx_coverage_absorb.
+// flx_coverage_absorb adds another object's array with flx_scan.hip's sum.
 // All stores are plain C++ vector stores; arithmetic on depths is modulo 2^32 (the differences are i32, their prefix sums never negative).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "flx_coverage.hpp"
-#include "flx_coverage_dev.hpp"
+#include "flx_scan_dev.hpp"
 #include "flx_wave.hpp"
 
 namespace flx {
@@ -48,34 +46,6 @@ __global__ void __launch_bounds__(THREADS) coverage_add_kernel(const CoverageJob
             pos += __shfl(incl, 63);
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------ the scan
-__global__ void __launch_bounds__(THREADS) coverage_scan_sums_kernel(const u32* __restrict__ a, u64 n, u32* __restrict__ sums) {
-    __shared__ u32 lds[THREADS / 64u];
-    u32 v[STRIP];
-    load_strip(a, n, (u64)blockIdx.x * TILE + (u64)threadIdx.x * STRIP, v);
-    u32 s = 0;
-#pragma unroll
-    for (u32 i = 0; i < STRIP; ++i) s += v[i];
-    u32 total;
-    (void)block_exclusive_scan(s, lds, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// scanned: the tile sums after their own inclusive scan (tile b starts from scanned[b - 1]); null for an array of one tile
-__global__ void __launch_bounds__(THREADS) coverage_scan_apply_kernel(u32* __restrict__ a, u64 n, const u32* __restrict__ scanned) {
-    __shared__ u32 lds[THREADS / 64u];
-    u64 const p0 = (u64)blockIdx.x * TILE + (u64)threadIdx.x * STRIP;
-    u32 v[STRIP];
-    load_strip(a, n, p0, v);
-#pragma unroll
-    for (u32 i = 1; i < STRIP; ++i) v[i] += v[i - 1];
-    u32 total;
-    u32 const before = block_exclusive_scan(v[STRIP - 1], lds, total) + (scanned && blockIdx.x > 0 ? scanned[blockIdx.x - 1] : 0u);
-#pragma unroll
-    for (u32 i = 0; i < STRIP; ++i) v[i] += before;
-    store_strip(a, n, p0, v);
 }
 
 // ------------------------------------------------------------------------------------------------ run heads
@@ -195,18 +165,6 @@ __global__ void __launch_bounds__(THREADS) coverage_windows_kernel(const u32* __
     if (part.key != ~0ull && (lane == 63u || next_key != part.key)) window_flush(out, part);
 }
 
-// ------------------------------------------------------------------------------------------------ coverage_sum
-__global__ void __launch_bounds__(THREADS) coverage_sum_kernel(u32* __restrict__ into, const u32* __restrict__ from, u64 n) {
-    u64 const p0 = (u64)blockIdx.x * TILE + (u64)threadIdx.x * STRIP;
-    if (p0 >= n) return;
-    u32 a[STRIP], b[STRIP];
-    load_strip(into, n, p0, a);
-    load_strip(from, n, p0, b);
-#pragma unroll
-    for (u32 i = 0; i < STRIP; ++i) a[i] += b[i];
-    store_strip(into, n, p0, a);
-}
-
 // ------------------------------------------------------------------------------------------------ launches (each one checked)
 static inline u32 tiles_of(u64 n) { return (u32)((n + TILE - 1) / TILE); }
 
@@ -214,14 +172,6 @@ int CoverageDevice::add(void* stream, const CoverageJob* d_jobs, u32 n_jobs, con
     if (n_jobs == 0) return 0;
     u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), 1u << 16);
     hipLaunchKernelGGL(coverage_add_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words, reinterpret_cast<int*>(d_acc), count_deletions);
-    return (int)hipGetLastError();
-}
-int CoverageDevice::scan_sums(void* stream, const u32* d_a, u64 n, u32* d_sums) {
-    hipLaunchKernelGGL(coverage_scan_sums_kernel, dim3(tiles_of(n)), dim3(THREADS), 0, (hipStream_t)stream, d_a, n, d_sums);
-    return (int)hipGetLastError();
-}
-int CoverageDevice::scan_apply(void* stream, u32* d_a, u64 n, const u32* d_scanned) {
-    hipLaunchKernelGGL(coverage_scan_apply_kernel, dim3(tiles_of(n)), dim3(THREADS), 0, (hipStream_t)stream, d_a, n, d_scanned);
     return (int)hipGetLastError();
 }
 int CoverageDevice::heads(void* stream, int mode, const u32* d_depth, u64 total, const u32* d_starts, u32 n_refs, u32 report_zero, u32* d_count_all,
@@ -235,11 +185,6 @@ int CoverageDevice::heads(void* stream, int mode, const u32* d_depth, u64 total,
 int CoverageDevice::windows(void* stream, const u32* d_depth, u64 total, const u32* d_starts, u32 n_refs, u64 window, const u64* d_bases, CoverageWindowAcc* d_out) {
     hipLaunchKernelGGL(coverage_windows_kernel, dim3(tiles_of(total)), dim3(THREADS), 0, (hipStream_t)stream, d_depth, total, d_starts, n_refs,
                        window == 0 || window >= COVERAGE_MAX_TOTAL ? COVERAGE_MAX_TOTAL : window, d_bases, d_out);
-    return (int)hipGetLastError();
-}
-int CoverageDevice::sum(void* stream, u32* d_into, const u32* d_from, u64 n) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(coverage_sum_kernel, dim3(tiles_of(n)), dim3(THREADS), 0, (hipStream_t)stream, d_into, d_from, n);
     return (int)hipGetLastError();
 }
 

@@ -14,7 +14,9 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "flx_internal.hpp"
@@ -86,6 +88,31 @@ inline bool coverage_plan(std::vector<u64> const& starts, flx_coverage_options c
     return true;
 }
 
+// Where the words of judged jobs (CoverageJob, PileupJob: word_off, n_words) lie in the pool that goes up: every word once, however many
+// jobs refer to it. pool receives the words in use in the order of the original pool, every job's word_off then indexes `pool`.
+template <class Job>
+void compact_words(std::vector<Job>& jobs, const uint32_t* cigar_words, std::vector<u32>& pool) {
+    struct Segment { u64 from, to, base; };
+    std::vector<std::pair<u64, u64>> spans;
+    spans.reserve(jobs.size());
+    for (auto const& j : jobs) spans.emplace_back(j.word_off, j.word_off + j.n_words);
+    std::sort(spans.begin(), spans.end());
+    std::vector<Segment> segments;
+    for (auto const& s : spans) {
+        if (!segments.empty() && s.first <= segments.back().to) segments.back().to = std::max(segments.back().to, s.second);
+        else segments.push_back(Segment{s.first, s.second, 0});
+    }
+    u64 used = 0;
+    for (auto& s : segments) { s.base = used; used += s.to - s.from; }
+    pool.resize(used);
+    for (auto const& s : segments) memcpy(pool.data() + s.base, cigar_words + s.from, (s.to - s.from) * 4);
+    for (auto& j : jobs) {
+        auto it = std::upper_bound(segments.begin(), segments.end(), j.word_off, [](u64 off, Segment const& s) { return off < s.from; });
+        Segment const& s = *(it - 1);
+        j.word_off = s.base + (j.word_off - s.from);
+    }
+}
+
 // the walk of one judged job, column by column into `depth`
 inline void coverage_walk(CoverageJob const& j, const uint32_t* cigar_words, bool count_deletions, uint32_t* depth) {
     u64 p = j.text_off;
@@ -112,15 +139,11 @@ inline void coverage_window_bases(std::vector<u64> const& starts, u64 window, st
 // concatenation, d_starts holds the n_refs + 1 sequence starts as u32)
 struct CoverageWindowAcc { unsigned long long depth_sum, covered; u32 max_depth, pad; };
 struct CoverageDevice {
-    static constexpr u32 SCAN_TILE = 4096;             // elements per scan tile, and tile sums one block of the next level scans
     static int add(void* stream, const CoverageJob* d_jobs, u32 n_jobs, const u32* d_words, u32* d_acc, u32 count_deletions);
-    static int scan_sums(void* stream, const u32* d_a, u64 n, u32* d_sums);
-    static int scan_apply(void* stream, u32* d_a, u64 n, const u32* d_scanned);
     // mode 0: the tiles' head counts; 1: the positions of all heads; 2: the reported runs (d_count_* scanned by then)
     static int heads(void* stream, int mode, const u32* d_depth, u64 total, const u32* d_starts, u32 n_refs, u32 report_zero, u32* d_count_all,
                      u32* d_count_rep, u32* d_heads, u64 n_heads, flx_depth_run* d_out);
     static int windows(void* stream, const u32* d_depth, u64 total, const u32* d_starts, u32 n_refs, u64 window, const u64* d_bases, CoverageWindowAcc* d_out);
-    static int sum(void* stream, u32* d_into, const u32* d_from, u64 n);
 };
 
 }  // namespace flx

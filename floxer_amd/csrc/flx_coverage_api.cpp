@@ -1,118 +1,36 @@
 // flx_coverage: the object behind the depth-of-coverage calls of the C ABI (include/floxer_amd.h). The rule and its checks:
-// flx_coverage.hpp; the kernels: flx_coverage.hip. The object owns one stream, the accumulator (a u32 per position of the concatenation
-// plus one, differences until flx_coverage_finish, depths behind it) and its staging buffers. Adds judge their records without the
-// object's lock and take it for the staging and the launch only, so several host threads may add at once.
+// flx_coverage.hpp; the kernels: flx_coverage.hip, the scan and the sum: flx_scan.hip; what it shares with the other side objects:
+// flx_object.hpp. The object owns one stream, the accumulator (a u32 per position of the concatenation plus one, differences until
+// flx_coverage_finish, depths behind it) and its staging buffers. Adds judge their records without the object's lock and take it for the
+// staging and the launch only, so several host threads may add at once.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <memory>
 #include <mutex>
-#include <thread>
 
 #include "flx_coverage.hpp"
-#include "flx_pipeline.hpp"
+#include "flx_object.hpp"
 
 using namespace flx;
 
-struct flx_coverage {
-    int device = 0;
+struct flx_coverage : PlaneObject {      // acc: total + 1 entries; FLX_COVERAGE_PROFILE: every add prints its upload, its kernel's device time and its wall time
     flx_coverage_options opt{};
-    std::vector<u64> starts;             // n_refs + 1
-    u64 total = 0;
-    hipStream_t stream = nullptr;
-    DeviceBuffer acc, d_starts;          // total + 1 entries; the starts as u32
     DeviceBuffer jobs, words;            // an add's staging: the counted records and the words they refer to
-    DeviceBuffer levels;                 // the scan's tile sums, one array per level (level_off, in entries)
-    std::vector<u64> level_off;
     DeviceBuffer count_all, count_rep;   // per tile of the accumulator: heads / reported heads, scanned by finish
-    DeviceBuffer chunk;                  // absorb: a piece of the other object's accumulator on this device
-    PinnedBuffer pinned;                 // absorb: the same piece on its way through the host
-    std::mutex mu;                       // staging, launches and `finished`
-    bool finished = false;
     u64 n_heads = 0, n_runs = 0;
-    bool profile = false;                // FLX_COVERAGE_PROFILE set (and not 0): every add prints its upload, its kernel's device time and its wall time to stderr
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    ~flx_coverage() {
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    u32 n_refs() const { return (u32)(starts.size() - 1); }
 };
 
 namespace {
 
-constexpr u64 TILE = CoverageDevice::SCAN_TILE;
-constexpr u64 ABSORB_CHUNK = 4ull << 20;             // entries per piece (16 MB)
-
-#define COV_LAUNCH(name, expr)                                                                                                     \
-    do {                                                                                                                           \
-        int const e__ = (expr);                                                                                                    \
-        if (e__ != 0) { set_error(std::string(name) + ": launch failed: " + hipGetErrorString((hipError_t)e__)); return FLX_ERR_NO_DEVICE; } \
-    } while (0)
-
-u64 tiles_of(u64 n) { return (n + TILE - 1) / TILE; }
-
-// inclusive prefix sum of a[0, n) in place; the tile sums of this level live in levels[level]
-int scan_in_place(flx_coverage* c, u32* a, u64 n, size_t level) {
-    u64 const nt = tiles_of(n);
-    if (nt <= 1) { COV_LAUNCH("coverage_scan_apply", CoverageDevice::scan_apply(c->stream, a, n, nullptr)); return FLX_OK; }
-    u32* const sums = c->levels.as<u32>() + c->level_off[level];
-    COV_LAUNCH("coverage_scan_sums", CoverageDevice::scan_sums(c->stream, a, n, sums));
-    int const rc = scan_in_place(c, sums, nt, level + 1);
-    if (rc) return rc;
-    COV_LAUNCH("coverage_scan_apply", CoverageDevice::scan_apply(c->stream, a, n, sums));
-    return FLX_OK;
-}
-
 int create(int device, std::vector<u64>&& starts, const flx_coverage_options* o, flx_coverage** out) {
-    FLX_HIP(hipSetDevice(device));
     auto c = std::make_unique<flx_coverage>();       // (an error below drops it: nothing stays allocated)
-    c->device = device;
     c->opt = coverage_options_or_default(o);
-    c->starts = std::move(starts);
-    c->total = c->starts.back();
-    if (const char* env = getenv("FLX_COVERAGE_PROFILE")) c->profile = strtol(env, nullptr, 10) != 0 || env[0] == '\0';
-    FLX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    int rc = c->acc.ensure((c->total + 1) * 4, true);
+    u64 const entries = starts.back() + 1;
+    int const rc = c->create(device, "FLX_COVERAGE_PROFILE", std::move(starts), entries, {&c->count_all, &c->count_rep});
     if (rc) return rc;
-    FLX_HIP(hipMemsetAsync(c->acc.ptr, 0, (c->total + 1) * 4, c->stream));
-    std::vector<u32> starts32(c->starts.begin(), c->starts.end());
-    if ((rc = c->d_starts.ensure(starts32.size() * 4, true))) return rc;
-    FLX_HIP(hipMemcpyAsync(c->d_starts.ptr, starts32.data(), starts32.size() * 4, hipMemcpyHostToDevice, c->stream));
-    u64 entries = 0;
-    for (u64 nt = tiles_of(c->total); nt > 1; nt = tiles_of(nt)) { c->level_off.push_back(entries); entries += (nt + 63) / 64 * 64; }
-    if (entries && (rc = c->levels.ensure(entries * 4, true))) return rc;
-    u64 const nt = tiles_of(c->total);
-    if ((rc = c->count_all.ensure(nt * 4, true)) || (rc = c->count_rep.ensure(nt * 4, true))) return rc;
-    FLX_HIP(hipStreamSynchronize(c->stream));
     *out = c.release();
     return FLX_OK;
-}
-
-// where the words of the counted records lie in the pool that goes up: every word once, however many records refer to it
-void compact_words(std::vector<CoverageJob>& jobs, const uint32_t* cigar_words, std::vector<u32>& pool) {
-    struct Segment { u64 from, to, base; };
-    std::vector<std::pair<u64, u64>> spans;
-    spans.reserve(jobs.size());
-    for (auto const& j : jobs) spans.emplace_back(j.word_off, j.word_off + j.n_words);
-    std::sort(spans.begin(), spans.end());
-    std::vector<Segment> segments;
-    for (auto const& s : spans) {
-        if (!segments.empty() && s.first <= segments.back().to) segments.back().to = std::max(segments.back().to, s.second);
-        else segments.push_back(Segment{s.first, s.second, 0});
-    }
-    u64 used = 0;
-    for (auto& s : segments) { s.base = used; used += s.to - s.from; }
-    pool.resize(used);
-    for (auto const& s : segments) memcpy(pool.data() + s.base, cigar_words + s.from, (s.to - s.from) * 4);
-    for (auto& j : jobs) {
-        auto it = std::upper_bound(segments.begin(), segments.end(), j.word_off, [](u64 off, Segment const& s) { return off < s.from; });
-        Segment const& s = *(it - 1);
-        j.word_off = s.base + (j.word_off - s.from);
-    }
 }
 
 // the judged jobs of one word pool: staged and launched under the object's lock
@@ -129,28 +47,18 @@ int commit(flx_coverage* c, std::vector<CoverageJob>& jobs, const uint32_t* ciga
     if ((rc = c->jobs.ensure(jobs.size() * sizeof(CoverageJob))) || (rc = c->words.ensure(pool.size() * 4))) return rc;
     FLX_HIP(hipMemcpyAsync(c->jobs.ptr, jobs.data(), jobs.size() * sizeof(CoverageJob), hipMemcpyHostToDevice, c->stream));
     FLX_HIP(hipMemcpyAsync(c->words.ptr, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (c->profile) {
-        if (!c->ev_a) { FLX_HIP(hipEventCreate(&c->ev_a)); FLX_HIP(hipEventCreate(&c->ev_b)); }
-        FLX_HIP(hipEventRecord(c->ev_a, c->stream));
-    }
-    COV_LAUNCH("coverage_add", CoverageDevice::add(c->stream, c->jobs.as<CoverageJob>(), (u32)jobs.size(), c->words.as<u32>(), c->acc.as<u32>(), c->opt.count_deletions));
-    if (c->profile) FLX_HIP(hipEventRecord(c->ev_b, c->stream));
+    if ((rc = c->span_begin())) return rc;
+    FLX_LAUNCH("coverage_add", CoverageDevice::add(c->stream, c->jobs.as<CoverageJob>(), (u32)jobs.size(), c->words.as<u32>(), c->acc.as<u32>(), c->opt.count_deletions));
+    if ((rc = c->span_end())) return rc;
     FLX_HIP(hipStreamSynchronize(c->stream));           // (the staging buffers are free for the next add)
     if (c->profile) {
-        float ms = 0;
-        FLX_HIP(hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+        float ms;
+        if ((rc = c->span_ms(ms))) return rc;
         double const wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[flx coverage] add: records %zu words %zu upload_bytes %zu coverage_add_ms %.3f wall_ms_behind_the_checks %.3f\n", jobs.size(), pool.size(),
                 jobs.size() * sizeof(CoverageJob) + pool.size() * 4, (double)ms, wall);
     }
     return FLX_OK;
-}
-
-bool finished_for_copy(const flx_coverage* c, const char* who) {
-    if (!c) { set_error(std::string(who) + ": null argument"); return false; }
-    std::lock_guard<std::mutex> g(const_cast<flx_coverage*>(c)->mu);
-    if (!c->finished) { set_error(std::string(who) + ": call flx_coverage_finish first"); return false; }
-    return true;
 }
 
 }  // namespace
@@ -167,11 +75,7 @@ extern "C" int flx_coverage_create(flx_ctx* ctx, const flx_coverage_options* o, 
     if (!coverage_options_valid(o) || !coverage_lengths_valid(ctx->hidx->seq_len.data(), (uint32_t)ctx->hidx->seq_len.size(), "flx_coverage_create", starts)) return FLX_ERR_INVALID;
     return create(ctx->device, std::move(starts), o, out);
 }
-extern "C" void flx_coverage_free(flx_coverage* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    delete c;
-}
+extern "C" void flx_coverage_free(flx_coverage* c) { free_object(c); }
 
 extern "C" int flx_coverage_add_records(flx_coverage* c, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words) {
     if (!c || (n && !records)) { set_error("flx_coverage_add_records: null argument"); return FLX_ERR_INVALID; }
@@ -182,29 +86,13 @@ extern "C" int flx_coverage_add_records(flx_coverage* c, const flx_record* recor
 extern "C" int flx_coverage_add_run(flx_coverage* c, const flx_run* run) {
     if (!c || !run) { set_error("flx_coverage_add_run: null argument"); return FLX_ERR_INVALID; }
     if (c->opt.min_mapq > 0 && !run->has_mapq) { set_error("flx_coverage_add_run: min_mapq needs a run made with flx_output_options.mapq"); return FLX_ERR_INVALID; }
-    // a run is its own records plus its per-lane parts, each over its own word pool: all are judged before any is added
-    std::vector<const flx_run*> pieces{run};
-    for (auto const& p : run->parts) pieces.push_back(&p);
-    // (the parts are independent: each is judged by a thread of its own, up to eight at a time; the first refusal in part order is reported)
+    // all pieces are judged before any is added
+    auto const pieces = run_pieces(run);
     std::vector<std::vector<CoverageJob>> jobs(pieces.size());
-    std::vector<std::string> refusals(pieces.size());
-    std::vector<char> refused(pieces.size(), 0);
-    auto judge = [&](size_t i) {
-        if (!coverage_plan(c->starts, c->opt, pieces[i]->records.data(), pieces[i]->records.size(), pieces[i]->cigars.data(), pieces[i]->cigars.size(), "flx_coverage_add_run", jobs[i])) {
-            refused[i] = 1;
-            refusals[i] = flx_last_error();      // (the message is the judging thread's own)
-        }
-    };
-    size_t const n_threads = std::min<size_t>(8, pieces.size());
-    if (n_threads <= 1) for (size_t i = 0; i < pieces.size(); ++i) judge(i);
-    else {
-        std::vector<std::thread> threads;
-        for (size_t t = 0; t < n_threads; ++t)
-            threads.emplace_back([&, t] { for (size_t i = t; i < pieces.size(); i += n_threads) judge(i); });
-        for (auto& t : threads) t.join();
-    }
-    for (size_t i = 0; i < pieces.size(); ++i)
-        if (refused[i]) { set_error(refusals[i]); return FLX_ERR_INVALID; }
+    if (!judge_in_parallel(pieces.size(), [&](size_t i) {
+            return coverage_plan(c->starts, c->opt, pieces[i]->records.data(), pieces[i]->records.size(), pieces[i]->cigars.data(), pieces[i]->cigars.size(), "flx_coverage_add_run", jobs[i]);
+        }))
+        return FLX_ERR_INVALID;
     for (size_t i = 0; i < pieces.size(); ++i) {
         int const rc = commit(c, jobs[i], pieces[i]->cigars.data(), "flx_coverage_add_run");
         if (rc) return rc;
@@ -219,24 +107,8 @@ extern "C" int flx_coverage_absorb(flx_coverage* into, flx_coverage* from) {
     if (into->finished || from->finished) { set_error("flx_coverage_absorb: a coverage object is finished"); return FLX_ERR_INVALID; }
     if (into->starts != from->starts) { set_error("flx_coverage_absorb: the objects belong to different reference lengths"); return FLX_ERR_INVALID; }
     if (!coverage_options_equal(into->opt, from->opt)) { set_error("flx_coverage_absorb: the objects have different options"); return FLX_ERR_INVALID; }
-    u64 const n = into->total + 1, piece = std::min(n, ABSORB_CHUNK);
-    FLX_HIP(hipSetDevice(into->device));
-    int rc;
-    if ((rc = into->pinned.ensure(piece * 4)) || (rc = into->chunk.ensure(piece * 4, true))) return rc;
-    for (u64 at = 0; at < n; at += piece) {
-        u64 const m = std::min(piece, n - at);
-        FLX_HIP(hipSetDevice(from->device));
-        FLX_HIP(hipMemcpyAsync(into->pinned.ptr, from->acc.as<u32>() + at, m * 4, hipMemcpyDeviceToHost, from->stream));
-        FLX_HIP(hipStreamSynchronize(from->stream));
-        FLX_HIP(hipSetDevice(into->device));
-        FLX_HIP(hipMemcpyAsync(into->chunk.ptr, into->pinned.ptr, m * 4, hipMemcpyHostToDevice, into->stream));
-        COV_LAUNCH("coverage_sum", CoverageDevice::sum(into->stream, into->acc.as<u32>() + at, into->chunk.as<u32>(), m));
-        FLX_HIP(hipStreamSynchronize(into->stream));    // (the piece's buffers are free again)
-    }
-    FLX_HIP(hipSetDevice(from->device));
-    FLX_HIP(hipMemsetAsync(from->acc.ptr, 0, n * 4, from->stream));
-    FLX_HIP(hipStreamSynchronize(from->stream));
-    return FLX_OK;
+    int const rc = absorb_plane(into, from, into->acc.as<u32>(), from->acc.as<u32>(), into->total + 1);
+    return rc ? rc : from->clear();
 }
 
 extern "C" int flx_coverage_finish(flx_coverage* c) {
@@ -244,12 +116,12 @@ extern "C" int flx_coverage_finish(flx_coverage* c) {
     std::lock_guard<std::mutex> g(c->mu);
     if (c->finished) { set_error("flx_coverage_finish: the coverage object is finished"); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(c->device));
-    int rc = scan_in_place(c, c->acc.as<u32>(), c->total, 0);
+    int rc = c->scan.inclusive(c->stream, c->acc.as<u32>(), c->total);
     if (rc) return rc;
-    u64 const nt = tiles_of(c->total);
-    COV_LAUNCH("coverage_heads", CoverageDevice::heads(c->stream, 0, c->acc.as<u32>(), c->total, c->d_starts.as<u32>(), c->n_refs(), c->opt.report_zero,
-                                                      c->count_all.as<u32>(), c->count_rep.as<u32>(), nullptr, 0, nullptr));
-    if ((rc = scan_in_place(c, c->count_all.as<u32>(), nt, 1)) || (rc = scan_in_place(c, c->count_rep.as<u32>(), nt, 1))) return rc;
+    u64 const nt = c->n_tiles();
+    FLX_LAUNCH("coverage_heads", CoverageDevice::heads(c->stream, 0, c->acc.as<u32>(), c->total, c->d_starts.as<u32>(), c->n_refs(), c->opt.report_zero,
+                                                       c->count_all.as<u32>(), c->count_rep.as<u32>(), nullptr, 0, nullptr));
+    if ((rc = c->scan.inclusive(c->stream, c->count_all.as<u32>(), nt)) || (rc = c->scan.inclusive(c->stream, c->count_rep.as<u32>(), nt))) return rc;
     u32 last[2] = {0, 0};
     FLX_HIP(hipMemcpyAsync(&last[0], c->count_all.as<u32>() + (nt - 1), 4, hipMemcpyDeviceToHost, c->stream));
     FLX_HIP(hipMemcpyAsync(&last[1], c->count_rep.as<u32>() + (nt - 1), 4, hipMemcpyDeviceToHost, c->stream));
@@ -266,7 +138,7 @@ extern "C" uint64_t flx_coverage_num_runs(const flx_coverage* c) {
     return c->finished ? c->n_runs : 0;
 }
 extern "C" int flx_coverage_copy_runs(const flx_coverage* cc, flx_depth_run* out, uint64_t capacity) {
-    if (!finished_for_copy(cc, "flx_coverage_copy_runs")) return FLX_ERR_INVALID;
+    if (!finished_for_copy(cc, "flx_coverage_copy_runs", "flx_coverage_finish")) return FLX_ERR_INVALID;
     flx_coverage* const c = const_cast<flx_coverage*>(cc);
     if (capacity < c->n_runs) { set_error("flx_coverage_copy_runs: the run buffer is too small, " + std::to_string(c->n_runs) + " runs"); return FLX_ERR_CAPACITY; }
     if (c->n_runs == 0) return FLX_OK;
@@ -277,7 +149,7 @@ extern "C" int flx_coverage_copy_runs(const flx_coverage* cc, flx_depth_run* out
     int rc;
     if ((rc = heads.ensure(c->n_heads * 4, true)) || (rc = runs.ensure(c->n_runs * sizeof(flx_depth_run), true))) return rc;
     for (int mode = 1; mode <= 2; ++mode)
-        COV_LAUNCH("coverage_heads", CoverageDevice::heads(c->stream, mode, c->acc.as<u32>(), c->total, c->d_starts.as<u32>(), c->n_refs(), c->opt.report_zero,
+        FLX_LAUNCH("coverage_heads", CoverageDevice::heads(c->stream, mode, c->acc.as<u32>(), c->total, c->d_starts.as<u32>(), c->n_refs(), c->opt.report_zero,
                                                           c->count_all.as<u32>(), c->count_rep.as<u32>(), heads.as<u32>(), c->n_heads, runs.as<flx_depth_run>()));
     FLX_HIP(hipMemcpyAsync(out, runs.ptr, c->n_runs * sizeof(flx_depth_run), hipMemcpyDeviceToHost, c->stream));
     FLX_HIP(hipStreamSynchronize(c->stream));
@@ -291,7 +163,7 @@ extern "C" uint64_t flx_coverage_num_windows(const flx_coverage* c, uint64_t win
     return bases.back();
 }
 extern "C" int flx_coverage_copy_windows(flx_coverage* c, uint64_t window, flx_depth_window* out, uint64_t capacity) {
-    if (!finished_for_copy(c, "flx_coverage_copy_windows")) return FLX_ERR_INVALID;
+    if (!finished_for_copy(c, "flx_coverage_copy_windows", "flx_coverage_finish")) return FLX_ERR_INVALID;
     if (window >= COVERAGE_MAX_TOTAL) window = 0;
     std::vector<u64> bases;
     coverage_window_bases(c->starts, window, bases);
@@ -307,7 +179,7 @@ extern "C" int flx_coverage_copy_windows(flx_coverage* c, uint64_t window, flx_d
         if ((rc = d_bases.ensure(bases.size() * 8, true)) || (rc = d_acc.ensure(n * sizeof(CoverageWindowAcc), true))) return rc;
         FLX_HIP(hipMemcpyAsync(d_bases.ptr, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, c->stream));
         FLX_HIP(hipMemsetAsync(d_acc.ptr, 0, n * sizeof(CoverageWindowAcc), c->stream));
-        COV_LAUNCH("coverage_windows", CoverageDevice::windows(c->stream, c->acc.as<u32>(), c->total, c->d_starts.as<u32>(), c->n_refs(), window, d_bases.as<u64>(), d_acc.as<CoverageWindowAcc>()));
+        FLX_LAUNCH("coverage_windows", CoverageDevice::windows(c->stream, c->acc.as<u32>(), c->total, c->d_starts.as<u32>(), c->n_refs(), window, d_bases.as<u64>(), d_acc.as<CoverageWindowAcc>()));
         FLX_HIP(hipMemcpyAsync(acc.data(), d_acc.ptr, n * sizeof(CoverageWindowAcc), hipMemcpyDeviceToHost, c->stream));
         FLX_HIP(hipStreamSynchronize(c->stream));
     }
@@ -322,7 +194,7 @@ extern "C" int flx_coverage_copy_windows(flx_coverage* c, uint64_t window, flx_d
 }
 
 extern "C" int flx_coverage_copy_depth(const flx_coverage* cc, uint32_t reference_id, uint64_t from, uint64_t to, uint32_t* out) {
-    if (!finished_for_copy(cc, "flx_coverage_copy_depth")) return FLX_ERR_INVALID;
+    if (!finished_for_copy(cc, "flx_coverage_copy_depth", "flx_coverage_finish")) return FLX_ERR_INVALID;
     flx_coverage* const c = const_cast<flx_coverage*>(cc);
     if (reference_id >= c->n_refs() || from > to || to > c->starts[reference_id + 1] - c->starts[reference_id]) { set_error("flx_coverage_copy_depth: a stretch outside the sequences"); return FLX_ERR_INVALID; }
     if (from == to) return FLX_OK;
@@ -336,8 +208,8 @@ extern "C" int flx_coverage_copy_depth(const flx_coverage* cc, uint32_t referenc
 
 extern "C" int flx_coverage_geometry(uint32_t out[2]) {
     if (!out) { set_error("flx_coverage_geometry: null argument"); return FLX_ERR_INVALID; }
-    out[0] = CoverageDevice::SCAN_TILE;
-    out[1] = CoverageDevice::SCAN_TILE;
+    out[0] = ScanDevice::SCAN_TILE;
+    out[1] = ScanDevice::SCAN_TILE;
     return FLX_OK;
 }
 

@@ -3,33 +3,21 @@
 // records without the object's lock (that is the host rule itself, into a buffer of the call's own) and takes the lock for upload, launch
 // and download, so calls from several host threads are serialised there. A large call is judged on up to eight threads of its own. With
 // device -1 nothing of the device exists and the judged summaries are the result. The writer is host code: it formats a call in full,
-// then writes it.
+// then writes it. What flx_paf shares with the other side objects: flx_object.hpp.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
-#include <thread>
 
+#include "flx_object.hpp"
 #include "flx_paf.hpp"
-#include "flx_pipeline.hpp"
 
 using namespace flx;
 
-struct flx_paf {
-    int device = 0;                      // -1: the host form
-    hipStream_t stream = nullptr;
+struct flx_paf : SideObject {            // mu: the buffers and the launches; FLX_PAF_PROFILE
     DeviceBuffer jobs, words, out;       // a call's staging: one PafJob per record, the stretch of the pool in use, the summaries
-    std::mutex mu;                       // the buffers and the launches
-    bool profile = false;                // FLX_PAF_PROFILE set (and not 0)
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    ~flx_paf() {
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 struct flx_paf_writer {
@@ -63,22 +51,10 @@ bool judge_all(const flx_record* records, uint64_t n, const uint32_t* cigar_word
                const uint64_t* ref_lens, uint32_t n_refs, const char* who, flx_paf_summary* judged) {
     u64 words = 0;
     for (uint64_t i = 0; i < n; ++i) words += records[i].cigar_length;
-    size_t const n_threads = (size_t)std::min<u64>({8, words >> 19, n});
-    if (n_threads <= 1) return paf_plan(records, 0, n, cigar_words, n_words, read_offsets, n_reads, ref_lens, n_refs, who, judged);
-    std::vector<std::string> refusals(n_threads);
-    std::vector<char> refused(n_threads, 0);
-    std::vector<std::thread> threads;
-    for (size_t t = 0; t < n_threads; ++t)
-        threads.emplace_back([&, t] {
-            if (!paf_plan(records, n * t / n_threads, n * (t + 1) / n_threads, cigar_words, n_words, read_offsets, n_reads, ref_lens, n_refs, who, judged)) {
-                refused[t] = 1;
-                refusals[t] = flx_last_error();      // (the message is the judging thread's own)
-            }
-        });
-    for (auto& t : threads) t.join();
-    for (size_t t = 0; t < n_threads; ++t)
-        if (refused[t]) { set_error(refusals[t]); return false; }
-    return true;
+    size_t const n_threads = (size_t)std::max<u64>(1, std::min<u64>({8, words >> 19, n}));
+    return judge_in_parallel(n_threads, [&](size_t t) {
+        return paf_plan(records, n * t / n_threads, n * (t + 1) / n_threads, cigar_words, n_words, read_offsets, n_reads, ref_lens, n_refs, who, judged);
+    });
 }
 
 void append_number(std::string& s, u64 v) {
@@ -95,20 +71,12 @@ extern "C" int flx_paf_create(int hip_device, flx_paf** out) {
     if (!out) { set_error("flx_paf_create: null argument"); return FLX_ERR_INVALID; }
     if (hip_device < -1) { set_error("flx_paf_create: the device is -1 (the host) or a HIP device"); return FLX_ERR_INVALID; }
     auto p = std::make_unique<flx_paf>();            // (an error below drops it: nothing stays allocated)
-    p->device = hip_device;
-    if (const char* env = getenv("FLX_PAF_PROFILE")) p->profile = strtol(env, nullptr, 10) != 0 || env[0] == '\0';
-    if (hip_device >= 0) {
-        FLX_HIP(hipSetDevice(hip_device));
-        FLX_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    }
+    int const rc = p->open(hip_device, "FLX_PAF_PROFILE");
+    if (rc) return rc;
     *out = p.release();
     return FLX_OK;
 }
-extern "C" void flx_paf_free(flx_paf* p) {
-    if (!p) return;
-    if (p->device >= 0) (void)hipSetDevice(p->device);
-    delete p;
-}
+extern "C" void flx_paf_free(flx_paf* p) { free_object(p); }
 
 extern "C" int flx_paf_summarize_host(const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words, const uint64_t* read_offsets,
                                       uint64_t n_reads, const uint64_t* ref_lens, uint32_t n_refs, flx_paf_summary* out) {
@@ -148,20 +116,14 @@ extern "C" int flx_paf_summarize(flx_paf* p, const flx_record* records, uint64_t
     if ((rc = grow(p->jobs, n * sizeof(PafJob))) || (rc = grow(p->words, (hi - lo) * 4 + 4)) || (rc = grow(p->out, n * sizeof(flx_paf_summary)))) return rc;
     FLX_HIP(hipMemcpyAsync(p->jobs.ptr, jobs.data(), n * sizeof(PafJob), hipMemcpyHostToDevice, p->stream));
     if (hi > lo) FLX_HIP(hipMemcpyAsync(p->words.ptr, cigar_words + lo, (hi - lo) * 4, hipMemcpyHostToDevice, p->stream));
-    if (p->profile) {
-        if (!p->ev_a) { FLX_HIP(hipEventCreate(&p->ev_a)); FLX_HIP(hipEventCreate(&p->ev_b)); }
-        FLX_HIP(hipEventRecord(p->ev_a, p->stream));
-    }
-    {
-        int const e = PafDevice::summarise(p->stream, p->jobs.as<PafJob>(), (u32)n, p->words.as<u32>(), p->out.as<flx_paf_summary>());
-        if (e != 0) { set_error(std::string("paf_summarise: launch failed: ") + hipGetErrorString((hipError_t)e)); return FLX_ERR_NO_DEVICE; }
-    }
-    if (p->profile) FLX_HIP(hipEventRecord(p->ev_b, p->stream));
+    if ((rc = p->span_begin())) return rc;
+    FLX_LAUNCH("paf_summarise", PafDevice::summarise(p->stream, p->jobs.as<PafJob>(), (u32)n, p->words.as<u32>(), p->out.as<flx_paf_summary>()));
+    if ((rc = p->span_end())) return rc;
     FLX_HIP(hipMemcpyAsync(out, p->out.ptr, n * sizeof(flx_paf_summary), hipMemcpyDeviceToHost, p->stream));
     FLX_HIP(hipStreamSynchronize(p->stream));          // (the staging buffers are free for the next call)
     if (p->profile) {
-        float ms = 0;
-        FLX_HIP(hipEventElapsedTime(&ms, p->ev_a, p->ev_b));
+        float ms;
+        if ((rc = p->span_ms(ms))) return rc;
         double const wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[flx paf] summarize: records %llu words %llu upload_bytes %llu paf_summarise_ms %.3f wall_ms %.3f\n", (unsigned long long)n,
                 (unsigned long long)(hi - lo), (unsigned long long)(n * sizeof(PafJob) + (hi - lo) * 4), (double)ms, wall);

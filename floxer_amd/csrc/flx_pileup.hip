@@ -8,13 +8,13 @@
 //                  of the read's letter there (ranks 1..4); the lane of an I word adds 1 to INS at its anchor, the column in front of it,
 //                  or the word's own position when no reference-consuming column precedes it in the record (a third wave-uniform carry).
 //   pileup_sites   over SCAN_TILE positions per block, behind the scans of DEPTH and DEL: mode 0 counts the tile's sites, the counts are
-//                  scanned with coverage's scan, mode 1 writes the sites in position order.
+//                  scanned with the same scan (flx_scan.hip), mode 1 writes the sites in position order.
 // All adds are device-scope integer atomicAdd, all stores plain C++ vector stores.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "flx_coverage_dev.hpp"
+#include "flx_scan_dev.hpp"
 #include "flx_pileup.hpp"
 
 namespace flx {

@@ -1,15 +1,15 @@
-// Device helpers of the tile kernels over position arrays, shared by flx_coverage.hip and flx_pileup.hip: a block of 256 threads takes one
-// tile of CoverageDevice::SCAN_TILE positions, a thread a strip of 16.
+// Device helpers of the tile kernels over position arrays, shared by flx_scan.hip, flx_coverage.hip and flx_pileup.hip: a block of 256
+// threads takes one tile of ScanDevice::SCAN_TILE positions, a thread a strip of 16.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "flx_coverage.hpp"
+#include "flx_scan.hpp"
 #include "flx_wave.hpp"
 
 namespace flx {
 namespace {
 
-constexpr u32 TILE = CoverageDevice::SCAN_TILE;        // elements per block
+constexpr u32 TILE = ScanDevice::SCAN_TILE;            // elements per block
 constexpr u32 THREADS = 256;
 constexpr u32 STRIP = TILE / THREADS;                  // contiguous elements per thread
 static_assert(STRIP == 16, "a thread's strip is four 16-byte loads");

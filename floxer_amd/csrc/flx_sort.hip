@@ -4,7 +4,7 @@
 //   sort_census       one launch over all 16 digits of the keys: 16 x 256 counters per block in LDS (integer atomics), added to the
 //                     global counters at the end. A digit with one value in every key has a counter equal to n: the host skips its pass.
 //   sort_histogram    a pass's digit counts per tile, in LDS with integer atomics; table[value * n_tiles + tile].
-//   (the scan)        the table's inclusive prefix sum with coverage's reduce-then-scan launches (flx_coverage.hip), two levels at most:
+//   (the scan)        the table's inclusive prefix sum with the reduce-then-scan launches of flx_scan.hip, two levels at most:
 //                     the host grows the tiles before the table outgrows them (sort_effective_tile).
 //   sort_scatter      stable: a block walks its tile 256 keys at a time. Within a wave the lanes with equal digits find each other with
 //                     eight ballots (one per bit of the digit); a key's rank among them is the number of lower lanes in that mask. The

@@ -2,62 +2,46 @@
 // kernels: flx_sort.hip. The object owns one stream, the key table (a SortKey and a SortMeta per record added, in adding order), the
 // staging buffers of an add and the ping-pong buffers of a sort. Adds judge their records without the object's lock and take it for
 // the staging and the launches only, so several host threads may add at once. With device -1 nothing of the device exists and the
-// same calls keep the keys in host vectors and order them with std::sort (flx_sort_host's code).
+// same calls keep the keys in host vectors and order them with std::sort (flx_sort_host's code). The scan of a pass's table:
+// flx_scan.hip; what the object shares with the other side objects: flx_object.hpp.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <numeric>
 #include <set>
 
-#include "flx_coverage.hpp"
-#include "flx_pipeline.hpp"
+#include "flx_object.hpp"
 #include "flx_sort.hpp"
 
 using namespace flx;
 
 namespace {
 constexpr u64 DEFAULT_INITIAL_CAPACITY = 1ull << 20;
-constexpr u64 SCAN_TILE = CoverageDevice::SCAN_TILE;
+constexpr u64 SCAN_TILE = ScanDevice::SCAN_TILE;
 }  // namespace
 
-struct flx_sort {
-    int device = 0;                      // -1: the host form
+struct flx_sort : SideObject {           // mu: the table, staging, launches and `finished`; FLX_SORT_PROFILE
     u32 n_refs = 0;
     u64 initial_capacity = DEFAULT_INITIAL_CAPACITY;
     u32 tile_keys = SortDevice::TILE_KEYS;
-    hipStream_t stream = nullptr;
-    std::mutex mu;                       // the table, staging, launches and `finished`
     bool finished = false;
     u64 count = 0, capacity = 0;         // records added; records the table holds
     std::set<u64> first_ordinals;        // of the adds so far
     DeviceBuffer keys, meta;             // the table
     DeviceBuffer records, words;         // an add's staging
     DeviceBuffer keys_a, keys_b, pay_a, pay_b;      // a sort's ping-pong buffers (an add's own records, or the whole table at finish)
-    DeviceBuffer table, sums, census;    // a pass's tile x digit table, its tile sums, the 16 x 256 digit counters
+    DeviceBuffer table, census;          // a pass's tile x digit table, the 16 x 256 digit counters
+    ScanDriver scan;                     // the table's scan
     DeviceBuffer entries;                // the sorted entries, behind finish
     std::vector<SortKey> h_keys;         // the host form's table
     std::vector<SortMeta> h_meta;
     std::vector<flx_sort_entry> h_entries;
-    bool profile = false;                // FLX_SORT_PROFILE set (and not 0)
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    ~flx_sort() {
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
-
-#define SORT_LAUNCH(name, expr)                                                                                                    \
-    do {                                                                                                                           \
-        int const e__ = (expr);                                                                                                    \
-        if (e__ != 0) { set_error(std::string(name) + ": launch failed: " + hipGetErrorString((hipError_t)e__)); return FLX_ERR_NO_DEVICE; } \
-    } while (0)
 
 struct Piece { const flx_record* records; u64 n; const u32* words; u64 n_words; };
 
@@ -79,11 +63,11 @@ int radix_sort(flx_sort* s, SortKey* a, SortKey* b, u32* pa, u32* pb, u64 n, Sor
     *passes = 0;
     if (n <= 1) return FLX_OK;
     u32 const tile = (u32)sort_effective_tile(n, s->tile_keys, SortDevice::THREADS, SCAN_TILE);
-    u64 const n_tiles = (n + tile - 1) / tile, n_table = n_tiles * SORT_RADIX, n_sums = (n_table + SCAN_TILE - 1) / SCAN_TILE;
+    u64 const n_tiles = (n + tile - 1) / tile, n_table = n_tiles * SORT_RADIX;
     int rc;
-    if ((rc = s->census.ensure(SORT_DIGITS * SORT_RADIX * 4, true)) || (rc = s->table.ensure(n_table * 4)) || (rc = s->sums.ensure(SCAN_TILE * 4, true))) return rc;
+    if ((rc = s->census.ensure(SORT_DIGITS * SORT_RADIX * 4, true)) || (rc = s->table.ensure(n_table * 4)) || (rc = s->scan.reserve(n_table))) return rc;
     FLX_HIP(hipMemsetAsync(s->census.ptr, 0, SORT_DIGITS * SORT_RADIX * 4, s->stream));
-    SORT_LAUNCH("sort_census", SortDevice::digit_census(s->stream, a, n, s->census.as<u32>()));
+    FLX_LAUNCH("sort_census", SortDevice::digit_census(s->stream, a, n, s->census.as<u32>()));
     std::vector<u32> counts(SORT_DIGITS * SORT_RADIX);
     FLX_HIP(hipMemcpyAsync(counts.data(), s->census.ptr, counts.size() * 4, hipMemcpyDeviceToHost, s->stream));
     FLX_HIP(hipStreamSynchronize(s->stream));
@@ -92,14 +76,9 @@ int radix_sort(flx_sort* s, SortKey* a, SortKey* b, u32* pa, u32* pb, u64 n, Sor
         for (u32 v = 0; v < SORT_RADIX; ++v) constant = constant || counts[d * SORT_RADIX + v] == n;
         if (constant) continue;
         u32* const table = s->table.as<u32>();
-        SORT_LAUNCH("sort_histogram", SortDevice::histogram(s->stream, a, n, d, tile, table));
-        if (n_sums <= 1) SORT_LAUNCH("sort_scan", CoverageDevice::scan_apply(s->stream, table, n_table, nullptr));
-        else {                                                          // (n_sums <= SCAN_TILE: sort_effective_tile saw to it)
-            SORT_LAUNCH("sort_scan", CoverageDevice::scan_sums(s->stream, table, n_table, s->sums.as<u32>()));
-            SORT_LAUNCH("sort_scan", CoverageDevice::scan_apply(s->stream, s->sums.as<u32>(), n_sums, nullptr));
-            SORT_LAUNCH("sort_scan", CoverageDevice::scan_apply(s->stream, table, n_table, s->sums.as<u32>()));
-        }
-        SORT_LAUNCH("sort_scatter", SortDevice::scatter(s->stream, a, pa, n, d, tile, table, b, pb));
+        FLX_LAUNCH("sort_histogram", SortDevice::histogram(s->stream, a, n, d, tile, table));
+        if ((rc = s->scan.inclusive(s->stream, table, n_table))) return rc;       // (two levels at most: sort_effective_tile saw to it)
+        FLX_LAUNCH("sort_scatter", SortDevice::scatter(s->stream, a, pa, n, d, tile, table, b, pb));
         std::swap(a, b);
         std::swap(pa, pb);
         ++*passes;
@@ -164,24 +143,22 @@ int add_pieces(flx_sort* s, std::vector<Piece> const& pieces, u64 first_ordinal,
     FLX_HIP(hipSetDevice(s->device));
     int rc = grow(s, s->count + total);
     if (rc) return rc;
-    if (s->profile) {
-        if (!s->ev_a) { FLX_HIP(hipEventCreate(&s->ev_a)); FLX_HIP(hipEventCreate(&s->ev_b)); }
-    }
     u64 upload = 0, at = 0;
-    float add_ms = 0;
+    float add_ms = 0, ms;
     for (auto const& p : pieces) {
         if (p.n == 0) continue;
         if ((rc = s->records.ensure(p.n * sizeof(flx_record))) || (rc = s->words.ensure(std::max<u64>(p.n_words, 1) * 4))) return rc;
         FLX_HIP(hipMemcpyAsync(s->records.ptr, p.records, p.n * sizeof(flx_record), hipMemcpyHostToDevice, s->stream));
         if (p.n_words) FLX_HIP(hipMemcpyAsync(s->words.ptr, p.words, p.n_words * 4, hipMemcpyHostToDevice, s->stream));
         upload += p.n * sizeof(flx_record) + p.n_words * 4;
-        if (s->profile) FLX_HIP(hipEventRecord(s->ev_a, s->stream));
+        if ((rc = s->span_begin())) return rc;
         // (a piece has fewer than 2^32 records: the object's limit was checked above)
-        SORT_LAUNCH("sort_keys_add", SortDevice::keys_add(s->stream, s->records.as<flx_record>(), (u32)p.n, s->words.as<u32>(), first_ordinal + at,
-                                                        s->keys.as<SortKey>() + s->count + at, s->meta.as<SortMeta>() + s->count + at));
-        if (s->profile) FLX_HIP(hipEventRecord(s->ev_b, s->stream));
+        FLX_LAUNCH("sort_keys_add", SortDevice::keys_add(s->stream, s->records.as<flx_record>(), (u32)p.n, s->words.as<u32>(), first_ordinal + at,
+                                                       s->keys.as<SortKey>() + s->count + at, s->meta.as<SortMeta>() + s->count + at));
+        if ((rc = s->span_end())) return rc;
         FLX_HIP(hipStreamSynchronize(s->stream));        // (the staging buffers are free for the next piece)
-        if (s->profile) { float ms = 0; FLX_HIP(hipEventElapsedTime(&ms, s->ev_a, s->ev_b)); add_ms += ms; }
+        if ((rc = s->span_ms(ms))) return rc;
+        add_ms += ms;
         at += p.n;
     }
     u32 passes = 0;
@@ -190,16 +167,16 @@ int add_pieces(flx_sort* s, std::vector<Piece> const& pieces, u64 first_ordinal,
         if ((rc = s->keys_a.ensure(total * sizeof(SortKey))) || (rc = s->keys_b.ensure(total * sizeof(SortKey))) || (rc = s->pay_a.ensure(total * 4)) ||
             (rc = s->pay_b.ensure(total * 4)))
             return rc;
-        if (s->profile) FLX_HIP(hipEventRecord(s->ev_a, s->stream));
+        if ((rc = s->span_begin())) return rc;
         FLX_HIP(hipMemcpyAsync(s->keys_a.ptr, s->keys.as<SortKey>() + s->count, total * sizeof(SortKey), hipMemcpyDeviceToDevice, s->stream));
-        SORT_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->pay_a.as<u32>(), total));
+        FLX_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->pay_a.as<u32>(), total));
         SortKey* sorted_keys;
         u32* sorted_payload;
         if ((rc = radix_sort(s, s->keys_a.as<SortKey>(), s->keys_b.as<SortKey>(), s->pay_a.as<u32>(), s->pay_b.as<u32>(), total, &sorted_keys, &sorted_payload, &passes))) return rc;
         FLX_HIP(hipMemcpyAsync(out_order, sorted_payload, total * 4, hipMemcpyDeviceToHost, s->stream));
-        if (s->profile) FLX_HIP(hipEventRecord(s->ev_b, s->stream));
+        if ((rc = s->span_end())) return rc;
         FLX_HIP(hipStreamSynchronize(s->stream));
-        if (s->profile) FLX_HIP(hipEventElapsedTime(&sort_ms, s->ev_a, s->ev_b));
+        if ((rc = s->span_ms(sort_ms))) return rc;
     }
     s->count += total;
     s->first_ordinals.insert(first_ordinal);
@@ -226,23 +203,15 @@ extern "C" int flx_sort_create(int hip_device, uint32_t n_refs, const flx_sort_o
     if (hip_device < -1) { set_error("flx_sort_create: a device below -1"); return FLX_ERR_INVALID; }
     if (!options_valid(o)) return FLX_ERR_INVALID;
     auto s = std::make_unique<flx_sort>();              // (an error below drops it: nothing stays allocated)
-    s->device = hip_device;
     s->n_refs = n_refs;
     if (o && o->initial_capacity) s->initial_capacity = o->initial_capacity;
     if (o && o->tile_keys) s->tile_keys = o->tile_keys;
-    if (const char* env = getenv("FLX_SORT_PROFILE")) s->profile = strtol(env, nullptr, 10) != 0 || env[0] == '\0';
-    if (hip_device >= 0) {
-        FLX_HIP(hipSetDevice(hip_device));
-        FLX_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    }
+    int const rc = s->open(hip_device, "FLX_SORT_PROFILE");
+    if (rc) return rc;
     *out = s.release();
     return FLX_OK;
 }
-extern "C" void flx_sort_free(flx_sort* s) {
-    if (!s) return;
-    if (s->device >= 0) (void)hipSetDevice(s->device);
-    delete s;
-}
+extern "C" void flx_sort_free(flx_sort* s) { free_object(s); }
 
 extern "C" int flx_sort_add_records(flx_sort* s, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words, uint64_t first_ordinal,
                                     uint32_t* out_order) {
@@ -251,9 +220,8 @@ extern "C" int flx_sort_add_records(flx_sort* s, const flx_record* records, uint
 }
 extern "C" int flx_sort_add_run(flx_sort* s, const flx_run* run, uint64_t first_ordinal, uint32_t* out_order) {
     if (!s || !run) { set_error("flx_sort_add_run: null argument"); return FLX_ERR_INVALID; }
-    // a run is its own records plus its per-lane parts, each over its own word pool, in the order flx_run_copy lists them
-    std::vector<Piece> pieces{Piece{run->records.data(), run->records.size(), run->cigars.data(), run->cigars.size()}};
-    for (auto const& p : run->parts) pieces.push_back(Piece{p.records.data(), p.records.size(), p.cigars.data(), p.cigars.size()});
+    std::vector<Piece> pieces;
+    for (const flx_run* p : run_pieces(run)) pieces.push_back(Piece{p->records.data(), p->records.size(), p->cigars.data(), p->cigars.size()});
     return add_pieces(s, pieces, first_ordinal, out_order, "flx_sort_add_run");
 }
 
@@ -279,19 +247,16 @@ extern "C" int flx_sort_finish(flx_sort* s) {
         if ((rc = s->keys_b.ensure(n * sizeof(SortKey), true)) || (rc = s->pay_a.ensure(n * 4, true)) || (rc = s->pay_b.ensure(n * 4, true)) ||
             (rc = s->entries.ensure(n * sizeof(flx_sort_entry), true)))
             return rc;
-        if (s->profile) {
-            if (!s->ev_a) { FLX_HIP(hipEventCreate(&s->ev_a)); FLX_HIP(hipEventCreate(&s->ev_b)); }
-            FLX_HIP(hipEventRecord(s->ev_a, s->stream));
-        }
-        SORT_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->pay_a.as<u32>(), n));
+        if ((rc = s->span_begin())) return rc;
+        FLX_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->pay_a.as<u32>(), n));
         SortKey* sorted_keys;
         u32* sorted_payload;
         // (the table itself is the first buffer: it is not read in adding order again)
         if ((rc = radix_sort(s, s->keys.as<SortKey>(), s->keys_b.as<SortKey>(), s->pay_a.as<u32>(), s->pay_b.as<u32>(), n, &sorted_keys, &sorted_payload, &passes))) return rc;
-        SORT_LAUNCH("sort_entries", SortDevice::entries(s->stream, sorted_keys, sorted_payload, s->meta.as<SortMeta>(), n, s->entries.ptr));
-        if (s->profile) FLX_HIP(hipEventRecord(s->ev_b, s->stream));
+        FLX_LAUNCH("sort_entries", SortDevice::entries(s->stream, sorted_keys, sorted_payload, s->meta.as<SortMeta>(), n, s->entries.ptr));
+        if ((rc = s->span_end())) return rc;
         FLX_HIP(hipStreamSynchronize(s->stream));
-        if (s->profile) FLX_HIP(hipEventElapsedTime(&ms, s->ev_a, s->ev_b));
+        if ((rc = s->span_ms(ms))) return rc;
         s->keys.release(); s->keys_a.release(); s->keys_b.release(); s->pay_a.release(); s->pay_b.release(); s->meta.release();
         s->table.release(); s->records.release(); s->words.release();
         s->capacity = 0;
@@ -329,7 +294,7 @@ extern "C" int flx_sort_geometry(uint32_t out[4]) {
     out[0] = SortDevice::TILE_KEYS;
     out[1] = SORT_DIGIT_BITS;
     out[2] = (uint32_t)DEFAULT_INITIAL_CAPACITY;
-    out[3] = CoverageDevice::SCAN_TILE;
+    out[3] = ScanDevice::SCAN_TILE;
     return FLX_OK;
 }
 

@@ -1,7 +1,7 @@
 // The coverage rule of flx_coverage.hpp (one host implementation, shared by flx_coverage_host and by the checks in front of every launch)
 // on random records against a definition that walks every column on its own, in arrays of exactly the needed size, so that a step
-// outside them is an AddressSanitizer report; then every refusal on one bad record behind good ones. Stand-alone, built with ASan +
-// UBSan by tests/test_coverage_host.py.
+// outside them is an AddressSanitizer report; then every refusal on one bad record behind good ones. In front of that compact_words, the
+// word pool that an add of coverage or pileup uploads. Stand-alone, built with ASan + UBSan by tests/test_coverage_host.py.
 #include <cstdint>
 #include <cstdio>
 #include <random>
@@ -15,7 +15,49 @@ static std::string last_error;
 void set_error(const std::string& m) { last_error = m; }
 }
 
+// compact_words on spans {word_off, n_words} of a pool of n_pool words (each word holds its own index, so a word is recognised wherever
+// it lands): every job reads the same words through the compacted pool as through the original, and the compacted pool holds each used
+// word once. Both pools have exactly their size, so a step outside them is an AddressSanitizer report.
+static bool compact_case(const char* name, uint64_t n_pool, std::vector<std::pair<uint64_t, uint32_t>> const& spans) {
+    std::vector<uint32_t> original(n_pool);
+    for (uint64_t i = 0; i < n_pool; ++i) original[i] = 1000u + (uint32_t)i;
+    std::vector<flx::CoverageJob> jobs;
+    for (auto const& s : spans) jobs.push_back(flx::CoverageJob{7 * jobs.size(), s.first, s.second, 0u});
+    std::vector<uint32_t> used(n_pool, 0);
+    for (auto const& s : spans)
+        for (uint32_t t = 0; t < s.second; ++t) used[s.first + t] = 1;
+    std::vector<uint32_t> pool{99u};                                      // (what it held before is dropped)
+    flx::compact_words(jobs, original.data(), pool);
+    std::vector<uint32_t> want_pool;
+    for (uint64_t i = 0; i < n_pool; ++i) if (used[i]) want_pool.push_back(original[i]);
+    if (pool != want_pool) { printf("compact_words, %s: the pool does not hold each used word once, in order\n", name); return false; }
+    if (jobs.size() != spans.size()) { printf("compact_words, %s: the number of jobs changed\n", name); return false; }
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        if (jobs[k].n_words != spans[k].second || jobs[k].text_off != 7 * k) { printf("compact_words, %s: job %zu changed beside its word_off\n", name, k); return false; }
+        if (jobs[k].word_off > pool.size() || jobs[k].n_words > pool.size() - jobs[k].word_off) { printf("compact_words, %s: job %zu lies outside the pool\n", name, k); return false; }
+        for (uint32_t t = 0; t < jobs[k].n_words; ++t)
+            if (pool[jobs[k].word_off + t] != original[spans[k].first + t]) { printf("compact_words, %s: job %zu reads another word at %u\n", name, k, t); return false; }
+    }
+    return true;
+}
+
+static bool compact_cases() {
+    std::mt19937_64 rng(7);
+    std::vector<std::pair<uint64_t, uint32_t>> random;
+    for (int k = 0; k < 300; ++k) { uint64_t const off = rng() % 500; random.emplace_back(off, 1 + (uint32_t)(rng() % std::min<uint64_t>(40, 500 - off))); }
+    return compact_case("overlapping spans", 40, {{20, 10}, {3, 9}, {25, 10}, {8, 6}}) &&
+           compact_case("nested spans", 40, {{5, 30}, {10, 4}, {12, 1}, {34, 1}, {5, 1}, {30, 9}}) &&
+           compact_case("touching spans", 40, {{10, 5}, {15, 5}, {0, 10}, {21, 4}}) &&              // (and a gap of one word at 20)
+           compact_case("identical spans", 40, {{17, 6}, {17, 6}, {17, 6}, {2, 3}, {2, 3}}) &&
+           compact_case("a span at the pool's last word", 40, {{39, 1}, {0, 2}, {36, 4}}) &&
+           compact_case("an empty job list", 40, {}) &&
+           compact_case("an empty job list over no pool", 0, {}) &&
+           compact_case("the whole pool, out of order", 12, {{6, 6}, {0, 6}}) &&
+           compact_case("random spans", 500, random);
+}
+
 int main() {
+    if (!compact_cases()) return 1;
     std::mt19937_64 rng(20240917);
     static const uint32_t ops[5] = {7, 8, 1, 2, 4};
     static const uint32_t flags[7] = {0, 16, 256, 272, 2048, 2064, 4};

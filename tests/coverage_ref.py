@@ -161,6 +161,33 @@ def random_words(rng, n_words, max_len=12, clips=True):
     return ws
 
 
+def joined(parts):
+    """(records, words) pairs, each over its own pool -> one pair over the pools' concatenation"""
+    recs, pools, at = [], [], 0
+    for rec, words in parts:
+        rec = rec.copy()
+        rec["coff"] += at
+        at += len(words)
+        recs.append(rec)
+        pools.append(words)
+    return np.concatenate(recs), np.concatenate(pools)
+
+
+def records_across(rng, at, tail):
+    """records on one sequence of at + tail positions (tail >= 3) whose array is handled in pieces of `at` entries. First, each of them
+    twice in a row (so that the even and the odd records both hold them): records on position 0, on the positions either side of index
+    `at`, one across it with an X, an I and a D there, and on the last position. Behind them random records: 300 anywhere, 150 within 300
+    positions of the start, 150 within 300 positions in front of index `at` up to the end."""
+    rows = [(0, 0, 0, 0, [word("X", 2), word("=", 8)]),
+            (16, 0, at - 3, 0, [word("=", 2), word("X", 1), word("I", 2), word("X", 1), word("D", 1), word("=", 1)]),     # X on at - 1 and on at, D on at + 1
+            (0, 0, at - 1, 0, [word("X", 1)]), (0, 0, at, 0, [word("X", 1)]), (0, 0, at + tail - 1, 0, [word("X", 1)]),
+            (16, 0, at - 1000, 0, [word("=", 1000 + tail - 1), word("I", 1), word("X", 1)])]                                # ends with the sequence
+    near = random_records(rng, [300 + tail], 150, max_words=12)
+    near[0]["pos"] += at - 300
+    return joined([records_of([row for row in rows for _ in range(2)]), random_records(rng, [at + tail], 300, max_words=40),
+                   random_records(rng, [300], 150, max_words=12), near])
+
+
 def random_records(rng, lengths, n, max_words=9):
     """n records of every flag and mapping quality, placed so that they fit their sequences"""
     rows = []

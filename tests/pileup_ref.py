@@ -7,7 +7,7 @@ uint32 in the order DEPTH, DEL, A, C, G, T, INS over the unpadded concatenation 
 import numpy as np
 
 import floxer_amd as F
-from coverage_ref import REC, counts as record_counts, random_records, records_of, span, starts_of, word  # noqa: F401 (shared with the tests)
+from coverage_ref import REC, counts as record_counts, random_records, records_across, records_of, span, starts_of, word  # noqa: F401 (shared with the tests)
 
 DEPTH, DEL, A, C, G, T, INS = range(7)
 COMPLEMENT = np.array([0, 4, 3, 2, 1, 5], dtype=np.uint8)

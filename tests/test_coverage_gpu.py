@@ -1,4 +1,4 @@
-"""Depth of coverage on the GPU (flx_coverage: kernels coverage_add, the three-launch scan, the run heads, coverage_windows, coverage_sum;
+"""Depth of coverage on the GPU (flx_coverage: kernels coverage_add, the three-launch scan, the run heads, coverage_windows, the absorb's sum;
 runs, the Python class and the CLI's --coverage outputs). Every expected value is the plain-numpy rule of tests/coverage_ref.py on the
 same records and words; the shapes sit on the kernels' boundaries (64 CIGAR words per pass, the scan's tile and second level)."""
 import ctypes as C
@@ -216,6 +216,28 @@ def test_order_of_adds_threads_and_absorb():
     assert len(other.runs()) == 0 and int(other.windows(0)["depth_sum"].sum()) == 0
     for cov in (one, ten, threaded, into, other):
         cov.close()
+
+
+@gpu
+def test_absorb_across_pieces():
+    """absorb moves an accumulator in pieces of 4 << 20 entries: here its total + 1 entries are one full piece and one piece of 6"""
+    piece, tail = 4 << 20, 5
+    lengths = [piece + tail]
+    rec, words = R.records_across(np.random.default_rng(41), piece, tail)
+    o = R.options(count_deletions=True, count_secondary=True)
+    want = R.depth(lengths, rec, words, o)
+    for half in (rec[::2], rec[1::2]):                                    # both objects hold depth at the ends and on both sides of the piece boundary
+        assert R.depth(lengths, half, words, o)[[0, piece - 1, piece, piece + 1, -1]].min() > 0
+    into, other = F.coverage(lengths=lengths, options=R.c_options(o)), F.coverage(lengths=lengths, options=R.c_options(o))
+    into.add_records(rec[::2], words)
+    other.add_records(rec[1::2], words)
+    into.absorb(other)
+    into.finish()
+    same(into, lengths, want, False, windows=(0, 1000))
+    other.finish()                                                        # absorbed: left cleared, in both pieces
+    assert len(other.runs()) == 0 and int(other.windows(0)["depth_sum"].sum()) == 0 and other.depth(0, 0, lengths[0]).max() == 0
+    into.close()
+    other.close()
 
 
 @gpu

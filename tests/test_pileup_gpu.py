@@ -291,6 +291,38 @@ def test_order_of_adds_threads_and_absorb():
 
 
 @gpu
+def test_absorb_across_pieces():
+    """absorb moves every plane in pieces of 4 << 20 entries: here a plane's total + 1 entries are one full piece and one piece of 6"""
+    piece, tail = 4 << 20, 5
+    lengths = [piece + tail]
+    rng = np.random.default_rng(43)
+    rec, words = R.records_across(rng, piece, tail)
+    reads = R.attach_reads(rng, rec, words)
+    o = dict(ANY, count_secondary=True)
+    want = R.counts(lengths, rec, words, reads, o)
+    stretches = [(0, 300), (piece - 300, piece + tail)]                   # the two ends and both sides of the piece boundary
+    for half in (rec[::2], rec[1::2]):                                    # both objects hold counts there
+        part = R.counts(lengths, half, words, reads, o)
+        assert part[R.DEPTH][[0, piece - 1, piece, -1]].min() > 0 and part[R.INS][piece - 1] > 0 and part[R.DEL][piece + 1] > 0
+        assert all((part[:, a:b].sum(axis=1) > 0).all() for a, b in stretches)
+    into, other = F.pileup(lengths=lengths, options=R.c_options(o)), F.pileup(lengths=lengths, options=R.c_options(o))
+    into.add_records(rec[::2], words, reads)
+    other.add_records(rec[1::2], words, reads)
+    into.absorb(other)
+    into.finish()
+    for a, b in stretches:
+        got = into.counts(0, a, b)
+        bad = np.argwhere(got != want[:, a:b])
+        assert len(bad) == 0, (a, bad[:8])
+    sites, exp = into.sites(), R.sites(lengths, want, o)
+    assert len(sites) == len(exp) and sites.tobytes() == exp.tobytes() and len(exp) > 300
+    other.finish()                                                        # absorbed: left cleared, in both pieces of every plane
+    assert len(other.sites()) == 0 and all(int(other.counts(0, a, b).sum()) == 0 for a, b in stretches)
+    into.close()
+    other.close()
+
+
+@gpu
 def test_lifetime_and_refusals():
     L = capi.lib()
     lengths = [700, 300]
