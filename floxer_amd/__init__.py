@@ -230,6 +230,23 @@ class context:
         check(lib().flx_ctx_get_search_counters(self.h, C.byref(sc)))
         return {n: int(getattr(sc, n)) for n, _ in capi.SearchCounters._fields_ if n != "reserved"}
 
+    def derived_info(self):
+        """the tables the context derived from its image when it was made (flx_ctx_derived_info, a test hook): filter_k, filter_tmin,
+        have_isa, have_filter, have_filter_mirrored"""
+        di = capi.DerivedInfo()
+        check(lib().flx_ctx_derived_info(self.h, C.byref(di)))
+        return {n: int(getattr(di, n)) for n, _ in capi.DerivedInfo._fields_ if n != "reserved"}
+
+    def copy_derived(self, which):
+        """one derived table read back from HBM (flx_ctx_copy_derived, a test hook): "isa" the inverse suffix array (uint32 per text
+        symbol), "filter" / "filter_mirrored" the presence filter's uint64 words. Raises FloxerError for a table the context has not."""
+        if which == "isa":
+            out = np.empty(self.index.text_length, dtype=np.uint32)
+        else:
+            out = np.empty((4 ** self.derived_info()["filter_k"] + 63) // 64, dtype=np.uint64)
+        check(lib().flx_ctx_copy_derived(self.h, {"isa": 0, "filter": 1, "filter_mirrored": 2}[which], out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     def kernel_stats(self):
         arr = (capi.KernelStat * 64)()
         n = C.c_uint32(64)

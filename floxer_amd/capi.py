@@ -229,6 +229,10 @@ class ClimbOptions(C.Structure):
     _fields_ = [("driver", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class DerivedInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("filter_k", "filter_tmin", "have_isa", "have_filter", "have_filter_mirrored")] + [("reserved", C.c_uint32 * 3)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("device_ms", C.c_double), ("algorithmic_bytes", C.c_uint64),
                 ("work_units", C.c_uint64)]
@@ -254,7 +258,7 @@ EXPORTED = [
     "flx_align_shapes", "flx_align_reads_gaps", "flx_align_reads_resident_gaps", "flx_align_batch_gaps", "flx_left_align", "flx_left_align_batch",
     "flx_realign", "flx_realign_batch", "flx_align_batch_realign", "flx_ctx_get_realign_counters", "flx_align_reads_realign",
     "flx_align_reads_resident_realign", "flx_run_copy_scores", "flx_sam_write_scored",
-    "flx_ctx_get_search_counters", "flx_climb_anchors",
+    "flx_ctx_get_search_counters", "flx_climb_anchors", "flx_ctx_derived_info", "flx_ctx_copy_derived",
     "flx_align_reads_cs", "flx_align_reads_resident_cs", "flx_run_num_cs_bytes", "flx_run_copy_cs", "flx_align_batch_cs", "flx_cs", "flx_cs_batch",
     "flx_sam_write_cs",
     "flx_coverage_create", "flx_coverage_create_for_lengths", "flx_coverage_free", "flx_coverage_add_run", "flx_coverage_add_records",
@@ -489,6 +493,8 @@ def lib():
     L.flx_ctx_reset_path_counters.argtypes = [C.c_void_p]
     L.flx_ctx_get_search_counters.argtypes = [C.c_void_p, C.POINTER(SearchCounters)]
     L.flx_climb_anchors.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ClimbOptions), u8p, u32p, u64p]
+    L.flx_ctx_derived_info.argtypes = [C.c_void_p, C.POINTER(DerivedInfo)]
+    L.flx_ctx_copy_derived.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
     L.flx_sim_genome.argtypes = [C.c_uint64, C.c_uint64, u8p]
     L.flx_sim_genome_repeats.argtypes = [C.c_uint64, C.c_uint64, u8p]
     L.flx_sim_reads.argtypes = [u8p, u64p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_uint64, u8p, C.c_uint64,

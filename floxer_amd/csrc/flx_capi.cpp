@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "flx_context.hpp"
+#include "flx_fm_core.hpp"
 
 namespace flx {
 const char* last_error_cstr();
@@ -320,6 +321,35 @@ int flx_ctx_get_search_counters(flx_ctx* ctx, flx_search_counters* out) {
     if (!ctx || !out) { set_error("null argument"); return FLX_ERR_INVALID; }
     std::lock_guard<std::mutex> g(ctx->mu);
     *out = ctx->search;
+    return FLX_OK;
+}
+
+// ---- the derived tables as they stand in HBM (flx_ctx_derived_info / flx_ctx_copy_derived, include/floxer_amd.h): a test hook. The tables
+// are written once, by derive_index when the context is made, and that launch is waited for there: a plain copy reads them.
+int flx_ctx_derived_info(flx_ctx* ctx, flx_derived_info* out) {
+    if (!ctx || !out) { set_error("flx_ctx_derived_info: null argument"); return FLX_ERR_INVALID; }
+    *out = flx_derived_info{};
+    out->filter_k = ctx->didx.filter_k;
+    out->filter_tmin = ctx->didx.filter_tmin;
+    out->have_isa = ctx->didx.isa != nullptr;
+    out->have_filter = ctx->didx.filter != nullptr;
+    out->have_filter_mirrored = ctx->didx.filter_m != nullptr;
+    return FLX_OK;
+}
+int flx_ctx_copy_derived(flx_ctx* ctx, int which, void* out, uint64_t bytes) {
+    if (!ctx || !out) { set_error("flx_ctx_copy_derived: null argument"); return FLX_ERR_INVALID; }
+    const void* src = nullptr;
+    uint64_t want = 0;
+    switch (which) {
+        case 0: src = ctx->didx.isa; want = (uint64_t)ctx->didx.n * 4; break;
+        case 1: src = ctx->didx.filter; want = filter_words(ctx->didx.filter_k) * 8; break;
+        case 2: src = ctx->didx.filter_m; want = filter_words(ctx->didx.filter_k) * 8; break;
+        default: set_error("flx_ctx_copy_derived: which must be 0 (inverse suffix array), 1 (filter) or 2 (mirrored filter)"); return FLX_ERR_INVALID;
+    }
+    if (!src) { set_error("flx_ctx_copy_derived: this context has no such table"); return FLX_ERR_INVALID; }
+    if (bytes != want) { set_error("flx_ctx_copy_derived: the table holds " + std::to_string(want) + " bytes, the caller gave " + std::to_string(bytes)); return FLX_ERR_INVALID; }
+    FLX_HIP(hipSetDevice(ctx->device));
+    FLX_HIP(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
     return FLX_OK;
 }
 

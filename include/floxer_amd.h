@@ -929,6 +929,17 @@ typedef struct flx_climb_options { uint32_t driver, reserved[3]; } flx_climb_opt
 int flx_climb_anchors(flx_ctx* ctx, const flx_params* params, const flx_reads* reads, const flx_climb_anchor* anchors, uint64_t n_anchors,
                       const flx_climb_options* options, uint8_t* out_status, uint32_t* out_node, uint64_t* out_requests);
 
+/* The tables a context derives from its image when it is made (a test hook for isa_kernel and filter_build_kernel, like flx_climb_anchors
+ * for the rounds): read back from HBM as they are, nothing in the context changes. flx_ctx_derived_info: the presence filter's K and the
+ * shortest string it answers for (both 0 without a filter), and which tables this context has (FLX_NO_DERIVED=1, FLX_FILTER_K=0 or a
+ * device without room leave them out; the mirrored filter only with FLX_MIRRORED_FILTER=1).
+ * flx_ctx_copy_derived: which = 0 the inverse suffix array (text_length u32: ISA[SA[row]] = row), 1 the presence filter, 2 the mirrored
+ * filter (each (4^K + 63) / 64 u64 words; bit numbering in DESIGN.md section 3). bytes must be exactly the table's size; a table the
+ * context does not have, another size, an unknown `which` or a null argument: FLX_ERR_INVALID with an error text, nothing copied. */
+typedef struct flx_derived_info { uint32_t filter_k, filter_tmin, have_isa, have_filter, have_filter_mirrored, reserved[3]; } flx_derived_info;
+int flx_ctx_derived_info(flx_ctx* ctx, flx_derived_info* out);
+int flx_ctx_copy_derived(flx_ctx* ctx, int which, void* out, uint64_t bytes);
+
 /* ------------------------------------------------------------------------------------------------ statistics (--stats)
  * replaces statistics::search_and_alignment_statistics (include/statistics.hpp:24-172, src/lib/statistics.cpp): the reference's
  * count and eighteen histograms, same names, thresholds and renderings. input_hint: NULL / "real_nanopore" / "simulated"
