@@ -19,6 +19,7 @@ libfloxer_amd.so:
     aligner(..., cs=cs_options()), cs_string(), cs_batch(), align_batch_cs()  not floxer's: minimap2's cs difference string, short or long form, built on the device behind the MD strings (opt-in)
     coverage(ctx, coverage_options()), coverage_host()  not floxer's: depth of coverage accumulated on the device from the records of runs: equal-depth runs, per-window sums (opt-in)
     pileup(ctx, pileup_options()), pileup_host(), pileup_sites_host()  not floxer's: per-position allele counts (depth, mismatch letters, deletions, insertions) accumulated on the device from the records of runs, and the table of candidate variant sites (opt-in)
+    sv(ctx, sv_options()), sv_host(), sv_clusters_host()  not floxer's: structural-variant signatures (long deletions, long insertions, split junctions) collected on the device from the records of runs, sorted and merged into clusters with their support (opt-in)
     record_sorter(n_refs), sort_host(), sort_geometry()  not floxer's: the coordinate order of records (reference, position, strand, then the caller's ordinal), sorted on the device by a radix sort over 128-bit keys (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
@@ -1283,6 +1284,130 @@ def pileup_sites_host(lengths, counts, options=None):
         check(rc)
     out = np.zeros(max(1, n.value), dtype=SITE_DTYPE)
     check(lib().flx_pileup_sites_host(ptr(lens, u64p), len(lens), opt, ptr(cnt, u32p), out.ctypes.data_as(C.POINTER(capi.PileupSite)), C.byref(n)))
+    return out[: n.value]
+
+
+# ------------------------------------------------------------------------------------------------ structural-variant signatures
+SV_SIGNATURE_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("res", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a", "<u4"), ("q", "<u4")])
+SV_CLUSTER_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("support", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a_min", "<u4"),
+                             ("pos_a_max", "<u4"), ("q_min", "<u4"), ("q_median", "<u4"), ("q_max", "<u4"), ("res", "<u4")])
+SV_TYPES = ("DEL", "INS", "BND")
+
+
+def sv_options(min_length=0, max_distance=0, min_support=0, count_secondary=False, min_mapq=0, initial_capacity=0):
+    """flx_sv_options: min_length: the fewest symbols of a D or I word that is a signature; max_distance: the largest gap, in pos_a and
+    in q, between neighbours of one cluster; min_support: the fewest members of a reported cluster; 0 takes the defaults 50, 100 and 2,
+    conventions of this project that are fitted to nothing. count_secondary: flag-256 records count (they never form junctions);
+    min_mapq: a record counts only with at least this mapping quality (needs runs made with output_options(mapq=True));
+    initial_capacity: the keys the table holds before it first grows (a test hook)"""
+    o = capi.SvOptions()
+    o.min_length, o.max_distance, o.min_support = int(min_length), int(max_distance), int(min_support)
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq = int(min_mapq)
+    o.initial_capacity = int(initial_capacity)
+    return o
+
+
+class sv:
+    """Structural-variant signatures over the sequences of a context's index (ctx) or over `lengths` on `device`: one signature per long
+    D word, long I word and junction between query-neighbouring records of a read; absorb the objects of other devices, finish once,
+    then read signatures() and clusters(). Not floxer's, and no variant caller: an exact table. Support counts records, not reads:
+    make the runs with output_options(drop_duplicates=True, max_alignments=1). Adds may come from several threads."""
+
+    def __init__(self, ctx=None, options=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_sv_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if lengths is None:
+                raise FloxerError("sv needs a context or a list of reference lengths")
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+            check(lib().flx_sv_create_for_lengths(int(device), ptr(lens, u64p), len(lens), opt, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_sv_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_run(self, run, read_lengths):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed;
+        read_lengths: the lengths of the reads of the batch the run was made from. With min_mapq a run made without
+        output_options(mapq=True) is refused. A raw handle goes through flx_sv_add_run, which forms a read's group within one piece of
+        the run; a RunResult holds the pieces' records in one array and goes through flx_sv_add_records. Both give the same groups:
+        all records of a read lie in one piece, next to each other, and neighbouring pieces hold different reads."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("sv.add_run: min_mapq needs a run made with output_options(mapq=True)")
+            return self.add_records(run.raw, run.cigars, read_lengths)
+        offs = _read_offsets(read_lengths)
+        check(lib().flx_sv_add_run(self.h, run, ptr(offs, u64p), len(offs) - 1))
+
+    def add_records(self, records, cigar_words, read_lengths):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        read_lengths: indexed by the records' `read`"""
+        rec, words = _records_and_words(records, cigar_words)
+        offs = _read_offsets(read_lengths)
+        check(lib().flx_sv_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p) if len(words) else None, len(words),
+                                       ptr(offs, u64p), len(offs) - 1))
+
+    def absorb(self, other):
+        check(lib().flx_sv_absorb(self.h, other.h))
+
+    def finish(self):
+        check(lib().flx_sv_finish(self.h))
+
+    def signatures(self):
+        """all signatures in key order, whatever min_support: a structured array of SV_SIGNATURE_DTYPE"""
+        out = np.zeros(1, dtype=SV_SIGNATURE_DTYPE)
+        check(lib().flx_sv_copy_signatures(self.h, 0, 0, out.ctypes.data_as(C.POINTER(capi.SvSignature))))       # (refused before finish)
+        n = lib().flx_sv_num_signatures(self.h)
+        out = np.zeros(max(1, n), dtype=SV_SIGNATURE_DTYPE)
+        check(lib().flx_sv_copy_signatures(self.h, 0, n, out.ctypes.data_as(C.POINTER(capi.SvSignature))))
+        return out[:n]
+
+    def clusters(self):
+        """the clusters with support >= min_support, in (class, coarse group, q) order: a structured array of SV_CLUSTER_DTYPE"""
+        n = lib().flx_sv_num_clusters(self.h)
+        out = np.zeros(max(1, n), dtype=SV_CLUSTER_DTYPE)
+        check(lib().flx_sv_copy_clusters(self.h, out.ctypes.data_as(C.POINTER(capi.SvCluster)), n))
+        return out[:n]
+
+
+def sv_host(lengths, records, cigar_words, read_lengths, options=None):
+    """the rule alone on the host (flx_sv_host): the signatures of the records in key order, a structured array of SV_SIGNATURE_DTYPE"""
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+    rec, words = _records_and_words(records, cigar_words)
+    offs = _read_offsets(read_lengths)
+    opt = C.byref(options) if options is not None else None
+    args = (ptr(lens, u64p) if len(lens) else None, len(lens), opt, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p) if len(words) else None,
+            len(words), ptr(offs, u64p), len(offs) - 1)
+    n = C.c_uint64(0)
+    rc = lib().flx_sv_host(*args, None, C.byref(n))
+    if rc not in (0, -3):                                               # (FLX_ERR_CAPACITY: n holds the need)
+        check(rc)
+    out = np.zeros(max(1, n.value), dtype=SV_SIGNATURE_DTYPE)
+    check(lib().flx_sv_host(*args, out.ctypes.data_as(C.POINTER(capi.SvSignature)), C.byref(n)))
+    return out[: n.value]
+
+
+def sv_clusters_host(signatures, options=None):
+    """the cluster rule alone on the host (flx_sv_clusters_host) over signatures in any order: a structured array of SV_CLUSTER_DTYPE"""
+    sig = np.ascontiguousarray(np.asarray(signatures, dtype=SV_SIGNATURE_DTYPE))
+    opt = C.byref(options) if options is not None else None
+    n = C.c_uint64(0)
+    rc = lib().flx_sv_clusters_host(opt, sig.ctypes.data_as(C.POINTER(capi.SvSignature)), len(sig), None, C.byref(n))
+    if rc not in (0, -3):
+        check(rc)
+    out = np.zeros(max(1, n.value), dtype=SV_CLUSTER_DTYPE)
+    check(lib().flx_sv_clusters_host(opt, sig.ctypes.data_as(C.POINTER(capi.SvSignature)), len(sig), out.ctypes.data_as(C.POINTER(capi.SvCluster)), C.byref(n)))
     return out[: n.value]
 
 

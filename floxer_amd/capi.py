@@ -165,6 +165,22 @@ class PileupSite(C.Structure):
                 ("alt", C.c_uint32 * 4), ("reserved", C.c_uint32)]
 
 
+class SvOptions(C.Structure):
+    _fields_ = [("min_length", C.c_uint32), ("max_distance", C.c_uint32), ("min_support", C.c_uint32), ("count_secondary", C.c_uint32),
+                ("min_mapq", C.c_uint32), ("reserved", C.c_uint32 * 3), ("initial_capacity", C.c_uint64)]
+
+
+class SvSignature(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("side_a", C.c_uint32), ("side_b", C.c_uint32), ("reserved", C.c_uint32), ("ref_a", C.c_int32),
+                ("ref_b", C.c_int32), ("pos_a", C.c_uint32), ("q", C.c_uint32)]
+
+
+class SvCluster(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("side_a", C.c_uint32), ("side_b", C.c_uint32), ("support", C.c_uint32), ("ref_a", C.c_int32),
+                ("ref_b", C.c_int32), ("pos_a_min", C.c_uint32), ("pos_a_max", C.c_uint32), ("q_min", C.c_uint32), ("q_median", C.c_uint32),
+                ("q_max", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SortOptions(C.Structure):
     _fields_ = [("initial_capacity", C.c_uint64), ("tile_keys", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
@@ -270,6 +286,8 @@ EXPORTED = [
     "flx_sort_create", "flx_sort_free", "flx_sort_add_records", "flx_sort_add_run", "flx_sort_finish", "flx_sort_num_records", "flx_sort_copy",
     "flx_sort_geometry", "flx_sort_host", "flx_sam_open_sorted",
     "flx_paf_create", "flx_paf_free", "flx_paf_summarize", "flx_paf_summarize_host", "flx_paf_open", "flx_paf_write", "flx_paf_close",
+    "flx_sv_create", "flx_sv_create_for_lengths", "flx_sv_free", "flx_sv_add_records", "flx_sv_add_run", "flx_sv_absorb", "flx_sv_finish",
+    "flx_sv_num_signatures", "flx_sv_copy_signatures", "flx_sv_num_clusters", "flx_sv_copy_clusters", "flx_sv_host", "flx_sv_clusters_host",
 ]
 
 _lib = None
@@ -439,6 +457,23 @@ def lib():
     L.flx_pileup_copy_counts.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
     L.flx_pileup_host.argtypes = [u64p, C.c_uint32, C.POINTER(PileupOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64, u32p]
     L.flx_pileup_sites_host.argtypes = [u64p, C.c_uint32, C.POINTER(PileupOptions), u32p, C.POINTER(PileupSite), u64p]
+    L.flx_sv_create.argtypes = [C.c_void_p, C.POINTER(SvOptions), C.POINTER(C.c_void_p)]
+    L.flx_sv_create_for_lengths.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(SvOptions), C.POINTER(C.c_void_p)]
+    L.flx_sv_free.restype = None
+    L.flx_sv_free.argtypes = [C.c_void_p]
+    L.flx_sv_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64]
+    L.flx_sv_add_run.argtypes = [C.c_void_p, C.c_void_p, u64p, C.c_uint64]
+    L.flx_sv_absorb.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_sv_finish.argtypes = [C.c_void_p]
+    L.flx_sv_num_signatures.restype = C.c_uint64
+    L.flx_sv_num_signatures.argtypes = [C.c_void_p]
+    L.flx_sv_copy_signatures.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SvSignature)]
+    L.flx_sv_num_clusters.restype = C.c_uint64
+    L.flx_sv_num_clusters.argtypes = [C.c_void_p]
+    L.flx_sv_copy_clusters.argtypes = [C.c_void_p, C.POINTER(SvCluster), C.c_uint64]
+    L.flx_sv_host.argtypes = [u64p, C.c_uint32, C.POINTER(SvOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64,
+                              C.POINTER(SvSignature), u64p]
+    L.flx_sv_clusters_host.argtypes = [C.POINTER(SvOptions), C.POINTER(SvSignature), C.c_uint64, C.POINTER(SvCluster), u64p]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

@@ -83,6 +83,9 @@ struct Options {
     std::string pileup;                                           // output file of the variant-site table; empty: not written
     uint64_t pileup_min_depth = 0, pileup_min_count = 0, pileup_min_permille = 0, pileup_min_mapq = 0;      // 0: the library's defaults
     bool pileup_secondary = false;
+    std::string sv;                                               // output file of the structural-variant cluster table; empty: not written
+    uint64_t sv_min_length = 0, sv_max_distance = 0, sv_min_support = 0, sv_min_mapq = 0;      // 0: the library's defaults
+    bool sv_secondary = false;
     bool sort_by_coordinate = false, bam_index = false;           // a coordinate-sorted BAM (flx_sam_open_sorted) and its BAI index
     std::string sort_tmp;                                         // the spill file's directory; empty: the output's
     std::string paf;                                              // the PAF output; empty: not written
@@ -149,6 +152,13 @@ const OptDef OPTS[] = {
     {0, "pileup-min-fraction", false, "not floxer's: and that count must be at least this fraction of the records over it, in (0, 1] (default 0.2, a convention fitted to nothing); needs --pileup"},
     {0, "pileup-secondary", true, "not floxer's: secondary records (flag 256) count too; needs --pileup"},
     {0, "pileup-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and --pileup"},
+    // nor these: structural-variant signatures (long deletions, long insertions, split junctions), sorted and clustered on the GPU (flx_sv, flx_sv.hpp)
+    {0, "sv-signatures", false, "not floxer's: clusters of structural-variant signatures, one line each (type DEL / INS / BND, name a, first and last position a, side a, name b, smallest, median and largest q, side b, support; positions are 1-based; q is a length for DEL and INS and a 1-based position for BND; sides are L / R for BND and . otherwise; <file.tsv>); exact counts of records, no variant calls: use -D -N 1; not with -w"},
+    {0, "sv-min-length", false, "not floxer's: a D or I word is a signature from this length on (default 50, a convention fitted to nothing); needs --sv-signatures"},
+    {0, "sv-max-distance", false, "not floxer's: neighbours of one cluster lie at most this far apart, in position and in q (default 100, a convention fitted to nothing); needs --sv-signatures"},
+    {0, "sv-min-support", false, "not floxer's: a cluster is written from this many records on (default 2, a convention fitted to nothing); needs --sv-signatures"},
+    {0, "sv-secondary", true, "not floxer's: secondary records (flag 256) count too, for DEL and INS (they never form junctions); needs --sv-signatures"},
+    {0, "sv-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and --sv-signatures"},
     // nor these: the output in coordinate order, its keys sorted on the GPU (flx_sort, flx_sort.hpp), and its BAI index
     {0, "sort-by-coordinate", true, "not floxer's: write the records in coordinate order (reference, position, strand; unmapped last) with @HD SO:coordinate; needs a .bam output"},
     {0, "bam-index", true, "not floxer's: write the BAI index <output>.bai as well; needs --sort-by-coordinate"},
@@ -292,6 +302,12 @@ Options parse_cli(int argc, char** argv) {
             o.pileup_min_permille = std::max<uint64_t>(1, flx_floating_point_error_aware_ceil(f * 1000.0));
         }
         else if (n == "pileup-secondary") o.pileup_secondary = true;
+        else if (n == "sv-signatures") o.sv = value;
+        else if (n == "sv-min-length") { o.sv_min_length = parse_u64(n, value); range_check(n, (double)o.sv_min_length, 1, 268435455.0); }
+        else if (n == "sv-max-distance") { o.sv_max_distance = parse_u64(n, value); range_check(n, (double)o.sv_max_distance, 1, 4294967295.0); }
+        else if (n == "sv-min-support") { o.sv_min_support = parse_u64(n, value); range_check(n, (double)o.sv_min_support, 1, 4294967295.0); }
+        else if (n == "sv-secondary") o.sv_secondary = true;
+        else if (n == "sv-min-mapq") { o.sv_min_mapq = parse_u64(n, value); range_check(n, (double)o.sv_min_mapq, 1, 254); }
         else if (n == "sort-by-coordinate") o.sort_by_coordinate = true;
         else if (n == "bam-index") o.bam_index = true;
         else if (n == "sort-tmp") { o.sort_tmp = value; if (value.empty()) throw CliError{"Validation failed for option --" + n + ": the directory's name is empty."}; }
@@ -359,6 +375,11 @@ Options parse_cli(int argc, char** argv) {
         throw CliError{"The options --pileup-min-depth, --pileup-min-count, --pileup-min-fraction, --pileup-secondary and --pileup-min-mapq need --pileup."};
     if (o.pileup_min_mapq && !o.mapping_quality) throw CliError{"The option --pileup-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
     if (!o.pileup.empty() && !has_ext(o.pileup, {"tsv"}, false)) throw CliError{"Validation failed for option --pileup: Expected one of the following valid extensions: [tsv]."};
+    if (!o.sv.empty() && o.without_cigar) throw CliError{"The option --sv-signatures needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.sv.empty() && (o.sv_min_length || o.sv_max_distance || o.sv_min_support || o.sv_secondary || o.sv_min_mapq))
+        throw CliError{"The options --sv-min-length, --sv-max-distance, --sv-min-support, --sv-secondary and --sv-min-mapq need --sv-signatures."};
+    if (o.sv_min_mapq && !o.mapping_quality) throw CliError{"The option --sv-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
+    if (!o.sv.empty() && !has_ext(o.sv, {"tsv"}, false)) throw CliError{"Validation failed for option --sv-signatures: Expected one of the following valid extensions: [tsv]."};
     if (!o.sort_by_coordinate && (o.bam_index || !o.sort_tmp.empty())) throw CliError{"The options --bam-index and --sort-tmp need --sort-by-coordinate."};
     if (o.sort_by_coordinate && !has_ext(o.output, {"bam"}, false)) throw CliError{"The option --sort-by-coordinate writes BAM and needs an -o/--output that ends in .bam."};
     if (!o.paf.empty() && o.without_cigar) throw CliError{"The option --paf needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
@@ -726,6 +747,29 @@ bool write_pileup(Options const& o, std::vector<flx_pileup*> const& piles, Refer
     return true;
 }
 
+// the structural-variant table: every device's signatures appended to the first object's, sorted and clustered there, and the clusters
+// written as text: positions 1-based; q is a length for DEL and INS and a 1-based position for BND; sides L / R for BND, . otherwise
+bool write_sv(Options const& o, std::vector<flx_sv*> const& svs, std::vector<std::string> const& names) {
+    for (size_t i = 1; i < svs.size(); ++i)
+        if (flx_sv_absorb(svs[0], svs[i]) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    flx_sv* const s = svs[0];
+    if (flx_sv_finish(s) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    std::vector<flx_sv_cluster> clusters(flx_sv_num_clusters(s));
+    if (flx_sv_copy_clusters(s, clusters.data(), clusters.size()) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    FILE* f = fopen(o.sv.c_str(), "w");
+    if (!f) { log_line("error", "cannot open output file: %s", o.sv.c_str()); return false; }
+    static const char* const types[3] = {"DEL", "INS", "BND"};
+    for (auto const& c : clusters) {
+        bool const bnd = c.type == 2;
+        unsigned long long const one = bnd ? 1 : 0;
+        fprintf(f, "%s\t%s\t%llu\t%llu\t%c\t%s\t%llu\t%llu\t%llu\t%c\t%u\n", types[c.type], names[(size_t)c.ref_a].c_str(), (unsigned long long)c.pos_a_min + 1,
+                (unsigned long long)c.pos_a_max + 1, bnd ? "LR"[c.side_a] : '.', names[(size_t)c.ref_b].c_str(), c.q_min + one, c.q_median + one, c.q_max + one,
+                bnd ? "LR"[c.side_b] : '.', c.support);
+    }
+    if (fclose(f) != 0) { log_line("error", "write error on the sv output"); return false; }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -821,6 +865,24 @@ int main(int argc, char** argv) {
             if (flx_pileup_create(c, &pile_opt, &pile) != FLX_OK) { log_line("error", "cannot set up the pileup accumulator: %s", flx_last_error()); return -1; }
             piles.push_back(pile);
         }
+    // the structural-variant signatures: one object per device too, fed with every batch's run and its reads' lengths
+    flx_sv_options sv_opt;
+    memset(&sv_opt, 0, sizeof(sv_opt));
+    sv_opt.min_length = (uint32_t)o.sv_min_length;
+    sv_opt.max_distance = (uint32_t)o.sv_max_distance;
+    sv_opt.min_support = (uint32_t)o.sv_min_support;
+    sv_opt.count_secondary = o.sv_secondary;
+    sv_opt.min_mapq = (uint32_t)o.sv_min_mapq;
+    std::vector<flx_sv*> svs;
+    if (!o.sv.empty()) {
+        if (!o.drop_duplicate_alignments)
+            log_line("warning", "--sv-signatures counts records, not reads: without -D/--drop-duplicate-alignments a read's records at one locus all add to a cluster's support (use -D -N 1).");
+        for (flx_ctx* c : ctxs) {
+            flx_sv* s = nullptr;
+            if (flx_sv_create(c, &sv_opt, &s) != FLX_OK) { log_line("error", "cannot set up the sv object: %s", flx_last_error()); return -1; }
+            svs.push_back(s);
+        }
+    }
 
     std::vector<const char*> ref_id_ptrs;
     for (auto const& s : ref.ids) ref_id_ptrs.push_back(s.c_str());
@@ -960,6 +1022,11 @@ int main(int argc, char** argv) {
             f.rc = flx_pileup_add_run(piles[at], run, b->pool.data(), b->offsets.data(), b->ids.size());
             if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
         }
+        if (!svs.empty()) {
+            size_t const at = std::find(ctxs.begin(), ctxs.end(), ctx) - ctxs.begin();
+            f.rc = flx_sv_add_run(svs[at], run, b->offsets.data(), b->ids.size());
+            if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
+        }
         f.recs.resize(flx_run_num_records(run));
         f.cig.resize(flx_run_num_cigar_words(run) + 1);
         f.skipped.resize(b->ids.size());
@@ -1088,6 +1155,8 @@ int main(int argc, char** argv) {
     for (flx_coverage* c : covs) flx_coverage_free(c);
     if (!piles.empty() && !failed.load() && !timed_out && !write_pileup(o, piles, ref)) failed.store(true);
     for (flx_pileup* c : piles) flx_pileup_free(c);
+    if (!svs.empty() && !failed.load() && !timed_out && !write_sv(o, svs, ref.ids)) failed.store(true);
+    for (flx_sv* c : svs) flx_sv_free(c);
     for (flx_ctx* c : ctxs) flx_ctx_destroy(c);
     flx_index_free(index);
     if (failed.load() || timed_out) return -1;

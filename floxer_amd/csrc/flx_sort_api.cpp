@@ -2,8 +2,9 @@
 // kernels: flx_sort.hip. The object owns one stream, the key table (a SortKey and a SortMeta per record added, in adding order), the
 // staging buffers of an add and the ping-pong buffers of a sort. Adds judge their records without the object's lock and take it for
 // the staging and the launches only, so several host threads may add at once. With device -1 nothing of the device exists and the
-// same calls keep the keys in host vectors and order them with std::sort (flx_sort_host's code). The scan of a pass's table:
-// flx_scan.hip; what the object shares with the other side objects: flx_object.hpp.
+// same calls keep the keys in host vectors and order them with std::sort (flx_sort_host's code). The host driver of the passes, which
+// flx_sv shares: flx_sort_driver.hpp; the scan of a pass's table: flx_scan.hip; what the object shares with the other side objects:
+// flx_object.hpp.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -14,27 +15,23 @@
 #include <set>
 
 #include "flx_object.hpp"
-#include "flx_sort.hpp"
+#include "flx_sort_driver.hpp"
 
 using namespace flx;
 
 namespace {
 constexpr u64 DEFAULT_INITIAL_CAPACITY = 1ull << 20;
-constexpr u64 SCAN_TILE = ScanDevice::SCAN_TILE;
 }  // namespace
 
 struct flx_sort : SideObject {           // mu: the table, staging, launches and `finished`; FLX_SORT_PROFILE
     u32 n_refs = 0;
     u64 initial_capacity = DEFAULT_INITIAL_CAPACITY;
-    u32 tile_keys = SortDevice::TILE_KEYS;
     bool finished = false;
     u64 count = 0, capacity = 0;         // records added; records the table holds
     std::set<u64> first_ordinals;        // of the adds so far
     DeviceBuffer keys, meta;             // the table
     DeviceBuffer records, words;         // an add's staging
-    DeviceBuffer keys_a, keys_b, pay_a, pay_b;      // a sort's ping-pong buffers (an add's own records, or the whole table at finish)
-    DeviceBuffer table, census;          // a pass's tile x digit table, the 16 x 256 digit counters
-    ScanDriver scan;                     // the table's scan
+    RadixSorter sorter;                  // the sort's driver with its ping-pong buffers (an add's own records, or the whole table at finish)
     DeviceBuffer entries;                // the sorted entries, behind finish
     std::vector<SortKey> h_keys;         // the host form's table
     std::vector<SortMeta> h_meta;
@@ -53,40 +50,6 @@ void host_order(const SortKey* keys, u64 n, std::vector<u32>& order) {
 }
 flx_sort_entry entry_of(SortKey const& k, SortMeta const& m) {
     return flx_sort_entry{sort_key_ordinal(k), sort_key_reference(k), sort_key_position(k), m.end, m.flag};
-}
-
-// Orders a[0, n) with its payload pa; b and pb are the second buffers. On return *sorted_keys / *sorted_payload name the buffers that
-// hold the result, *passes the passes run. The stream is idle on return.
-int radix_sort(flx_sort* s, SortKey* a, SortKey* b, u32* pa, u32* pb, u64 n, SortKey** sorted_keys, u32** sorted_payload, u32* passes) {
-    *sorted_keys = a;
-    *sorted_payload = pa;
-    *passes = 0;
-    if (n <= 1) return FLX_OK;
-    u32 const tile = (u32)sort_effective_tile(n, s->tile_keys, SortDevice::THREADS, SCAN_TILE);
-    u64 const n_tiles = (n + tile - 1) / tile, n_table = n_tiles * SORT_RADIX;
-    int rc;
-    if ((rc = s->census.ensure(SORT_DIGITS * SORT_RADIX * 4, true)) || (rc = s->table.ensure(n_table * 4)) || (rc = s->scan.reserve(n_table))) return rc;
-    FLX_HIP(hipMemsetAsync(s->census.ptr, 0, SORT_DIGITS * SORT_RADIX * 4, s->stream));
-    FLX_LAUNCH("sort_census", SortDevice::digit_census(s->stream, a, n, s->census.as<u32>()));
-    std::vector<u32> counts(SORT_DIGITS * SORT_RADIX);
-    FLX_HIP(hipMemcpyAsync(counts.data(), s->census.ptr, counts.size() * 4, hipMemcpyDeviceToHost, s->stream));
-    FLX_HIP(hipStreamSynchronize(s->stream));
-    for (u32 d = 0; d < SORT_DIGITS; ++d) {
-        bool constant = false;                                          // one value in every key: the pass would move nothing
-        for (u32 v = 0; v < SORT_RADIX; ++v) constant = constant || counts[d * SORT_RADIX + v] == n;
-        if (constant) continue;
-        u32* const table = s->table.as<u32>();
-        FLX_LAUNCH("sort_histogram", SortDevice::histogram(s->stream, a, n, d, tile, table));
-        if ((rc = s->scan.inclusive(s->stream, table, n_table))) return rc;       // (two levels at most: sort_effective_tile saw to it)
-        FLX_LAUNCH("sort_scatter", SortDevice::scatter(s->stream, a, pa, n, d, tile, table, b, pb));
-        std::swap(a, b);
-        std::swap(pa, pb);
-        ++*passes;
-    }
-    FLX_HIP(hipStreamSynchronize(s->stream));
-    *sorted_keys = a;
-    *sorted_payload = pa;
-    return FLX_OK;
 }
 
 // the table holds at least `need` records afterwards, its first `count` as before; a failure leaves it as it was
@@ -164,15 +127,15 @@ int add_pieces(flx_sort* s, std::vector<Piece> const& pieces, u64 first_ordinal,
     u32 passes = 0;
     float sort_ms = 0;
     if (out_order) {
-        if ((rc = s->keys_a.ensure(total * sizeof(SortKey))) || (rc = s->keys_b.ensure(total * sizeof(SortKey))) || (rc = s->pay_a.ensure(total * 4)) ||
-            (rc = s->pay_b.ensure(total * 4)))
+        if ((rc = s->sorter.keys_a.ensure(total * sizeof(SortKey))) || (rc = s->sorter.keys_b.ensure(total * sizeof(SortKey))) || (rc = s->sorter.pay_a.ensure(total * 4)) ||
+            (rc = s->sorter.pay_b.ensure(total * 4)))
             return rc;
         if ((rc = s->span_begin())) return rc;
-        FLX_HIP(hipMemcpyAsync(s->keys_a.ptr, s->keys.as<SortKey>() + s->count, total * sizeof(SortKey), hipMemcpyDeviceToDevice, s->stream));
-        FLX_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->pay_a.as<u32>(), total));
+        FLX_HIP(hipMemcpyAsync(s->sorter.keys_a.ptr, s->keys.as<SortKey>() + s->count, total * sizeof(SortKey), hipMemcpyDeviceToDevice, s->stream));
+        FLX_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->sorter.pay_a.as<u32>(), total));
         SortKey* sorted_keys;
         u32* sorted_payload;
-        if ((rc = radix_sort(s, s->keys_a.as<SortKey>(), s->keys_b.as<SortKey>(), s->pay_a.as<u32>(), s->pay_b.as<u32>(), total, &sorted_keys, &sorted_payload, &passes))) return rc;
+        if ((rc = s->sorter.sort(s->stream, s->sorter.keys_a.as<SortKey>(), s->sorter.keys_b.as<SortKey>(), s->sorter.pay_a.as<u32>(), s->sorter.pay_b.as<u32>(), total, &sorted_keys, &sorted_payload, &passes))) return rc;
         FLX_HIP(hipMemcpyAsync(out_order, sorted_payload, total * 4, hipMemcpyDeviceToHost, s->stream));
         if ((rc = s->span_end())) return rc;
         FLX_HIP(hipStreamSynchronize(s->stream));
@@ -205,7 +168,7 @@ extern "C" int flx_sort_create(int hip_device, uint32_t n_refs, const flx_sort_o
     auto s = std::make_unique<flx_sort>();              // (an error below drops it: nothing stays allocated)
     s->n_refs = n_refs;
     if (o && o->initial_capacity) s->initial_capacity = o->initial_capacity;
-    if (o && o->tile_keys) s->tile_keys = o->tile_keys;
+    if (o && o->tile_keys) s->sorter.tile_keys = o->tile_keys;
     int const rc = s->open(hip_device, "FLX_SORT_PROFILE");
     if (rc) return rc;
     *out = s.release();
@@ -244,21 +207,20 @@ extern "C" int flx_sort_finish(flx_sort* s) {
     if (n) {
         FLX_HIP(hipSetDevice(s->device));
         int rc;
-        if ((rc = s->keys_b.ensure(n * sizeof(SortKey), true)) || (rc = s->pay_a.ensure(n * 4, true)) || (rc = s->pay_b.ensure(n * 4, true)) ||
+        if ((rc = s->sorter.keys_b.ensure(n * sizeof(SortKey), true)) || (rc = s->sorter.pay_a.ensure(n * 4, true)) || (rc = s->sorter.pay_b.ensure(n * 4, true)) ||
             (rc = s->entries.ensure(n * sizeof(flx_sort_entry), true)))
             return rc;
         if ((rc = s->span_begin())) return rc;
-        FLX_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->pay_a.as<u32>(), n));
+        FLX_LAUNCH("sort_iota", SortDevice::iota(s->stream, s->sorter.pay_a.as<u32>(), n));
         SortKey* sorted_keys;
         u32* sorted_payload;
         // (the table itself is the first buffer: it is not read in adding order again)
-        if ((rc = radix_sort(s, s->keys.as<SortKey>(), s->keys_b.as<SortKey>(), s->pay_a.as<u32>(), s->pay_b.as<u32>(), n, &sorted_keys, &sorted_payload, &passes))) return rc;
+        if ((rc = s->sorter.sort(s->stream, s->keys.as<SortKey>(), s->sorter.keys_b.as<SortKey>(), s->sorter.pay_a.as<u32>(), s->sorter.pay_b.as<u32>(), n, &sorted_keys, &sorted_payload, &passes))) return rc;
         FLX_LAUNCH("sort_entries", SortDevice::entries(s->stream, sorted_keys, sorted_payload, s->meta.as<SortMeta>(), n, s->entries.ptr));
         if ((rc = s->span_end())) return rc;
         FLX_HIP(hipStreamSynchronize(s->stream));
         if ((rc = s->span_ms(ms))) return rc;
-        s->keys.release(); s->keys_a.release(); s->keys_b.release(); s->pay_a.release(); s->pay_b.release(); s->meta.release();
-        s->table.release(); s->records.release(); s->words.release();
+        s->keys.release(); s->meta.release(); s->sorter.release(); s->records.release(); s->words.release();
         s->capacity = 0;
     }
     s->finished = true;

@@ -814,6 +814,79 @@ int  flx_sort_geometry(uint32_t out[4]);
 int  flx_sort_host(uint32_t n_refs, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
                    const uint64_t* ordinals, flx_sort_entry* out_sorted);
 
+/* ------------------------------------------------------------------------------------------------ structural-variant signatures
+ * Not floxer's, and pileup's sibling for events too long for one position: where is the sample rearranged, and how many records say so?
+ * An sv object on a device collects one signature per long deletion, long insertion and split junction of the records added, orders
+ * them with the key sort (floxer_amd/csrc/flx_sort.hip) and merges neighbours into clusters with their support. No variant caller: no
+ * genotypes, no quality model; it is the exact table a caller starts from. It allocates nothing per reference position. The rule
+ * (floxer_amd/csrc/flx_sv.hpp), words len << 4 | op with = 7, X 8, I 1, D 2, S 4, positions 0-based and local to their sequence:
+ *   - which records count: exactly the coverage calls' filter (flag & 4 never, flag & 256 only with count_secondary, 2048 always, with
+ *     min_mapq > 0 only records whose `reserved` is at least that);
+ *   - DEL (type 0): every D word of a counted record with len >= min_length; pos_a = its first deleted column, q = len, ref_b = ref_a,
+ *     both sides 0. INS (type 1): every I word with len >= min_length; pos_a = the position of the record's preceding
+ *     reference-consuming column, or the record's first reference-consuming column when none precedes the word (pileup's anchor);
+ *     q = len, ref_b = ref_a, both sides 0;
+ *   - BND (type 2): one per pair of query-neighbouring records of a read. A read's group is the maximal run of neighbouring records of
+ *     the given array (within one piece of a run) with equal read_index; its members are its counted records with flag & 256 clear
+ *     (secondaries never form junctions, whatever count_secondary says). Each member has a query interval on the read as given (the PAF
+ *     summary's query_start / query_end); members are ordered by (query_start, index in the array). Each consecutive pair (a, b) gives
+ *     one junction of two ends, with rs = position and re = position + the summed = X D lengths: the end of a is (ref_a, re_a - 1,
+ *     side R = 1) when a is forward and (ref_a, rs_a, side L = 0) when a is reverse; the end of b is (ref_b, rs_b, L) when b is forward
+ *     and (ref_b, re_b - 1, R) when b is reverse. The two ends are put in ascending (ref, pos, side) order: the smaller is end a, its
+ *     position pos_a; the other's position is q. A read and its reverse complement, mapped to the same places, give equal signatures;
+ *   - refused (FLX_ERR_INVALID, on the host before any launch; the object stays as it was): all that the coverage calls refuse (a
+ *     counted record without CIGAR words, as a run made with without_cigar has them; words outside the pool; an op other than = X I D S;
+ *     a zero-length word; a reference_id outside the list; a negative position; a span that ends behind its sequence), a read_index
+ *     outside the reads, query-consuming lengths that do not sum to the read's length, no reference-consuming column, an S word with
+ *     other words on both sides, a group of more than 64 members, 2^30 sequences or more, min_mapq > 0 on a run made without mapq;
+ *   - a signature is one 128-bit key, hi = type << 62 | side_a << 61 | side_b << 60 | ref_a << 30 | ref_b, lo = pos_a << 32 | q: the
+ *     class (type, sides, ref_a, ref_b) orders ahead of the coordinates;
+ *   - clusters, made by flx_sv_finish in two levels: (1) in key order a coarse group breaks between neighbours whose class differs or
+ *     whose pos_a differ by more than max_distance; (2) within a coarse group, in (q, pos_a) order, a cluster breaks where q differs
+ *     from its predecessor by more than max_distance. A cluster reports its class, support (the number of its members), pos_a_min,
+ *     pos_a_max, q_min, q_max and q_median, the q of member (support - 1) / 2 in that order. Clusters come in the order of (2); those
+ *     with support < min_support are dropped. This is single linkage: a chain of close signatures can span more than max_distance;
+ *   - 0 takes the defaults min_length 50, max_distance 100, min_support 2: conventions of this project, fitted to nothing;
+ *   - support counts records, not reads: at default flags a read writes some forty records at one locus that share one CIGAR. Make the
+ *     runs with flx_output_options.drop_duplicates and max_alignments_per_read 1.
+ * Equal keys are interchangeable, so both tables are functions of the multiset of signatures alone: nothing depends on the order of
+ * adds, host threads, batch cuts or devices. Only read lengths are needed (read i has read_offsets[i + 1] - read_offsets[i] letters),
+ * never letters. options NULL: all zero; the reserved fields must be 0; initial_capacity (a test hook) is the keys the table holds
+ * before it first grows. Adds may come from several host threads: judging happens outside the object's lock, upload and launches
+ * inside it. The key table grows by reallocation and a device-to-device copy; a failed allocation is FLX_ERR_NO_DEVICE and leaves the
+ * object as it was; at most 2^32 - 1 signatures, FLX_ERR_CAPACITY beyond. A kernel that finds a record at odds with the host's
+ * judgement makes the add return FLX_ERR_INTERNAL. flx_sv_add_run walks a run and its parts and judges everything before it adds
+ * anything. flx_sv_absorb: `into` receives `from`'s signatures, `from` is left empty; equal lengths and options, both unfinished; the
+ * two may live on different devices. flx_sv_finish is final: a later add, absorb or finish is FLX_ERR_INVALID, and the num and copy
+ * calls work only behind it (flx_sv_num_*: 0 before); a finish that fails (FLX_ERR_NO_DEVICE: it allocates its sort buffers and
+ * tables) leaves the object unfinished, and empty when it failed behind the first sort (its buffers are reused). flx_sv_copy_signatures: all signatures [from, to) in key order, whatever
+ * min_support. flx_sv_copy_clusters: FLX_ERR_CAPACITY when capacity is below flx_sv_num_clusters.
+ * flx_sv_host: the rule alone on the host, no device: *n_signatures holds the capacity of `out` on entry and the number of signatures
+ * on return, in key order (FLX_ERR_CAPACITY when that is more; `out` may be NULL with capacity 0); the same refusals, `out` untouched
+ * when it refuses. flx_sv_clusters_host: the clusters of n signatures in any order, the same way.
+ * FLX_SV_PROFILE (environment): every add and the finish print records, words, signatures, passes, device time and wall time to stderr. */
+typedef struct flx_sv flx_sv;
+typedef struct flx_sv_options { uint32_t min_length, max_distance, min_support, count_secondary, min_mapq; uint32_t reserved[3]; uint64_t initial_capacity; } flx_sv_options;
+typedef struct flx_sv_signature { uint32_t type, side_a, side_b, reserved; int32_t ref_a, ref_b; uint32_t pos_a, q; } flx_sv_signature;
+typedef struct flx_sv_cluster { uint32_t type, side_a, side_b, support; int32_t ref_a, ref_b; uint32_t pos_a_min, pos_a_max, q_min, q_median, q_max, reserved; } flx_sv_cluster;
+int  flx_sv_create(flx_ctx* ctx, const flx_sv_options* o, flx_sv** out);
+int  flx_sv_create_for_lengths(int hip_device, const uint64_t* ref_lens, uint32_t n_refs, const flx_sv_options* o, flx_sv** out);
+void flx_sv_free(flx_sv* s);
+int  flx_sv_add_records(flx_sv* s, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                        const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_sv_add_run(flx_sv* s, const flx_run* run, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_sv_absorb(flx_sv* into, flx_sv* from);
+int  flx_sv_finish(flx_sv* s);
+uint64_t flx_sv_num_signatures(const flx_sv* s);
+int  flx_sv_copy_signatures(const flx_sv* s, uint64_t from, uint64_t to, flx_sv_signature* out);
+uint64_t flx_sv_num_clusters(const flx_sv* s);
+int  flx_sv_copy_clusters(const flx_sv* s, flx_sv_cluster* out, uint64_t capacity);
+int  flx_sv_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_sv_options* o, const flx_record* records, uint64_t n,
+                 const uint32_t* cigar_words, uint64_t n_words, const uint64_t* read_offsets, uint64_t n_reads,
+                 flx_sv_signature* out, uint64_t* n_signatures /* in: capacity, out: needed */);
+int  flx_sv_clusters_host(const flx_sv_options* o, const flx_sv_signature* signatures, uint64_t n, flx_sv_cluster* out,
+                          uint64_t* n_clusters /* in: capacity, out: needed */);
+
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
  * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
