@@ -31,12 +31,27 @@ import numpy as np
 from . import capi
 from .capi import FloxerError, check, lib, ptr, as_u8, u8p, u32p, u64p
 
+# The library asks the HIP runtime for its hardware queues when it is loaded (hw_queue_request below), and the runtime reads the request
+# when it initialises, with the process's first HIP call. So the library is loaded with the package, not by the first call into it: a
+# program that imports torch, imports this package and only then touches the GPU gets the request in time. (A library that is not built
+# stays the error of the first call that needs it.)
+if capi.os.path.exists(capi.LIB_PATH):
+    lib()
+
 CIGAR_OPS = "MIDNSHP=X"
 NULL_ID = 0xFFFFFFFF
 
 ORDER = {"errors_first": 0, "count_first": 1, "none": 2}          # search.cpp:59-69
 CHOICE = {"round_robin": 0, "full_groups": 1, "first_reported": 2}  # search.cpp:71-81
 MODE_EXISTS, MODE_WITHOUT_CIGAR, MODE_WITH_CIGAR = 0, 1, 2
+
+
+def hw_queue_request():
+    """(requested, found): the GPU_MAX_HW_QUEUES the library wrote when it was loaded (FLX_HW_QUEUES, default 16, 4 .. 32; 0 when
+    FLX_HW_QUEUES=0 made it leave the variable alone) and the value it found there (-1: the variable was unset)"""
+    requested, found = C.c_int(0), C.c_int(-1)
+    check(lib().flx_hw_queue_request(C.byref(requested), C.byref(found)))
+    return requested.value, found.value
 
 
 def cigar_string(words):
@@ -247,6 +262,13 @@ class context:
             out = np.empty((4 ** self.derived_info()["filter_k"] + 63) // 64, dtype=np.uint64)
         check(lib().flx_ctx_copy_derived(self.h, {"isa": 0, "filter": 1, "filter_mirrored": 2}[which], out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
+
+    def lane_overlap(self, n_lanes, iterations):
+        """(start_ms, stop_ms), two lists of n_lanes floats (flx_ctx_lane_overlap, a test hook): one one-wave kernel of `iterations`
+        dependent steps on each of the first n_lanes lanes' streams; when each started and stopped, behind one reference event"""
+        start, stop = (C.c_float * n_lanes)(), (C.c_float * n_lanes)()
+        check(lib().flx_ctx_lane_overlap(self.h, n_lanes, iterations, start, stop))
+        return list(start), list(stop)
 
     def kernel_stats(self):
         arr = (capi.KernelStat * 64)()

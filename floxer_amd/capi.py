@@ -275,6 +275,7 @@ EXPORTED = [
     "flx_realign", "flx_realign_batch", "flx_align_batch_realign", "flx_ctx_get_realign_counters", "flx_align_reads_realign",
     "flx_align_reads_resident_realign", "flx_run_copy_scores", "flx_sam_write_scored",
     "flx_ctx_get_search_counters", "flx_climb_anchors", "flx_ctx_derived_info", "flx_ctx_copy_derived",
+    "flx_hw_queue_request", "flx_ctx_lane_overlap",
     "flx_align_reads_cs", "flx_align_reads_resident_cs", "flx_run_num_cs_bytes", "flx_run_copy_cs", "flx_align_batch_cs", "flx_cs", "flx_cs_batch",
     "flx_sam_write_cs",
     "flx_coverage_create", "flx_coverage_create_for_lengths", "flx_coverage_free", "flx_coverage_add_run", "flx_coverage_add_records",
@@ -328,6 +329,15 @@ def lib():
                           "(floxer_amd has no CPU fallback)")
     _share_torchs_hip_runtime()
     L = C.CDLL(LIB_PATH)
+    # (the library writes its hardware-queue request into the process's environment when it is loaded, flx_hw_queue_request; os.environ is
+    # Python's copy from start-up, which child processes inherit: it follows)
+    getenv = C.CDLL(None).getenv
+    getenv.restype, getenv.argtypes = C.c_char_p, [C.c_char_p]
+    value = getenv(b"GPU_MAX_HW_QUEUES")
+    if value is None:
+        os.environ.pop("GPU_MAX_HW_QUEUES", None)
+    else:
+        os.environ["GPU_MAX_HW_QUEUES"] = value.decode()
     L.flx_last_error.restype = C.c_char_p
     L.flx_version.restype = C.c_char_p
     L.flx_ceil_div.restype = C.c_uint64
@@ -530,6 +540,8 @@ def lib():
     L.flx_climb_anchors.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ClimbOptions), u8p, u32p, u64p]
     L.flx_ctx_derived_info.argtypes = [C.c_void_p, C.POINTER(DerivedInfo)]
     L.flx_ctx_copy_derived.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
+    L.flx_hw_queue_request.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.flx_ctx_lane_overlap.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.flx_sim_genome.argtypes = [C.c_uint64, C.c_uint64, u8p]
     L.flx_sim_genome_repeats.argtypes = [C.c_uint64, C.c_uint64, u8p]
     L.flx_sim_reads.argtypes = [u8p, u64p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_uint64, u8p, C.c_uint64,

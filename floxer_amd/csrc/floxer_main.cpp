@@ -836,6 +836,12 @@ int main(int argc, char** argv) {
         ctxs.push_back(c);
     }
     log_line("info", "running on %zu HIP device context%s", ctxs.size(), ctxs.size() == 1 ? "" : "s");
+    {
+        int requested = 0, found = -1;
+        flx_hw_queue_request(&requested, &found);
+        if (requested) log_line("debug", "hardware queues: asked the HIP runtime for %d (FLX_HW_QUEUES; GPU_MAX_HW_QUEUES on entry: %d, -1 = unset)", requested, found);
+        else log_line("debug", "hardware queues: GPU_MAX_HW_QUEUES left as found (%d, -1 = unset; FLX_HW_QUEUES=0)", found);
+    }
     // the depth track: one accumulator per device, fed by every batch that device aligns and summed into the first after the last batch
     flx_coverage_options cov_opt;
     memset(&cov_opt, 0, sizeof(cov_opt));

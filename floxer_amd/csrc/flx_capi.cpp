@@ -29,9 +29,33 @@ int flx_index_build_on_device(int hip_device, const uint8_t* concat, const uint6
 }
 // ---------------------------------------------------------------- context
 // ROCm multiplexes a process's HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); kernels of lanes that share a
-// queue do not overlap. The HIP runtime reads the variable when it initialises, so it is set when this library is loaded (an
-// existing value wins). A host program that initialises HIP before loading the library sets it itself.
-__attribute__((constructor)) static void flx_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
+// queue do not overlap. The HIP runtime reads the variable when it initialises, so it is written when this library is loaded, over
+// whatever is there: FLX_HW_QUEUES queues (default 16, also for a value that is no number; clamped to 4 .. 32: below 4 a host
+// program's captured graphs can crash on replay in this runtime). FLX_HW_QUEUES=0 leaves the variable as it was found, for whoever
+// chooses the runtime's value themselves. A host program that initialises HIP before loading the library sets it itself.
+namespace {
+int hw_queues_requested = 0, hw_queues_found = -1;
+__attribute__((constructor)) void flx_request_hw_queues() {
+    if (const char* was = getenv("GPU_MAX_HW_QUEUES")) hw_queues_found = atoi(was);
+    long want = 16;
+    if (const char* env = getenv("FLX_HW_QUEUES")) {
+        char* end = nullptr;
+        long const v = strtol(env, &end, 10);
+        if (end != env && *end == 0) want = v;
+    }
+    if (want == 0) return;
+    want = std::max(4l, std::min(32l, want));
+    char text[8];
+    snprintf(text, sizeof text, "%ld", want);
+    if (setenv("GPU_MAX_HW_QUEUES", text, 1) == 0) hw_queues_requested = (int)want;
+}
+}  // namespace
+
+int flx_hw_queue_request(int* requested, int* found) {
+    if (requested) *requested = hw_queues_requested;
+    if (found) *found = hw_queues_found;
+    return FLX_OK;
+}
 
 int flx_device_count(void) {
     int count = 0;
@@ -350,6 +374,50 @@ int flx_ctx_copy_derived(flx_ctx* ctx, int which, void* out, uint64_t bytes) {
     if (bytes != want) { set_error("flx_ctx_copy_derived: the table holds " + std::to_string(want) + " bytes, the caller gave " + std::to_string(bytes)); return FLX_ERR_INVALID; }
     FLX_HIP(hipSetDevice(ctx->device));
     FLX_HIP(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
+    return FLX_OK;
+}
+
+// ---- do the lanes' streams overlap (flx_ctx_lane_overlap, include/floxer_amd.h): a test hook. One bounded one-wave kernel per lane
+// between two events of its own, all lanes waited for; events and the kernels' output block live for the call only, nothing of a
+// run's path is touched.
+int flx_ctx_lane_overlap(flx_ctx* ctx, uint32_t n_lanes, uint32_t iterations, float* start_ms, float* stop_ms) {
+    if (!ctx || !start_ms || !stop_ms) { set_error("flx_ctx_lane_overlap: null argument"); return FLX_ERR_INVALID; }
+    if (n_lanes == 0 || n_lanes > ctx->lanes.size()) { set_error("flx_ctx_lane_overlap: the context has " + std::to_string(ctx->lanes.size()) + " lanes, the caller asked for " + std::to_string(n_lanes)); return FLX_ERR_INVALID; }
+    for (uint32_t l = 0; l < n_lanes; ++l)
+        if (!ctx->lanes[l]->own_stream) { set_error("flx_ctx_lane_overlap: lane " + std::to_string(l) + " has no stream of its own (FLX_STREAMS)"); return FLX_ERR_INVALID; }
+    iterations = std::min<uint32_t>(iterations, 1u << 24);
+    int rc = ctx->sync_all();
+    if (rc) return rc;
+    FLX_HIP(hipSetDevice(ctx->device));
+    struct Probe {
+        hipEvent_t ref = nullptr;
+        std::vector<hipEvent_t> a, b;
+        u32* out = nullptr;
+        ~Probe() {
+            for (hipEvent_t e : a) if (e) (void)hipEventDestroy(e);
+            for (hipEvent_t e : b) if (e) (void)hipEventDestroy(e);
+            if (ref) (void)hipEventDestroy(ref);
+            if (out) (void)hipFree(out);
+        }
+    } p;
+    p.a.assign(n_lanes, nullptr);
+    p.b.assign(n_lanes, nullptr);
+    FLX_HIP(hipEventCreate(&p.ref));
+    for (uint32_t l = 0; l < n_lanes; ++l) { FLX_HIP(hipEventCreate(&p.a[l])); FLX_HIP(hipEventCreate(&p.b[l])); }
+    FLX_HIP(hipMalloc((void**)&p.out, (size_t)n_lanes * 64 * sizeof(u32)));
+    FLX_HIP(hipEventRecord(p.ref, ctx->lanes[0]->own_stream));
+    for (uint32_t l = 0; l < n_lanes && !rc; ++l) {
+        hipStream_t const s = ctx->lanes[l]->own_stream;
+        FLX_HIP(hipEventRecord(p.a[l], s));
+        rc = DeviceApi::lane_overlap_probe(s, iterations, p.out + (size_t)l * 64);
+        FLX_HIP(hipEventRecord(p.b[l], s));
+    }
+    for (uint32_t l = 0; l < n_lanes; ++l) FLX_HIP(hipStreamSynchronize(ctx->lanes[l]->own_stream));
+    if (rc) { set_error(std::string("lane_overlap_probe: ") + hipGetErrorString((hipError_t)rc)); return FLX_ERR_NO_DEVICE; }
+    for (uint32_t l = 0; l < n_lanes; ++l) {
+        FLX_HIP(hipEventElapsedTime(&start_ms[l], p.ref, p.a[l]));
+        FLX_HIP(hipEventElapsedTime(&stop_ms[l], p.ref, p.b[l]));
+    }
     return FLX_OK;
 }
 

@@ -396,6 +396,9 @@ struct DeviceApi {
     // flx_stage.hip: every item's words copied from device memory to where the host reads them (page-locked mapped memory), with ordinary
     // vector stores (one launch)
     static int publish_stage(void* stream, PublishList const& L);
+    // flx_stage.hip: one wave running a dependent integer chain of `iterations` steps, its 64 results stored to d_out (the probe of
+    // flx_ctx_lane_overlap: a kernel of a known length that reads no memory and waits for nothing)
+    static int lane_overlap_probe(void* stream, u32 iterations, u32* d_out);
     // suffix array of text[0, n) on the device (a suffix that is a prefix of another sorts first); out: n entries on the host
     static int suffix_array(int hip_device, const u8* text, u64 n, u32* out);
     // suffix array, BWT of the text and of the reversed text and both occurrence tables (n / 64 + 1 blocks each), built on the

@@ -49,4 +49,20 @@ int DeviceApi::publish_stage(void* stream, PublishList const& L) {
     return (int)hipGetLastError();
 }
 
+// The probe of flx_ctx_lane_overlap: one wave that keeps one SIMD busy for a time that `iterations` fixes. Every step needs the one
+// before it, nothing is read from memory and nothing is waited for; the one store at the end keeps the chain alive. out: 64 words.
+__global__ void __launch_bounds__(64) lane_overlap_kernel(u32 iterations, u32* __restrict__ out) {
+    u32 x = threadIdx.x + 1u;
+    for (u32 i = 0; i < iterations; ++i) {
+        x ^= x >> 7;
+        x = x * 0x9E3779B1u + i;
+    }
+    out[threadIdx.x] = x;
+}
+
+int DeviceApi::lane_overlap_probe(void* stream, u32 iterations, u32* d_out) {
+    hipLaunchKernelGGL(lane_overlap_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, iterations, d_out);
+    return (int)hipGetLastError();
+}
+
 }  // namespace flx

@@ -1013,6 +1013,22 @@ typedef struct flx_derived_info { uint32_t filter_k, filter_tmin, have_isa, have
 int flx_ctx_derived_info(flx_ctx* ctx, flx_derived_info* out);
 int flx_ctx_copy_derived(flx_ctx* ctx, int which, void* out, uint64_t bytes);
 
+/* The hardware queues the library asked the HIP runtime for when it was loaded. The runtime spreads a process's streams over
+ * GPU_MAX_HW_QUEUES hardware queues and kernels of streams that share a queue do not overlap, so at load the library writes
+ * FLX_HW_QUEUES into that variable, over whatever is there: default 16 (also for a value that is no number), clamped to 4 .. 32;
+ * FLX_HW_QUEUES=0 leaves the variable exactly as it was found. The runtime reads the variable when it initialises: a host program
+ * that makes its first HIP call before it loads the library sets the variable itself.
+ * requested (may be NULL): what the library wrote, 0 if it left the variable alone; found (may be NULL): the variable's value on
+ * entry, -1 if it was unset. */
+int flx_hw_queue_request(int* requested, int* found);
+
+/* Do the lanes' streams overlap on the GPU (a test hook; nothing of a run's path is touched): on each of the first n_lanes lanes' own
+ * streams an event, one kernel of one wave that runs a dependent integer chain of `iterations` steps (capped at 1 << 24) and reads
+ * nothing, and a second event; all lanes are waited for. start_ms / stop_ms (n_lanes floats each): the events' times in ms behind a
+ * reference event recorded first. Kernels of lanes that share a hardware queue show up one behind the other. The context must be
+ * idle. n_lanes 0 or above the context's lanes, or a null argument: FLX_ERR_INVALID. */
+int flx_ctx_lane_overlap(flx_ctx* ctx, uint32_t n_lanes, uint32_t iterations, float* start_ms, float* stop_ms);
+
 /* ------------------------------------------------------------------------------------------------ statistics (--stats)
  * replaces statistics::search_and_alignment_statistics (include/statistics.hpp:24-172, src/lib/statistics.cpp): the reference's
  * count and eighteen histograms, same names, thresholds and renderings. input_hint: NULL / "real_nanopore" / "simulated"
