@@ -74,7 +74,7 @@ struct Lane {
     int id = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     DeviceBuffer seq, seq_rev, peq, peq_rev, scheme, seeds, stack, hits, counters, rows, rows_out, qpack, items;
-    DeviceBuffer jobs, job_out, trace, tjobs, tjob_out, cigar, md, md_jobs, md_out, user_text, user_text_rev, lastrow, row_windows, row_out,
+    DeviceBuffer jobs, job_out, trace, tjobs, tjob_out, cigar, md, md_out, user_text, user_text_rev, lastrow, row_windows, row_out,
         seed_cnt, hit_off, grouped, sel_stat, sel_n, sel_off, sel_out, sel_tmp, sel_rows, sel_row_off, sel_sparse, sel_lists, vr, seed_gen, mailboxes, ext_jobs, ext_out, tail_jobs, tail_out, cigar_la, la_jobs, la_stat, cigar_ra, ra_jobs, ra_stat, cs, cs_jobs, cs_out;
     size_t trace_budget_bytes = 0;
     std::vector<PendingTiming> pending;
@@ -92,6 +92,10 @@ struct Lane {
     PinnedBuffer results;
     size_t results_used = 0;
     static constexpr size_t RESULT_BLOCK_BYTES = 1u << 20;
+    // the bytes result_slot hands out at most: RESULT_BLOCK_BYTES, or less under FLX_RESULT_BLOCK_BYTES (a test hook, read when the block
+    // is first made; 0: no block at all, every table takes its copy path)
+    size_t results_limit = RESULT_BLOCK_BYTES;
+    bool results_limit_read = false;
     void* result_slot(size_t bytes); // null: no room (the caller copies instead)
     bool has_run = false;            // a chunk has run here (its workspaces have their working sizes)
     double hits_per_seed = 0, items_per_seed = 0, sel_rows_per_seed = 0;      // of the last search here: the next one's buffers are sized for that and a margin

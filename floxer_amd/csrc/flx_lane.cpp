@@ -59,9 +59,15 @@ void* Lane::stage_begin(size_t bytes) {
     return staging.ptr;
 }
 void* Lane::result_slot(size_t bytes) {
-    if (!results.ptr && results.ensure(RESULT_BLOCK_BYTES)) { (void)hipGetLastError(); return nullptr; }
+    if (!results_limit_read) {
+        const char* const env = getenv("FLX_RESULT_BLOCK_BYTES");
+        if (env) results_limit = std::min<size_t>(strtoull(env, nullptr, 10), RESULT_BLOCK_BYTES);
+        results_limit_read = true;
+    }
+    if (results_limit == 0) return nullptr;
+    if (!results.ptr && results.ensure(results_limit)) { (void)hipGetLastError(); return nullptr; }
     size_t const at = (results_used + 63) & ~(size_t)63;
-    if (bytes == 0 || at + bytes > results.cap) return nullptr;
+    if (bytes == 0 || at + bytes > results_limit) return nullptr;      // (the limit, not results.cap: ensure may have allocated slack)
     results_used = at + bytes;
     return (char*)results.ptr + at;
 }
@@ -78,7 +84,7 @@ struct Workspace { const char* name; DeviceBuffer Lane::*member; };
 #define FLX_WS(m) Workspace{#m, &Lane::m}
 constexpr Workspace WORKSPACES[] = {
     FLX_WS(seq), FLX_WS(seq_rev), FLX_WS(peq), FLX_WS(peq_rev), FLX_WS(scheme), FLX_WS(seeds), FLX_WS(stack), FLX_WS(hits), FLX_WS(counters), FLX_WS(rows),
-    FLX_WS(rows_out), FLX_WS(jobs), FLX_WS(job_out), FLX_WS(trace), FLX_WS(tjobs), FLX_WS(tjob_out), FLX_WS(cigar), FLX_WS(md), FLX_WS(md_jobs), FLX_WS(md_out), FLX_WS(user_text), FLX_WS(user_text_rev),
+    FLX_WS(rows_out), FLX_WS(jobs), FLX_WS(job_out), FLX_WS(trace), FLX_WS(tjobs), FLX_WS(tjob_out), FLX_WS(cigar), FLX_WS(md), FLX_WS(md_out), FLX_WS(user_text), FLX_WS(user_text_rev),
     FLX_WS(lastrow), FLX_WS(row_windows), FLX_WS(row_out), FLX_WS(seed_cnt), FLX_WS(hit_off), FLX_WS(grouped), FLX_WS(sel_stat), FLX_WS(sel_n), FLX_WS(sel_off),
     FLX_WS(sel_out), FLX_WS(sel_tmp), FLX_WS(sel_rows), FLX_WS(sel_row_off), FLX_WS(sel_sparse), FLX_WS(sel_lists), FLX_WS(vr), FLX_WS(qpack), FLX_WS(items),
     FLX_WS(seed_gen), FLX_WS(mailboxes), FLX_WS(ext_jobs), FLX_WS(ext_out), FLX_WS(tail_jobs), FLX_WS(tail_out), FLX_WS(cigar_la), FLX_WS(la_jobs), FLX_WS(la_stat), FLX_WS(cigar_ra), FLX_WS(ra_jobs), FLX_WS(ra_stat), FLX_WS(cs), FLX_WS(cs_jobs), FLX_WS(cs_out)};

@@ -1,6 +1,7 @@
 // What the pieces of the host pipeline share: flx_lane.cpp (buffers, lanes, copies), flx_seeding.cpp (K1/K2 + anchor selection),
-// flx_align_jobs.cpp (K0/K3/K4/K5 job batches), flx_verify.cpp (one chunk of reads: align_slice and its stages) and
-// flx_pipeline.cpp (read batches, chunking over lanes, the C ABI of runs).
+// flx_align_jobs.cpp (K0/K3/K4 job batches), flx_traceback.cpp with flx_traceback.hpp (K5 and the passes behind it),
+// flx_align_capi.cpp (the C ABI of job batches and of a kernel alone), flx_verify.cpp (one chunk of reads: align_slice and its stages)
+// and flx_pipeline.cpp (read batches, chunking over lanes, the C ABI of runs).
 #pragma once
 
 #include <chrono>
@@ -121,11 +122,19 @@ struct TraceResult {
     u32 ed = 0;                 // ed the edit distance K4 found (nm without the option)
     u64 cs_off = 0; u32 cs_len = 0;      // its cs string (flx_cs.hip) in the caller's cs pool, when wanted
 };
-// the cs strings of the traced paths (flx_cs.hip) for the traces that want them: form 1 (short) or 2 (long), the device query pool's
-// letters (q_off addresses them as it does the Peq planes) and the host pool the bytes land in (shared by duplicates like the CIGAR words)
-struct CsWant { u32 form; const u8* d_query; hvec<u8>* pool; };
 // the values of the tail rule (flx_tails.hpp) for the traces that want it, defaults resolved
 struct TailParams { u32 w, x_drop, min_rows; };
+// What a trace wants beyond score, begin and CIGAR (default: nothing). Every pass runs behind K5 on each traced path (flx_traceback.hpp).
+struct RealignScores;
+struct TraceWants {
+    hvec<u8>* md_pool = nullptr;             // the MD strings (flx_md.hip), their bytes into this pool (shared by duplicates like the CIGAR words)
+    const TailParams* tails = nullptr;       // the paths' tails (flx_tails.hip), in TraceResult::tail
+    bool left_align = false;                 // gaps left-aligned (flx_leftalign.hip) before the MD string, cs string and tails are read off them
+    const RealignScores* realign = nullptr;  // the paths realigned under these scores (flx_realign.hip) before all of that
+    u32 cs_form = 0;                         // the cs strings (flx_cs.hip), form 1 (short) or 2 (long), read off the final words,
+    hvec<u8>* cs_pool = nullptr;             // their bytes into this pool
+    const u8* d_query = nullptr;             // the device query pool's letters (q_off addresses them as it does the Peq planes): left-align, realign and cs read them
+};
 // host milliseconds of the host-rounds form, summed over a chunk's rounds (FLX_HOST_PROFILE); owned by the chunk
 struct ExistsTimes { double ms[4] = {0, 0, 0, 0}; double build_requests = 0; };      // ms: dedup, cluster, GPU round trip, scatter
 
@@ -133,35 +142,15 @@ u64 round_span_percent();       // a round tests the nodes of [smallest, smalles
 u64 align_few_waves();          // FLX_ALIGN_FEW_WAVES overrides the threshold (tests force either form)
 // score + end column for every request (no trace)
 int run_score_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, const char* kernel_name);
-// score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates).
-// md_pool != null: the MD string of every traced path as well (flx_md.hip), its bytes in md_pool (shared like the CIGAR words);
-// tails != null: the tails of every traced path as well (flx_tails.hip), in TraceResult::tail;
-// d_la_query != null: the device query pool's letters (q_off addresses them as it does the Peq planes), and every traced path's gaps are
-// left-aligned behind K5 (flx_leftalign.hip) before its MD string and tails are read off it
-// d_ra_query != null: the same letters, and every traced path is realigned under *realign behind K5 (flx_realign.hip) before all of that
-// cs != null: the cs string of every traced path as well (flx_cs.hip), read off the final words behind md_build
-struct RealignScores;
-int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                   hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr,
-                   const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr, const CsWant* cs = nullptr);
+// score, begin position and CIGAR for every request (alignment.cpp:147-180); CIGAR words land in cigar_pool (shared by duplicates)
+int run_trace_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<TraceResult>& results, hvec<u32>& cigar_pool,
+                   TraceWants const& wants);
 // the same for root windows: anchors of one locus share one DP over the union of their windows
-int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs,
-                         hvec<TraceResult>& results, hvec<u32>& cigar_pool, hvec<u8>* md_pool = nullptr, const TailParams* tails = nullptr, const u8* d_la_query = nullptr,
-                         const RealignScores* realign = nullptr, const u8* d_ra_query = nullptr, const CsWant* cs = nullptr);
-// one cs_build launch over words and DevTraceOuts made on the host (flx_cs_batch): slabs receives the jobs' slabs (slab_bytes bytes),
-// lens the length of every job's string
-int run_cs_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevCsJob> const& jobs,
-                u32 form, u64 slab_bytes, hvec<u8>& slabs, hvec<u32>& lens);
-// one cigar_left_align launch over words and DevTraceOuts made on the host (flx_left_align_batch): out_words receives the second buffer
-// (words_out words), touts the rewritten DevTraceOuts
-int run_left_align_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts,
-                        hvec<DevLeftAlignJob> const& jobs, u64 words_out, hvec<u32>& out_words);
-// cigar_realign over words and DevTraceOuts made on the host (flx_realign_batch), cut into launches that fit the lane's trace arena:
-// jobs[i].trace_cap = the trace words job i needs on entry; out_words receives the second buffer, touts the rewritten DevTraceOuts
-int run_realign_jobs(Lane* lane, const u8* d_text, const u8* d_query, const u32* words, u64 n_words, hvec<DevTraceOut>& touts, hvec<DevRealignJob>& jobs,
-                     RealignScores const& scores, u64 words_out, hvec<u32>& out_words, hvec<DevRealignStat>& stats);
-// one cigar_tails launch over words and DevTraceOuts made on the host (flx_cigar_tails_batch)
-int run_tail_jobs(Lane* lane, const u32* words, u64 n_words, hvec<DevTraceOut> const& touts, hvec<DevTailJob> const& jobs, hvec<DevTailOut>& outs);
+int run_trace_jobs_union(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<TraceResult>& results, hvec<u32>& cigar_pool,
+                         TraceWants const& wants);
+// the distinct requests of `reqs` and every request's index among them; the launch shape of every request of one call
+void dedup_requests(hvec<AlignRequest> const& reqs, hvec<AlignRequest>& uniq, hvec<u32>& uniq_of);
+int choose_shapes(hvec<AlignRequest> const& reqs, hvec<AlignShape>& shapes);
 // existence tests of one round: outs[i].score is 0xFFFFFFFF for "no alignment within k"
 int run_exists_jobs(Lane* lane, const u8* d_text, const u64* d_peq, hvec<AlignRequest> const& reqs, hvec<DevAlignOut>& outs, ExistsTimes& times);
 // extension jobs of partial records' ends (ed_extend, flx_extend.hip): one launch, outs[i] for jobs[i] (out_index is set here)
@@ -249,9 +238,15 @@ struct Slice {
     // traces windows of the slice's reads (root windows, partial records): CIGAR words into cig, MD strings into md when wanted
     // tails: the paths' tails as well (align_roots alone asks for them)
     int trace_windows(Lane* lane, const flx_reads* RD, hvec<AlignRequest> const& reqs, hvec<TraceResult>& tres, const TailParams* tails = nullptr) {
-        CsWant const want_cs{cs_form, RD->d_pool.as<u8>(), &cs};
-        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, want_md ? &md : nullptr, tails, want_left_align ? RD->d_pool.as<u8>() : nullptr,
-                                    realign, realign ? RD->d_pool.as<u8>() : nullptr, cs_form ? &want_cs : nullptr);
+        TraceWants wants;
+        wants.md_pool = want_md ? &md : nullptr;
+        wants.tails = tails;
+        wants.left_align = want_left_align;
+        wants.realign = realign;             // (null unless the option is active)
+        wants.cs_form = cs_form;
+        wants.cs_pool = &cs;
+        wants.d_query = RD->d_pool.as<u8>();
+        return run_trace_jobs_union(lane, lane->ctx->didx.text, RD->d_peq.as<u64>(), reqs, tres, cig, wants);
     }
 };
 
