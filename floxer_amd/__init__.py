@@ -20,6 +20,7 @@ libfloxer_amd.so:
     coverage(ctx, coverage_options()), coverage_host()  not floxer's: depth of coverage accumulated on the device from the records of runs: equal-depth runs, per-window sums (opt-in)
     pileup(ctx, pileup_options()), pileup_host(), pileup_sites_host()  not floxer's: per-position allele counts (depth, mismatch letters, deletions, insertions) accumulated on the device from the records of runs, and the table of candidate variant sites (opt-in)
     sv(ctx, sv_options()), sv_host(), sv_clusters_host()  not floxer's: structural-variant signatures (long deletions, long insertions, split junctions) collected on the device from the records of runs, sorted and merged into clusters with their support (opt-in)
+    errprof(ctx, errprof_options()), errprof_host()  not floxer's: the error profile of the records of runs (which letter is read as which, indel lengths and homopolymer context, errors by position in the read, identities, error-free stretches), summed on the device (opt-in)
     record_sorter(n_refs), sort_host(), sort_geometry()  not floxer's: the coordinate order of records (reference, position, strand, then the caller's ordinal), sorted on the device by a radix sort over 128-bit keys (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
@@ -1307,6 +1308,123 @@ def pileup_sites_host(lengths, counts, options=None):
     out = np.zeros(max(1, n.value), dtype=SITE_DTYPE)
     check(lib().flx_pileup_sites_host(ptr(lens, u64p), len(lens), opt, ptr(cnt, u32p), out.ctypes.data_as(C.POINTER(capi.PileupSite)), C.byref(n)))
     return out[: n.value]
+
+
+# ------------------------------------------------------------------------------------------------ error profile of the alignments
+ERRPROF_SECTIONS = tuple(name for name, _ in capi.ERRPROF_SECTIONS if name != "reserved")
+ERRPROF_TOTALS = ("records", "matches", "mismatches", "ins_events", "ins_bases", "del_events", "del_bases", "clip_bases")
+
+
+def errprof_options(count_secondary=False, min_mapq=0, flush_threshold=0):
+    """flx_errprof_options: count_secondary: flag-256 records count; min_mapq: a record counts only with at least this mapping quality
+    (needs runs made with output_options(mapq=True)); flush_threshold: the columns plus rows after which a wave of the kernel adds its
+    on-chip sums to the table (a test hook; 0 takes 2^30; no sum depends on it)"""
+    o = capi.ErrprofOptions()
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq = int(min_mapq)
+    o.flush_threshold = int(flush_threshold)
+    return o
+
+
+def _errprof_dict(table):
+    return {name: np.array(getattr(table, name), dtype=np.uint64) for name in ERRPROF_SECTIONS}
+
+
+def _concatenated_text(text):
+    """(ranks of the unpadded concatenation, lengths) of a list of rank arrays; a single array is one sequence"""
+    if isinstance(text, np.ndarray) and text.ndim == 1:
+        text = [text]
+    seqs = [as_u8(t) for t in text]
+    return (np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint8)), [len(s) for s in seqs]
+
+
+class errprof:
+    """Error profile of the records added: which letter is read as which, the lengths of insertions and deletions and how many sit in
+    homopolymers, errors by position in the read, identities and the lengths of error-free stretches, summed on the device. Over the text
+    of a context's index (ctx), or over `text` on `device`: a list of rank arrays, or their concatenation with `lengths`. table() gives the
+    sums so far at any time; absorb the objects of other devices. Not floxer's. Adds may come from several threads."""
+
+    def __init__(self, ctx=None, options=None, text=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_errprof_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if text is None:
+                raise FloxerError("errprof needs a context or a reference text")
+            concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+            lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+            if int(lens.sum()) != len(concat):
+                raise FloxerError("errprof: the lengths do not sum to the text's length")
+            check(lib().flx_errprof_create_for_text(int(device), ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_errprof_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run, reads):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed;
+        reads: the batch the run was made from: a list of rank arrays or (pool, offsets). With min_mapq a run made without
+        output_options(mapq=True) is refused."""
+        if isinstance(reads, resident_reads):
+            return self.add_resident(run, reads)
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("errprof.add: min_mapq needs a run made with output_options(mapq=True)")
+            return self.add_records(run.raw, run.cigars, reads)
+        pool, offs, n = _pool_and_offsets(reads)
+        check(lib().flx_errprof_add_run(self.h, run, ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def add_resident(self, run, reads):
+        """run: a raw flx_run handle; reads: the resident_reads batch it was made from: its letters are read in HBM when it lives on this
+        object's device"""
+        if isinstance(run, RunResult):
+            raise FloxerError("errprof.add_resident: a RunResult needs the reads in host memory; a resident batch goes with a raw run handle")
+        check(lib().flx_errprof_add_run_resident(self.h, run, reads.h))
+
+    def add_records(self, records, cigar_words, reads):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        reads: a list of rank arrays or (pool, offsets), indexed by the records' `read`"""
+        rec, words = _records_and_words(records, cigar_words)
+        pool, offs, n = _pool_and_offsets(reads)
+        check(lib().flx_errprof_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words),
+                                            ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def absorb(self, other):
+        check(lib().flx_errprof_absorb(self.h, other.h))
+
+    def table(self):
+        """the sums so far: a dict of uint64 arrays by the names of ERRPROF_SECTIONS (PAIR_EQ and PAIR_X: 36 entries, t * 6 + q)"""
+        t = capi.ErrprofTable()
+        check(lib().flx_errprof_copy(self.h, C.byref(t)))
+        return _errprof_dict(t)
+
+
+def errprof_host(text, lengths, records, cigar_words, reads, options=None, table=None):
+    """the rule alone on the host (flx_errprof_host): text: the ranks of the unpadded concatenation of the sequences (or a list of rank
+    arrays with lengths None); table: a dict as errprof.table() gives it, which is added to. Returns such a dict."""
+    concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+    lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+    if int(lens.sum()) != len(concat):
+        raise FloxerError("errprof_host: the lengths do not sum to the text's length")
+    rec, words = _records_and_words(records, cigar_words)
+    pool, offs, n = _pool_and_offsets(reads)
+    t = capi.ErrprofTable()
+    if table is not None:
+        for name in ERRPROF_SECTIONS:
+            getattr(t, name)[:] = [int(x) for x in table[name]]
+    check(lib().flx_errprof_host(ptr(concat, u8p), ptr(lens, u64p), len(lens), C.byref(options) if options is not None else None,
+                                 rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(pool, u8p), ptr(offs, u64p), n,
+                                 C.byref(t)))
+    return _errprof_dict(t)
 
 
 # ------------------------------------------------------------------------------------------------ structural-variant signatures

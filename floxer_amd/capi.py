@@ -181,6 +181,20 @@ class SvCluster(C.Structure):
                 ("q_max", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ErrprofOptions(C.Structure):
+    _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("flush_threshold", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+# flx_errprof_table: its sections in their fixed order, u64 each
+ERRPROF_SECTIONS = (("PAIR_EQ", 36), ("PAIR_X", 36), ("INS_LEN", 64), ("DEL_LEN", 64), ("INS_LETTER", 6), ("DEL_LETTER", 6), ("HP_DEL", 34), ("HP_INS", 34),
+                    ("POS_MATCH", 100), ("POS_MISMATCH", 100), ("POS_INS", 100), ("POS_CLIP", 100), ("POS_DEL", 100), ("EQ_RUN", 256), ("IDENTITY", 101),
+                    ("TOTALS", 8), ("reserved", 7))
+
+
+class ErrprofTable(C.Structure):
+    _fields_ = [(name, C.c_uint64 * n) for name, n in ERRPROF_SECTIONS]
+
+
 class SortOptions(C.Structure):
     _fields_ = [("initial_capacity", C.c_uint64), ("tile_keys", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
@@ -289,6 +303,8 @@ EXPORTED = [
     "flx_paf_create", "flx_paf_free", "flx_paf_summarize", "flx_paf_summarize_host", "flx_paf_open", "flx_paf_write", "flx_paf_close",
     "flx_sv_create", "flx_sv_create_for_lengths", "flx_sv_free", "flx_sv_add_records", "flx_sv_add_run", "flx_sv_absorb", "flx_sv_finish",
     "flx_sv_num_signatures", "flx_sv_copy_signatures", "flx_sv_num_clusters", "flx_sv_copy_clusters", "flx_sv_host", "flx_sv_clusters_host",
+    "flx_errprof_create", "flx_errprof_create_for_text", "flx_errprof_free", "flx_errprof_add_records", "flx_errprof_add_run",
+    "flx_errprof_add_run_resident", "flx_errprof_absorb", "flx_errprof_copy", "flx_errprof_host",
 ]
 
 _lib = None
@@ -484,6 +500,17 @@ def lib():
     L.flx_sv_host.argtypes = [u64p, C.c_uint32, C.POINTER(SvOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64,
                               C.POINTER(SvSignature), u64p]
     L.flx_sv_clusters_host.argtypes = [C.POINTER(SvOptions), C.POINTER(SvSignature), C.c_uint64, C.POINTER(SvCluster), u64p]
+    L.flx_errprof_create.argtypes = [C.c_void_p, C.POINTER(ErrprofOptions), C.POINTER(C.c_void_p)]
+    L.flx_errprof_create_for_text.argtypes = [C.c_int, u8p, u64p, C.c_uint32, C.POINTER(ErrprofOptions), C.POINTER(C.c_void_p)]
+    L.flx_errprof_free.restype = None
+    L.flx_errprof_free.argtypes = [C.c_void_p]
+    L.flx_errprof_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64]
+    L.flx_errprof_add_run.argtypes = [C.c_void_p, C.c_void_p, u8p, u64p, C.c_uint64]
+    L.flx_errprof_add_run_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flx_errprof_absorb.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_errprof_copy.argtypes = [C.c_void_p, C.POINTER(ErrprofTable)]
+    L.flx_errprof_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(ErrprofOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64,
+                                   C.POINTER(ErrprofTable)]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

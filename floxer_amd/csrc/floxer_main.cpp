@@ -86,6 +86,9 @@ struct Options {
     std::string sv;                                               // output file of the structural-variant cluster table; empty: not written
     uint64_t sv_min_length = 0, sv_max_distance = 0, sv_min_support = 0, sv_min_mapq = 0;      // 0: the library's defaults
     bool sv_secondary = false;
+    std::string error_profile;                                    // output file of the error profile; empty: not written
+    uint64_t error_profile_min_mapq = 0;
+    bool error_profile_secondary = false;
     bool sort_by_coordinate = false, bam_index = false;           // a coordinate-sorted BAM (flx_sam_open_sorted) and its BAI index
     std::string sort_tmp;                                         // the spill file's directory; empty: the output's
     std::string paf;                                              // the PAF output; empty: not written
@@ -159,6 +162,10 @@ const OptDef OPTS[] = {
     {0, "sv-min-support", false, "not floxer's: a cluster is written from this many records on (default 2, a convention fitted to nothing); needs --sv-signatures"},
     {0, "sv-secondary", true, "not floxer's: secondary records (flag 256) count too, for DEL and INS (they never form junctions); needs --sv-signatures"},
     {0, "sv-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and --sv-signatures"},
+    // nor these: the error profile of the alignments, summed on the GPU (flx_errprof, flx_errprof.hpp)
+    {0, "error-profile", false, "not floxer's: how the reads err, one counter per line (section, keys, count: which letter is read as which, insertion and deletion lengths and their homopolymer context, errors by position in the read, identities, error-free stretches) and summary lines with the error rate in ppm, the figure to hold against --error-probability; <file.tsv>; exact counts of records: use -D -N 1; not with -w"},
+    {0, "error-profile-secondary", true, "not floxer's: secondary records (flag 256) count too; needs --error-profile"},
+    {0, "error-profile-min-mapq", false, "not floxer's: only records of at least this mapping quality count (1..254); needs -Q and --error-profile"},
     // nor these: the output in coordinate order, its keys sorted on the GPU (flx_sort, flx_sort.hpp), and its BAI index
     {0, "sort-by-coordinate", true, "not floxer's: write the records in coordinate order (reference, position, strand; unmapped last) with @HD SO:coordinate; needs a .bam output"},
     {0, "bam-index", true, "not floxer's: write the BAI index <output>.bai as well; needs --sort-by-coordinate"},
@@ -308,6 +315,9 @@ Options parse_cli(int argc, char** argv) {
         else if (n == "sv-min-support") { o.sv_min_support = parse_u64(n, value); range_check(n, (double)o.sv_min_support, 1, 4294967295.0); }
         else if (n == "sv-secondary") o.sv_secondary = true;
         else if (n == "sv-min-mapq") { o.sv_min_mapq = parse_u64(n, value); range_check(n, (double)o.sv_min_mapq, 1, 254); }
+        else if (n == "error-profile") o.error_profile = value;
+        else if (n == "error-profile-secondary") o.error_profile_secondary = true;
+        else if (n == "error-profile-min-mapq") { o.error_profile_min_mapq = parse_u64(n, value); range_check(n, (double)o.error_profile_min_mapq, 1, 254); }
         else if (n == "sort-by-coordinate") o.sort_by_coordinate = true;
         else if (n == "bam-index") o.bam_index = true;
         else if (n == "sort-tmp") { o.sort_tmp = value; if (value.empty()) throw CliError{"Validation failed for option --" + n + ": the directory's name is empty."}; }
@@ -380,6 +390,10 @@ Options parse_cli(int argc, char** argv) {
         throw CliError{"The options --sv-min-length, --sv-max-distance, --sv-min-support, --sv-secondary and --sv-min-mapq need --sv-signatures."};
     if (o.sv_min_mapq && !o.mapping_quality) throw CliError{"The option --sv-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
     if (!o.sv.empty() && !has_ext(o.sv, {"tsv"}, false)) throw CliError{"Validation failed for option --sv-signatures: Expected one of the following valid extensions: [tsv]."};
+    if (!o.error_profile.empty() && o.without_cigar) throw CliError{"The option --error-profile needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
+    if (o.error_profile.empty() && (o.error_profile_secondary || o.error_profile_min_mapq)) throw CliError{"The options --error-profile-secondary and --error-profile-min-mapq need --error-profile."};
+    if (o.error_profile_min_mapq && !o.mapping_quality) throw CliError{"The option --error-profile-min-mapq judges the records' mapping quality and needs -Q/--mapping-quality."};
+    if (!o.error_profile.empty() && !has_ext(o.error_profile, {"tsv"}, false)) throw CliError{"Validation failed for option --error-profile: Expected one of the following valid extensions: [tsv]."};
     if (!o.sort_by_coordinate && (o.bam_index || !o.sort_tmp.empty())) throw CliError{"The options --bam-index and --sort-tmp need --sort-by-coordinate."};
     if (o.sort_by_coordinate && !has_ext(o.output, {"bam"}, false)) throw CliError{"The option --sort-by-coordinate writes BAM and needs an -o/--output that ends in .bam."};
     if (!o.paf.empty() && o.without_cigar) throw CliError{"The option --paf needs the alignments' CIGARs and cannot be combined with -w/--without-cigar."};
@@ -747,6 +761,57 @@ bool write_pileup(Options const& o, std::vector<flx_pileup*> const& piles, Refer
     return true;
 }
 
+// the error profile: every device's table summed into the first and written as text, one line per counter in the table's fixed order
+// (section, keys, count; zero counters too, so the file's shape never changes), then the summary lines. Letters: . for rank 0, then A C G T N.
+bool write_error_profile(Options const& o, std::vector<flx_errprof*> const& profs) {
+    for (size_t i = 1; i < profs.size(); ++i)
+        if (flx_errprof_absorb(profs[0], profs[i]) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    flx_errprof_table t;
+    if (flx_errprof_copy(profs[0], &t) != FLX_OK) { log_line("error", "%s", flx_last_error()); return false; }
+    FILE* f = fopen(o.error_profile.c_str(), "w");
+    if (!f) { log_line("error", "cannot open output file: %s", o.error_profile.c_str()); return false; }
+    static const char letter[6] = {'.', 'A', 'C', 'G', 'T', 'N'};
+    auto const u = [](uint64_t v) { return (unsigned long long)v; };
+    auto const pairs = [&](const char* name, const uint64_t* v) {
+        for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) fprintf(f, "%s\t%c\t%c\t%llu\n", name, letter[a], letter[b], u(v[a * 6 + b]));
+    };
+    // keys first .. first + n - 1; the last key is `last` when given ("64+"), the one before it `before_last` ("32+" in front of "mixed")
+    auto const numbered = [&](const char* name, const uint64_t* v, int n, int first, const char* last = nullptr, const char* before_last = nullptr) {
+        for (int i = 0; i < n; ++i) {
+            if (last && i == n - 1) fprintf(f, "%s\t%s\t%llu\n", name, last, u(v[i]));
+            else if (before_last && i == n - 2) fprintf(f, "%s\t%s\t%llu\n", name, before_last, u(v[i]));
+            else fprintf(f, "%s\t%d\t%llu\n", name, first + i, u(v[i]));
+        }
+    };
+    auto const letters = [&](const char* name, const uint64_t* v) { for (int a = 0; a < 6; ++a) fprintf(f, "%s\t%c\t%llu\n", name, letter[a], u(v[a])); };
+    pairs("PAIR_EQ", t.pair_eq);
+    pairs("PAIR_X", t.pair_x);
+    numbered("INS_LEN", t.ins_len, 64, 1, "64+");
+    numbered("DEL_LEN", t.del_len, 64, 1, "64+");
+    letters("INS_LETTER", t.ins_letter);
+    letters("DEL_LETTER", t.del_letter);
+    numbered("HP_DEL", t.hp_del, 34, 0, "mixed", "32+");
+    numbered("HP_INS", t.hp_ins, 34, 0, "mixed", "32+");
+    numbered("POS_MATCH", t.pos_match, 100, 0);
+    numbered("POS_MISMATCH", t.pos_mismatch, 100, 0);
+    numbered("POS_INS", t.pos_ins, 100, 0);
+    numbered("POS_CLIP", t.pos_clip, 100, 0);
+    numbered("POS_DEL", t.pos_del, 100, 0);
+    numbered("EQ_RUN", t.eq_run, 256, 1, "256+");
+    numbered("IDENTITY", t.identity, 101, 0);
+    static const char* const totals[8] = {"records", "matches", "mismatches", "ins_events", "ins_bases", "del_events", "del_bases", "clip_bases"};
+    for (int i = 0; i < 8; ++i) fprintf(f, "TOTALS\t%s\t%llu\n", totals[i], u(t.totals[i]));
+    uint64_t const matches = t.totals[1], mismatches = t.totals[2], ins = t.totals[4], del = t.totals[6], columns = matches + mismatches + ins + del;
+    auto const ppm = [&](uint64_t v) { return columns ? u((uint64_t)((unsigned __int128)v * 1000000u / columns)) : 0ull; };
+    uint64_t unequal = 0;
+    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) if (a != b) unequal += t.pair_eq[a * 6 + b];
+    fprintf(f, "summary\tcolumns\t%llu\nsummary\terror_rate_ppm\t%llu\nsummary\tmismatch_ppm\t%llu\nsummary\tinsertion_ppm\t%llu\nsummary\tdeletion_ppm\t%llu\nsummary\teq_columns_unequal\t%llu\n",
+            u(columns), ppm(mismatches + ins + del), ppm(mismatches), ppm(ins), ppm(del), u(unequal));
+    if (fclose(f) != 0) { log_line("error", "write error on the error-profile output"); return false; }
+    if (unequal) log_line("warning", "--error-profile: %llu columns of = words hold unequal letters (eq_columns_unequal): the records do not fit the reference or the reads", u(unequal));
+    return true;
+}
+
 // the structural-variant table: every device's signatures appended to the first object's, sorted and clustered there, and the clusters
 // written as text: positions 1-based; q is a length for DEL and INS and a 1-based position for BND; sides L / R for BND, . otherwise
 bool write_sv(Options const& o, std::vector<flx_sv*> const& svs, std::vector<std::string> const& names) {
@@ -889,6 +954,21 @@ int main(int argc, char** argv) {
             svs.push_back(s);
         }
     }
+    // the error profile: one table per device context too, fed behind the pileup with every batch's run and its own host reads
+    flx_errprof_options prof_opt;
+    memset(&prof_opt, 0, sizeof(prof_opt));
+    prof_opt.count_secondary = o.error_profile_secondary;
+    prof_opt.min_mapq = (uint32_t)o.error_profile_min_mapq;
+    std::vector<flx_errprof*> profs;
+    if (!o.error_profile.empty()) {
+        if (!o.drop_duplicate_alignments)
+            log_line("warning", "--error-profile counts records, not reads: without -D/--drop-duplicate-alignments a read's records at one locus all add their columns (use -D -N 1).");
+        for (flx_ctx* c : ctxs) {
+            flx_errprof* e = nullptr;
+            if (flx_errprof_create(c, &prof_opt, &e) != FLX_OK) { log_line("error", "cannot set up the error-profile object: %s", flx_last_error()); return -1; }
+            profs.push_back(e);
+        }
+    }
 
     std::vector<const char*> ref_id_ptrs;
     for (auto const& s : ref.ids) ref_id_ptrs.push_back(s.c_str());
@@ -1028,6 +1108,11 @@ int main(int argc, char** argv) {
             f.rc = flx_pileup_add_run(piles[at], run, b->pool.data(), b->offsets.data(), b->ids.size());
             if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
         }
+        if (!profs.empty()) {
+            size_t const at = std::find(ctxs.begin(), ctxs.end(), ctx) - ctxs.begin();
+            f.rc = flx_errprof_add_run(profs[at], run, b->pool.data(), b->offsets.data(), b->ids.size());
+            if (f.rc != FLX_OK) { f.err = flx_last_error(); flx_run_free(run); f.batch = std::move(b); return f; }
+        }
         if (!svs.empty()) {
             size_t const at = std::find(ctxs.begin(), ctxs.end(), ctx) - ctxs.begin();
             f.rc = flx_sv_add_run(svs[at], run, b->offsets.data(), b->ids.size());
@@ -1163,6 +1248,8 @@ int main(int argc, char** argv) {
     for (flx_pileup* c : piles) flx_pileup_free(c);
     if (!svs.empty() && !failed.load() && !timed_out && !write_sv(o, svs, ref.ids)) failed.store(true);
     for (flx_sv* c : svs) flx_sv_free(c);
+    if (!profs.empty() && !failed.load() && !timed_out && !write_error_profile(o, profs)) failed.store(true);
+    for (flx_errprof* c : profs) flx_errprof_free(c);
     for (flx_ctx* c : ctxs) flx_ctx_destroy(c);
     flx_index_free(index);
     if (failed.load() || timed_out) return -1;

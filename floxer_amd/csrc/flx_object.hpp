@@ -1,4 +1,4 @@
-// What the side objects behind the C ABI share (flx_coverage, flx_pileup, flx_sort, flx_paf, flx_sv; each in its own *_api.cpp): the base with the
+// What the side objects behind the C ABI share (flx_coverage, flx_pileup, flx_sort, flx_paf, flx_sv, flx_errprof; each in its own *_api.cpp): the base with the
 // device, the stream, the lock and the profile's events; the pieces of a run; judging on several threads; and, for coverage and pileup,
 // the base of an accumulator of u32 planes over the concatenation of the sequences with its scan and its absorb.
 #pragma once

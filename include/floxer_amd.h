@@ -887,6 +887,74 @@ int  flx_sv_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_sv_options
 int  flx_sv_clusters_host(const flx_sv_options* o, const flx_sv_signature* signatures, uint64_t n, flx_sv_cluster* out,
                           uint64_t* n_clusters /* in: capacity, out: needed */);
 
+/* ------------------------------------------------------------------------------------------------ error profile of the alignments
+ * Not floxer's. How do the reads err? Which letter is read as which, how long insertions and deletions are, how many of them sit in
+ * homopolymers, whether a read's ends are worse than its middle, how identities are distributed and how long the error-free stretches
+ * are: the figures behind --error-probability, summed on the device from the records' = X I D S words, the reads' letters and the
+ * reference text in HBM. An error-profile object holds one flx_errprof_table of u64 counters (9 KB). The rule
+ * (floxer_amd/csrc/flx_errprof.hpp):
+ *   - which records count: exactly coverage's filter. flag & 4 never; flag & 256 only with count_secondary; 2048 always; with
+ *     min_mapq > 0 only if flx_record.reserved >= min_mapq;
+ *   - the walk starts at `position` with row 0 of the record's oriented sequence (the read as given for flag bit 16 clear, its reverse
+ *     complement for bit 16 set). t[p]: the reference rank at position p; q[r]: the oriented read rank at row r; [s0, s1): the record's
+ *     sequence; len: the read's length; g(r) = reverse ? len - 1 - r : r, the row in the read as given; bin(r) = g(r) * 100 / len in
+ *     64-bit integers, 0..99 (0 for a read without letters). Ranks are 0..5 and index the 6 x 6 and 6-entry sections directly;
+ *       pair_eq[t * 6 + q], pair_x[t * 6 + q]: + 1 per column of an = word, of an X word; both letters are read for every column, so
+ *          pair_eq off its diagonal is an integrity figure: 0 for this aligner's own runs, and nothing relies on that;
+ *       ins_len, del_len: a word of length L adds 1 at min(L, 64) - 1; the last entry is "64 or longer";
+ *       ins_letter[q], del_letter[t]: + 1 per inserted read letter, per deleted reference letter;
+ *       hp_del[34]: for a D word over [p, p + L) with a = t[p]: entry 33 when a is not in 1..4 or a deleted letter differs from a; else
+ *          min(32, left + L + right), left the run of a from p - 1 downwards while the position is >= s0, right the run of a from p + L
+ *          upwards while the position is < s1, each stopped at 32;
+ *       hp_ins[34]: for an I word of letters q[r, r + L) with a = q[r]: p is the reference position of the next reference-consuming
+ *          column (`position` when nothing precedes the word; it may be the record's end and may be s1); entry 33 when a is not in 1..4
+ *          or the letters differ; else min(32, left + right), left the run of a from p - 1 downwards (>= s0), right the run of a from p
+ *          upwards (< s1), each stopped at 32; an inserted run next to no equal letter is entry 0. Runs never cross a sequence boundary;
+ *       pos_match, pos_mismatch, pos_ins, pos_clip [100]: + 1 at bin(r) per row of an =, X, I, S word;
+ *       pos_del[100]: + 1 per D word (not per base) at bin(min(r, len - 1)), r the row the walk has reached;
+ *       eq_run[256]: an = word of length L adds 1 at min(L, 256) - 1 (words are counted: neighbouring = words are not merged);
+ *       identity[101]: once per record at matches * 100 / (matches + mismatches + ins_bases + del_bases);
+ *       totals[8]: records, matches, mismatches, ins_events, ins_bases, del_events, del_bases, clip_bases;
+ *   - refused (FLX_ERR_INVALID, on the host before any launch; the object stays as it was): all that the pileup calls refuse (and with
+ *     them the coverage calls), and a record whose reference-consuming plus query-consuming lengths reach 2^31. A reference text with a
+ *     rank above 5 is refused at create. Read ranks above 5 are outside the read pool's contract and count as 5.
+ * options NULL: all zero; reserved fields must be 0. flush_threshold (a test hook): a wave of the kernel adds its on-chip u32 sums to
+ * the table once the columns plus rows it has walked since its last flush reach this; 0 takes 2^30, above 2^31 is refused; no sum
+ * depends on it. flx_errprof_create reads the reference letters from the context's own text in HBM (no second copy) and counts as a
+ * live object of the context: flx_ctx_destroy refuses until it is freed. flx_errprof_create_for_text uploads the unpadded concatenation
+ * of the sequences' ranks itself (coverage's limits on the lengths); hip_device -1 is refused (the host form is flx_errprof_host).
+ * Reads are given as flx_align_reads takes them. Adds may come from several host threads at once. flx_errprof_add_run walks a run and
+ * its parts and judges everything before adding anything; it needs min_mapq == 0 or a run made with flx_output_options.mapq, and
+ * refuses a run made with without_cigar. flx_errprof_add_run_resident reads the letters from the batch's device pool when the batch
+ * lives on the object's device, and takes the staged path otherwise. flx_errprof_absorb: into += from, `from` is left cleared; equal
+ * lengths, count_secondary and min_mapq; the two may live on different devices. flx_errprof_copy gives the sums so far, at any time:
+ * there is no finish call. Everything is integer: nothing depends on the order of adds, the number of calls, host threads, resident
+ * or host reads, or devices. flx_errprof_host: the rule alone on the host, no device: `table` is added to; the same refusals, and the
+ * table is untouched when it refuses. FLX_ERRPROF_PROFILE (environment): every add prints its records, words, uploaded bytes,
+ * errprof_add's device time and its wall time to stderr.
+ * Not here: base qualities, per-read tables, denominators for the homopolymer entries (how many reference runs of each length were
+ * covered). */
+typedef struct flx_errprof flx_errprof;
+typedef struct flx_errprof_options { uint32_t count_secondary, min_mapq, flush_threshold; uint32_t reserved[5]; } flx_errprof_options;
+typedef struct flx_errprof_table {
+    uint64_t pair_eq[36], pair_x[36], ins_len[64], del_len[64], ins_letter[6], del_letter[6], hp_del[34], hp_ins[34];
+    uint64_t pos_match[100], pos_mismatch[100], pos_ins[100], pos_clip[100], pos_del[100], eq_run[256], identity[101], totals[8];
+    uint64_t reserved[7];
+} flx_errprof_table;
+int  flx_errprof_create(flx_ctx* ctx, const flx_errprof_options* o, flx_errprof** out);
+int  flx_errprof_create_for_text(int hip_device, const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs,
+                                 const flx_errprof_options* o, flx_errprof** out);
+void flx_errprof_free(flx_errprof* p);
+int  flx_errprof_add_records(flx_errprof* p, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                             const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_errprof_add_run(flx_errprof* p, const flx_run* run, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_errprof_add_run_resident(flx_errprof* p, const flx_run* run, const flx_reads* reads);
+int  flx_errprof_absorb(flx_errprof* into, flx_errprof* from);
+int  flx_errprof_copy(const flx_errprof* p, flx_errprof_table* out);
+int  flx_errprof_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs, const flx_errprof_options* o,
+                      const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words, const uint8_t* read_pool,
+                      const uint64_t* read_offsets, uint64_t n_reads, flx_errprof_table* table /* added to */);
+
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
  * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
