@@ -21,6 +21,7 @@ libfloxer_amd.so:
     pileup(ctx, pileup_options()), pileup_host(), pileup_sites_host()  not floxer's: per-position allele counts (depth, mismatch letters, deletions, insertions) accumulated on the device from the records of runs, and the table of candidate variant sites (opt-in)
     sv(ctx, sv_options()), sv_host(), sv_clusters_host()  not floxer's: structural-variant signatures (long deletions, long insertions, split junctions) collected on the device from the records of runs, sorted and merged into clusters with their support (opt-in)
     errprof(ctx, errprof_options()), errprof_host()  not floxer's: the error profile of the records of runs (which letter is read as which, indel lengths and homopolymer context, errors by position in the read, identities, error-free stretches), summed on the device (opt-in)
+    grid_caps()                           a test hook: the most blocks each capped launch asks for, by kernel name
     record_sorter(n_refs), sort_host(), sort_geometry()  not floxer's: the coordinate order of records (reference, position, strand, then the caller's ordinal), sorted on the device by a radix sort over 128-bit keys (opt-in)
 
 The compute runs in hand-written HIP kernels; nothing here falls back to a CPU implementation.
@@ -1569,6 +1570,18 @@ def sort_geometry():
     g = np.zeros(4, dtype=np.uint32)
     check(lib().flx_sort_geometry(ptr(g, u32p)))
     return tuple(int(x) for x in g)
+
+
+GRID_CAP_NAMES = ("md_build", "cs_build", "cigar_left_align", "cigar_tails", "ed_extend", "cigar_realign", "paf_summarise", "coverage_add", "pileup_add",
+                  "sv_extract", "sort_keys_add", "errprof_add", "sort_census", "sort_strided", "sv_strided")
+
+
+def grid_caps():
+    """name -> the most blocks that launch asks for (behind them a wave or a thread takes further jobs in turns): a test hook. The
+    first seven have one wave per block, the next five four waves with a record each, the last three 256 threads with an element each"""
+    g = np.zeros(16, dtype=np.uint32)
+    check(lib().flx_grid_caps(ptr(g, u32p)))
+    return {name: int(g[i]) for i, name in enumerate(GRID_CAP_NAMES)}
 
 
 class record_sorter:

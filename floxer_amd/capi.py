@@ -305,6 +305,7 @@ EXPORTED = [
     "flx_sv_num_signatures", "flx_sv_copy_signatures", "flx_sv_num_clusters", "flx_sv_copy_clusters", "flx_sv_host", "flx_sv_clusters_host",
     "flx_errprof_create", "flx_errprof_create_for_text", "flx_errprof_free", "flx_errprof_add_records", "flx_errprof_add_run",
     "flx_errprof_add_run_resident", "flx_errprof_absorb", "flx_errprof_copy", "flx_errprof_host",
+    "flx_grid_caps",
 ]
 
 _lib = None
@@ -467,6 +468,7 @@ def lib():
     L.flx_sort_num_records.argtypes = [C.c_void_p]
     L.flx_sort_copy.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SortEntry)]
     L.flx_sort_geometry.argtypes = [u32p]
+    L.flx_grid_caps.argtypes = [u32p]
     L.flx_sort_host.argtypes = [C.c_uint32, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u64p, C.POINTER(SortEntry)]
     L.flx_pileup_create.argtypes = [C.c_void_p, C.POINTER(PileupOptions), C.POINTER(C.c_void_p)]
     L.flx_pileup_create_for_lengths.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(PileupOptions), C.POINTER(C.c_void_p)]

@@ -9,6 +9,13 @@
 #include "flx_leftalign.hpp"
 #include "flx_cs.hpp"
 #include "flx_traceback.hpp"
+#include "flx_realign.hpp"
+#include "flx_paf.hpp"
+#include "flx_coverage.hpp"
+#include "flx_pileup.hpp"
+#include "flx_sort.hpp"
+#include "flx_sv.hpp"
+#include "flx_errprof.hpp"
 
 using namespace flx;
 
@@ -385,4 +392,14 @@ extern "C" int flx_cs_batch(flx_ctx* ctx, const uint8_t* ref_pool, uint64_t ref_
     return pack_in_job_order("flx_cs_batch: the output byte pool is too small", n_jobs, call.out_cap, out_n_bytes, out_bytes, slabs.data(),
                              [&](uint64_t i) { return pass.outs[i].len; }, [&](uint64_t i) { return pass.jobs[i].cs_off; },
                              [&](uint64_t i, u64 at) { out[i] = flx_md_ref{at, pass.outs[i].len, 0}; });
+}
+
+// ------------------------------------------------------------------------------------------------ grid caps
+extern "C" int flx_grid_caps(uint32_t out[16]) {
+    if (!out) { set_error("flx_grid_caps: null argument"); return FLX_ERR_INVALID; }
+    u32 const caps[16] = {MD_GRID_CAP, CS_GRID_CAP, LEFT_ALIGN_GRID_CAP, TAILS_GRID_CAP, EXTEND_GRID_CAP, REALIGN_GRID_CAP, PAF_GRID_CAP,
+                          CoverageDevice::ADD_GRID_CAP, PileupDevice::ADD_GRID_CAP, SvDevice::EXTRACT_GRID_CAP, SortDevice::KEYS_GRID_CAP,
+                          ErrprofDevice::ADD_GRID_CAP, SortDevice::CENSUS_GRID_CAP, SortDevice::STRIDED_GRID_CAP, SvDevice::STRIDED_GRID_CAP, 0};
+    std::copy(caps, caps + 16, out);
+    return FLX_OK;
 }

@@ -170,7 +170,7 @@ static inline u32 tiles_of(u64 n) { return (u32)((n + TILE - 1) / TILE); }
 
 int CoverageDevice::add(void* stream, const CoverageJob* d_jobs, u32 n_jobs, const u32* d_words, u32* d_acc, u32 count_deletions) {
     if (n_jobs == 0) return 0;
-    u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), 1u << 16);
+    u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), ADD_GRID_CAP);
     hipLaunchKernelGGL(coverage_add_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words, reinterpret_cast<int*>(d_acc), count_deletions);
     return (int)hipGetLastError();
 }

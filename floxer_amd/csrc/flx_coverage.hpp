@@ -139,6 +139,7 @@ inline void coverage_window_bases(std::vector<u64> const& starts, u64 window, st
 // concatenation, d_starts holds the n_refs + 1 sequence starts as u32)
 struct CoverageWindowAcc { unsigned long long depth_sum, covered; u32 max_depth, pad; };
 struct CoverageDevice {
+    static constexpr u32 ADD_GRID_CAP = 1u << 16;      // most blocks (four waves, a record each at a time) of a coverage_add launch
     static int add(void* stream, const CoverageJob* d_jobs, u32 n_jobs, const u32* d_words, u32* d_acc, u32 count_deletions);
     // mode 0: the tiles' head counts; 1: the positions of all heads; 2: the reported runs (d_count_* scanned by then)
     static int heads(void* stream, int mode, const u32* d_depth, u64 total, const u32* d_starts, u32 n_refs, u32 report_zero, u32* d_count_all,

@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(64) cs_build_kernel(const u8* __restrict__ tex
 int DeviceApi::cs_build(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevCsJob* d_jobs,
                         u32 n_jobs, u32 form, u8* d_cs, DevCsOut* d_out) {
     if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(cs_build_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), 0, (hipStream_t)stream, d_text, d_query, d_cigar, d_trace_out, d_jobs,
+    hipLaunchKernelGGL(cs_build_kernel, dim3(std::min(n_jobs, CS_GRID_CAP)), dim3(64), 0, (hipStream_t)stream, d_text, d_query, d_cigar, d_trace_out, d_jobs,
                        n_jobs, form, d_cs, d_out);
     return (int)hipGetLastError();
 }

@@ -159,7 +159,7 @@ int ErrprofDevice::add(void* stream, const ErrprofJob* d_jobs, u32 n_jobs, const
                        u32 flush_threshold) {
     if (n_jobs == 0) return 0;
     // capped as pileup_add's grid is, but lower: every wave ends with a flush of its table, so a wave should take several records
-    u32 const blocks = std::min<u32>((n_jobs + EP_WAVES - 1) / EP_WAVES, 1u << 11);
+    u32 const blocks = std::min<u32>((n_jobs + EP_WAVES - 1) / EP_WAVES, ADD_GRID_CAP);
     hipLaunchKernelGGL(errprof_add_kernel, dim3(blocks), dim3(EP_THREADS), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words, d_text, d_letters, d_table, flush_threshold);
     return (int)hipGetLastError();
 }

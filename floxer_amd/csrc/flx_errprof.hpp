@@ -231,6 +231,7 @@ inline void errprof_walk(ErrprofJob const& j, const uint32_t* cigar_words, const
 
 // ---- the launch of flx_errprof.hip (returns the hipError_t of its launch; pointers are device pointers)
 struct ErrprofDevice {
+    static constexpr u32 ADD_GRID_CAP = 1u << 11;      // most blocks (four waves, a record each at a time) of an errprof_add launch
     static int add(void* stream, const ErrprofJob* d_jobs, u32 n_jobs, const u32* d_words, const u8* d_text, const u8* d_letters, unsigned long long* d_table,
                    u32 flush_threshold);
 };

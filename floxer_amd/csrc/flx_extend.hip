@@ -115,7 +115,7 @@ size_t DeviceApi::extend_lds_bytes(u32 d_max) { return (size_t)2 * (2 * (size_t)
 
 int DeviceApi::extend(void* stream, const u8* d_text, const u8* d_query, const DevExtendJob* d_jobs, u32 n_jobs, u32 lds_d, DevExtendOut* d_out) {
     if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(ed_extend_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), extend_lds_bytes(lds_d), (hipStream_t)stream, d_text, d_query, d_jobs,
+    hipLaunchKernelGGL(ed_extend_kernel, dim3(std::min(n_jobs, EXTEND_GRID_CAP)), dim3(64), extend_lds_bytes(lds_d), (hipStream_t)stream, d_text, d_query, d_jobs,
                        n_jobs, lds_d, d_out);
     return (int)hipGetLastError();
 }

@@ -176,6 +176,7 @@ struct DevMdOut { u32 len; u32 pad; };             // len 0xFFFFFFFF: the slab w
 // one '^' per D op: letters + '^' <= 2 nm. Every event is preceded by one number and the end adds one: nm + 1 numbers, each the length
 // of a run of '=' columns, which is at most the number of query rows: <= 102 400 (align_supported_max_query), six digits. 8 nm + 6 in all.
 constexpr u64 md_slab_bytes(u64 nm) { return 8 * nm + 6; }
+constexpr u32 MD_GRID_CAP = 1u << 16;         // most blocks (one wave, one job at a time) of an md_build launch; the jobs behind them are taken in turns
 
 // ---- cs strings of traced paths (flx_cs.hip; the rule: flx_cs.hpp), one job per trace job: the kernel reads that job's DevTraceOut and
 // CIGAR words where K5 (or cigar_realign / cigar_left_align) left them, the window in the text and the oriented query in the query pool
@@ -197,6 +198,7 @@ static_assert(sizeof(DevCsJob) == 48, "device layout");
 //   long form:   the '=' words hold one '=' each and m - x - i letters: (m - x - i) + (nm + 1) + 3 x + 2 i + 2 d = m + nm + 1 + 2 x + i
 //                + 2 d <= m + 3 nm + 1; reached by = X = X ... = with single X columns
 constexpr u64 cs_slab_bytes(u64 nm, u64 m, u32 form) { return form == 2u ? m + 3 * nm + 1 : 10 * nm + 7; }
+constexpr u32 CS_GRID_CAP = 1u << 16;         // most blocks (one wave, one job at a time) of a cs_build launch; the jobs behind them are taken in turns
 
 // ---- chimeric tails of traced paths (flx_tails.hip; the rule: flx_tails.hpp), one job per trace job: the kernel reads that job's
 // DevTraceOut and CIGAR words where K5 left them on the device
@@ -207,6 +209,7 @@ struct DevTailJob {
 };
 struct DevTailOut { u32 left_rows, left_cols, left_errors, left_words, right_rows, right_cols, right_errors, right_words; };   // = flx_tail_result
 static_assert(sizeof(DevTailOut) == 32 && sizeof(DevTailOut) == sizeof(flx_tail_result), "one 32-byte result per job");
+constexpr u32 TAILS_GRID_CAP = 1u << 16;      // most blocks (one wave, one job at a time) of a cigar_tails launch; the jobs behind them are taken in turns
 
 // ---- left-aligned gaps of traced paths (flx_leftalign.hip; the rule: flx_leftalign.hpp), one job per trace job: the kernel reads that
 // job's DevTraceOut and CIGAR words where K5 left them, writes the normalised words into a second slab and rewrites the DevTraceOut
@@ -219,6 +222,7 @@ struct DevLeftAlignJob {
     u32 out_index;                                 // the trace job's DevTraceOut and this job's DevLeftAlignStat
 };
 struct DevLeftAlignStat { u32 words_in, letters, gaps, moved; };   // words read, letters compared (per sequence), gap words, gap words that moved or merged
+constexpr u32 LEFT_ALIGN_GRID_CAP = 1u << 16; // most blocks (one wave, one job at a time) of a cigar_left_align launch; the jobs behind them are taken in turns
 
 // ---- affine-gap realignment of traced paths (flx_realign.hip; the rule: flx_realign.hpp), one job per path: the kernel reads the job's
 // DevTraceOut and CIGAR words, runs the banded DP with its trace in the job's part of the trace arena, writes the new words right to
@@ -249,6 +253,7 @@ struct DevExtendJob {
 struct DevExtendOut { u32 rows, cols, errors, reason; u32 last_d; u32 pad[3]; };      // last_d: the d the scan stopped at ((last_d + 1)^2 wavefront cells)
 constexpr u32 EXTEND_DEFAULT_WEIGHT = 4, EXTEND_DEFAULT_XDROP = 100, EXTEND_DEFAULT_MAX_ERRORS = 1024;
 constexpr u32 EXTEND_MAX_ERRORS = 4093;       // two wavefronts of 2 d + 5 words in 64 KiB of LDS (2 * (2 * 4093 + 5) * 4 = 65528); the packed (row, diagonal) maximum holds more
+constexpr u32 EXTEND_GRID_CAP = 1u << 16;     // most blocks (one wave, one job at a time) of an ed_extend launch; the jobs behind them are taken in turns
 constexpr u32 EXTEND_MAX_WEIGHT = 0xFFFFu, EXTEND_MAX_XDROP = 1u << 30, EXTEND_MAX_ROWS = (1u << 19) - 1;
 
 // ------------------------------------------------------------------------------------------------ verification rounds on the device

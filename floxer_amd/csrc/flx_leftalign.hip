@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(64) cigar_left_align_kernel(const u8* __restri
 int DeviceApi::cigar_left_align(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, DevTraceOut* d_trace_out, const DevLeftAlignJob* d_jobs,
                                 u32 n_jobs, u32* d_cigar_out, DevLeftAlignStat* d_stats) {
     if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(cigar_left_align_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), 0, (hipStream_t)stream, d_text, d_query, d_cigar, d_trace_out, d_jobs,
+    hipLaunchKernelGGL(cigar_left_align_kernel, dim3(std::min(n_jobs, LEFT_ALIGN_GRID_CAP)), dim3(64), 0, (hipStream_t)stream, d_text, d_query, d_cigar, d_trace_out, d_jobs,
                        n_jobs, d_cigar_out, d_stats);
     return (int)hipGetLastError();
 }

@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(64) md_build_kernel(const u8* __restrict__ tex
 int DeviceApi::md_build(void* stream, const u8* d_text, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevMdJob* d_jobs, u32 n_jobs,
                         u8* d_md, DevMdOut* d_out) {
     if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(md_build_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), 0, (hipStream_t)stream, d_text, d_cigar, d_trace_out, d_jobs, n_jobs,
+    hipLaunchKernelGGL(md_build_kernel, dim3(std::min(n_jobs, MD_GRID_CAP)), dim3(64), 0, (hipStream_t)stream, d_text, d_cigar, d_trace_out, d_jobs, n_jobs,
                        d_md, d_out);
     return (int)hipGetLastError();
 }

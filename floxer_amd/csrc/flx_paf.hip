@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(64) paf_summarise_kernel(const PafJob* __restr
 int PafDevice::summarise(void* stream, const PafJob* d_jobs, u32 n_jobs, const u32* d_words, flx_paf_summary* d_out) {
     if (n_jobs == 0) return 0;
     static_assert(sizeof(flx_paf_summary) == 32, "eight u32 fields");
-    hipLaunchKernelGGL(paf_summarise_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words,
+    hipLaunchKernelGGL(paf_summarise_kernel, dim3(std::min(n_jobs, PAF_GRID_CAP)), dim3(64), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words,
                        reinterpret_cast<u32*>(d_out));
     return (int)hipGetLastError();
 }

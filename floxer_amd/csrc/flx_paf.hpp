@@ -27,6 +27,7 @@
 namespace flx {
 
 constexpr u64 PAF_MAX_SUM = 1ull << 31;                // every sum of a summary stays below it
+constexpr u32 PAF_GRID_CAP = 1u << 16;                   // most blocks (one wave, one record at a time) of a paf_summarise launch; the records behind them are taken in turns
 constexpr u32 PAF_VIOLATION = 0xFFFFFFFFu;             // the kernel's mark in every field of a summary it could not make
 
 inline bool paf_record_mapped(flx_record const& r) { return !(r.flag & 4u) && r.reference_id >= 0; }

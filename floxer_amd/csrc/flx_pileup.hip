@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(THREADS) pileup_sites_kernel(const u32* __rest
 // ------------------------------------------------------------------------------------------------ launches (each one checked)
 int PileupDevice::add(void* stream, const PileupJob* d_jobs, u32 n_jobs, const u32* d_words, const u8* d_letters, u32* d_acc, u64 stride) {
     if (n_jobs == 0) return 0;
-    u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), 1u << 16);
+    u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), ADD_GRID_CAP);
     hipLaunchKernelGGL(pileup_add_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words, d_letters, reinterpret_cast<int*>(d_acc), stride);
     return (int)hipGetLastError();
 }

@@ -125,6 +125,7 @@ inline void pileup_walk(PileupJob const& j, const uint32_t* cigar_words, const u
 // ---- the launches of flx_pileup.hip (each returns the hipError_t of its launch; pointers are device pointers). The accumulator is seven
 // planes of `stride` entries each (stride >= total + 1, a multiple of 64); DEPTH and DEL are difference arrays until the finish scan.
 struct PileupDevice {
+    static constexpr u32 ADD_GRID_CAP = 1u << 16;      // most blocks (four waves, a record each at a time) of a pileup_add launch
     static int add(void* stream, const PileupJob* d_jobs, u32 n_jobs, const u32* d_words, const u8* d_letters, u32* d_acc, u64 stride);
     // mode 0: d_count[tile] = the tile's sites; mode 1: the sites themselves (d_count scanned by then)
     static int sites(void* stream, int mode, const u32* d_acc, u64 stride, u64 total, const u32* d_starts, u32 n_refs, PileupThresholds t, u32* d_count,

@@ -236,7 +236,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) ci
 int DeviceApi::cigar_realign(void* stream, const u8* d_text, const u8* d_query, const u32* d_cigar, DevTraceOut* d_trace_out, const DevRealignJob* d_jobs,
                              u32 n_jobs, RealignScores const& s, u32* d_trace, u32* d_cigar_out, DevRealignStat* d_stats) {
     if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(cigar_realign_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), 0, (hipStream_t)stream, d_text, d_query, d_cigar, d_trace_out, d_jobs,
+    hipLaunchKernelGGL(cigar_realign_kernel, dim3(std::min(n_jobs, REALIGN_GRID_CAP)), dim3(64), 0, (hipStream_t)stream, d_text, d_query, d_cigar, d_trace_out, d_jobs,
                        n_jobs, s.a, s.b, s.o, s.e, s.w, d_trace, d_cigar_out, d_stats);
     return (int)hipGetLastError();
 }

@@ -104,6 +104,7 @@ inline uint64_t realign_nm_bound(uint32_t nm, RealignScores const& s) { return (
 // the stripe]; rows 0..m; B = hi - lo + 1 cells per row. A band wider than the hand-over row the kernel keeps in LDS adds 2 B words in
 // front (H and F of a stripe's last row).
 constexpr uint32_t REALIGN_LDS_BAND = 1024u;
+constexpr uint32_t REALIGN_GRID_CAP = 1u << 16;            // most blocks (one wave each) of a cigar_realign launch
 inline uint64_t realign_trace_words(uint32_t m, uint64_t band_cells) {
     uint64_t const stripes = ((uint64_t)m + 64u) / 64u, per_row = (band_cells + 7u) / 8u;
     return stripes * per_row * 64u + (band_cells > REALIGN_LDS_BAND ? 2u * band_cells : 0u);

@@ -166,18 +166,18 @@ static inline u32 tiles_of(u64 n, u32 tile_keys) { return (u32)((n + tile_keys -
 
 int SortDevice::keys_add(void* stream, const flx_record* d_records, uint32_t n, const uint32_t* d_words, uint64_t first_ordinal, SortKey* d_keys, SortMeta* d_meta) {
     if (n == 0) return 0;
-    u32 const blocks = std::min<u32>((n + WAVES - 1) / WAVES, 1u << 16);
+    u32 const blocks = std::min<u32>((n + WAVES - 1) / WAVES, KEYS_GRID_CAP);
     hipLaunchKernelGGL(sort_keys_add_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, d_records, n, d_words, first_ordinal, d_keys, d_meta);
     return (int)hipGetLastError();
 }
 int SortDevice::iota(void* stream, uint32_t* d_payload, uint64_t n) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sort_iota_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_payload, n);
+    hipLaunchKernelGGL(sort_iota_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_payload, n);
     return (int)hipGetLastError();
 }
 int SortDevice::digit_census(void* stream, const SortKey* d_keys, uint64_t n, uint32_t* d_counts) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sort_census_kernel, dim3(strided_blocks(n, 1024u)), dim3(THREADS), 0, (hipStream_t)stream, d_keys, n, d_counts);
+    hipLaunchKernelGGL(sort_census_kernel, dim3(strided_blocks(n, CENSUS_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_keys, n, d_counts);
     return (int)hipGetLastError();
 }
 int SortDevice::histogram(void* stream, const SortKey* d_keys, uint64_t n, uint32_t digit, uint32_t tile_keys, uint32_t* d_table) {
@@ -192,7 +192,7 @@ int SortDevice::scatter(void* stream, const SortKey* d_keys, const uint32_t* d_p
 }
 int SortDevice::entries(void* stream, const SortKey* d_keys, const uint32_t* d_payload, const SortMeta* d_meta, uint64_t n, void* d_entries) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sort_entries_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_keys, d_payload, d_meta, n,
+    hipLaunchKernelGGL(sort_entries_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_keys, d_payload, d_meta, n,
                        reinterpret_cast<flx_sort_entry*>(d_entries));
     return (int)hipGetLastError();
 }

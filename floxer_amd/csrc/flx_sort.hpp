@@ -127,6 +127,9 @@ inline bool sort_plan(uint32_t n_refs, const Record* records, uint64_t n, const 
 struct SortDevice {
     static constexpr uint32_t THREADS = 256;           // a block, and the keys it takes per step of its tile
     static constexpr uint32_t TILE_KEYS = 2048;        // default keys per tile
+    static constexpr uint32_t KEYS_GRID_CAP = 1u << 16;      // most blocks (four waves, a record each at a time) of a sort_keys_add launch
+    static constexpr uint32_t CENSUS_GRID_CAP = 1024u;       // most blocks of a sort_census launch: a block gathers its counts over all its turns
+    static constexpr uint32_t STRIDED_GRID_CAP = 1u << 14;   // most blocks of sort_iota and sort_entries: a thread strides on by the grid
     // one wave per record: keys[i], meta[i] and payload[i] = payload_base + i from records[i] (a flx_record array) and its words
     static int keys_add(void* stream, const flx_record* d_records, uint32_t n, const uint32_t* d_words, uint64_t first_ordinal, SortKey* d_keys,
                         SortMeta* d_meta);

@@ -222,45 +222,45 @@ __global__ void __launch_bounds__(THREADS) sv_signatures_kernel(const SortKey* _
 int SvDevice::extract(void* stream, const SvJob* d_jobs, u32 n_jobs, const u32* d_words, u32 min_length, SortKey* d_keys, SvSegment* d_segments, u32* d_flag) {
     if (n_jobs == 0) return 0;
     static_assert(sizeof(SvSegment) == 32, "eight u32 fields");
-    u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), 1u << 16);
+    u32 const blocks = std::min<u32>((n_jobs + THREADS / 64u - 1) / (THREADS / 64u), EXTRACT_GRID_CAP);
     hipLaunchKernelGGL(sv_extract_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, d_jobs, n_jobs, d_words, min_length, d_keys,
                        reinterpret_cast<u32*>(d_segments), d_flag);
     return (int)hipGetLastError();
 }
 int SvDevice::junctions(void* stream, const SvMember* d_members, u32 n_members, const SvSegment* d_segments, SortKey* d_keys, u32* d_flag) {
     if (n_members == 0) return 0;
-    hipLaunchKernelGGL(sv_junctions_kernel, dim3(strided_blocks(n_members, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_members, n_members, d_segments, d_keys, d_flag);
+    hipLaunchKernelGGL(sv_junctions_kernel, dim3(strided_blocks(n_members, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_members, n_members, d_segments, d_keys, d_flag);
     return (int)hipGetLastError();
 }
 int SvDevice::coarse_flags(void* stream, const SortKey* d_sorted, u64 n, u32 max_distance, u32* d_flags) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sv_coarse_flags_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, n, max_distance, d_flags);
+    hipLaunchKernelGGL(sv_coarse_flags_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, n, max_distance, d_flags);
     return (int)hipGetLastError();
 }
 int SvDevice::regroup(void* stream, const SortKey* d_sorted, const u32* d_groups, u64 n, SortKey* d_keys2) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sv_regroup_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, d_groups, n, d_keys2);
+    hipLaunchKernelGGL(sv_regroup_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, d_groups, n, d_keys2);
     return (int)hipGetLastError();
 }
 int SvDevice::fine_flags(void* stream, const SortKey* d_sorted2, u64 n, u32 max_distance, u32* d_flags) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sv_fine_flags_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted2, n, max_distance, d_flags);
+    hipLaunchKernelGGL(sv_fine_flags_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted2, n, max_distance, d_flags);
     return (int)hipGetLastError();
 }
 int SvDevice::cluster_heads(void* stream, const u32* d_ids, u64 n, u32* d_starts, flx_sv_cluster* d_clusters) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sv_cluster_heads_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_ids, n, d_starts, d_clusters);
+    hipLaunchKernelGGL(sv_cluster_heads_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_ids, n, d_starts, d_clusters);
     return (int)hipGetLastError();
 }
 int SvDevice::cluster_bounds(void* stream, const SortKey* d_sorted2, const u32* d_ids, u64 n, flx_sv_cluster* d_clusters) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sv_cluster_bounds_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted2, d_ids, n, d_clusters);
+    hipLaunchKernelGGL(sv_cluster_bounds_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted2, d_ids, n, d_clusters);
     return (int)hipGetLastError();
 }
 int SvDevice::cluster_fill(void* stream, const SortKey* d_sorted, const SortKey* d_sorted2, const u32* d_payload2, const u32* d_starts, u64 n, u64 n_clusters,
                            flx_sv_cluster* d_clusters) {
     if (n_clusters == 0) return 0;
-    hipLaunchKernelGGL(sv_cluster_fill_kernel, dim3(strided_blocks(n_clusters, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, d_sorted2, d_payload2, d_starts,
+    hipLaunchKernelGGL(sv_cluster_fill_kernel, dim3(strided_blocks(n_clusters, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, d_sorted2, d_payload2, d_starts,
                        n, n_clusters, d_clusters);
     return (int)hipGetLastError();
 }
@@ -273,7 +273,7 @@ int SvDevice::compact(void* stream, int mode, const flx_sv_cluster* d_clusters, 
 }
 int SvDevice::signatures(void* stream, const SortKey* d_sorted, u64 n, flx_sv_signature* d_out) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sv_signatures_kernel, dim3(strided_blocks(n, 1u << 14)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, n, d_out);
+    hipLaunchKernelGGL(sv_signatures_kernel, dim3(strided_blocks(n, STRIDED_GRID_CAP)), dim3(THREADS), 0, (hipStream_t)stream, d_sorted, n, d_out);
     return (int)hipGetLastError();
 }
 

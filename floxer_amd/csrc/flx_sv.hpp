@@ -254,6 +254,8 @@ inline void sv_clusters_host(const SortKey* sorted, uint64_t n, SvThresholds con
 
 // ---- the launches of flx_sv.hip (each returns the hipError_t of its launch; pointers are device pointers)
 struct SvDevice {
+    static constexpr u32 EXTRACT_GRID_CAP = 1u << 16;  // most blocks (four waves, a job each at a time) of an sv_extract launch
+    static constexpr u32 STRIDED_GRID_CAP = 1u << 14;  // most blocks of the launches with one thread per member, key or cluster: a thread strides on by the grid
     // one wave per job: its DEL / INS keys at d_keys[job.key_off ..] and d_segments[job]; *d_flag becomes nonzero when a job's words
     // disagree with the host's judgement (its segment is marked, no key is written outside its stretch)
     static int extract(void* stream, const SvJob* d_jobs, u32 n_jobs, const u32* d_words, u32 min_length, SortKey* d_keys, SvSegment* d_segments, u32* d_flag);

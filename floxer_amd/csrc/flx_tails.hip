@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(64) cigar_tails_kernel(const u32* __restrict__
 
 int DeviceApi::cigar_tails(void* stream, const u32* d_cigar, const DevTraceOut* d_trace_out, const DevTailJob* d_jobs, u32 n_jobs, DevTailOut* d_out) {
     if (n_jobs == 0) return 0;
-    hipLaunchKernelGGL(cigar_tails_kernel, dim3(std::min(n_jobs, 1u << 16)), dim3(64), 0, (hipStream_t)stream, d_cigar, d_trace_out, d_jobs, n_jobs, d_out);
+    hipLaunchKernelGGL(cigar_tails_kernel, dim3(std::min(n_jobs, TAILS_GRID_CAP)), dim3(64), 0, (hipStream_t)stream, d_cigar, d_trace_out, d_jobs, n_jobs, d_out);
     return (int)hipGetLastError();
 }
 

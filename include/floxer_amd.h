@@ -814,6 +814,15 @@ int  flx_sort_geometry(uint32_t out[4]);
 int  flx_sort_host(uint32_t n_refs, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
                    const uint64_t* ordinals, flx_sort_entry* out_sorted);
 
+/* ------------------------------------------------------------------------------------------------ grid caps
+ * flx_grid_caps (a test hook): the most blocks each capped launch asks for. Behind its cap a wave (or a thread) takes further jobs in
+ * turns, so a test that wants those turns sizes its input from here. One wave per job, blocks of one wave: out[0] md_build,
+ * out[1] cs_build, out[2] cigar_left_align, out[3] cigar_tails, out[4] ed_extend, out[5] cigar_realign, out[6] paf_summarise. One wave
+ * per record, blocks of four waves: out[7] coverage_add, out[8] pileup_add, out[9] sv_extract, out[10] sort_keys_add, out[11]
+ * errprof_add. One thread per element, blocks of 256: out[12] sort_census, out[13] sort_iota and sort_entries, out[14] sv_junctions,
+ * sv_coarse_flags, sv_regroup, sv_fine_flags, sv_cluster_heads, sv_cluster_bounds, sv_cluster_fill and sv_signatures. out[15] is 0. */
+int  flx_grid_caps(uint32_t out[16]);
+
 /* ------------------------------------------------------------------------------------------------ structural-variant signatures
  * Not floxer's, and pileup's sibling for events too long for one position: where is the sample rearranged, and how many records say so?
  * An sv object on a device collects one signature per long deletion, long insertion and split junction of the records added, orders
