@@ -33,8 +33,9 @@ def show(path):
     return "".join(f"{ln}{OPS[op]}" for op, ln in path)
 
 
-def left_align(path, ref, qry, begin):
-    """the rule: the words left to right into an output list"""
+def left_align(path, ref, qry, begin, gaps=None):
+    """the rule: the words left to right into an output list. gaps (a list): receives (columns shifted, merged with a gap word in front)
+    for every gap word of the path, in order"""
     out = []
     r, q = begin, 0
     for op, ln in path:
@@ -48,13 +49,14 @@ def left_align(path, ref, qry, begin):
             continue
         seq = ref if op == D else qry
         c = r if op == D else q
-        L, shift = ln, 0
+        L, shift, merged = ln, 0, False
         while out:
             p_op, p_len = out[-1]
             if p_op == op:
                 out.pop()
                 L += p_len
                 c -= p_len
+                merged = True
                 continue
             if p_op != EQ:
                 break
@@ -75,6 +77,8 @@ def left_align(path, ref, qry, begin):
         out.append((op, L))
         if shift:
             out.append((EQ, shift))
+        if gaps is not None:
+            gaps.append((shift, merged))
         if op == D:
             r += ln
         else:

@@ -49,6 +49,21 @@ int main() {
             if (ring_steps(n, m, k, W, R) != (u64)hi + ring_offset((u32)Lg - 1, R, d) + 1 || hi != (int)((n - 1) >> 4)) { if (bad++ < 5) printf("FAIL steps: n %u m %u k %u W %u R %u\n", n, m, k, W, R); }
         }
     }
-    printf("%s %d shapes that never waited, %d schedules walked, %d failures\n", bad ? "FAILURES" : "ok", no_wait_checked, simulated, bad);
+    // the hand-over queue of a ring that waits (ring_queue_for): delay + 1 slots are in use at once - what the last lane leaves at step
+    // T - 1 must not land on what the first lane still has to take from step T - 1 - delay -, the slot count is a power of two (the kernel
+    // masks its indices), at least 32, never twice what is needed beyond that, and a ring that never waits has none. Every delay the
+    // shapes may have, the delays that are themselves powers of two among them: there delay slots are one too few.
+    int queues_checked = 0, exact_powers = 0;
+    for (u32 delay = 0; delay + 1u <= RING_QUEUE_MAX; ++delay) {
+        u32 const q = ring_queue_for(delay);
+        ++queues_checked;
+        if (delay == 0) { if (q != 0) { if (bad++ < 5) printf("FAIL a ring that never waits has %u slots\n", q); } continue; }
+        bool const pow2 = q != 0 && (q & (q - 1u)) == 0;
+        bool const holds = q >= delay + 1u, tight = q == 32u || q / 2u < delay + 1u;
+        if ((delay & (delay - 1u)) == 0 && delay >= 32u) ++exact_powers;
+        if (!pow2 || !holds || !tight || q > RING_QUEUE_MAX) { if (bad++ < 5) printf("FAIL queue: delay %u slots %u\n", delay, q); }
+    }
+    if (exact_powers < 2) { ++bad; printf("FAIL vacuous: %d delays that are a power of two of 32 or more\n", exact_powers); }
+    printf("%s %d shapes that never waited, %d schedules walked, %d queue sizes, %d failures\n", bad ? "FAILURES" : "ok", no_wait_checked, simulated, queues_checked, bad);
     return bad ? 1 : 0;
 }

@@ -157,6 +157,77 @@ def test_root_stage_every_member_aligned_on_its_own(root_stage_expected):
         assert run["records"] == records
 
 
+# ---------------------------------------------------------------- 2b. the last row's ties and its threshold
+TIE_PERIOD = 64          # <= k = 80 (1 kb @ 8 %): a window holds the ends of neighbouring copies, 64 columns apart: one lane of lastrow_min
+TIE_K = 80
+
+
+def last_row(window, query):
+    """D[m][c], c = 0 .. n, of the semi-global matrix (the window's ends are free), row by row"""
+    window, query = np.asarray(window, dtype=np.int64), np.asarray(query, dtype=np.int64)
+    js = np.arange(len(window) + 1)
+    row = np.zeros(len(window) + 1, dtype=np.int64)
+    for i in range(1, len(query) + 1):
+        cand = row + 1
+        cand[1:] = np.minimum(cand[1:], row[:-1] + (window != query[i - 1]))
+        cand[0] = i
+        row = np.minimum.accumulate(cand - js) + js
+    return row
+
+
+def tie_inputs():
+    """8 reads of 1 kb on a 200 kb text: six as they come, one out of a tandem array of 40 copies of a 64-base unit (2 % mismatches),
+    one with exactly k = 80 substitutions, one every 12 or 13 bases. Returns (genome, reads, index of the tandem read, of the other,
+    the other's locus)."""
+    genome = S.make_genome(200000, 1, seed=741)
+    rng = np.random.default_rng(742)
+    array = np.tile(rng.integers(1, 5, size=TIE_PERIOD, dtype=np.uint8), 40)
+    genome[0][80000: 80000 + len(array)] = array
+    reads, _, _ = S.make_reads(genome, 6, 1000, 0.08, seed=743)
+    r = array[10: 1010].copy()
+    for p in rng.choice(1000, size=20, replace=False):
+        r[p] = (r[p] % 4) + 1
+    reads.append(np.ascontiguousarray(r))
+    locus = 150000
+    r = genome[0][locus: locus + 1000].copy()
+    for p in (np.arange(TIE_K) * 12.5).astype(int) + 3:
+        r[p] = (r[p] % 4) + 1
+    reads.append(np.ascontiguousarray(r))
+    return genome, reads, 6, 7, locus
+
+
+def test_root_stage_takes_the_rightmost_of_two_minima_64_columns_apart_and_a_minimum_of_exactly_k():
+    """lastrow_min at its two comparisons, through the only door it has (the union form of the root stage), against the oracle. A lane
+    of its wave reads the columns c, c + 64, ..: two minima of a member's last row that lie 64 columns apart are one lane's, and the later
+    one must win there before the wave's reduction sees either. And a member whose minimum is exactly its k has an alignment. Both
+    situations are shown on the CPU first: on the last row of the matrix for the tandem read, by the oracle's own DP for the other."""
+    genome, reads, tandem, at_k, locus = tie_inputs()
+    exp = O.Index(genome).run(reads, O.params(error_probability=0.08), threads=8)
+    rows = {i: [r for r in exp.records() if r[0] == i] for i in (tandem, at_k)}
+    # the read with k substitutions: one record, NM == k, and no alignment within k - 1
+    window = genome[0][locus - TIE_K: locus + 1000 + TIE_K]
+    assert [(r[1] & 4, r[3], r[4]) for r in rows[at_k]] == [(0, locus, TIE_K)]
+    assert O.align(window, reads[at_k], TIE_K, mode=0, algo=0)[0] == TIE_K and O.align(window, reads[at_k], TIE_K - 1, mode=0, algo=0) is None
+    # the tandem read: behind its primary record's end the last row holds the same minimum 64 columns earlier
+    primary = [r for r in rows[tandem] if not r[1] & (4 | 256)]
+    assert len(primary) == 1 and len(rows[tandem]) > 1
+    span = sum(int(n) for n, op in re.findall(r"(\d+)([=XID])", primary[0][5]) if op != "I")
+    end = primary[0][3] + span
+    strand = reads[tandem] if not primary[0][1] & 16 else O.revcomp(reads[tandem])
+    row = last_row(genome[0][end - 1000 - 2 * TIE_K: end], strand)
+    best = np.flatnonzero(row == row.min())
+    assert row.min() == primary[0][4] <= TIE_K and best[-1] == len(row) - 1 and len(row) - 1 - TIE_PERIOD in best, (row.min(), best[-5:])
+    with _env(FLX_LANES="1"):
+        ctx = F.context(F.fmindex(genome))
+    ctx.enable_kernel_timing(True)
+    got = F.aligner(ctx, F.params(error_probability=0.08)).align_reads(reads)
+    stats = ctx.kernel_stats()
+    ctx.close()
+    assert stats["ed_lastrow_min"]["launches"] >= 1 and stats["ed_lastrow_min"]["work_units"] > len(reads)      # the union form ran, over more windows than reads
+    assert got.skipped.tolist() == exp.skipped.tolist()
+    assert got.records() == exp.records()
+
+
 # ---------------------------------------------------------------- 3. empty and degenerate chunks
 def test_chunk_without_a_root_and_chunk_with_one_root(text_1mb, capfd):
     """a chunk none of whose reads reaches a root (random reads: no K4, no windows, no traceback job) and a chunk with exactly one root

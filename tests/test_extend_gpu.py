@@ -139,6 +139,73 @@ def test_kernel_matches_the_rule_on_its_edge_cases(small_ctx):
             assert res[name][:3] == res[name[:-1] + "-"][:3], name
 
 
+def matrix(q, t):
+    """D[i][j], the unit-cost edit distance between the first i rows and the first j symbols (D[0][0] = 0), every cell, row by row"""
+    q, t = np.asarray(q, dtype=np.int64), np.asarray(t, dtype=np.int64)
+    js = np.arange(len(t) + 1)
+    D = np.zeros((len(q) + 1, len(t) + 1), dtype=np.int64)
+    D[0] = js
+    for i in range(1, len(q) + 1):
+        cand = D[i - 1] + 1
+        cand[1:] = np.minimum(cand[1:], D[i - 1][:-1] + (t != q[i - 1]))
+        D[i] = np.minimum.accumulate(cand - js) + js
+    return D
+
+
+def scan(D, weight):
+    """per d = 0 .. m(last row): (R(d), score(d), the running maximum's drop G(d) - score(d)) read off the matrix"""
+    mins = D.min(axis=1)
+    out, G = [], None
+    for d in range(int(mins[-1]) + 1):
+        R = int(np.flatnonzero(mins <= d)[-1])
+        score = R - weight * d
+        G = score if G is None else max(G, score)
+        out.append((R, score, G - score))
+    return out
+
+
+@gpu
+def test_kernel_ties_of_the_diagonal_the_drop_and_the_stop_reasons(small_ctx):
+    """three situations the random jobs do not hold, each shown on the full matrix before the kernel is asked: two diagonals that reach
+    R(d*) (the smallest column wins), a drop of exactly x_drop in front of a new maximum (the scan goes on: the test is strict), and a
+    step at which the drop exceeds x_drop and the last row is reached together (the reason is the x-drop, which is asked first)."""
+    ctx, _ = small_ctx
+    rng = np.random.default_rng(21)
+    rnd = lambda n: rng.integers(1, 5, size=n, dtype=np.uint8)
+    J = Jobs()
+    # 1. behind 30 exact rows: a substitution on diagonal 0 or a deleted symbol on diagonal +1, then 20 rows of one letter on either
+    P = rnd(30)
+    P[-1] = 2
+    q = np.concatenate([P, np.full(20, 1), np.full(40, 3)]).astype(np.uint8)
+    t = np.concatenate([P, [2], np.full(21, 1), np.full(60, 4)]).astype(np.uint8)
+    i1, j1, d1, _ = rule(q, t)
+    D = matrix(q, t)
+    assert (i1, d1) == (50, 1) and np.flatnonzero(D[i1] == d1).tolist() == [50, 51] and j1 == 50
+    J.both("two diagonals reach R(1)", q, t)
+    # 2. a valley of 8 substitutions, exactly x_drop deep, and 232 exact rows behind it
+    t = rnd(400)
+    q = np.concatenate([t[:60], [other(x) for x in t[60:68]], t[68:300]]).astype(np.uint8)
+    steps = scan(matrix(q, t), W)
+    depth = max(drop for _, _, drop in steps)
+    floor = [d for d, (_, _, drop) in enumerate(steps) if drop == depth]
+    assert depth > 0 and floor and steps[-1][0] == 300 and steps[-1][2] == 0 and len(steps) - 1 > floor[-1]      # the last d is the new maximum
+    assert rule(q, t, W, depth, DMAX) == (300, 300, len(steps) - 1, 2) and rule(q, t, W, depth - 1, DMAX)[:3] == (60, 60, 0)
+    J.both("a drop of exactly x_drop, then a new maximum", q, t, x=depth)
+    J.both("a drop of x_drop + 1", q, t, x=depth - 1)
+    # 3. 60 exact rows and 30 substituted ones to the last row; x_drop one below the drop at the d that reaches it
+    t = rnd(200)
+    q = np.concatenate([t[:60], [other(x) for x in t[60:90]]]).astype(np.uint8)
+    steps = scan(matrix(q, t), W)
+    d_last = len(steps) - 1
+    assert steps[d_last][0] == 90 and all(R < 90 for R, _, _ in steps[:-1])
+    x = steps[d_last][2] - 1
+    assert x >= 1 and all(drop <= x for _, _, drop in steps[:-1])                 # no earlier step stops the scan
+    assert rule(q, t, W, x, DMAX) == (60, 60, 0, 1) and rule(q, t, W, x + 1, DMAX) == (60, 60, 0, 2)
+    J.both("the drop and the last row in one step", q, t, x=x)
+    J.both("the last row one step before the drop", q, t, x=x + 1)
+    J.run(ctx)
+
+
 @gpu
 def test_kernel_300_random_jobs_in_one_launch_and_the_contexts_text(small_ctx):
     ctx, ref = small_ctx

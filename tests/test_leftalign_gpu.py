@@ -152,6 +152,29 @@ def test_kernel_matches_the_rule_on_the_smallest_shapes_that_can_go_wrong(ctx):
 
 
 @gpu
+def test_kernel_counts_the_gap_words_that_moved_or_merged(ctx):
+    """the launch's work units are the gap words that moved or merged (DevLeftAlignStat::moved), counted here by the Python rule: a gap
+    word counts when it shifts at least one column or joins a gap word of its kind in front of it. The cases hold gap words that merge
+    without shifting (the word-by-word form of a pass), that shift without merging (both forms) and that do neither."""
+    cases = [c for _, _, c in kernel_cases()]
+    want, kinds = 0, set()
+    for c in cases:
+        gaps = []
+        R.left_align(*c, gaps=gaps)
+        assert len(gaps) == sum(op in (I, D) for op, _ in c[0])
+        want += sum(1 for shift, merged in gaps if shift or merged)
+        kinds |= {(shift > 0, merged) for shift, merged in gaps}
+    assert kinds == {(False, False), (True, False), (False, True), (True, True)}, kinds      # not vacuous, on the rule alone
+    ctx.enable_kernel_timing(True)
+    ctx.reset_kernel_stats()
+    run_kernel(ctx, cases)
+    st = ctx.kernel_stats()
+    ctx.enable_kernel_timing(False)
+    assert list(st) == ["cigar_left_align"] and st["cigar_left_align"]["launches"] == 1
+    assert st["cigar_left_align"]["work_units"] == want, (st["cigar_left_align"]["work_units"], want)
+
+
+@gpu
 def test_kernel_random_paths_in_one_launch_and_bad_jobs_launch_nothing(ctx):
     cases = R.random_corpus(29, 3000) + R.random_corpus(37, 3000, repeats=True)      # the second half: neighbouring words of one op
     rng = random.Random(31)

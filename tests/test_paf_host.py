@@ -142,11 +142,21 @@ def test_every_refusal_leaves_the_output_untouched():
     refused((0, 1, 0, 2, 0, [W("S", 4)]), 4, "no reference-consuming column", "no reference-consuming column")
     big = [W("I", (1 << 28) - 1)] * 9 + [W("=", 1)]
     refused((0, 1, 0, 2, 0, big), 9 * ((1 << 28) - 1) + 1, "2^31", "2^31")
+    # the bound itself: query-consuming lengths of exactly 2^31 are refused, 2^31 - 1 (below) are summarised
+    at_limit = [W("I", (1 << 28) - 1)] * 8 + [W("=", 8)]
+    assert sum(w >> 4 for w in at_limit) == 1 << 31
+    refused((0, 1, 0, 2, 0, at_limit), 1 << 31, "2^31", "2^31")
     handle.close()
     # what is fine: a span that ends exactly at its sequence's end, a D-only record, the same bad words in an unmapped record
     rec, words = R.records_of(good + [(0, 3, 4, 2, 0, [W("S", 9), W("=", 60)]), (0, 3, 0, 3, 4, [W("D", 4)]), (4, 0, 0, 9, 0, [W("M", 3)])])
     read_lengths = good_lens + [69, 0]
     assert _both(rec, words, read_lengths).tobytes() == R.summarize(rec, words, read_lengths, REF_LENS).tobytes()
+    # one row below the bound: 2^31 - 1 query-consuming lengths (no letters are read: the read is its length alone)
+    below = [W("I", (1 << 28) - 1)] * 8 + [W("=", 7)]
+    rec, words = R.records_of(good + [(0, 1, 0, 2, 0, below)])
+    read_lengths = good_lens + [(1 << 31) - 1]
+    got = _both(rec, words, read_lengths)
+    assert got.tobytes() == R.summarize(rec, words, read_lengths, REF_LENS).tobytes() and int(got[2]["query_end"]) == (1 << 31) - 1
     # the lengths themselves, and a null output
     out = np.zeros(5, dtype=F.PAF_SUMMARY_DTYPE)
     assert _call_host(rec, words, read_lengths, [50, 1 << 31], out) == -1 and "2^31" in capi.lib().flx_last_error().decode()
