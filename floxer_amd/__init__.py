@@ -1428,6 +1428,150 @@ def errprof_host(text, lengths, records, cigar_words, reads, options=None, table
     return _errprof_dict(t)
 
 
+# ------------------------------------------------------------------------------------------------ consensus sequence
+CHANGE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<u4"), ("kind", "<u4"), ("ref_rank", "<u4"), ("alt_rank", "<u4"), ("length", "<u4"), ("count", "<u4"),
+                         ("cov", "<u4"), ("letters", "<u8")])
+ALLELE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<u4"), ("length", "<u4"), ("count", "<u4"), ("letters", "<u8")])
+CONSENSUS_KINDS = ("SUB", "DEL", "INS")
+
+
+def consensus_options(count_secondary=False, min_mapq=0, min_depth=0, min_count=0, min_permille=0, mask_low_depth=False):
+    """flx_consensus_options: count_secondary and min_mapq as pileup_options has them; a position with DEPTH + DEL below min_depth keeps
+    the reference letter (N with mask_low_depth); a call other than the reference letter, and the winning insertion behind a position,
+    stand only with a count >= min_count and count * 1000 >= min_permille * (DEPTH + DEL); 0 takes the defaults 3, 2 and 500,
+    conventions of this project that are fitted to nothing"""
+    o = capi.ConsensusOptions()
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq = int(min_mapq)
+    o.min_depth, o.min_count, o.min_permille = int(min_depth), int(min_count), int(min_permille)
+    o.mask_low_depth = 1 if mask_low_depth else 0
+    return o
+
+
+def consensus_geometry():
+    """(grid cap of consensus_ins_keys in blocks, its waves per block, the longest allele) (flx_consensus_geometry, a test hook)"""
+    out = np.zeros(4, dtype=np.uint32)
+    check(lib().flx_consensus_geometry(ptr(out, u32p)))
+    return tuple(int(x) for x in out[:3])
+
+
+def consensus_letters_of(letters, length):
+    """the inserted letters of a change or an allele as a string: two bits each from the top of `letters`"""
+    return "".join("ACGT"[(int(letters) >> (62 - 2 * k)) & 3] for k in range(int(length)))
+
+
+class consensus:
+    """Reference-guided consensus of the records added: pileup's counts plus the letters of every insertion of up to 32 bases, called on
+    the device at finish. Over the text of a context's index (ctx), or over `text` on `device`: a list of rank arrays, or their
+    concatenation with `lengths`. finish once, then read letters(ref), changes() and alleles(). One device: there is no absorb. Not
+    floxer's. Adds may come from several threads."""
+
+    def __init__(self, ctx=None, options=None, text=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_consensus_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if text is None:
+                raise FloxerError("consensus needs a context or a reference text")
+            concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+            lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+            if int(lens.sum()) != len(concat):
+                raise FloxerError("consensus: the lengths do not sum to the text's length")
+            check(lib().flx_consensus_create_for_text(int(device), ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_consensus_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run, reads):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed;
+        reads: the batch the run was made from: a list of rank arrays, (pool, offsets), or a resident_reads batch (with a raw handle
+        only). With min_mapq a run made without output_options(mapq=True) is refused."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("consensus.add: min_mapq needs a run made with output_options(mapq=True)")
+            if isinstance(reads, resident_reads):
+                raise FloxerError("consensus.add: a RunResult needs the reads in host memory; a resident batch goes with a raw run handle")
+            return self.add_records(run.raw, run.cigars, reads)
+        if isinstance(reads, resident_reads):
+            check(lib().flx_consensus_add_run_resident(self.h, run, reads.h))
+        else:
+            pool, offs, n = _pool_and_offsets(reads)
+            check(lib().flx_consensus_add_run(self.h, run, ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def add_records(self, records, cigar_words, reads):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        reads: a list of rank arrays or (pool, offsets), indexed by the records' `read`"""
+        rec, words = _records_and_words(records, cigar_words)
+        pool, offs, n = _pool_and_offsets(reads)
+        check(lib().flx_consensus_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words),
+                                              ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def finish(self):
+        check(lib().flx_consensus_finish(self.h))
+
+    def letters(self, ref):
+        """the consensus of sequence ref as a str (possibly empty)"""
+        n = lib().flx_consensus_num_letters(self.h, int(ref))
+        out = np.zeros(max(1, n), dtype=np.uint8)
+        check(lib().flx_consensus_copy_letters(self.h, int(ref), out.ctypes.data_as(C.c_char_p), n))
+        return out[:n].tobytes().decode("ascii")
+
+    def changes(self):
+        """every place the consensus departs from the text, in position order: a structured array of CHANGE_DTYPE"""
+        n = lib().flx_consensus_num_changes(self.h)
+        out = np.zeros(max(1, n), dtype=CHANGE_DTYPE)
+        check(lib().flx_consensus_copy_changes(self.h, out.ctypes.data_as(C.POINTER(capi.ConsensusChange)), n))
+        return out[:n]
+
+    def alleles(self):
+        """every insertion allele with its count, in key order (a test hook): a structured array of ALLELE_DTYPE"""
+        n = lib().flx_consensus_num_alleles(self.h)
+        out = np.zeros(max(1, n), dtype=ALLELE_DTYPE)
+        check(lib().flx_consensus_copy_alleles(self.h, out.ctypes.data_as(C.POINTER(capi.ConsensusAllele)), n))
+        return out[:n]
+
+
+def consensus_host(text, lengths, records, cigar_words, reads, options=None):
+    """the rule alone on the host (flx_consensus_host): text and lengths as errprof_host takes them. Returns (letters, changes, alleles):
+    a list of str per sequence and two structured arrays (CHANGE_DTYPE, ALLELE_DTYPE)."""
+    concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+    lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+    if int(lens.sum()) != len(concat):
+        raise FloxerError("consensus_host: the lengths do not sum to the text's length")
+    rec, words = _records_and_words(records, cigar_words)
+    pool, offs, n = _pool_and_offsets(reads)
+    opt = C.byref(options) if options is not None else None
+    offsets = np.zeros(len(lens) + 1, dtype=np.uint64)
+    need = [C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)]
+
+    def call(letters, changes, alleles):
+        return lib().flx_consensus_host(ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p),
+                                        len(words), ptr(pool, u8p), ptr(offs, u64p), n, ptr(offsets, u64p),
+                                        letters.ctypes.data_as(C.c_char_p) if letters is not None else None, C.byref(need[0]),
+                                        changes.ctypes.data_as(C.POINTER(capi.ConsensusChange)) if changes is not None else None, C.byref(need[1]),
+                                        alleles.ctypes.data_as(C.POINTER(capi.ConsensusAllele)) if alleles is not None else None, C.byref(need[2]))
+
+    rc = call(None, None, None)
+    if rc not in (0, -3):                                               # (FLX_ERR_CAPACITY: need holds the sizes)
+        check(rc)
+    letters = np.zeros(max(1, need[0].value), dtype=np.uint8)
+    changes = np.zeros(max(1, need[1].value), dtype=CHANGE_DTYPE)
+    alleles = np.zeros(max(1, need[2].value), dtype=ALLELE_DTYPE)
+    check(call(letters, changes, alleles))
+    text_out = letters[: need[0].value].tobytes().decode("ascii")
+    return ([text_out[int(offsets[r]): int(offsets[r + 1])] for r in range(len(lens))], changes[: need[1].value], alleles[: need[2].value])
+
+
 # ------------------------------------------------------------------------------------------------ structural-variant signatures
 SV_SIGNATURE_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("res", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a", "<u4"), ("q", "<u4")])
 SV_CLUSTER_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("support", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a_min", "<u4"),

@@ -185,6 +185,20 @@ class ErrprofOptions(C.Structure):
     _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("flush_threshold", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+class ConsensusOptions(C.Structure):
+    _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("min_depth", C.c_uint32), ("min_count", C.c_uint32),
+                ("min_permille", C.c_uint32), ("mask_low_depth", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ConsensusChange(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("kind", C.c_uint32), ("ref_rank", C.c_uint32), ("alt_rank", C.c_uint32),
+                ("length", C.c_uint32), ("count", C.c_uint32), ("cov", C.c_uint32), ("letters", C.c_uint64)]
+
+
+class ConsensusAllele(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("length", C.c_uint32), ("count", C.c_uint32), ("letters", C.c_uint64)]
+
+
 # flx_errprof_table: its sections in their fixed order, u64 each
 ERRPROF_SECTIONS = (("PAIR_EQ", 36), ("PAIR_X", 36), ("INS_LEN", 64), ("DEL_LEN", 64), ("INS_LETTER", 6), ("DEL_LETTER", 6), ("HP_DEL", 34), ("HP_INS", 34),
                     ("POS_MATCH", 100), ("POS_MISMATCH", 100), ("POS_INS", 100), ("POS_CLIP", 100), ("POS_DEL", 100), ("EQ_RUN", 256), ("IDENTITY", 101),
@@ -305,6 +319,10 @@ EXPORTED = [
     "flx_sv_num_signatures", "flx_sv_copy_signatures", "flx_sv_num_clusters", "flx_sv_copy_clusters", "flx_sv_host", "flx_sv_clusters_host",
     "flx_errprof_create", "flx_errprof_create_for_text", "flx_errprof_free", "flx_errprof_add_records", "flx_errprof_add_run",
     "flx_errprof_add_run_resident", "flx_errprof_absorb", "flx_errprof_copy", "flx_errprof_host",
+    "flx_consensus_create", "flx_consensus_create_for_text", "flx_consensus_free", "flx_consensus_add_records", "flx_consensus_add_run",
+    "flx_consensus_add_run_resident", "flx_consensus_finish", "flx_consensus_num_letters", "flx_consensus_copy_letters",
+    "flx_consensus_num_changes", "flx_consensus_copy_changes", "flx_consensus_num_alleles", "flx_consensus_copy_alleles",
+    "flx_consensus_geometry", "flx_consensus_host",
     "flx_grid_caps",
 ]
 
@@ -513,6 +531,26 @@ def lib():
     L.flx_errprof_copy.argtypes = [C.c_void_p, C.POINTER(ErrprofTable)]
     L.flx_errprof_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(ErrprofOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64,
                                    C.POINTER(ErrprofTable)]
+    L.flx_consensus_create.argtypes = [C.c_void_p, C.POINTER(ConsensusOptions), C.POINTER(C.c_void_p)]
+    L.flx_consensus_create_for_text.argtypes = [C.c_int, u8p, u64p, C.c_uint32, C.POINTER(ConsensusOptions), C.POINTER(C.c_void_p)]
+    L.flx_consensus_free.restype = None
+    L.flx_consensus_free.argtypes = [C.c_void_p]
+    L.flx_consensus_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64]
+    L.flx_consensus_add_run.argtypes = [C.c_void_p, C.c_void_p, u8p, u64p, C.c_uint64]
+    L.flx_consensus_add_run_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flx_consensus_finish.argtypes = [C.c_void_p]
+    L.flx_consensus_num_letters.restype = C.c_uint64
+    L.flx_consensus_num_letters.argtypes = [C.c_void_p, C.c_uint32]
+    L.flx_consensus_copy_letters.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64]
+    L.flx_consensus_num_changes.restype = C.c_uint64
+    L.flx_consensus_num_changes.argtypes = [C.c_void_p]
+    L.flx_consensus_copy_changes.argtypes = [C.c_void_p, C.POINTER(ConsensusChange), C.c_uint64]
+    L.flx_consensus_num_alleles.restype = C.c_uint64
+    L.flx_consensus_num_alleles.argtypes = [C.c_void_p]
+    L.flx_consensus_copy_alleles.argtypes = [C.c_void_p, C.POINTER(ConsensusAllele), C.c_uint64]
+    L.flx_consensus_geometry.argtypes = [u32p]
+    L.flx_consensus_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(ConsensusOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64,
+                                     u64p, C.c_char_p, u64p, C.POINTER(ConsensusChange), u64p, C.POINTER(ConsensusAllele), u64p]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

@@ -273,6 +273,7 @@ int flx_ctx_destroy(flx_ctx* ctx) {
         if (ctx->live_reads > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_reads) + " read batch(es) of this context are still alive (flx_reads_free them first)"); return FLX_ERR_INVALID; }
         // and a live error-profile object reads this context's text
         if (ctx->live_errprofs > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_errprofs) + " error-profile object(s) of this context are still alive (flx_errprof_free them first)"); return FLX_ERR_INVALID; }
+        if (ctx->live_consensus > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_consensus) + " consensus object(s) of this context are still alive (flx_consensus_free them first)"); return FLX_ERR_INVALID; }
     }
     delete ctx;
     return FLX_OK;

@@ -1,9 +1,11 @@
-// What the side objects behind the C ABI share (flx_coverage, flx_pileup, flx_sort, flx_paf, flx_sv, flx_errprof; each in its own *_api.cpp): the base with the
-// device, the stream, the lock and the profile's events; the pieces of a run; judging on several threads; and, for coverage and pileup,
-// the base of an accumulator of u32 planes over the concatenation of the sequences with its scan and its absorb.
+// What the side objects behind the C ABI share (flx_coverage, flx_pileup, flx_sort, flx_paf, flx_sv, flx_errprof, flx_consensus; each in its own
+// *_api.cpp): the base with the device, the stream, the lock and the profile's events; the pieces of a run; judging on several threads;
+// the staging of the reads' letters; and, for coverage, pileup and the consensus, the base of an accumulator of u32 planes over the
+// concatenation of the sequences with its scan and its absorb.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -90,7 +92,39 @@ bool judge_in_parallel(size_t n, F&& judge) {
     return true;
 }
 
-// Coverage and pileup: u32 planes over the unpadded concatenation of the sequences, differences until the object's finish.
+// Where the letters of the reads come from (pileup, the error profile, the consensus): the caller's rank pool (forward sequences: a
+// reverse complement is made here with the rank routine) or a batch's host copy (both orientations, flx_reads::pool).
+struct Letters {
+    const uint8_t* read_pool = nullptr;
+    const uint64_t* read_offsets = nullptr;
+    const flx_reads* batch = nullptr;
+    uint64_t n_reads = 0;
+    u64 length(u64 i) const { return batch ? batch->lens[i] : read_offsets[i + 1] - read_offsets[i]; }
+    void oriented(u64 i, bool reverse, u8* out) const {
+        u64 const len = length(i);
+        if (batch) memcpy(out, batch->pool.data() + batch->pool_off[i] + (reverse ? len : 0), len);
+        else if (reverse) reverse_complement(read_pool + read_offsets[i], len, out);
+        else memcpy(out, read_pool + read_offsets[i], len);
+    }
+};
+
+// the oriented sequences the jobs refer to (a job has read_index, reverse and seq_off), each once per orientation used, and every
+// job's seq_off into them
+template <class Job>
+void stage_letters(std::vector<Job>& jobs, Letters const& src, std::vector<u8>& pool) {
+    std::vector<u64> keys;
+    keys.reserve(jobs.size());
+    for (auto const& j : jobs) keys.push_back(j.read_index * 2 + j.reverse);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    std::vector<u64> off(keys.size() + 1, 0);
+    for (size_t k = 0; k < keys.size(); ++k) off[k + 1] = off[k] + src.length(keys[k] >> 1);
+    pool.resize(off.back());
+    for (size_t k = 0; k < keys.size(); ++k) src.oriented(keys[k] >> 1, (keys[k] & 1) != 0, pool.data() + off[k]);
+    for (auto& j : jobs) j.seq_off = off[(size_t)(std::lower_bound(keys.begin(), keys.end(), j.read_index * 2 + j.reverse) - keys.begin())];
+}
+
+// Coverage, pileup and the consensus: u32 planes over the unpadded concatenation of the sequences, differences until the object's finish.
 struct PlaneObject : SideObject {
     static constexpr u64 ABSORB_CHUNK = 4ull << 20;    // entries per piece of an absorb (16 MB)
     std::vector<u64> starts;             // n_refs + 1

@@ -36,36 +36,6 @@ int create(int device, std::vector<u64>&& starts, const flx_pileup_options* o, f
     return FLX_OK;
 }
 
-// Where the letters of the reads come from: the caller's rank pool (forward sequences: a reverse complement is made here with the
-// rank routine) or a batch's host copy (both orientations, flx_reads::pool).
-struct Letters {
-    const uint8_t* read_pool = nullptr;
-    const uint64_t* read_offsets = nullptr;
-    const flx_reads* batch = nullptr;
-    uint64_t n_reads = 0;
-    u64 length(u64 i) const { return batch ? batch->lens[i] : read_offsets[i + 1] - read_offsets[i]; }
-    void oriented(u64 i, bool reverse, u8* out) const {
-        u64 const len = length(i);
-        if (batch) memcpy(out, batch->pool.data() + batch->pool_off[i] + (reverse ? len : 0), len);
-        else if (reverse) reverse_complement(read_pool + read_offsets[i], len, out);
-        else memcpy(out, read_pool + read_offsets[i], len);
-    }
-};
-
-// the oriented sequences the jobs refer to, each once per orientation used, and every job's seq_off into them
-void stage_letters(std::vector<PileupJob>& jobs, Letters const& src, std::vector<u8>& pool) {
-    std::vector<u64> keys;
-    keys.reserve(jobs.size());
-    for (auto const& j : jobs) keys.push_back(j.read_index * 2 + j.reverse);
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    std::vector<u64> off(keys.size() + 1, 0);
-    for (size_t k = 0; k < keys.size(); ++k) off[k + 1] = off[k] + src.length(keys[k] >> 1);
-    pool.resize(off.back());
-    for (size_t k = 0; k < keys.size(); ++k) src.oriented(keys[k] >> 1, (keys[k] & 1) != 0, pool.data() + off[k]);
-    for (auto& j : jobs) j.seq_off = off[(size_t)(std::lower_bound(keys.begin(), keys.end(), j.read_index * 2 + j.reverse) - keys.begin())];
-}
-
 // the judged jobs of one word pool: staged, then uploaded and launched under the object's lock. resident: the letters are read from the
 // batch's device pool (on this object's device); otherwise the oriented sequences in use go up from `src`.
 int commit(flx_pileup* c, std::vector<PileupJob>& jobs, const uint32_t* cigar_words, Letters const& src, const flx_reads* resident, const char* who) {

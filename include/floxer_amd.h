@@ -964,6 +964,67 @@ int  flx_errprof_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens,
                       const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words, const uint8_t* read_pool,
                       const uint64_t* read_offsets, uint64_t n_reads, flx_errprof_table* table /* added to */);
 
+/* ------------------------------------------------------------------------------------------------ consensus sequence
+ * Not floxer's, and the step behind pileup: the sequence the reads vote for, guided by the reference (polishing a draft, or a sample
+ * rebuilt from a related reference). A consensus object holds pileup's seven u32 planes over the concatenation of the sequences (28
+ * bytes per reference base) plus one 16-byte key per insertion event, and reads the reference text in HBM. The rule
+ * (floxer_amd/csrc/flx_consensus.hpp):
+ *   - which records count, what is refused and the seven sums: pileup's, with count_secondary and min_mapq;
+ *   - every I word of a counted record is an event. Its anchor is the position of the record's preceding reference-consuming column.
+ *     It is an allele when such a column precedes it in the record, its length is 1..32 and all its letters of the oriented sequence
+ *     have rank 1..4; otherwise it is dropped (longer insertions are the structural-variant object's business). Equal (anchor, length,
+ *     letters) are one allele with a count; the winner at an anchor is the allele with the largest count, ties to the smaller
+ *     (anchor, length, letters lexicographic);
+ *   - the call at a position: R the text's rank, cov = DEPTH + DEL, n[r] = plane r + (R == r ? DEPTH - A - C - G - T : 0) for r in A,
+ *     C, G, T, n[DEL] = DEL. cov < min_depth: uncalled, R's letter (N with mask_low_depth), no insertion, no change. Otherwise best is
+ *     the largest of the five, ties to R, else to the first of A, C, G, T, DEL; a best other than R stands only with n[best] >=
+ *     min_count and n[best] * 1000 >= min_permille * cov (64-bit), else R stays. A rank outside 1..4 is written N; DEL emits no
+ *     letter. The winning insertion behind the position is applied iff cov >= min_depth and its count meets the same two thresholds,
+ *     also when the position itself is called DEL. 0 takes the defaults 3 / 2 / 500: conventions of this project, fitted to nothing;
+ *   - the outputs: per sequence its letters as ASCII (possibly none); the changes, every place the consensus departs from the text in
+ *     position order (kind 0 SUB, 1 DEL, 2 INS; a SUB or DEL row in front of the INS row of the same position; length 1 for SUB and
+ *     DEL; alt_rank the called rank for SUB and 0 otherwise; count the winning count; letters the inserted letters, two bits each
+ *     from bit 62 down, letter k at bits 63 - 2k and 62 - 2k holding rank - 1, and 0 for SUB and DEL); and, as a test hook, the alleles
+ *     in key order.
+ * flx_consensus_create reads the context's own text in HBM (no second copy) and counts as a live object of the context:
+ * flx_ctx_destroy refuses until it is freed. flx_consensus_create_for_text uploads the unpadded concatenation of the sequences' ranks
+ * itself; hip_device -1 is refused (the host form is flx_consensus_host). options NULL: all zero; the reserved fields must be 0 and
+ * min_permille at most 1000. The add calls are pileup's: adds may come from several host threads at once, a run made with
+ * without_cigar is refused, min_mapq needs a run made with flx_output_options.mapq; a refused add leaves the object as it was. The keys
+ * grow by doubling up to 2^32 - 1 events; a failed growth is reported and leaves the object as it was. flx_consensus_finish is final: a
+ * later add or finish is FLX_ERR_INVALID, and the copy calls work only behind it. If all letters together would reach 2^32 it returns
+ * FLX_ERR_CAPACITY and the object holds no result. flx_consensus_copy_letters, flx_consensus_copy_changes and
+ * flx_consensus_copy_alleles return FLX_ERR_CAPACITY with the needed size in the message when capacity is too small.
+ * flx_consensus_geometry (a test hook): out[0] the grid cap of consensus_ins_keys in blocks, out[1] its waves per block, out[2] the
+ * longest allele, out[3] 0. flx_consensus_host: the rule alone on the host, no device, the same refusals: letter_offsets (n_refs + 1
+ * entries) and the three tables; each n_* holds the capacity on entry and the need on return (FLX_ERR_CAPACITY when one is too small;
+ * nothing is written then but the needs). Objects of several devices are not merged: there is no absorb call.
+ * FLX_CONSENSUS_PROFILE (environment): every add and the finish print their sizes, device time and wall time to stderr. */
+typedef struct flx_consensus flx_consensus;
+typedef struct flx_consensus_options { uint32_t count_secondary, min_mapq, min_depth, min_count, min_permille, mask_low_depth; uint32_t reserved[2]; } flx_consensus_options;
+typedef struct flx_consensus_change { int32_t reference_id; uint32_t position /* 0-based */, kind, ref_rank, alt_rank, length, count, cov; uint64_t letters; } flx_consensus_change;
+typedef struct flx_consensus_allele { int32_t reference_id; uint32_t position /* the anchor, 0-based */, length, count; uint64_t letters; } flx_consensus_allele;
+int  flx_consensus_create(flx_ctx* ctx, const flx_consensus_options* o, flx_consensus** out);
+int  flx_consensus_create_for_text(int hip_device, const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs,
+                                   const flx_consensus_options* o, flx_consensus** out);
+void flx_consensus_free(flx_consensus* p);
+int  flx_consensus_add_records(flx_consensus* p, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                               const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_consensus_add_run(flx_consensus* p, const flx_run* run, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_consensus_add_run_resident(flx_consensus* p, const flx_run* run, const flx_reads* reads);
+int  flx_consensus_finish(flx_consensus* p);
+uint64_t flx_consensus_num_letters(const flx_consensus* p, uint32_t reference_id);
+int  flx_consensus_copy_letters(const flx_consensus* p, uint32_t reference_id, char* out, uint64_t capacity);
+uint64_t flx_consensus_num_changes(const flx_consensus* p);
+int  flx_consensus_copy_changes(const flx_consensus* p, flx_consensus_change* out, uint64_t capacity);
+uint64_t flx_consensus_num_alleles(const flx_consensus* p);
+int  flx_consensus_copy_alleles(const flx_consensus* p, flx_consensus_allele* out, uint64_t capacity);
+int  flx_consensus_geometry(uint32_t out[4]);
+int  flx_consensus_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs, const flx_consensus_options* o,
+                        const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words, const uint8_t* read_pool,
+                        const uint64_t* read_offsets, uint64_t n_reads, uint64_t* letter_offsets, char* letters, uint64_t* n_letters,
+                        flx_consensus_change* changes, uint64_t* n_changes, flx_consensus_allele* alleles, uint64_t* n_alleles);
+
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
  * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
