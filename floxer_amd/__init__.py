@@ -1572,6 +1572,144 @@ def consensus_host(text, lengths, records, cigar_words, reads, options=None):
     return ([text_out[int(offsets[r]): int(offsets[r + 1])] for r in range(len(lens))], changes[: need[1].value], alleles[: need[2].value])
 
 
+# ------------------------------------------------------------------------------------------------ diploid small-variant calls
+VARIANT_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<u4"), ("kind", "<u4"), ("ref_rank", "<u4"), ("alt_rank", "<u4"), ("length", "<u4"), ("ref_count", "<u4"),
+                          ("alt_count", "<u4"), ("cov", "<u4"), ("gt", "<u4"), ("gq", "<u4"), ("qual", "<u4"), ("pl", "<u4", (3,)), ("reserved", "<u4"),
+                          ("letters", "<u8")])
+VARIANT_ALLELE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<u4"), ("kind", "<u4"), ("length", "<u4"), ("count", "<u4"), ("reserved", "<u4"), ("letters", "<u8")])
+VARIANT_KINDS = ("SNV", "DEL", "INS")
+
+
+def variants_options(count_secondary=False, min_mapq=0, min_depth=0, min_qual=0, max_del=0, cost_match=0, cost_mismatch=0, cost_het=0, prior_het=0, prior_hom=0):
+    """flx_variants_options: count_secondary and min_mapq as pileup_options has them; a call is written only with DEPTH + DEL >= min_depth
+    and a quality of at least min_qual (centi-phred); a deletion of more than max_del bases is no allele; the five costs of the genotype
+    model in centi-phred (-1000 log10 of a probability). 0 takes the defaults 4, 2000, 50 and 36 / 1574 / 325 / 3000 / 3301 (a per-read
+    error of 0.08, a heterozygosity of 0.001), conventions of this project that are fitted to nothing"""
+    o = capi.VariantsOptions()
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq = int(min_mapq)
+    o.min_depth, o.min_qual, o.max_del = int(min_depth), int(min_qual), int(max_del)
+    o.cost_match, o.cost_mismatch, o.cost_het, o.prior_het, o.prior_hom = int(cost_match), int(cost_mismatch), int(cost_het), int(prior_het), int(prior_hom)
+    return o
+
+
+def variants_geometry():
+    """(grid cap of variants_indel_keys in blocks, its waves per block, the longest insertion, the default max_del) (flx_variants_geometry,
+    a test hook)"""
+    out = np.zeros(4, dtype=np.uint32)
+    check(lib().flx_variants_geometry(ptr(out, u32p)))
+    return tuple(int(x) for x in out)
+
+
+def variants_genotype(ref_n, alt_n, oth, options=None):
+    """the genotype of one candidate (flx_variants_genotype, a test hook): dict(gt, gq, qual, pl, row); gt 0 = 0/0, 1 = 0/1, 2 = 1/1; row:
+    whether a call would be written with cov = ref_n + alt_n + oth"""
+    out = np.zeros(8, dtype=np.uint32)
+    check(lib().flx_variants_genotype(C.byref(options) if options is not None else None, int(ref_n), int(alt_n), int(oth), ptr(out, u32p)))
+    return dict(gt=int(out[0]), gq=int(out[1]), qual=int(out[2]), pl=[int(x) for x in out[3:6]], row=bool(out[6]))
+
+
+class variants:
+    """Diploid small-variant calls of the records added: pileup's counts plus one key per insertion of up to 32 bases and per deletion of
+    up to max_del, genotyped on the device at finish. Over the text of a context's index (ctx), or over `text` on `device`: a list of
+    rank arrays, or their concatenation with `lengths`. finish once, then read rows() and alleles(). One device: there is no absorb.
+    Not floxer's. Adds may come from several threads."""
+
+    def __init__(self, ctx=None, options=None, text=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_variants_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if text is None:
+                raise FloxerError("variants needs a context or a reference text")
+            concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+            lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+            if int(lens.sum()) != len(concat):
+                raise FloxerError("variants: the lengths do not sum to the text's length")
+            check(lib().flx_variants_create_for_text(int(device), ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_variants_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run, reads):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed;
+        reads: the batch the run was made from: a list of rank arrays, (pool, offsets), or a resident_reads batch (with a raw handle
+        only). With min_mapq a run made without output_options(mapq=True) is refused."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("variants.add: min_mapq needs a run made with output_options(mapq=True)")
+            if isinstance(reads, resident_reads):
+                raise FloxerError("variants.add: a RunResult needs the reads in host memory; a resident batch goes with a raw run handle")
+            return self.add_records(run.raw, run.cigars, reads)
+        if isinstance(reads, resident_reads):
+            check(lib().flx_variants_add_run_resident(self.h, run, reads.h))
+        else:
+            pool, offs, n = _pool_and_offsets(reads)
+            check(lib().flx_variants_add_run(self.h, run, ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def add_records(self, records, cigar_words, reads):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        reads: a list of rank arrays or (pool, offsets), indexed by the records' `read`"""
+        rec, words = _records_and_words(records, cigar_words)
+        pool, offs, n = _pool_and_offsets(reads)
+        check(lib().flx_variants_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words),
+                                             ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def finish(self):
+        check(lib().flx_variants_finish(self.h))
+
+    def rows(self):
+        """the calls in position order, an SNV in front of the indel of the same position: a structured array of VARIANT_DTYPE"""
+        n = lib().flx_variants_num_rows(self.h)
+        out = np.zeros(max(1, n), dtype=VARIANT_DTYPE)
+        check(lib().flx_variants_copy_rows(self.h, out.ctypes.data_as(C.POINTER(capi.Variant)), n))
+        return out[:n]
+
+    def alleles(self):
+        """every insertion and deletion allele with its count, in key order (a test hook): a structured array of VARIANT_ALLELE_DTYPE"""
+        n = lib().flx_variants_num_alleles(self.h)
+        out = np.zeros(max(1, n), dtype=VARIANT_ALLELE_DTYPE)
+        check(lib().flx_variants_copy_alleles(self.h, out.ctypes.data_as(C.POINTER(capi.VariantAllele)), n))
+        return out[:n]
+
+
+def variants_host(text, lengths, records, cigar_words, reads, options=None):
+    """the rule alone on the host (flx_variants_host): text and lengths as errprof_host takes them. Returns (rows, alleles): two
+    structured arrays (VARIANT_DTYPE, VARIANT_ALLELE_DTYPE)."""
+    concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+    lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+    if int(lens.sum()) != len(concat):
+        raise FloxerError("variants_host: the lengths do not sum to the text's length")
+    rec, words = _records_and_words(records, cigar_words)
+    pool, offs, n = _pool_and_offsets(reads)
+    opt = C.byref(options) if options is not None else None
+    need = [C.c_uint64(0), C.c_uint64(0)]
+
+    def call(rows, alleles):
+        return lib().flx_variants_host(ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p),
+                                       len(words), ptr(pool, u8p), ptr(offs, u64p), n,
+                                       rows.ctypes.data_as(C.POINTER(capi.Variant)) if rows is not None else None, C.byref(need[0]),
+                                       alleles.ctypes.data_as(C.POINTER(capi.VariantAllele)) if alleles is not None else None, C.byref(need[1]))
+
+    rc = call(None, None)
+    if rc not in (0, -3):                                               # (FLX_ERR_CAPACITY: need holds the sizes)
+        check(rc)
+    rows = np.zeros(max(1, need[0].value), dtype=VARIANT_DTYPE)
+    alleles = np.zeros(max(1, need[1].value), dtype=VARIANT_ALLELE_DTYPE)
+    check(call(rows, alleles))
+    return rows[: need[0].value], alleles[: need[1].value]
+
+
 # ------------------------------------------------------------------------------------------------ structural-variant signatures
 SV_SIGNATURE_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("res", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a", "<u4"), ("q", "<u4")])
 SV_CLUSTER_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("support", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a_min", "<u4"),

@@ -199,6 +199,23 @@ class ConsensusAllele(C.Structure):
     _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("length", C.c_uint32), ("count", C.c_uint32), ("letters", C.c_uint64)]
 
 
+class VariantsOptions(C.Structure):
+    _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("min_depth", C.c_uint32), ("min_qual", C.c_uint32), ("max_del", C.c_uint32),
+                ("cost_match", C.c_uint32), ("cost_mismatch", C.c_uint32), ("cost_het", C.c_uint32), ("prior_het", C.c_uint32), ("prior_hom", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class Variant(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("kind", C.c_uint32), ("ref_rank", C.c_uint32), ("alt_rank", C.c_uint32),
+                ("length", C.c_uint32), ("ref_count", C.c_uint32), ("alt_count", C.c_uint32), ("cov", C.c_uint32), ("gt", C.c_uint32), ("gq", C.c_uint32),
+                ("qual", C.c_uint32), ("pl", C.c_uint32 * 3), ("reserved", C.c_uint32), ("letters", C.c_uint64)]
+
+
+class VariantAllele(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("kind", C.c_uint32), ("length", C.c_uint32), ("count", C.c_uint32),
+                ("reserved", C.c_uint32), ("letters", C.c_uint64)]
+
+
 # flx_errprof_table: its sections in their fixed order, u64 each
 ERRPROF_SECTIONS = (("PAIR_EQ", 36), ("PAIR_X", 36), ("INS_LEN", 64), ("DEL_LEN", 64), ("INS_LETTER", 6), ("DEL_LETTER", 6), ("HP_DEL", 34), ("HP_INS", 34),
                     ("POS_MATCH", 100), ("POS_MISMATCH", 100), ("POS_INS", 100), ("POS_CLIP", 100), ("POS_DEL", 100), ("EQ_RUN", 256), ("IDENTITY", 101),
@@ -323,6 +340,9 @@ EXPORTED = [
     "flx_consensus_add_run_resident", "flx_consensus_finish", "flx_consensus_num_letters", "flx_consensus_copy_letters",
     "flx_consensus_num_changes", "flx_consensus_copy_changes", "flx_consensus_num_alleles", "flx_consensus_copy_alleles",
     "flx_consensus_geometry", "flx_consensus_host",
+    "flx_variants_create", "flx_variants_create_for_text", "flx_variants_free", "flx_variants_add_records", "flx_variants_add_run",
+    "flx_variants_add_run_resident", "flx_variants_finish", "flx_variants_num_rows", "flx_variants_copy_rows", "flx_variants_num_alleles",
+    "flx_variants_copy_alleles", "flx_variants_geometry", "flx_variants_genotype", "flx_variants_host",
     "flx_grid_caps",
 ]
 
@@ -551,6 +571,24 @@ def lib():
     L.flx_consensus_geometry.argtypes = [u32p]
     L.flx_consensus_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(ConsensusOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64,
                                      u64p, C.c_char_p, u64p, C.POINTER(ConsensusChange), u64p, C.POINTER(ConsensusAllele), u64p]
+    L.flx_variants_create.argtypes = [C.c_void_p, C.POINTER(VariantsOptions), C.POINTER(C.c_void_p)]
+    L.flx_variants_create_for_text.argtypes = [C.c_int, u8p, u64p, C.c_uint32, C.POINTER(VariantsOptions), C.POINTER(C.c_void_p)]
+    L.flx_variants_free.restype = None
+    L.flx_variants_free.argtypes = [C.c_void_p]
+    L.flx_variants_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64]
+    L.flx_variants_add_run.argtypes = [C.c_void_p, C.c_void_p, u8p, u64p, C.c_uint64]
+    L.flx_variants_add_run_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flx_variants_finish.argtypes = [C.c_void_p]
+    L.flx_variants_num_rows.restype = C.c_uint64
+    L.flx_variants_num_rows.argtypes = [C.c_void_p]
+    L.flx_variants_copy_rows.argtypes = [C.c_void_p, C.POINTER(Variant), C.c_uint64]
+    L.flx_variants_num_alleles.restype = C.c_uint64
+    L.flx_variants_num_alleles.argtypes = [C.c_void_p]
+    L.flx_variants_copy_alleles.argtypes = [C.c_void_p, C.POINTER(VariantAllele), C.c_uint64]
+    L.flx_variants_geometry.argtypes = [u32p]
+    L.flx_variants_genotype.argtypes = [C.POINTER(VariantsOptions), C.c_uint64, C.c_uint64, C.c_uint64, u32p]
+    L.flx_variants_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(VariantsOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64,
+                                    C.POINTER(Variant), u64p, C.POINTER(VariantAllele), u64p]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

@@ -1025,6 +1025,78 @@ int  flx_consensus_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_len
                         const uint64_t* read_offsets, uint64_t n_reads, uint64_t* letter_offsets, char* letters, uint64_t* n_letters,
                         flx_consensus_change* changes, uint64_t* n_changes, flx_consensus_allele* alleles, uint64_t* n_alleles);
 
+/* ------------------------------------------------------------------------------------------------ diploid small-variant calls
+ * Not floxer's, and the step behind the consensus: which small variants the sample carries and in which genotype, as rows a VCF is
+ * written from (the tool floxer_variants does that). A variants object holds pileup's seven u32 planes plus one more over the
+ * concatenation of the sequences (32 bytes per reference base) plus one 16-byte key per insertion or deletion event, and reads the
+ * reference text in HBM. The rule (floxer_amd/csrc/flx_variants.hpp), integer arithmetic throughout:
+ *   - which records count, what is refused and the seven sums: pileup's, with count_secondary and min_mapq;
+ *   - every I word and every D word of a counted record is an event. Its anchor a is the position of the record's preceding
+ *     reference-consuming column. An I word is an allele when such a column precedes it, its length is 1..32 and all its letters of the
+ *     oriented sequence have rank 1..4; a D word when such a column precedes it and its length is 1..max_del (0 takes 50, range
+ *     1..2^28 - 1; longer deletions are the structural-variant object's business); everything else is dropped. Equal (anchor, kind,
+ *     length, letters) are one allele with a count, in the order deletions before insertions, shorter first, then letters; events(a)
+ *     is the sum of the counts at a, the winner the allele with the largest count, ties to the smaller key;
+ *   - costs in centi-phred (-1000 log10 of a probability): cost_match m (a read shows the allele of a homozygous genotype),
+ *     cost_mismatch x (anything else), cost_het h (either allele of a heterozygous genotype), prior_het and prior_hom (the priors of
+ *     0/1 and 1/1). 0 takes 36 / 1574 / 325 / 3000 / 3301, the values for a per-read error of 0.08 and a heterozygosity of 0.001:
+ *     conventions of this project, fitted to nothing. The library never computes a logarithm. Refused: m >= h, h >= x (the model would
+ *     be degenerate), any cost above 2^20 (the sums stay inside 64 bits);
+ *   - the SNV candidate at p, only where the text's rank R is 1..4: cov = DEPTH + DEL, n[r] as the consensus has it (the = columns
+ *     credited to R), alt the r != R with the largest n[r], ties to the smallest rank, none when that count is 0; ref_n = n[R],
+ *     alt_n = n[alt], oth = cov - ref_n - alt_n;
+ *   - the indel candidate at an anchor a with an allele: cov = DEPTH[a] + DEL[a], alt_n the winner's count, oth = events(a) - alt_n,
+ *     ref_n = cov - events(a), saturating at 0 (a record that ends exactly on a counts towards ref: a known over-count);
+ *   - the genotype, for both: L_RR = ref_n m + (alt_n + oth) x, L_RA = (ref_n + alt_n) h + oth x, L_AA = alt_n m + (ref_n + oth) x;
+ *     Q_RR = L_RR, Q_RA = L_RA + prior_het, Q_AA = L_AA + prior_hom; the genotype is the smallest Q, ties in the order RR, RA, AA. A row
+ *     is written iff the genotype is not RR, cov >= min_depth (0 takes 4) and qual = Q_RR - min(Q_RA, Q_AA) >= min_qual (centi-phred, 0
+ *     takes 2000). gq = (the second smallest Q - the smallest) / 100, at most 99; pl[g] = (L_g - min L) / 100; qual and pl saturate at
+ *     2^32 - 1, as do ref_count, alt_count and cov;
+ *   - the rows, in position order, the SNV row in front of the indel row of the same position (the anchor for indels): kind 0 SNV, 1
+ *     DEL, 2 INS; ref_rank the text's rank at the position; alt_rank the called rank for an SNV and 0 otherwise; length 1 for an SNV;
+ *     gt 1 = 0/1, 2 = 1/1; letters the inserted letters as the consensus packs them, 0 otherwise; reserved 0. Biallelic: one SNV and
+ *     one indel row per position at most. An SNV inside a called deletion is written independently: there is no * allele. No strand
+ *     bias, no base qualities. The alleles (a test hook) in key order.
+ * Create, add, finish, copy, the lifetime, the refusals and the profile switch (FLX_VARIANTS_PROFILE) are the consensus object's:
+ * flx_variants_create reads the context's text and counts as a live object of the context (flx_ctx_destroy refuses until it is freed);
+ * adds may come from several host threads; a refused add leaves the object as it was; the keys grow by doubling up to 2^32 - 1 events,
+ * a budget that insertion and deletion events share (more: FLX_ERR_CAPACITY); flx_variants_finish is final; 2^32 rows or more:
+ * FLX_ERR_CAPACITY and no result. flx_variants_geometry (a test hook): out[0] the grid cap of variants_indel_keys in blocks, out[1] its
+ * waves per block, out[2] the longest insertion, out[3] the default max_del. flx_variants_host: the rule alone on the host, no device,
+ * the same refusals; each n_* holds the capacity on entry and the need on return (FLX_ERR_CAPACITY when one is too small; nothing is
+ * written then but the needs). flx_variants_genotype (a test hook): the genotype of one candidate under the options' costs, counts
+ * below 2^34 each: out = gt (0 = 0/0), gq, qual, pl[0..2], then 1 if a row would be written with cov = ref_n + alt_n + oth, then 0. */
+typedef struct flx_variants flx_variants;
+typedef struct flx_variants_options {
+    uint32_t count_secondary, min_mapq, min_depth, min_qual, max_del, cost_match, cost_mismatch, cost_het, prior_het, prior_hom;
+    uint32_t reserved[2];
+} flx_variants_options;
+typedef struct flx_variant {
+    int32_t reference_id;
+    uint32_t position /* 0-based */, kind, ref_rank, alt_rank, length, ref_count, alt_count, cov, gt, gq, qual, pl[3], reserved;
+    uint64_t letters;
+} flx_variant;
+typedef struct flx_variant_allele { int32_t reference_id; uint32_t position /* the anchor, 0-based */, kind, length, count, reserved; uint64_t letters; } flx_variant_allele;
+int  flx_variants_create(flx_ctx* ctx, const flx_variants_options* o, flx_variants** out);
+int  flx_variants_create_for_text(int hip_device, const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs,
+                                  const flx_variants_options* o, flx_variants** out);
+void flx_variants_free(flx_variants* p);
+int  flx_variants_add_records(flx_variants* p, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                              const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_variants_add_run(flx_variants* p, const flx_run* run, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_variants_add_run_resident(flx_variants* p, const flx_run* run, const flx_reads* reads);
+int  flx_variants_finish(flx_variants* p);
+uint64_t flx_variants_num_rows(const flx_variants* p);
+int  flx_variants_copy_rows(const flx_variants* p, flx_variant* out, uint64_t capacity);
+uint64_t flx_variants_num_alleles(const flx_variants* p);
+int  flx_variants_copy_alleles(const flx_variants* p, flx_variant_allele* out, uint64_t capacity);
+int  flx_variants_geometry(uint32_t out[4]);
+int  flx_variants_genotype(const flx_variants_options* o, uint64_t ref_n, uint64_t alt_n, uint64_t oth, uint32_t out[8]);
+int  flx_variants_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs, const flx_variants_options* o,
+                       const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words, const uint8_t* read_pool,
+                       const uint64_t* read_offsets, uint64_t n_reads, flx_variant* rows, uint64_t* n_rows, flx_variant_allele* alleles,
+                       uint64_t* n_alleles);
+
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
  * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
