@@ -1710,6 +1710,140 @@ def variants_host(text, lengths, records, cigar_words, reads, options=None):
     return rows[: need[0].value], alleles[: need[1].value]
 
 
+# ------------------------------------------------------------------------------------------------ read-backed phasing
+PHASE_SITE_DTYPE = np.dtype([("ref", "<i4"), ("pos", "<u4"), ("kind", "<u4"), ("alt_rank", "<u4"), ("length", "<u4"), ("reserved", "<u4"), ("letters", "<u8")])
+PHASE_RESULT_DTYPE = np.dtype([("phase_set", "<u4"), ("phased", "<u4"), ("phase", "<u4"), ("cis", "<u4"), ("trans", "<u4"), ("keep", "<u4"), ("swap", "<u4"), ("reserved", "<u4")])
+PHASE_TAG_DTYPE = np.dtype([("add", "<u4"), ("read", "<u4"), ("hap", "<u4"), ("phase_set", "<u4"), ("h1", "<u4"), ("h2", "<u4"), ("n_slots", "<u4"), ("reserved", "<u4")])
+
+
+def phase_options(count_secondary=False, min_mapq=0, min_link=0, min_margin=0, refine_rounds=0, skip_refine=False):
+    """flx_phase_options: count_secondary and min_mapq as pileup_options has them; neighbouring sites are joined when the records for
+    and against differ by at least min_link; a record is tagged when its observations for one haplotype lead by at least min_margin;
+    refine_rounds rounds of votes (at most 8), none with skip_refine. 0 takes the defaults 2 / 1 / 1, conventions of this project that
+    are fitted to nothing"""
+    o = capi.PhaseOptions()
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq, o.min_link, o.min_margin, o.refine_rounds = int(min_mapq), int(min_link), int(min_margin), int(refine_rounds)
+    o.skip_refine = 1 if skip_refine else 0
+    return o
+
+
+def phase_geometry():
+    """(grid cap of phase_observe in blocks, its waves per block, the scan tile, the longest insertion) (flx_phase_geometry, a test hook)"""
+    out = np.zeros(4, dtype=np.uint32)
+    check(lib().flx_phase_geometry(ptr(out, u32p)))
+    return tuple(int(x) for x in out)
+
+
+def phase_sites_from_rows(rows):
+    """the sites of a variants result: its heterozygous rows (gt == 1), in their order, as an array of PHASE_SITE_DTYPE"""
+    rows = np.asarray(rows, dtype=VARIANT_DTYPE)
+    het = rows[rows["gt"] == 1]
+    out = np.zeros(len(het), dtype=PHASE_SITE_DTYPE)
+    for name in ("ref", "pos", "kind", "alt_rank", "length", "letters"):
+        out[name] = het[name]
+    return out
+
+
+def _phase_sites(sites):
+    return np.ascontiguousarray(np.asarray(sites, dtype=PHASE_SITE_DTYPE))
+
+
+class phase:
+    """Read-backed phasing of the heterozygous `sites` (an array of PHASE_SITE_DTYPE, phase_sites_from_rows makes one) by the records
+    added: one observation per record and site in its span, links between neighbouring sites, phase sets, haplotype tags, rounds of
+    votes. For a context (ctx), or over `text` on `device`: a list of rank arrays, or their concatenation with `lengths`. finish once,
+    then read results() and tags(). One device: there is no absorb. Not floxer's. Adds may come from several threads."""
+
+    def __init__(self, ctx=None, options=None, sites=None, text=None, lengths=None, device=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        sites = _phase_sites(sites if sites is not None else [])
+        sp = sites.ctypes.data_as(C.POINTER(capi.PhaseSite))
+        if ctx is not None:
+            check(lib().flx_phase_create(ctx.h, opt, sp, len(sites), C.byref(self.h)))
+        else:
+            if text is None:
+                raise FloxerError("phase needs a context or a reference text")
+            concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+            lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+            if int(lens.sum()) != len(concat):
+                raise FloxerError("phase: the lengths do not sum to the text's length")
+            check(lib().flx_phase_create_for_text(int(device), ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, sp, len(sites), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_phase_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run, reads):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed;
+        reads: the batch the run was made from: a list of rank arrays, (pool, offsets), or a resident_reads batch (with a raw handle
+        only). With min_mapq a run made without output_options(mapq=True) is refused."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("phase.add: min_mapq needs a run made with output_options(mapq=True)")
+            if isinstance(reads, resident_reads):
+                raise FloxerError("phase.add: a RunResult needs the reads in host memory; a resident batch goes with a raw run handle")
+            return self.add_records(run.raw, run.cigars, reads)
+        if isinstance(reads, resident_reads):
+            check(lib().flx_phase_add_run_resident(self.h, run, reads.h))
+        else:
+            pool, offs, n = _pool_and_offsets(reads)
+            check(lib().flx_phase_add_run(self.h, run, ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def add_records(self, records, cigar_words, reads):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to;
+        reads: a list of rank arrays or (pool, offsets), indexed by the records' `read`"""
+        rec, words = _records_and_words(records, cigar_words)
+        pool, offs, n = _pool_and_offsets(reads)
+        check(lib().flx_phase_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(pool, u8p), ptr(offs, u64p), n))
+
+    def finish(self):
+        check(lib().flx_phase_finish(self.h))
+
+    def results(self):
+        """one row per site, in the sites' order: a structured array of PHASE_RESULT_DTYPE"""
+        n = lib().flx_phase_num_sites(self.h)
+        out = np.zeros(max(1, n), dtype=PHASE_RESULT_DTYPE)
+        check(lib().flx_phase_copy_results(self.h, out.ctypes.data_as(C.POINTER(capi.PhaseResult)), n))
+        return out[:n]
+
+    def tags(self):
+        """one row per counted record, in counting order: a structured array of PHASE_TAG_DTYPE"""
+        n = lib().flx_phase_num_tags(self.h)
+        out = np.zeros(max(1, n), dtype=PHASE_TAG_DTYPE)
+        check(lib().flx_phase_copy_tags(self.h, out.ctypes.data_as(C.POINTER(capi.PhaseTag)), n))
+        return out[:n]
+
+
+def phase_host(text, lengths, sites, records, cigar_words, reads, options=None):
+    """the rule alone on the host (flx_phase_host): text and lengths as variants_host takes them. Returns (results, tags): two
+    structured arrays (PHASE_RESULT_DTYPE, PHASE_TAG_DTYPE)."""
+    concat, lens = (as_u8(text), list(lengths)) if lengths is not None else _concatenated_text(text)
+    lens = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+    if int(lens.sum()) != len(concat):
+        raise FloxerError("phase_host: the lengths do not sum to the text's length")
+    sites = _phase_sites(sites)
+    rec, words = _records_and_words(records, cigar_words)
+    pool, offs, n = _pool_and_offsets(reads)
+    opt = C.byref(options) if options is not None else None
+    need = C.c_uint64(len(rec))
+    results = np.zeros(max(1, len(sites)), dtype=PHASE_RESULT_DTYPE)
+    tags = np.zeros(max(1, len(rec)), dtype=PHASE_TAG_DTYPE)
+    check(lib().flx_phase_host(ptr(concat, u8p), ptr(lens, u64p), len(lens), opt, sites.ctypes.data_as(C.POINTER(capi.PhaseSite)), len(sites),
+                               rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p), len(words), ptr(pool, u8p), ptr(offs, u64p), n,
+                               results.ctypes.data_as(C.POINTER(capi.PhaseResult)), tags.ctypes.data_as(C.POINTER(capi.PhaseTag)), C.byref(need)))
+    return results[: len(sites)], tags[: need.value]
+
+
 # ------------------------------------------------------------------------------------------------ structural-variant signatures
 SV_SIGNATURE_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("res", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a", "<u4"), ("q", "<u4")])
 SV_CLUSTER_DTYPE = np.dtype([("type", "<u4"), ("side_a", "<u4"), ("side_b", "<u4"), ("support", "<u4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("pos_a_min", "<u4"),

@@ -216,6 +216,24 @@ class VariantAllele(C.Structure):
                 ("reserved", C.c_uint32), ("letters", C.c_uint64)]
 
 
+class PhaseOptions(C.Structure):
+    _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("min_link", C.c_uint32), ("min_margin", C.c_uint32), ("refine_rounds", C.c_uint32),
+                ("skip_refine", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PhaseSite(C.Structure):
+    _fields_ = [("reference_id", C.c_int32), ("position", C.c_uint32), ("kind", C.c_uint32), ("alt_rank", C.c_uint32), ("length", C.c_uint32), ("reserved", C.c_uint32),
+                ("letters", C.c_uint64)]
+
+
+class PhaseResult(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("phase_set", "phased", "phase", "cis", "trans", "keep", "swap", "reserved")]
+
+
+class PhaseTag(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("add", "read", "hap", "phase_set", "h1", "h2", "n_slots", "reserved")]
+
+
 # flx_errprof_table: its sections in their fixed order, u64 each
 ERRPROF_SECTIONS = (("PAIR_EQ", 36), ("PAIR_X", 36), ("INS_LEN", 64), ("DEL_LEN", 64), ("INS_LETTER", 6), ("DEL_LETTER", 6), ("HP_DEL", 34), ("HP_INS", 34),
                     ("POS_MATCH", 100), ("POS_MISMATCH", 100), ("POS_INS", 100), ("POS_CLIP", 100), ("POS_DEL", 100), ("EQ_RUN", 256), ("IDENTITY", 101),
@@ -343,6 +361,8 @@ EXPORTED = [
     "flx_variants_create", "flx_variants_create_for_text", "flx_variants_free", "flx_variants_add_records", "flx_variants_add_run",
     "flx_variants_add_run_resident", "flx_variants_finish", "flx_variants_num_rows", "flx_variants_copy_rows", "flx_variants_num_alleles",
     "flx_variants_copy_alleles", "flx_variants_geometry", "flx_variants_genotype", "flx_variants_host",
+    "flx_phase_create", "flx_phase_create_for_text", "flx_phase_free", "flx_phase_add_records", "flx_phase_add_run", "flx_phase_add_run_resident",
+    "flx_phase_finish", "flx_phase_num_sites", "flx_phase_copy_results", "flx_phase_num_tags", "flx_phase_copy_tags", "flx_phase_geometry", "flx_phase_host",
     "flx_grid_caps",
 ]
 
@@ -589,6 +609,23 @@ def lib():
     L.flx_variants_genotype.argtypes = [C.POINTER(VariantsOptions), C.c_uint64, C.c_uint64, C.c_uint64, u32p]
     L.flx_variants_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(VariantsOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64,
                                     C.POINTER(Variant), u64p, C.POINTER(VariantAllele), u64p]
+    L.flx_phase_create.argtypes = [C.c_void_p, C.POINTER(PhaseOptions), C.POINTER(PhaseSite), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.flx_phase_create_for_text.argtypes = [C.c_int, u8p, u64p, C.c_uint32, C.POINTER(PhaseOptions), C.POINTER(PhaseSite), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.flx_phase_free.restype = None
+    L.flx_phase_free.argtypes = [C.c_void_p]
+    L.flx_phase_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p, C.c_uint64]
+    L.flx_phase_add_run.argtypes = [C.c_void_p, C.c_void_p, u8p, u64p, C.c_uint64]
+    L.flx_phase_add_run_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.flx_phase_finish.argtypes = [C.c_void_p]
+    L.flx_phase_num_sites.restype = C.c_uint64
+    L.flx_phase_num_sites.argtypes = [C.c_void_p]
+    L.flx_phase_copy_results.argtypes = [C.c_void_p, C.POINTER(PhaseResult), C.c_uint64]
+    L.flx_phase_num_tags.restype = C.c_uint64
+    L.flx_phase_num_tags.argtypes = [C.c_void_p]
+    L.flx_phase_copy_tags.argtypes = [C.c_void_p, C.POINTER(PhaseTag), C.c_uint64]
+    L.flx_phase_geometry.argtypes = [u32p]
+    L.flx_phase_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(PhaseOptions), C.POINTER(PhaseSite), C.c_uint64, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p,
+                                 C.c_uint64, C.POINTER(PhaseResult), C.POINTER(PhaseTag), u64p]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

@@ -1097,6 +1097,68 @@ int  flx_variants_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens
                        const uint64_t* read_offsets, uint64_t n_reads, flx_variant* rows, uint64_t* n_rows, flx_variant_allele* alleles,
                        uint64_t* n_alleles);
 
+/* ------------------------------------------------------------------------------------------------ read-backed phasing
+ * Not floxer's, and the step behind the variant calls: which of the heterozygous calls lie on the same chromosome copy, and which
+ * records come from which copy (the tool floxer_phase writes both, as a phased VCF and a table of haplotype tags). A phase object
+ * holds its sites, one byte per (counted record, site in its span) and 32 bytes per counted record in HBM; it never reads the
+ * reference text on the device. The rule (floxer_amd/csrc/flx_phase.hpp), integer arithmetic throughout:
+ *   - the sites are given at create time, strictly increasing by (reference_id, position, kind): kind 0 SNV, 1 DEL, 2 INS as
+ *     flx_variant has them, position the SNV's position or the indel's anchor, letters as the consensus packs them (0 for an SNV or a
+ *     DEL). Refused: an SNV whose text rank is outside 1..4 or equals alt_rank, or whose alt_rank is outside 1..4; a DEL that runs past
+ *     its sequence; an INS of more than 32 letters or with bits behind its length; letters on an SNV or a DEL; a non-zero reserved;
+ *     sites out of order (FLX_ERR_INVALID); more than 2^32 - 2 sites (FLX_ERR_CAPACITY);
+ *   - which records count and what is refused: pileup's, with count_secondary and min_mapq. The unit of phasing is the counted record,
+ *     not the read;
+ *   - a counted record has one slot for every site whose anchor lies inside its reference span, and one observation per slot: REF 0,
+ *     ALT 1, NONE 2. An SNV: the record's column there is an = word: REF; an X word whose oriented letter is alt_rank: ALT; anything
+ *     else NONE. A DEL or INS with anchor a: E is the run of I and D words directly behind the column at a (empty unless a is the last
+ *     column of its word); a word of E whose allele key (flx_variants' key, deletions of any length) is the site's: ALT; otherwise, E
+ *     empty, the column = or X and a + 1 inside the span: REF; otherwise NONE;
+ *   - links: for neighbouring sites i and i + 1, over the records that observe both with REF or ALT, cis(i) counts equal alleles and
+ *     trans(i) unequal ones; connected(i) iff both lie in one sequence and |cis - trans| >= min_link (0 takes 2); a phase set is a
+ *     maximal run of connected neighbours, its id the index of its first site; p(first) = 0, p(i + 1) = p(i) ^ (trans(i) > cis(i));
+ *     a set of one site is unphased; p = 0 puts ALT on haplotype 1 (1|0), p = 1 on haplotype 2 (0|1);
+ *   - tags: a record belongs to the phase set in which it has the most REF/ALT observations of phased sites (ties to the first; none:
+ *     hap 0, phase_set 2^32 - 1); there h1 counts allele ^ p == 1, h2 the rest; hap 1 if h1 - h2 >= min_margin, 2 if h2 - h1 >=
+ *     min_margin (0 takes 1), else 0;
+ *   - refinement, refine_rounds times (0 takes 1, at most 8, skip_refine: none): every tagged record votes at the REF/ALT slots of its
+ *     set, keep(i) for x == (hap == 1), swap(i) otherwise; p(i) flips where swap > keep; the tags are made again. keep and swap as
+ *     reported are the last round's, before its flips.
+ * Known limits: links join neighbouring sites only, so one site of noise (a false 0/1) splits a set in two; no base qualities, no
+ * read-pair or supplementary linkage; the defaults 2 / 1 / 1 are conventions of this project, fitted to nothing.
+ * Create, add, finish, copy, the lifetime, the refusals and the profile switch (FLX_PHASE_PROFILE) are the variants object's:
+ * flx_phase_create counts as a live object of the context (flx_ctx_destroy refuses until it is freed); adds may come from several host
+ * threads; a refused add leaves the object as it was; observations and records grow by doubling, up to 2^32 - 1 slots in all (more:
+ * FLX_ERR_CAPACITY); flx_phase_finish is final. Results: one row per site. Tags: one per counted record in counting order (adds in
+ * the order they took the object's lock, a run's pieces in flx_run_copy's order, records in order); add is the 0-based serial of the
+ * add call, read the record's read_index. flx_phase_geometry (a test hook): out[0] the grid cap of phase_observe in blocks, out[1] its
+ * waves per block, out[2] the scan tile, out[3] the longest insertion. flx_phase_host: the rule alone on the host, no device, the same
+ * refusals; results takes n_sites rows; *n_tags holds the capacity on entry and the need on return (FLX_ERR_CAPACITY when too small;
+ * nothing else is written then). */
+typedef struct flx_phase flx_phase;
+typedef struct flx_phase_options { uint32_t count_secondary, min_mapq, min_link, min_margin, refine_rounds, skip_refine; uint32_t reserved[2]; } flx_phase_options;
+typedef struct flx_phase_site { int32_t reference_id; uint32_t position /* 0-based */, kind, alt_rank, length, reserved; uint64_t letters; } flx_phase_site;
+typedef struct flx_phase_result { uint32_t phase_set, phased, phase, cis, trans, keep, swap, reserved; } flx_phase_result;
+typedef struct flx_phase_tag { uint32_t add, read, hap, phase_set, h1, h2, n_slots, reserved; } flx_phase_tag;
+int  flx_phase_create(flx_ctx* ctx, const flx_phase_options* o, const flx_phase_site* sites, uint64_t n_sites, flx_phase** out);
+int  flx_phase_create_for_text(int hip_device, const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs,
+                               const flx_phase_options* o, const flx_phase_site* sites, uint64_t n_sites, flx_phase** out);
+void flx_phase_free(flx_phase* p);
+int  flx_phase_add_records(flx_phase* p, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words,
+                           const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_phase_add_run(flx_phase* p, const flx_run* run, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads);
+int  flx_phase_add_run_resident(flx_phase* p, const flx_run* run, const flx_reads* reads);
+int  flx_phase_finish(flx_phase* p);
+uint64_t flx_phase_num_sites(const flx_phase* p);
+int  flx_phase_copy_results(const flx_phase* p, flx_phase_result* out, uint64_t capacity);
+uint64_t flx_phase_num_tags(const flx_phase* p);
+int  flx_phase_copy_tags(const flx_phase* p, flx_phase_tag* out, uint64_t capacity);
+int  flx_phase_geometry(uint32_t out[4]);
+int  flx_phase_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, uint32_t n_refs, const flx_phase_options* o,
+                    const flx_phase_site* sites, uint64_t n_sites, const flx_record* records, uint64_t n, const uint32_t* cigar_words,
+                    uint64_t n_words, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads, flx_phase_result* results,
+                    flx_phase_tag* tags, uint64_t* n_tags);
+
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
  * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
