@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "flx_internal.hpp"
+#include "flx_myers.hpp"
 #include "flx_wave.hpp"
 
 namespace flx {
@@ -82,6 +83,9 @@ template <int W, bool TRACE>
 __device__ __forceinline__ void ed_block_body(const u8* __restrict__ text, const u64* __restrict__ peq, const DevAlignJob* __restrict__ jobs, u32 n_jobs,
                                               u32 log2_r, DevAlignOut* __restrict__ out, u32 blk, u64* __restrict__ lds_eq,
                                               u64* __restrict__ trace, u16* __restrict__ lastrow, u32 queue, u32* __restrict__ err) {
+    // The column step (flx_myers.hpp) in its three-input form, but for the four-word trace kernel: at its 168 registers (three waves per
+    // SIMD) that form spills 96 bytes per lane, the plain 64-bit one does not (profiles/myers_bitop3_resources.txt).
+    constexpr bool kPlainStep = TRACE && W == 4;
     u32 const lane = lane_id();
     u32 const R = 1u << log2_r;
     u32 const p = lane & (R - 1u);
@@ -225,7 +229,8 @@ __device__ __forceinline__ void ed_block_body(const u8* __restrict__ text, const
             bool const last = g == Lg - 1;
             uint4 tq = tq_pre;
             if (pre_b != b) __builtin_memcpy(&tq, ref + 16 * b, 16);
-            u32 const quad[4] = {tq.x, tq.y, tq.z, tq.w};
+            u32 quad[4] = {tq.x, tq.y, tq.z, tq.w};
+            if (n - 16 * b < 16) myers_patch_symbols(quad, n - 16 * b);      // (the window ends in this block: symbol 6 in the columns past it)
             u32 cw = 0;
             u64 const slot = ((u64)T * R + p) * W;        // this lane's words at this block-step
             flush();
@@ -255,7 +260,8 @@ __device__ __forceinline__ void ed_block_body(const u8* __restrict__ text, const
                 u32 cwi = cw_in;
                 int bb = b;
                 asm volatile("" : "+v"(qv[0]), "+v"(qv[1]), "+v"(qv[2]), "+v"(qv[3]), "+v"(cwi), "+v"(bb));
-                u32 acc = 0;
+                u32 acc = 0, acc_hn = 0;                  // (the form that does not track: the hp bits in acc, the hn bits in acc_hn)
+                if (TRACE) cbits[0] = cwi;                // (what enters the first word from above is the incoming carry word itself)
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
                     __builtin_amdgcn_sched_barrier(0);    // (nothing moves across four columns: the form without comparisons would have all sixteen columns' loads in flight)
@@ -263,42 +269,38 @@ __device__ __forceinline__ void ed_block_body(const u8* __restrict__ text, const
                     for (int i = 0; i < 4; ++i) {
                         int const j = 4 * qd + i;
                         int const c = 16 * bb + j;
-                        u32 sym = (qv[qd] >> (8 * i)) & 0xFFu;
-                        sym = c < n ? sym : 6u;
-                        u64 c_hp = (cwi >> (2 * j)) & 1u, c_hn = (cwi >> (2 * j + 1)) & 1u;
+                        u32 const sym = (qv[qd] >> (8 * i)) & 0xFFu;
+                        u32 c_hp = (cwi >> (2 * j)) & 1u, c_hn = (cwi >> (2 * j + 1)) & 1u;
                         const u64* __restrict__ eqp = &lds_eq[(sym * 64u + lane) * W];
                         u64 hp_last = 0, hn_last = 0;
 #pragma unroll
                         for (int w = 0; w < W; ++w) {
-                            if (TRACE) cbits[w] |= ((u32)c_hp | ((u32)c_hn << 1)) << (2 * j);
-                            u64 const eq = eqp[w];
-                            u64 const pv = vp[w], mv = vn[w];
-                            u64 const x = eq | mv;
-                            u64 const tt = pv + (x & pv) + c_hn;
-                            u64 const d0 = (tt ^ pv) | x;
-                            u64 const hn = pv & d0;
-                            u64 const hp = mv | ~(pv | d0);
-                            u64 const xh = (hp << 1) | c_hp;
-                            vn[w] = xh & d0;
-                            vp[w] = (hn << 1) | ~(xh | d0) | c_hn;
-                            if (w + 1 < W || TRACK) { c_hp = hp >> 63; c_hn = hn >> 63; }
+                            if (TRACE && w > 0) cbits[w] |= (c_hp | (c_hn << 1)) << (2 * j);
+                            u64 hp, hn;
+                            if constexpr (kPlainStep) myers_step_u64(eqp[w], vp[w], vn[w], c_hp, c_hn, hp, hn);
+                            else myers_step(eqp[w], vp[w], vn[w], c_hp, c_hn, hp, hn);
+                            if (w + 1 < W || TRACK) { c_hp = (u32)(hp >> 63); c_hn = (u32)(hn >> 63); }
                             if (w + 1 == W) { hp_last = hp; hn_last = hn; }
                         }
                         if (TRACK) {
-                            acc |= ((u32)c_hp | ((u32)c_hn << 1)) << (2 * j);
-                            bot += (int)(u32)c_hp - (int)(u32)c_hn;       // the group's last row is its last word's bit 63
+                            acc |= (c_hp | (c_hn << 1)) << (2 * j);
+                            bot += (int)c_hp - (int)c_hn;       // the group's last row is its last word's bit 63
                             if (last && c < n && bot <= best) { best = bot; best_col = c + 1; }
                             if (TRACE && c < n) {
                                 u32 const v16 = (u32)min(bot, 0xFFFF);
                                 rowv[j >> 1] = (j & 1) ? (rowv[j >> 1] & 0xFFFFu) | (v16 << 16) : (rowv[j >> 1] & 0xFFFF0000u) | v16;
                             }
                         } else {
-                            // (column j's pair ends at bits 2j, 2j + 1 once the fifteen columns after it have pushed it down)
-                            acc = (acc >> 2) | (((u32)(hp_last >> 32) >> 1) & 0x40000000u) | ((u32)(hn_last >> 32) & 0x80000000u);
+                            // (one instruction per carry bit; the carry word's layout is put together behind the block: myers_carry_word)
+                            acc = funnel_up1(acc, (u32)(hp_last >> 32));
+                            acc_hn = funnel_up1(acc_hn, (u32)(hn_last >> 32));
                         }
                     }
                 }
-                if (!TRACK) bot += (int)__popc(acc & 0x55555555u) - (int)__popc(acc & 0xAAAAAAAAu);
+                if (!TRACK) {
+                    bot += (int)__popc(acc) - (int)__popc(acc_hn);
+                    acc = myers_carry_word(acc, acc_hn);
+                }
                 return acc;
             };
             cw = __any(last) ? block16(std::true_type{}) : block16(std::false_type{});
@@ -561,7 +563,7 @@ __global__ void __launch_bounds__(64) ed_traceback_wave_kernel(const u8* __restr
                                                                u32 n_jobs, u32* __restrict__ cigar, DevTraceOut* __restrict__ out) {
     __shared__ ulonglong2 win[64 * 17];              // [window * 17 + column % 16] = {hp, vp} of the window's word after that column (17: no bank conflicts)
     __shared__ u32 win_valid[64];                    // non-zero: the window was computed
-    __shared__ u64 eqm[TBW_WORDS][6];                // equality masks of the round's words
+    __shared__ u64 eqm[TBW_WORDS][8];                // equality masks of the round's words by symbol (6, 7: past the window, only the padding rows match)
     __shared__ u8 refs[TBW_REF];                     // reference symbols of columns [ref_base, ref_base + TBW_REF)
     u32 const lane = threadIdx.x & 63u;
     __builtin_amdgcn_s_setprio(2);                   // (short launches that hold much LDS go first on a shared SIMD: they leave sooner)
@@ -616,6 +618,30 @@ __global__ void __launch_bounds__(64) ed_traceback_wave_kernel(const u8* __restr
         {
             int const w = gw_top - (int)(lane / TBW_BLOCKS);
             u32 valid = 0;
+            // equality masks of the word, padding rows included: the lane of the word's first window builds them, for the word's eight
+            // windows and for the walk
+            if (w >= 0 && lane % TBW_BLOCKS == 0) {
+                int const rs = 64 * w - pad;
+                u64 const padmask = rs <= -64 ? ~0ull : rs < 0 ? (1ull << (u32)(-rs)) - 1ull : 0ull;
+                i64 const off = (i64)job.q_off + rs;
+#pragma unroll
+                for (u32 sy = 0; sy < 6; ++sy) {
+                    u64 v = 0;
+                    if (rs > -64) {
+                        if (off >= 0) {
+                            u64 const a = (u64)off >> 6;
+                            u32 const sh = (u32)off & 63u;
+                            u64 const lo = peq[a * 6 + sy];
+                            u64 const hi = peq[(a + 1) * 6 + sy];
+                            v = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+                        } else v = peq[sy] << (u32)(-off);
+                    }
+                    eqm[lane / TBW_BLOCKS][sy] = v | padmask;
+                }
+                eqm[lane / TBW_BLOCKS][6] = padmask;
+                eqm[lane / TBW_BLOCKS][7] = padmask;
+            }
+            __syncthreads();
             if (w >= 0) {
                 int const g = w / W, ww = w - g * W, p = g % R;
                 int const b = first_block(w, diag) + (int)(lane % TBW_BLOCKS);
@@ -624,31 +650,6 @@ __global__ void __launch_bounds__(64) ed_traceback_wave_kernel(const u8* __restr
                 int const b_lo = max(0, r0 - k) >> 4;
                 int b_hi = min(n - 1, r1 - 1 + band_hi) >> 4;
                 if (g + 1 < Lg) b_hi = max(b_hi, max(0, r1 - k) >> 4);
-                // equality masks of the word, padding rows included (the lane of the word's first window also keeps them for the walk)
-                u64 eq[6];
-                int const rs = 64 * w - pad;
-                u64 const padmask = rs <= -64 ? ~0ull : rs < 0 ? (1ull << (u32)(-rs)) - 1ull : 0ull;
-                {
-                    i64 const off = (i64)job.q_off + rs;
-#pragma unroll
-                    for (u32 sy = 0; sy < 6; ++sy) {
-                        u64 v = 0;
-                        if (rs > -64) {
-                            if (off >= 0) {
-                                u64 const a = (u64)off >> 6;
-                                u32 const sh = (u32)off & 63u;
-                                u64 const lo = peq[a * 6 + sy];
-                                u64 const hi = peq[(a + 1) * 6 + sy];
-                                v = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-                            } else v = peq[sy] << (u32)(-off);
-                        }
-                        eq[sy] = v | padmask;
-                    }
-                    if (lane % TBW_BLOCKS == 0) {
-#pragma unroll
-                        for (u32 sy = 0; sy < 6; ++sy) eqm[lane / TBW_BLOCKS][sy] = eq[sy];
-                    }
-                }
                 // all 16 columns of the block must be in the symbol cache
                 if (b >= b_lo && b <= b_hi && 16 * b >= ref_base && 16 * b + 16 <= ref_base + (int)TBW_REF) {
                     u64 const slot = ((u64)(b + g + (g / R) * ring_wait) * R + p) * W + ww;
@@ -658,17 +659,9 @@ __global__ void __launch_bounds__(64) ed_traceback_wave_kernel(const u8* __restr
 #pragma unroll 4
                     for (u32 sidx = 0; sidx < 16u; ++sidx) {
                         u32 const cb = (cw >> (2u * sidx)) & 3u;
-                        u64 const c_hp = cb & 1u, c_hn = cb >> 1;
                         u32 const rsym = refs[16 * b + (int)sidx - ref_base] & 7u;
-                        u64 const e = rsym == 0 ? eq[0] : rsym == 1 ? eq[1] : rsym == 2 ? eq[2] : rsym == 3 ? eq[3] : rsym == 4 ? eq[4] : rsym == 5 ? eq[5] : padmask;
-                        u64 const x_ = e | mv;
-                        u64 const sum = pv + (x_ & pv) + c_hn;
-                        u64 const d0 = (sum ^ pv) | x_;
-                        u64 const hn = pv & d0;
-                        u64 const hp = mv | ~(pv | d0);
-                        u64 const xh = (hp << 1) | c_hp;
-                        mv = xh & d0;
-                        pv = (hn << 1) | ~(xh | d0) | c_hn;
+                        u64 hp, hn;
+                        myers_step(eqm[lane / TBW_BLOCKS][rsym], pv, mv, cb & 1u, cb >> 1, hp, hn);
                         ulonglong2 o;
                         o.x = hp;
                         o.y = pv;
