@@ -1968,6 +1968,46 @@ def sv_clusters_host(signatures, options=None):
     return out[: n.value]
 
 
+# ------------------------------------------------------------------------------------------------ structural-variant calls
+SVCALL_ROW_DTYPE = np.dtype([("cluster", "<u4"), ("type", "<u4"), ("ref", "<i4"), ("pos_a_min", "<u4"), ("pos_a_max", "<u4"), ("q_min", "<u4"), ("q_median", "<u4"),
+                             ("q_max", "<u4"), ("alt_n", "<u4"), ("ref_n", "<u4"), ("span_n", "<u4"), ("gt", "<u4"), ("gq", "<u4"), ("qual", "<u4"), ("pl", "<u4", (3,)),
+                             ("pass", "<u4")])
+
+
+def svcall_options(count_secondary=False, min_mapq=0, flank=0, min_depth=0, min_qual=0, cost_match=0, cost_mismatch=0, cost_het=0, prior_het=0, prior_hom=0):
+    """flx_svcall_options: flank: the columns a record must reach on both sides of a cluster to count as spanning it; min_depth: the
+    fewest records (ref_n + alt_n) of a passing row; min_qual: its smallest quality in centi-phred; the five costs of the genotype
+    model in centi-phred, flx_variants' own. 0 takes the defaults 50, 4, 2000 and 36 / 1574 / 325 / 3000 / 3301, conventions of this
+    project that are fitted to nothing. count_secondary: flag-256 records count; min_mapq: a record counts only with at least this
+    mapping quality (the records' `res`, as runs made with output_options(mapq=True) fill it)"""
+    o = capi.SvcallOptions()
+    o.count_secondary = 1 if count_secondary else 0
+    o.min_mapq, o.flank, o.min_depth, o.min_qual = int(min_mapq), int(flank), int(min_depth), int(min_qual)
+    o.cost_match, o.cost_mismatch, o.cost_het, o.prior_het, o.prior_hom = int(cost_match), int(cost_mismatch), int(cost_het), int(prior_het), int(prior_hom)
+    return o
+
+
+def _sv_clusters(clusters):
+    return np.ascontiguousarray(np.asarray(clusters, dtype=SV_CLUSTER_DTYPE))
+
+
+def svcall_host(lengths, records, cigar_words, clusters, options=None):
+    """the rule alone on the host (flx_svcall_host): the rows of the clusters over the records, a structured array of SVCALL_ROW_DTYPE"""
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+    rec, words = _records_and_words(records, cigar_words)
+    cl = _sv_clusters(clusters)
+    opt = C.byref(options) if options is not None else None
+    args = (ptr(lens, u64p) if len(lens) else None, len(lens), opt, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p) if len(words) else None,
+            len(words), cl.ctypes.data_as(C.POINTER(capi.SvCluster)) if len(cl) else None, len(cl))
+    n = C.c_uint64(0)
+    rc = lib().flx_svcall_host(*args, None, C.byref(n))
+    if rc not in (0, -3):                                               # (FLX_ERR_CAPACITY: n holds the need)
+        check(rc)
+    out = np.zeros(max(1, n.value), dtype=SVCALL_ROW_DTYPE)
+    check(lib().flx_svcall_host(*args, out.ctypes.data_as(C.POINTER(capi.SvcallRow)), C.byref(n)))
+    return out[: n.value]
+
+
 # ------------------------------------------------------------------------------------------------ coordinate order of records
 SORT_ENTRY_DTYPE = np.dtype([("ordinal", "<u8"), ("ref", "<i4"), ("pos", "<i4"), ("end", "<u4"), ("flag", "<u4")])
 

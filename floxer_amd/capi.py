@@ -234,6 +234,18 @@ class PhaseTag(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("add", "read", "hap", "phase_set", "h1", "h2", "n_slots", "reserved")]
 
 
+class SvcallOptions(C.Structure):
+    _fields_ = [("count_secondary", C.c_uint32), ("min_mapq", C.c_uint32), ("flank", C.c_uint32), ("min_depth", C.c_uint32), ("min_qual", C.c_uint32),
+                ("cost_match", C.c_uint32), ("cost_mismatch", C.c_uint32), ("cost_het", C.c_uint32), ("prior_het", C.c_uint32), ("prior_hom", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class SvcallRow(C.Structure):
+    _fields_ = [("cluster", C.c_uint32), ("type", C.c_uint32), ("ref", C.c_int32), ("pos_a_min", C.c_uint32), ("pos_a_max", C.c_uint32), ("q_min", C.c_uint32),
+                ("q_median", C.c_uint32), ("q_max", C.c_uint32), ("alt_n", C.c_uint32), ("ref_n", C.c_uint32), ("span_n", C.c_uint32), ("gt", C.c_uint32),
+                ("gq", C.c_uint32), ("qual", C.c_uint32), ("pl", C.c_uint32 * 3), ("pass", C.c_uint32)]
+
+
 # flx_errprof_table: its sections in their fixed order, u64 each
 ERRPROF_SECTIONS = (("PAIR_EQ", 36), ("PAIR_X", 36), ("INS_LEN", 64), ("DEL_LEN", 64), ("INS_LETTER", 6), ("DEL_LETTER", 6), ("HP_DEL", 34), ("HP_INS", 34),
                     ("POS_MATCH", 100), ("POS_MISMATCH", 100), ("POS_INS", 100), ("POS_CLIP", 100), ("POS_DEL", 100), ("EQ_RUN", 256), ("IDENTITY", 101),
@@ -363,6 +375,7 @@ EXPORTED = [
     "flx_variants_copy_alleles", "flx_variants_geometry", "flx_variants_genotype", "flx_variants_host",
     "flx_phase_create", "flx_phase_create_for_text", "flx_phase_free", "flx_phase_add_records", "flx_phase_add_run", "flx_phase_add_run_resident",
     "flx_phase_finish", "flx_phase_num_sites", "flx_phase_copy_results", "flx_phase_num_tags", "flx_phase_copy_tags", "flx_phase_geometry", "flx_phase_host",
+    "flx_svcall_host",
     "flx_grid_caps",
 ]
 
@@ -626,6 +639,8 @@ def lib():
     L.flx_phase_geometry.argtypes = [u32p]
     L.flx_phase_host.argtypes = [u8p, u64p, C.c_uint32, C.POINTER(PhaseOptions), C.POINTER(PhaseSite), C.c_uint64, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, u8p, u64p,
                                  C.c_uint64, C.POINTER(PhaseResult), C.POINTER(PhaseTag), u64p]
+    L.flx_svcall_host.argtypes = [u64p, C.c_uint32, C.POINTER(SvcallOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, C.POINTER(SvCluster), C.c_uint64,
+                                  C.POINTER(SvcallRow), u64p]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

@@ -1159,6 +1159,42 @@ int  flx_phase_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, u
                     uint64_t n_words, const uint8_t* read_pool, const uint64_t* read_offsets, uint64_t n_reads, flx_phase_result* results,
                     flx_phase_tag* tags, uint64_t* n_tags);
 
+/* ------------------------------------------------------------------------------------------------ structural-variant calls
+ * Not floxer's, and the step behind the structural-variant signatures: the DEL and INS clusters of an flx_sv object genotyped from the
+ * same records. What flx_sv does not keep is how many counted records cover a cluster's locus without carrying the event; this rule
+ * counts them. Only the host form exists (flx_svcall_host: no device, no object, no tool). The rule
+ * (floxer_amd/csrc/flx_svcall.hpp), integer arithmetic throughout:
+ *   - which records count and what is refused: coverage's, with count_secondary and min_mapq; records and words, no reads;
+ *   - a span: [rs, re) on sequence ref, rs the record's position, re = rs + the summed = X D lengths;
+ *   - the clusters are an array as flx_sv_copy_clusters returns it. Refused (FLX_ERR_INVALID, nothing written): a type above 2, a
+ *     reference id outside the lengths (a DEL or INS with ref_b != ref_a too), pos_a_min > pos_a_max, a DEL or INS without
+ *     q_min <= q_median <= q_max, a DEL with pos_a_max + q_max past its sequence, an INS with pos_a_max at or past its sequence's
+ *     end, a non-zero reserved field. BND clusters are accepted and get no row;
+ *   - the count of a DEL or INS cluster on sequence r of length n_r: lo = pos_a_min, hi = pos_a_max + q_max (DEL) or pos_a_max + 1
+ *     (INS), lo' = lo >= flank ? lo - flank : 0, hi' = min(hi + flank, n_r) (flank: 0 takes 50, at most 2^20); span_n = the spans
+ *     with ref == r, rs <= lo' and re >= hi'; alt_n = support; ref_n = span_n > alt_n ? span_n - alt_n : 0; dp = ref_n + alt_n;
+ *   - the genotype is flx_variants' of (ref_n, alt_n, 0) with its five costs, their defaults 36 / 1574 / 325 / 3000 / 3301 and its
+ *     checks; pass = 1 iff gt != 0, dp >= min_depth (0 takes 4) and qual >= min_qual (0 takes 2000);
+ *   - one row per DEL / INS cluster in the input's order, failing ones included; `cluster` is the index in the input.
+ * Known limits: a carrier that does not span the flanks counts in alt_n and not in span_n, so ref_n errs low by at most that many; a
+ * record with two signatures in one cluster counts twice in alt_n; single linkage is inherited from the clusters; BND clusters are not
+ * called; there is no inserted sequence; an event larger than the read's error budget leaves the read unmapped and is never seen. The
+ * defaults are conventions of this project, fitted to nothing.
+ * flx_svcall_host: *n_rows holds the capacity on entry and the need on return (FLX_ERR_CAPACITY when too small; nothing else is
+ * written then). */
+typedef struct flx_svcall_options {
+    uint32_t count_secondary, min_mapq, flank, min_depth, min_qual, cost_match, cost_mismatch, cost_het, prior_het, prior_hom;
+    uint32_t reserved[2];
+} flx_svcall_options;
+typedef struct flx_svcall_row {
+    uint32_t cluster, type;
+    int32_t ref;
+    uint32_t pos_a_min, pos_a_max, q_min, q_median, q_max, alt_n, ref_n, span_n, gt, gq, qual, pl[3], pass;
+} flx_svcall_row;
+int  flx_svcall_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_svcall_options* o, const flx_record* records, uint64_t n,
+                     const uint32_t* cigar_words, uint64_t n_words, const flx_sv_cluster* clusters, uint64_t n_clusters, flx_svcall_row* rows,
+                     uint64_t* n_rows);
+
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
  * The rule (floxer_amd/csrc/flx_paf.hpp), for a record with flag & 4 clear and reference_id >= 0, words len << 4 | op with = 7, X 8,
