@@ -20,6 +20,7 @@ libfloxer_amd.so:
     coverage(ctx, coverage_options()), coverage_host()  not floxer's: depth of coverage accumulated on the device from the records of runs: equal-depth runs, per-window sums (opt-in)
     pileup(ctx, pileup_options()), pileup_host(), pileup_sites_host()  not floxer's: per-position allele counts (depth, mismatch letters, deletions, insertions) accumulated on the device from the records of runs, and the table of candidate variant sites (opt-in)
     sv(ctx, sv_options()), sv_host(), sv_clusters_host()  not floxer's: structural-variant signatures (long deletions, long insertions, split junctions) collected on the device from the records of runs, sorted and merged into clusters with their support (opt-in)
+    svcaller(ctx, svcall_options()), svcall_host(), svcaller_geometry()  not floxer's: the DEL and INS clusters of an sv object genotyped from the records of the same runs (how many records span a cluster's locus, counted on the device over the sorted spans), as rows with GT, GQ, QUAL and PL; device=-1 is the host form (opt-in)
     errprof(ctx, errprof_options()), errprof_host()  not floxer's: the error profile of the records of runs (which letter is read as which, indel lengths and homopolymer context, errors by position in the read, identities, error-free stretches), summed on the device (opt-in)
     grid_caps()                           a test hook: the most blocks each capped launch asks for, by kernel name
     record_sorter(n_refs), sort_host(), sort_geometry()  not floxer's: the coordinate order of records (reference, position, strand, then the caller's ordinal), sorted on the device by a radix sort over 128-bit keys (opt-in)
@@ -2006,6 +2007,87 @@ def svcall_host(lengths, records, cigar_words, clusters, options=None):
     out = np.zeros(max(1, n.value), dtype=SVCALL_ROW_DTYPE)
     check(lib().flx_svcall_host(*args, out.ctypes.data_as(C.POINTER(capi.SvcallRow)), C.byref(n)))
     return out[: n.value]
+
+
+SVCALL_SPAN_DTYPE = np.dtype([("ref", "<i4"), ("rs", "<u4"), ("re", "<u4"), ("res", "<u4")])
+
+
+def svcaller_geometry():
+    """a test hook: the most blocks of an svcall_spans launch and of an svcall_count launch, the waves of a block (a wave takes one record
+    or one row at a time), and the sort's tile in keys"""
+    out = np.zeros(4, dtype=np.uint32)
+    check(lib().flx_svcaller_geometry(ptr(out, u32p)))
+    return dict(spans_grid_cap=int(out[0]), count_grid_cap=int(out[1]), waves_per_block=int(out[2]), sort_tile=int(out[3]))
+
+
+class svcaller:
+    """Structural-variant calls over the sequences of a context's index (ctx) or over `lengths` on `device` (-1: the host form, which
+    touches nothing of the device): every run's records are added as spans, the objects of other devices absorbed, and finish(clusters)
+    genotypes the DEL and INS clusters of an sv object fed the same runs; then read rows() and spans(). Adds may come from several
+    threads. initial_capacity: the spans the table holds before it first grows (a test hook; 0 takes 2^16)."""
+
+    def __init__(self, ctx=None, options=None, lengths=None, device=0, initial_capacity=0):
+        self.h = C.c_void_p()
+        self.min_mapq = int(options.min_mapq) if options is not None else 0
+        opt = C.byref(options) if options is not None else None
+        if ctx is not None:
+            check(lib().flx_svcaller_create(ctx.h, opt, C.byref(self.h)))
+        else:
+            if lengths is None:
+                raise FloxerError("svcaller needs a context or a list of reference lengths")
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
+            check(lib().flx_svcaller_create_for_lengths(int(device), ptr(lens, u64p) if len(lens) else None, len(lens), opt, int(initial_capacity), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().flx_svcaller_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, run):
+        """run: a RunResult (its records and CIGAR words are added), or a raw flx_run handle (ctypes.c_void_p) that has not been freed.
+        With min_mapq a run made without output_options(mapq=True) is refused."""
+        if isinstance(run, RunResult):
+            if self.min_mapq > 0 and run.has_mapq is False:
+                raise FloxerError("svcaller.add: min_mapq needs a run made with output_options(mapq=True)")
+            return self.add_records(run.raw, run.cigars)
+        check(lib().flx_svcaller_add_run(self.h, run))
+
+    def add_records(self, records, cigar_words):
+        """records: an array of the C ABI's flx_record (RunResult.raw's dtype); cigar_words: the uint32 pool their offsets refer to"""
+        rec, words = _records_and_words(records, cigar_words)
+        check(lib().flx_svcaller_add_records(self.h, rec.ctypes.data_as(C.POINTER(capi.Record)), len(rec), ptr(words, u32p) if len(words) else None, len(words)))
+
+    def absorb(self, other):
+        check(lib().flx_svcaller_absorb(self.h, other.h))
+
+    def finish(self, clusters):
+        """clusters: sv.clusters() of an sv object fed the same runs (a structured array of SV_CLUSTER_DTYPE). Final."""
+        cl = _sv_clusters(clusters)
+        check(lib().flx_svcaller_finish(self.h, cl.ctypes.data_as(C.POINTER(capi.SvCluster)) if len(cl) else None, len(cl)))
+
+    def max_span(self):
+        return int(lib().flx_svcaller_max_span(self.h))
+
+    def spans(self):
+        """all spans in (ref, rs, re) order: a structured array of SVCALL_SPAN_DTYPE"""
+        check(lib().flx_svcaller_copy_spans(self.h, 0, 0, None))       # (refused before finish)
+        n = lib().flx_svcaller_num_spans(self.h)
+        out = np.zeros(max(1, n), dtype=SVCALL_SPAN_DTYPE)
+        check(lib().flx_svcaller_copy_spans(self.h, 0, n, out.ctypes.data_as(C.POINTER(capi.SvcallSpan))))
+        return out[:n]
+
+    def rows(self):
+        """one row per DEL / INS cluster in the clusters' order: a structured array of SVCALL_ROW_DTYPE"""
+        n = lib().flx_svcaller_num_rows(self.h)
+        out = np.zeros(max(1, n), dtype=SVCALL_ROW_DTYPE)
+        check(lib().flx_svcaller_copy_rows(self.h, out.ctypes.data_as(C.POINTER(capi.SvcallRow)), n))
+        return out[:n]
 
 
 # ------------------------------------------------------------------------------------------------ coordinate order of records

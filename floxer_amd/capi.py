@@ -246,6 +246,10 @@ class SvcallRow(C.Structure):
                 ("gq", C.c_uint32), ("qual", C.c_uint32), ("pl", C.c_uint32 * 3), ("pass", C.c_uint32)]
 
 
+class SvcallSpan(C.Structure):
+    _fields_ = [("ref", C.c_int32), ("rs", C.c_uint32), ("re", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # flx_errprof_table: its sections in their fixed order, u64 each
 ERRPROF_SECTIONS = (("PAIR_EQ", 36), ("PAIR_X", 36), ("INS_LEN", 64), ("DEL_LEN", 64), ("INS_LETTER", 6), ("DEL_LETTER", 6), ("HP_DEL", 34), ("HP_INS", 34),
                     ("POS_MATCH", 100), ("POS_MISMATCH", 100), ("POS_INS", 100), ("POS_CLIP", 100), ("POS_DEL", 100), ("EQ_RUN", 256), ("IDENTITY", 101),
@@ -376,6 +380,9 @@ EXPORTED = [
     "flx_phase_create", "flx_phase_create_for_text", "flx_phase_free", "flx_phase_add_records", "flx_phase_add_run", "flx_phase_add_run_resident",
     "flx_phase_finish", "flx_phase_num_sites", "flx_phase_copy_results", "flx_phase_num_tags", "flx_phase_copy_tags", "flx_phase_geometry", "flx_phase_host",
     "flx_svcall_host",
+    "flx_svcaller_create", "flx_svcaller_create_for_lengths", "flx_svcaller_free", "flx_svcaller_add_records", "flx_svcaller_add_run", "flx_svcaller_absorb",
+    "flx_svcaller_finish", "flx_svcaller_num_spans", "flx_svcaller_num_rows", "flx_svcaller_max_span", "flx_svcaller_copy_spans", "flx_svcaller_copy_rows",
+    "flx_svcaller_geometry",
     "flx_grid_caps",
 ]
 
@@ -641,6 +648,23 @@ def lib():
                                  C.c_uint64, C.POINTER(PhaseResult), C.POINTER(PhaseTag), u64p]
     L.flx_svcall_host.argtypes = [u64p, C.c_uint32, C.POINTER(SvcallOptions), C.POINTER(Record), C.c_uint64, u32p, C.c_uint64, C.POINTER(SvCluster), C.c_uint64,
                                   C.POINTER(SvcallRow), u64p]
+    L.flx_svcaller_create.argtypes = [C.c_void_p, C.POINTER(SvcallOptions), C.POINTER(C.c_void_p)]
+    L.flx_svcaller_create_for_lengths.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(SvcallOptions), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.flx_svcaller_free.restype = None
+    L.flx_svcaller_free.argtypes = [C.c_void_p]
+    L.flx_svcaller_add_records.argtypes = [C.c_void_p, C.POINTER(Record), C.c_uint64, u32p, C.c_uint64]
+    L.flx_svcaller_add_run.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_svcaller_absorb.argtypes = [C.c_void_p, C.c_void_p]
+    L.flx_svcaller_finish.argtypes = [C.c_void_p, C.POINTER(SvCluster), C.c_uint64]
+    L.flx_svcaller_num_spans.restype = C.c_uint64
+    L.flx_svcaller_num_spans.argtypes = [C.c_void_p]
+    L.flx_svcaller_num_rows.restype = C.c_uint64
+    L.flx_svcaller_num_rows.argtypes = [C.c_void_p]
+    L.flx_svcaller_max_span.restype = C.c_uint32
+    L.flx_svcaller_max_span.argtypes = [C.c_void_p]
+    L.flx_svcaller_copy_spans.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SvcallSpan)]
+    L.flx_svcaller_copy_rows.argtypes = [C.c_void_p, C.POINTER(SvcallRow), C.c_uint64]
+    L.flx_svcaller_geometry.argtypes = [u32p]
     L.flx_paf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.flx_paf_free.restype = None
     L.flx_paf_free.argtypes = [C.c_void_p]

@@ -276,6 +276,7 @@ int flx_ctx_destroy(flx_ctx* ctx) {
         if (ctx->live_consensus > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_consensus) + " consensus object(s) of this context are still alive (flx_consensus_free them first)"); return FLX_ERR_INVALID; }
         if (ctx->live_variants > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_variants) + " variants object(s) of this context are still alive (flx_variants_free them first)"); return FLX_ERR_INVALID; }
         if (ctx->live_phases > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_phases) + " phase object(s) of this context are still alive (flx_phase_free them first)"); return FLX_ERR_INVALID; }
+        if (ctx->live_svcallers > 0) { set_error("flx_ctx_destroy: " + std::to_string(ctx->live_svcallers) + " svcaller object(s) of this context are still alive (flx_svcaller_free them first)"); return FLX_ERR_INVALID; }
     }
     delete ctx;
     return FLX_OK;

@@ -129,6 +129,7 @@ struct flx_ctx {
     int live_consensus = 0;          // consensus objects that read this context's text (flx_consensus_create) and are not yet freed (guarded by spare_mu): the same
     int live_variants = 0;           // variants objects that read this context's text (flx_variants_create) and are not yet freed (guarded by spare_mu): the same
     int live_phases = 0;             // phase objects made on this context (flx_phase_create) and not yet freed (guarded by spare_mu): the same
+    int live_svcallers = 0;          // svcaller objects made on this context (flx_svcaller_create) and not yet freed (guarded by spare_mu): the same
     bool external_stream = false;    // a caller-owned stream is installed on lane 0: run on that lane only
     // accounting
     bool timing = false;

@@ -1,7 +1,7 @@
 // Structural-variant calls (flx_svcall, include/floxer_amd.h): the rule, in one place. The judgement of options, records and clusters,
-// the span of a record, the window of a cluster in the sorted spans, its count, its genotype and its row (FLX_HD: written so that
-// kernels can run them as they stand; no kernel does yet) and the whole finish on the host. The C ABI, flx_svcall_host:
-// flx_svcall_api.cpp. Integers throughout.
+// the span of a record, the window of a cluster in the sorted spans, its count, its genotype and its row (FLX_HD: the kernels of
+// flx_svcall.hip run them as they stand) and the whole finish on the host. The one-call C ABI, flx_svcall_host: flx_svcall_api.cpp;
+// the object fed run by run, flx_svcaller: flx_svcaller_api.cpp with flx_svcaller.hpp; the tool: floxer_sv_main.cpp. Integers throughout.
 //
 // Positions are 0-based and local to their sequence, as flx_sv has them.
 //   which records count   coverage's filter, coverage_record_counts (flx_coverage.hpp), with count_secondary and min_mapq
@@ -26,8 +26,7 @@
 //   the rows              one per DEL / INS cluster in the input's order, failing ones included.
 // Known limits: a carrier that does not span the flanks counts in alt_n and not in span_n, so ref_n errs low by at most that many; a
 // record with two signatures in one cluster counts twice in alt_n; single linkage is the clusters'; no BND calls; no inserted
-// sequence; the host form only, no device object yet; an event larger than the read's error budget leaves the read unmapped and is
-// never seen.
+// sequence; an event larger than the read's error budget leaves the read unmapped and is never seen.
 #pragma once
 #include "flx_sv.hpp"
 #include "flx_variants.hpp"

@@ -1,6 +1,7 @@
 // flx_svcall: the structural-variant calling rule behind the C ABI (include/floxer_amd.h). The rule and its checks: flx_svcall.hpp.
-// Only the host form exists: flx_svcall_host takes the records and the clusters of an flx_sv object (flx_sv_copy_clusters) and returns
-// one row per DEL / INS cluster. No device is touched.
+// The one-call host form: flx_svcall_host takes all records of a run and the clusters of an flx_sv object (flx_sv_copy_clusters) and
+// returns one row per DEL / INS cluster. No device is touched. The object that is fed batch by batch, on a device or on the host:
+// flx_svcaller_api.cpp.
 #include <cstring>
 
 #include "flx_svcall.hpp"

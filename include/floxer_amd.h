@@ -1162,7 +1162,8 @@ int  flx_phase_host(const uint8_t* ref_ranks_concat, const uint64_t* ref_lens, u
 /* ------------------------------------------------------------------------------------------------ structural-variant calls
  * Not floxer's, and the step behind the structural-variant signatures: the DEL and INS clusters of an flx_sv object genotyped from the
  * same records. What flx_sv does not keep is how many counted records cover a cluster's locus without carrying the event; this rule
- * counts them. Only the host form exists (flx_svcall_host: no device, no object, no tool). The rule
+ * counts them. Three forms run the one rule: flx_svcall_host (all records in one call, no device), the flx_svcaller object below (fed
+ * batch by batch, on a device or, with device -1, on the host) and the tool floxer_sv. The rule
  * (floxer_amd/csrc/flx_svcall.hpp), integer arithmetic throughout:
  *   - which records count and what is refused: coverage's, with count_secondary and min_mapq; records and words, no reads;
  *   - a span: [rs, re) on sequence ref, rs the record's position, re = rs + the summed = X D lengths;
@@ -1194,6 +1195,42 @@ typedef struct flx_svcall_row {
 int  flx_svcall_host(const uint64_t* ref_lens, uint32_t n_refs, const flx_svcall_options* o, const flx_record* records, uint64_t n,
                      const uint32_t* cigar_words, uint64_t n_words, const flx_sv_cluster* clusters, uint64_t n_clusters, flx_svcall_row* rows,
                      uint64_t* n_rows);
+
+/* The object: one span per counted record, added run by run, then the rows of the clusters that flx_sv_copy_clusters gave.
+ *   - create: for a context's index (counted there: flx_ctx_destroy refuses while one is alive) or for reference lengths on
+ *     hip_device; hip_device -1 is the host form, which touches nothing of the device and keeps the spans in host memory.
+ *     initial_capacity: the spans the table holds before it first grows by doubling (0 takes 2^16; a test hook).
+ *   - add_records / add_run: judged like flx_svcall_host's records (coverage's refusals and messages); a refused add leaves the object
+ *     as it was. A run made without CIGARs is refused, with min_mapq also a run made without flx_output_options.mapq. Several host
+ *     threads may add at once. More than 2^32 - 1 spans: FLX_ERR_CAPACITY. FLX_ERR_INTERNAL: a kernel found a record at odds with
+ *     the host's judgement; the add is not counted.
+ *   - absorb: `from`'s spans move into `into` (equal lengths and options, both unfinished, both on devices - which may differ - or
+ *     both host forms); `from` is left empty.
+ *   - finish is final: it judges the clusters as flx_svcall_host does (a refusal is FLX_ERR_INVALID and leaves the object unfinished
+ *     and unchanged, so that a later finish with good clusters works), orders the spans and makes one row per DEL / INS cluster in
+ *     the input's order. Behind it a further add, absorb or finish is FLX_ERR_INVALID. num_spans, num_rows and max_span (the longest
+ *     span, which bounds every window) are 0 before it, and the copy calls are refused.
+ *   - copy_spans: the spans [from, to) in (ref, rs, re) order; a stretch outside them is FLX_ERR_INVALID.
+ *   - copy_rows: capacity is the number of rows `out` holds. capacity < num_rows: FLX_ERR_CAPACITY and nothing is written;
+ *     otherwise exactly num_rows rows are written. out may be NULL only when there are no rows.
+ *   - geometry: out = {the most blocks of an svcall_spans launch, the most blocks of an svcall_count launch, the waves of a block (a
+ *     wave takes one record or one row at a time), the sort's tile in keys}. */
+typedef struct flx_svcaller flx_svcaller;
+typedef struct flx_svcall_span { int32_t ref; uint32_t rs, re, reserved; } flx_svcall_span;
+int  flx_svcaller_create(flx_ctx* ctx, const flx_svcall_options* o, flx_svcaller** out);
+int  flx_svcaller_create_for_lengths(int hip_device, const uint64_t* ref_lens, uint32_t n_refs, const flx_svcall_options* o,
+                                     uint64_t initial_capacity, flx_svcaller** out);
+void flx_svcaller_free(flx_svcaller* s);
+int  flx_svcaller_add_records(flx_svcaller* s, const flx_record* records, uint64_t n, const uint32_t* cigar_words, uint64_t n_words);
+int  flx_svcaller_add_run(flx_svcaller* s, const flx_run* run);
+int  flx_svcaller_absorb(flx_svcaller* into, flx_svcaller* from);
+int  flx_svcaller_finish(flx_svcaller* s, const flx_sv_cluster* clusters, uint64_t n_clusters);
+uint64_t flx_svcaller_num_spans(const flx_svcaller* s);
+uint64_t flx_svcaller_num_rows(const flx_svcaller* s);
+uint32_t flx_svcaller_max_span(const flx_svcaller* s);
+int  flx_svcaller_copy_spans(const flx_svcaller* s, uint64_t from, uint64_t to, flx_svcall_span* out);
+int  flx_svcaller_copy_rows(const flx_svcaller* s, flx_svcall_row* out, uint64_t capacity);
+int  flx_svcaller_geometry(uint32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------ PAF output
  * Not floxer's. A PAF line carries no SEQ, QUAL or CIGAR but per record numbers that are reductions over its CIGAR words: a summary.
